@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — OT-CFM train-step throughput on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one synthetic minibatch already resident in HBM
 (config C3: x0 ~ N(0,I) in R^784, x1 MNIST-like, B = 4096 per GPU):
@@ -14,15 +14,23 @@ batch k, like data-loader workers: N prefetch jobs in flight, each coupling G co
 their G assignment problems go through ONE chain of launches (cfm_assign_exact_batch_f32; same kernels and the
 same per-problem state machine as G single solves, bit-equal results).  The pipeline starts empty inside the timed
 region and is drained inside it: K timed steps contain exactly K couplings and K model updates.
-Host RNG draws stay on the main thread, in order.  `value` is that schedule; `value_sequential`
+Host RNG draws stay on the main thread, in order.  `value` is that schedule; `value_sequential` (--full)
 is the same K steps strictly one after the other (what an unmodified training script gets).
 N > 1: one process per GPU (torchrun), every rank couples its own minibatch (no collective in
 the OT path), the model is data parallel (gradient all-reduce over RCCL), and the final x_t of the
 timed region is all-gathered once (the north star's "all-gather of the final samples"), inside
 the timed region; weak scaling.  Rank 0 prints ONE JSON line.
 
-Also in the line (rank 0, N = 1): `roofline` of the coupling's dominant kernel family (the exact solver's chip-wide
-kernels asg_auction + asg_step, per solve from an un-overlapped leg, and for the batch-of-4 form the schedule runs),
+A plain run sets up, runs W warm-up steps, times ONE region of exactly K steps, writes the arrays of the last timed
+step if --dump-outputs is given (DIR/<name>.npy: t, xt, ut of the coupling; loss, parameters and gradients of the
+model step) and prints the line: `value` = N x B x K / time of the region, `ms_per_step` = that time / K.  Everything
+else below runs with --full only.
+
+With --full, `value` is the median of --repeats such regions (51 by default, fewer for long regions: at most
+20 000 timed steps in all; the counts follow from K alone), the dump is taken after the last of them,
+and the line also carries (rank 0, N = 1): `value_sequential`, `steady_state`, `roofline` of the coupling's dominant
+kernel family (the exact solver's chip-wide kernels asg_auction + asg_step, per solve from an un-overlapped leg, and
+for the batch-of-4 form the schedule runs),
 `value_public_api` (the sequential and the pipelined loop through FM.sample_location_and_conditional_flow[_group],
 asserted bit-equal to the composition timed above), `c2` / `c5` (BASELINE configs[1] / configs[4]: Sinkhorn
 iterations/s as the median of 7 windows with the solver's state after each, and, for C5, the dopri5 sampling time),
@@ -162,16 +170,50 @@ def run_steps(pool, first, count, couple, model_step, draw, prefetcher=None, dep
 
 
 def timed_region(D, sync, pool, warmup, steps, couple, model_step, draw, prefetcher, depth, device=None, group=1,
-                 couple_group=None, ramp=(), tail=()):
+                 couple_group=None, ramp=(), tail=(), keep=None):
     """Warm-up, barrier + sync, K steps + ONE all-gather of the final samples, sync + barrier; the
-    MAX over ranks of the elapsed time.  Returns (elapsed_s, gathered_final_xt)."""
+    MAX over ranks of the elapsed time.  Returns (elapsed_s, gathered_final_xt).  keep: a dict that receives the last
+    step's (t, xt, ut) as "last"."""
     run_steps(pool, 0, warmup, couple, model_step, draw, prefetcher, depth, group, couple_group, ramp, tail)
     D.barrier(); sync()
     t0 = time.perf_counter()
     last = run_steps(pool, warmup, steps, couple, model_step, draw, prefetcher, depth, group, couple_group, ramp, tail)
     gathered = D.all_gather_samples(last[1]) if last is not None else None
     sync(); D.barrier()
+    if keep is not None:
+        keep["last"] = last
     return D.max_over_ranks(time.perf_counter() - t0, device), gathered
+
+
+FULL_STEPS = 20000      # --full: step budget of the repeated loops (their counts follow from K alone, never from time)
+
+
+def full_repeats(steps, want=51):
+    """Regions of `steps` steps a repeated --full loop runs by default: `want`, fewer when they would exceed FULL_STEPS."""
+    return min(want, max(1, FULL_STEPS // max(1, steps)))
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """Write `arrays` (name -> float32 / float64 NumPy array) as path/<name>.npy.  Should they exceed DUMP_BYTES in
+    all, every array above 1 MiB keeps a fixed, seeded sample of its rows, and the row indices go beside it as
+    <name>.rows.npy (float64)."""
+    import zlib
+    os.makedirs(path, exist_ok=True)
+    out = dict(arrays)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES:
+        frac = 0.9 * DUMP_BYTES / total
+        for name, a in arrays.items():
+            if a.ndim >= 1 and a.shape[0] > 1 and a.nbytes > (1 << 20):
+                rng = np.random.default_rng(zlib.crc32(name.encode()))
+                rows = np.sort(rng.choice(a.shape[0], size=max(1, int(a.shape[0] * frac)), replace=False))
+                out[name], out[name + ".rows"] = a[rows], rows.astype(np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return sorted(out)
 
 
 # --------------------------------------------------------------------------- side legs (rank 0, N = 1)
@@ -752,10 +794,11 @@ def main():
     ap.add_argument("--model-step", default="fused", choices=["fused", "eager"],
                     help="fused: cfm_amd.RegressionStep (one C call: forward + MSE + backward, then the one-launch Adam); "
                          "eager: the reference's four lines on the autograd.Function path")
-    ap.add_argument("--repeats", type=int, default=51,
+    ap.add_argument("--repeats", type=int, default=None,
                     help="the timed region (warm-up, barrier, K steps, barrier) is repeated this many times, each on a fresh "
                          "empty pipeline; `value` is the MEDIAN region, every region's ms/step is in the line together with "
-                         "its p95 / max (VERDICT r5 #2: a median of 7 hid a second mode at 1.9 ms)")
+                         "its p95 / max (VERDICT r5 #2: a median of 7 hid a second mode at 1.9 ms).  Default: 1; with --full "
+                         "51, fewer when K x 51 exceeds 20000 steps")
     ap.add_argument("--seq-repeats", type=int, default=7, help="repeats of the sequential (un-overlapped) loops")
     ap.add_argument("--blocking-sync", type=int, default=int(os.environ.get("CFM_BLOCKING_SYNC", "1")),
                     help="1: the prefetch workers' solver waits block in the kernel driver (hipEventBlockingSync) instead of "
@@ -776,14 +819,24 @@ def main():
                     help="A/B switch (not used by the default run): 'theta,eps0,eps_last,stop_frac' for cfm_assign_set_params (0 / -1 keep)")
     ap.add_argument("--public-only", action="store_true",
                     help="diagnostics: ONE headline region, then only the pipelined loop through the public API, --repeats times")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-legs", action="store_true", help="skip the C1 / C2 / C5 / roofline legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline region: the sequential and steady-state "
+                         "loops, the public-API loops, the C1 / C2 / C5 / roofline legs, the CPU baseline and the parity "
+                         "against the reference path")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the arrays of the last one as DIR/<name>.npy (t, xt, ut of the "
+                         "coupling; loss, parameters and gradients of the model step; at most 64 MiB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and parity legs")
+    ap.add_argument("--no-legs", action="store_true", help="with --full: skip the C1 / C2 / C5 / roofline legs")
     ap.add_argument("--host-cost", action="store_true",
                     help="with --cpu-standin: device work replaced by waits of its measured duration; the line carries the "
                          "host CPU time per step (max over ranks)")
     ap.add_argument("--cpu-standin", action="store_true",
                     help="launcher self-test on CPU tensors over gloo (no measurement; see cpu_standin_main)")
     args = ap.parse_args()
+    pub_repeats = args.repeats if args.repeats is not None else full_repeats(args.steps)     # --public-only
+    if args.repeats is None:
+        args.repeats = full_repeats(args.steps) if args.full else 1
     if os.environ.get("CFM_BENCH_WATCHDOG"):     # debugging aid: dump every thread's Python stack and exit if the run hangs
         import faulthandler
         faulthandler.dump_traceback_later(int(os.environ["CFM_BENCH_WATCHDOG"]), exit=True)
@@ -860,6 +913,7 @@ def main():
         return outs
 
     reg = cfm_amd.RegressionStep(model, opt) if args.model_step == "fused" else None
+    eager_loss = {}
 
     def model_step(t, xt, ut):
         if args.mode != "train":
@@ -873,6 +927,7 @@ def main():
         loss = torch.mean((vt - ut) ** 2)
         loss.backward()
         opt.step()
+        eager_loss["loss"] = loss
 
     pre = None
     ramp = tuple(int(x) for x in args.ramp.split(",") if x.strip()) if (args.pipeline and args.group > 1) else ()
@@ -904,14 +959,17 @@ def main():
         fb = (ctypes.c_int * 2)(); lib_.cfm_assign_debug_fallback(fb)
         return int(fb[0]), int(fb[1])
     fb_start = fallbacks()[0]
-    regions = []
     thr0 = thread_cpu_seconds()
     cpu0, wall0 = time.process_time(), time.perf_counter()
-    for _ in range(1 if args.public_only else max(1, args.repeats)):
+    kept = {}
+
+    def headline_region():
         el, gathered = timed_region(D, torch.cuda.synchronize, pool, args.warmup, args.steps, couple, model_step,
-                                    draw, pre, args.pipeline, dev, args.group, couple_group, ramp, tail)
+                                    draw, pre, args.pipeline, dev, args.group, couple_group, ramp, tail, keep=kept)
         assert gathered is None or gathered.shape[0] == world * B
-        regions.append(el)
+        kept["gathered"] = gathered
+        return el
+    regions = [headline_region() for _ in range(1 if args.public_only else max(1, args.repeats))]
     # host CPU time of this rank (all threads: the loop + the prefetch workers + the HIP runtime's own) per step, warm-up
     # steps included in the denominator; with spinning event waits every worker in a solve costs a full core
     host_cpu_ms = (time.process_time() - cpu0) / (len(regions) * (args.steps + args.warmup)) * 1e3
@@ -923,19 +981,36 @@ def main():
                           key=lambda kv: -kv[1])[:8]
     fb_headline = fallbacks()[0] - fb_start
     elapsed = float(np.median(regions))
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path holds after its last step (the last region's), before anything else runs
+        arrays = dict(zip(("t", "xt", "ut"), kept.get("last") or ()))
+        if world > 1:
+            arrays["xt_all_ranks"] = kept["gathered"]
+        if args.mode == "train":
+            loss = reg.loss if reg is not None else eager_loss.get("loss")
+            if loss is not None:
+                arrays["loss"] = loss
+            for name, p in model.named_parameters():
+                arrays["param." + name] = p
+                if p.grad is not None:
+                    arrays["grad." + name] = p.grad
+        arrays = {k: v.detach().cpu().numpy() for k, v in arrays.items()}
+        arrays = {k: v if v.dtype in (np.float32, np.float64) else v.astype(np.float32) for k, v in arrays.items()}
+        dumped = dump_outputs(args.dump_outputs, arrays)
     # the same loop over a region ten times as long (N = 1): what a step costs once the empty pipeline's fill and its
     # drain (a first coupling nothing overlaps: ~2.6 ms of a 20-step region) are amortised.  Reported next to `value`,
     # never instead of it.
     steady = None
-    if pre is not None and world == 1 and not args.no_legs and not args.public_only:
-        ks = 10 * args.steps
+    if args.full and pre is not None and world == 1 and not args.no_legs and not args.public_only:
+        ks = min(10 * args.steps, max(args.steps, FULL_STEPS))
         long_regions = [timed_region(D, torch.cuda.synchronize, pool, args.warmup, ks, couple, model_step, draw, pre,
                                      args.pipeline, dev, args.group, couple_group, ramp, tail)[0] for _ in range(3)]
         el = float(np.median(long_regions))
         steady = {"steps": ks, "repeats": 3, "ms_per_step": el / ks * 1e3, "value": B * ks / el,
                   "ms_per_step_all": [round(r / ks * 1e3, 4) for r in long_regions],
-                  "note": "same schedule, region of 10 x K steps (fill + drain of the pipeline amortised); "
-                          "`value` is the K-step region"}
+                  "note": "same schedule, region of 10 x K steps (at most max(K, 20000); fill + drain of the pipeline "
+                          "amortised); `value` is the K-step region"}
     if pre is not None:
         pre.close()
     if main_stream is not None:
@@ -943,7 +1018,7 @@ def main():
         torch.cuda.set_stream(torch.cuda.default_stream(dev))
     # the same K steps strictly one after the other (no overlap at all): what an unmodified script gets
     seq_s, seq_all = None, []
-    if args.pipeline and world == 1:
+    if args.full and args.pipeline and world == 1:
         n_seq = min(20, args.steps)
         run_steps(pool, 0, 2, couple, model_step, draw)
         for _ in range(max(1, args.seq_repeats)):
@@ -957,7 +1032,7 @@ def main():
     # (the host RNG is then consumed inside the calls — on the worker threads in the pipelined loop).  Both are first
     # asserted BIT-EQUAL to the hand-composed couple() / couple_group() the headline schedule runs, from one RNG state.
     public = None
-    if world == 1 and args.pipeline and args.group > 1 and (not args.no_legs or args.public_only):
+    if world == 1 and args.pipeline and args.group > 1 and ((args.full and not args.no_legs) or args.public_only):
         def rng_get():
             return np.random.get_state(), torch.get_rng_state(), torch.cuda.get_rng_state(dev)
 
@@ -997,7 +1072,7 @@ def main():
             pre2.prime(lambda k=k: couple_group_pub([pool[q % len(pool)] for q in range(k)], None))
         pub_regions = [timed_region(D, torch.cuda.synchronize, pool, args.warmup, args.steps, couple_pub, model_step, no_draw,
                                     pre2, args.pipeline, dev, args.group, couple_group_pub, ramp, tail)[0]
-                       for _ in range(max(1, args.repeats))]
+                       for _ in range(max(1, pub_repeats if args.public_only else args.repeats))]
         pre2.close()
         pe, ps = float(np.median(pub_regions)), float(np.median(pub_seq))
         public = {"bit_equal_to_headline_composition": bool(bit_equal),
@@ -1056,7 +1131,9 @@ def main():
         "steady_state": steady,
         "value_public_api": public,
     }
-    if world == 1 and not args.no_legs and not args.public_only:
+    if dumped is not None:
+        out["outputs_dumped"] = dumped
+    if args.full and world == 1 and not args.no_legs and not args.public_only:
         with torch.cuda.stream(torch.cuda.Stream()):
             out["roofline"] = assign_roofline(dev, pool, lib_, _lib, ot, B)
             out["c1"] = c1_latency(dev)
@@ -1071,7 +1148,7 @@ def main():
         out["aux"] = aux_legs(dev)
     else:
         out["roofline"] = {"bound": "hbm", "achieved": None, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": None,
-                           "traffic": None, "note": "reported at N = 1 only"}
+                           "traffic": None, "note": "reported at N = 1 with --full only"}
     # The driver's record keeps the scalar keys of `roofline` / `config` / `cpu_baseline` only (BENCH_r05: nested objects
     # and the top-level extras were dropped): the second half of BASELINE's metric ("+ Sinkhorn iters/sec") and the other
     # configs' figures are repeated there as flat scalars.  The HBM figure of C2 is the MATRIX-STREAMING
@@ -1109,7 +1186,7 @@ def main():
                    "partial_it_s": out["aux"].get("partial_iters_per_s")})
         out["config"].update({"sinkhorn_c2": c2["config"], "sinkhorn_c5": c5["config"],
                               "c1": "B=256, d=2 exact OT (8gaussians -> moons)"})
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         cb = cpu_baseline(B, d)
         out["cpu_baseline"] = cb
         # the per-config CPU figures next to the GPU ones they belong to

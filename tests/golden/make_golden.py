@@ -24,6 +24,9 @@ Fixture provenance
                       runner/src/models/components/sinkhorn_knopp_unbalanced.py imported unmodified
                       (pure NumPy) and run to its fixed point: unbalanced plans for three (reg, reg_m),
                       and balanced entropic plans through reg_m_1 = reg_m_2 = 1e12.
+  crosscheck_cases.npz  reference classes on the seeded inputs of tests/test_reference_crosscheck.py (the
+                      exact-OT step through the stand-in, the closed forms) and the outcome of the reference's
+                      own sample_map / constructor-error assertions with the stand-in on the path.
 """
 import os
 import sys
@@ -302,7 +305,56 @@ def refsk_cases():
     return out
 
 
+CROSSCHECK_STEP = ((64, (2,)), (128, (2, 2, 2)), (100, (5,)))
+CROSSCHECK_CLOSED = (("icfm", "ConditionalFlowMatcher"), ("target", "TargetConditionalFlowMatcher"),
+                     ("vp", "VariancePreservingConditionalFlowMatcher"))
+CROSSCHECK_SIGMAS = (0.0, 5e-4, 0.5, 1.5, 0, 1)
+
+
+def crosscheck_cases(cfm, ot):
+    """What tests/test_reference_crosscheck.py compares the oracle with: the reference classes' t / xt / ut / eps on
+    seeded inputs (the exact-OT step through the stand-in, and the closed forms), and the outcome of the reference's
+    own sample_map(replace=False) / constructor-error assertions run with the stand-in on the path."""
+    out = {}
+    for B, shape in CROSSCHECK_STEP:
+        key = f"step|{B}|{'x'.join(map(str, shape))}"
+        g = torch.Generator().manual_seed(B)
+        x0, x1 = torch.randn(B, *shape, generator=g), torch.randn(B, *shape, generator=g)
+        fm = cfm.ExactOptimalTransportConditionalFlowMatcher(sigma=0.25)
+        torch.manual_seed(3); np.random.seed(3)
+        t, xt, ut, eps = fm.sample_location_and_conditional_flow(x0, x1, return_noise=True)
+        for k, v in (("x0", x0), ("x1", x1), ("t", t), ("xt", xt), ("ut", ut), ("eps", eps)):
+            out[f"{key}|{k}"] = v.numpy()
+    for method, cls in CROSSCHECK_CLOSED:
+        for sigma in CROSSCHECK_SIGMAS:
+            key = f"closed|{method}|{sigma!r}"
+            g = torch.Generator().manual_seed(zlib.crc32(key.encode()) % (2**31))
+            x0, x1 = torch.randn(32, 3, 4, generator=g), torch.randn(32, 3, 4, generator=g)
+            fm = getattr(cfm, cls)(sigma=sigma)
+            torch.manual_seed(9)
+            t, xt, ut, eps = fm.sample_location_and_conditional_flow(x0, x1, return_noise=True)
+            for k, v in (("x0", x0), ("x1", x1), ("t", t), ("xt", xt), ("ut", ut), ("eps", eps)):
+                out[f"{key}|{k}"] = v.numpy()
+    s = ot.OTPlanSampler(method="exact")
+    pm = np.random.default_rng(0).permutation(np.eye(64), axis=1)
+    np.random.seed(0)
+    ii, jj = s.sample_map(pm, batch_size=64, replace=False)
+    out.update(own_pm=pm, own_i=np.asarray(ii), own_j=np.asarray(jj))
+    for name, fn in (("own_raises_unknown_method", lambda: ot.OTPlanSampler(method="nope")),
+                     ("own_raises_sb_sigma0", lambda: cfm.SchrodingerBridgeConditionalFlowMatcher(sigma=0.0))):
+        try:
+            fn()
+            out[name] = np.array(False)
+        except ValueError:
+            out[name] = np.array(True)
+    return out
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "crosscheck":  # reference classes, imported unmodified
+        np.savez_compressed(os.path.join(HERE, "crosscheck_cases.npz"), **crosscheck_cases(*ref_import.import_reference()))
+        print("crosscheck_cases.npz", os.path.getsize(os.path.join(HERE, "crosscheck_cases.npz")))
+        return
     if len(sys.argv) > 1 and sys.argv[1] == "refsk":      # reference-held NumPy Sinkhorn, imported unmodified
         np.savez_compressed(os.path.join(HERE, "refsk_cases.npz"), **refsk_cases())
         print("refsk_cases.npz", os.path.getsize(os.path.join(HERE, "refsk_cases.npz")))
@@ -325,6 +377,7 @@ def main():
     np.savez_compressed(os.path.join(HERE, "ode2_cases.npz"), **ode2_cases())
     np.savez_compressed(os.path.join(HERE, "metrics_cases.npz"), **metrics_cases())
     np.savez_compressed(os.path.join(HERE, "metrics_cases.npz"), **metrics_cases())
+    np.savez_compressed(os.path.join(HERE, "crosscheck_cases.npz"), **crosscheck_cases(cfm, ot))
     for f in sorted(os.listdir(HERE)):
         if f.endswith(".npz"):
             print(f, os.path.getsize(os.path.join(HERE, f)))

@@ -1,28 +1,29 @@
-"""CPU, build container only: the oracle against the LIVE reference imported from
-/root/reference (skipped where the reference tree is absent, e.g. on the GPU box)."""
+"""CPU: the oracle against outputs of the reference's own classes, recorded by tests/golden/make_golden.py
+(`crosscheck` -> tests/golden/crosscheck_cases.npz) on the seeded inputs stored next to them."""
+import os
+
 import numpy as np
 import pytest
 import torch
 
 import cfm_oracle as oracle
-import ref_import
-
-pytestmark = pytest.mark.skipif(not ref_import.available(), reason="reference tree not present")
 
 
 @pytest.fixture(scope="module")
-def ref():
-    return ref_import.import_reference()
+def ref(golden_dir):
+    with np.load(os.path.join(golden_dir, "crosscheck_cases.npz")) as z:
+        return {k: z[k] for k in z.files}
+
+
+def _case(ref, key):
+    return [torch.from_numpy(ref[f"{key}|{k}"]) for k in ("x0", "x1", "t", "xt", "ut", "eps")]
 
 
 @pytest.mark.parametrize("B,shape", [(64, (2,)), (128, (2, 2, 2)), (100, (5,))])
 def test_exact_ot_step_matches_reference(ref, B, shape):
-    cfm, ot = ref
+    x0, x1, t, xt, ut, eps = _case(ref, f"step|{B}|{'x'.join(map(str, shape))}")
     g = torch.Generator().manual_seed(B)
-    x0, x1 = torch.randn(B, *shape, generator=g), torch.randn(B, *shape, generator=g)
-    fm = cfm.ExactOptimalTransportConditionalFlowMatcher(sigma=0.25)
-    torch.manual_seed(3); np.random.seed(3)
-    t, xt, ut, eps = fm.sample_location_and_conditional_flow(x0, x1, return_noise=True)
+    assert torch.equal(x0, torch.randn(B, *shape, generator=g)) and torch.equal(x1, torch.randn(B, *shape, generator=g))
     torch.manual_seed(3); np.random.seed(3)
     t2, xt2, ut2, eps2, _ = oracle.ot_cfm_step(x0, x1, sigma=0.25)
     assert torch.equal(t, t2) and torch.equal(eps, eps2)
@@ -36,25 +37,36 @@ def test_exact_ot_step_matches_reference(ref, B, shape):
 ])
 @pytest.mark.parametrize("sigma", [0.0, 5e-4, 0.5, 1.5, 0, 1])
 def test_closed_forms_match_reference(ref, method, cls, kw, sigma):
-    cfm, _ = ref
-    x0, x1 = torch.randn(32, 3, 4), torch.randn(32, 3, 4)
-    fm = getattr(cfm, cls)(sigma=sigma, **kw)
-    torch.manual_seed(9)
-    t, xt, ut, eps = fm.sample_location_and_conditional_flow(x0, x1, return_noise=True)
+    x0, x1, t, xt, ut, eps = _case(ref, f"closed|{method}|{sigma!r}")
+    assert x0.shape == (32, 3, 4) and t.shape == (32,)
     xt2, ut2 = oracle.xt_ut(method, x0, x1, t, eps, sigma)
     assert torch.all(xt.eq(xt2)) and torch.all(ut.eq(ut2))
 
 
 def test_reference_own_tests_pass_with_standin(ref):
-    """The stand-in is faithful enough for the reference's own assertions."""
-    cfm, ot = ref
-    s = ot.OTPlanSampler(method="exact")
-    rng = np.random.default_rng(0)
-    pm = rng.permutation(np.eye(64), axis=1)
-    ii, jj = s.sample_map(pm, batch_size=64, replace=False)
+    """The stand-in is faithful enough for the reference's own assertions: the reference's
+    sample_map(replace=False), recorded on a permutation plan, recovered the plan; the stand-in's emd finds that plan
+    and the reference's draw reproduces the recorded pairs on it; the package raises where the reference raised."""
+    import os
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "ot_standin"))
+    import ot
+    from cfm_amd.conditional_flow_matching import SchrodingerBridgeConditionalFlowMatcher
+    from cfm_amd.optimal_transport import OTPlanSampler
+    pm = ref["own_pm"]
+    assert np.array_equal(pm, np.random.default_rng(0).permutation(np.eye(64), axis=1))
+    ii, jj = ref["own_i"], ref["own_j"]
     rec = np.zeros((64, 64)); rec[ii, jj] = 1
     assert np.array_equal(rec, pm)
+    # the stand-in's exact plan for a cost that is zero on the permutation and one elsewhere (what get_map hands on)
+    pi = ot.emd(ot.unif(64), ot.unif(64), 1.0 - pm)
+    assert np.array_equal(pi * 64, pm)
+    # the reference's sample_map draw (np.random.choice over the flattened plan, without replacement) on that plan
+    np.random.seed(0)
+    p = pi.flatten(); p = p / p.sum()
+    assert np.array_equal(np.divmod(np.random.choice(64 * 64, p=p, size=64, replace=False), 64), (ii, jj))
+    assert bool(ref["own_raises_unknown_method"]) and bool(ref["own_raises_sb_sigma0"])
     with pytest.raises(ValueError):
-        ot.OTPlanSampler(method="nope")
+        OTPlanSampler(method="nope")
     with pytest.raises(ValueError):
-        cfm.SchrodingerBridgeConditionalFlowMatcher(sigma=0.0)
+        SchrodingerBridgeConditionalFlowMatcher(sigma=0.0)

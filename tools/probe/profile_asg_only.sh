@@ -3,7 +3,7 @@
 # kernel statistics of the default bench command): re-run after a change that touches only the exact solver.
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/prof; mkdir -p $O/raw
-rocprofv3 --kernel-trace --output-format csv -d $O/raw/bench -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_under_trace.json.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $O/raw/bench -- python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline > $O/bench_under_trace.json.log 2>&1
 python tools/prof_summary.py stats $O/raw/bench $O/bench_kernel_stats.csv
 python tools/overlap_report.py $O/raw/bench > $O/bench_overlap.txt 2>&1
 for C in FETCH_SIZE WRITE_SIZE; do

@@ -4,7 +4,7 @@
 #   exact-assignment solves, MFMA-busy counters of the MFMA-bearing kernels.  Summaries land in gpurun_out/prof/.
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/prof; rm -rf $O; mkdir -p $O/raw
-rocprofv3 --kernel-trace --output-format csv -d $O/raw/bench -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_under_trace.json.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $O/raw/bench -- python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline > $O/bench_under_trace.json.log 2>&1
 python tools/prof_summary.py stats $O/raw/bench $O/bench_kernel_stats.csv
 for C in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --pmc $C --kernel-trace --output-format csv -d $O/raw/asg_$C -- python tools/asg_trace.py run > $O/asg_$C.log 2>&1
