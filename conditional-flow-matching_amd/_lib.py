@@ -82,6 +82,10 @@ SIGNATURES = {
     "cfm_ode_euler_mlp_f32": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "cfm_ode_dopri5_mlp_f32": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _i, _f, _f, _vp, _vp, _vp,
                                    _vp, _vp]),
+    "cfm_mlp_divergence_f32": (_i, [_vp, _vp, _vp, _i, _vp, _i, _f, _i, _vp, _vp, _vp, _vp, _vp]),
+    "cfm_ode_euler_cnf_mlp_f32": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "cfm_ode_dopri5_cnf_mlp_f32": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _f, _f, _vp, _vp, _vp,
+                                       _vp, _vp]),
 }
 # helpers that are not part of the documented ABI (tuning / replace=False bookkeeping)
 EXTRA_SIGNATURES = {

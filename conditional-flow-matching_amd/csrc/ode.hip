@@ -202,10 +202,65 @@ static int read_red(hipStream_t s, const double* dev, int count, double* host) {
     return 0;
 }
 
+template <int MODE>
 static int ode_dopri5_small(const float* const* W, const float* const* b, const int* dims, int B, int d,
-                            const float* t_span, int n_t, float atol, float rtol, float* traj,
-                            int* n_steps, int* nfe, float* xbuf, float* kbuf, float* tspan_dev,
+                            const float* t_span, int n_t, float tsign, const float* eps, float atol, float rtol,
+                            float* traj, int* n_steps, int* nfe, float* xbuf, float* kbuf, float* tspan_dev,
                             void* state_dev, char* sync_dev, float t0, float dt0, int evals0, hipStream_t s);
+
+// Time direction of a t_span (torchdyn's rule): a strictly decreasing grid is integrated as
+// g(s, y) = -f(-s, y) on s = -t_span.  ts receives the (increasing) grid the solver steps on; the returned sign
+// goes into the field's time argument (f is evaluated at sign * s) and into every stage / init-step coefficient
+// (y = x + (sign * dt) * sum a k), so the field arithmetic never changes and the solve is, bit for bit, the
+// forward solve of the field whose time column and last layer are negated.  0: not strictly monotone.
+static float ode_direction(const float* t_span, int n_t, float* ts) {
+    int up = 1, down = 1;
+    for (int k = 0; k + 1 < n_t; ++k) {
+        if (!(t_span[k + 1] > t_span[k])) up = 0;
+        if (!(t_span[k + 1] < t_span[k])) down = 0;
+    }
+    if (!up && !down) return 0.f;
+    const float sg = up ? 1.f : -1.f;
+    for (int k = 0; k < n_t; ++k) ts[k] = sg * t_span[k];
+    return sg;
+}
+
+// Hairer II.4 initial step of the host drivers (d0, d1, d2 as RMS norms over n elements).  f(t, x, k) evaluates
+// the field at solver time t (s-space: the caller applies the time sign); hsign = the time sign.
+template <class F>
+static int ode_init_step(F&& f, size_t n, float t, float hsign, float atol, float rtol, const OdeWs& w,
+                         hipStream_t s, float* dt_out) {
+    const int nb = ode_blocks(n);
+    const float order = 5.f;
+    auto rms = [&](double sumsq) -> float { return (float)sqrt(sumsq / (double)n); };
+    int rc = cfm_hip(hipMemsetAsync(w.red, 0, 64, s));
+    if (rc) return rc;
+    hipLaunchKernelGGL(ode_sqnorm, dim3(nb), dim3(256), 0, s, n, w.x, (const float*)nullptr, w.x, atol, rtol, w.red + 0);
+    hipLaunchKernelGGL(ode_sqnorm, dim3(nb), dim3(256), 0, s, n, w.k[0], (const float*)nullptr, w.x, atol, rtol, w.red + 1);
+    double r2[3];
+    rc = read_red(s, w.red, 2, r2);
+    if (rc) return rc;
+    const float d0 = rms(r2[0]), d1 = rms(r2[1]);
+    const float h0 = (d0 < 1e-5f || d1 < 1e-5f) ? 1e-6f : 0.01f * d0 / d1;
+    Stages st{}; st.n = 1; st.c[0] = 1.f;
+    for (int q = 0; q < 7; ++q) st.k[q] = w.k[0];
+    hipLaunchKernelGGL(ode_combine, dim3(nb), dim3(256), 0, s, n, w.x, hsign * h0, st, w.xt, (float*)nullptr);
+    rc = f(t + h0, w.xt, w.k[1]);
+    if (rc) return rc;
+    hipLaunchKernelGGL(ode_sqnorm, dim3(nb), dim3(256), 0, s, n, w.k[1], w.k[0], w.x, atol, rtol, w.red + 2);
+    rc = read_red(s, w.red + 2, 1, r2);
+    if (rc) return rc;
+    const float d2 = rms(r2[0]) / h0;
+    float h1;
+    if (d1 <= 1e-15f && d2 <= 1e-15f) h1 = fmaxf(1e-6f, h0 * 1e-3f);
+    else h1 = powf(0.01f / fmaxf(d1, d2), 1.0f / (order + 1.f));
+    *dt_out = fminf(100.f * h0, h1);
+    return 0;
+}
+
+static int ode_dopri5_layers(const float* const* W, const float* const* b, const int* dims, int n_layers, int d,
+                             const float* x0, int B, const float* t_span, int n_t, float tsign, float atol,
+                             float rtol, float* traj, int* n_steps, int* nfe, void* ws, void* stream);
 
 extern "C" int cfm_ode_dopri5_mlp_f32(const float* const* W, const float* const* b, const int* dims,
                                       int n_layers, const float* x0, int B, const float* t_span,
@@ -215,8 +270,19 @@ extern "C" int cfm_ode_dopri5_mlp_f32(const float* const* W, const float* const*
     if (!W || !b || !x0 || !t_span || !traj || !ws || B <= 0 || n_t < 2) return CFM_EINVAL;
     int rc = check_mlp(dims, n_layers, &d);
     if (rc) return rc;
-    for (int k = 0; k + 1 < n_t; ++k)
-        if (!(t_span[k + 1] > t_span[k])) return CFM_EINVAL;   // forward integration only
+    float* ts = (float*)malloc(sizeof(float) * (size_t)n_t);   // the grid in solver time (s = sign * t)
+    if (!ts) return CFM_EINVAL;
+    const float tsign = ode_direction(t_span, n_t, ts);
+    if (tsign == 0.f) { free(ts); return CFM_EINVAL; }          // strictly monotone t_span only
+    rc = ode_dopri5_layers(W, b, dims, n_layers, d, x0, B, ts, n_t, tsign, atol, rtol, traj, n_steps, nfe, ws, stream);
+    free(ts);
+    return rc;
+}
+
+static int ode_dopri5_layers(const float* const* W, const float* const* b, const int* dims, int n_layers, int d,
+                             const float* x0, int B, const float* t_span, int n_t, float tsign, float atol,
+                             float rtol, float* traj, int* n_steps, int* nfe, void* ws, void* stream) {
+    int rc;
     hipStream_t s = (hipStream_t)stream;
     const int width = maxwidth(dims, n_layers);
     OdeWs w = ode_carve(ws, B, width, d);
@@ -227,7 +293,7 @@ extern "C" int cfm_ode_dopri5_mlp_f32(const float* const* W, const float* const*
 
     auto f = [&](float t, const float* xin, float* kout) -> int {
         ++evals;
-        return cfm_mlp_forward_impl(xin, nullptr, t, 1, 0, W, b, dims, n_layers, B, kout, w.act, s);
+        return cfm_mlp_forward_impl(xin, nullptr, tsign * t, 1, 0, W, b, dims, n_layers, B, kout, w.act, s);
     };
     auto rms = [&](double sumsq) -> float { return (float)sqrt(sumsq / (double)n); };
 
@@ -243,36 +309,14 @@ extern "C" int cfm_ode_dopri5_mlp_f32(const float* const* W, const float* const*
 
     // ---- init_step (Hairer II.4) ----
     float dt;
-    {
-        rc = cfm_hip(hipMemsetAsync(w.red, 0, 64, s));
-        if (rc) return rc;
-        hipLaunchKernelGGL(ode_sqnorm, dim3(nb), dim3(256), 0, s, n, w.x, (const float*)nullptr, w.x, atol, rtol, w.red + 0);
-        hipLaunchKernelGGL(ode_sqnorm, dim3(nb), dim3(256), 0, s, n, w.k[0], (const float*)nullptr, w.x, atol, rtol, w.red + 1);
-        double r2[3];
-        rc = read_red(s, w.red, 2, r2);
-        if (rc) return rc;
-        const float d0 = rms(r2[0]), d1 = rms(r2[1]);
-        const float h0 = (d0 < 1e-5f || d1 < 1e-5f) ? 1e-6f : 0.01f * d0 / d1;
-        Stages st{}; st.n = 1; st.c[0] = 1.f;
-        for (int q = 0; q < 7; ++q) st.k[q] = w.k[0];
-        hipLaunchKernelGGL(ode_combine, dim3(nb), dim3(256), 0, s, n, w.x, h0, st, w.xt, (float*)nullptr);
-        rc = f(t + h0, w.xt, w.k[1]);
-        if (rc) return rc;
-        hipLaunchKernelGGL(ode_sqnorm, dim3(nb), dim3(256), 0, s, n, w.k[1], w.k[0], w.x, atol, rtol, w.red + 2);
-        rc = read_red(s, w.red + 2, 1, r2);
-        if (rc) return rc;
-        const float d2 = rms(r2[0]) / h0;
-        float h1;
-        if (d1 <= 1e-15f && d2 <= 1e-15f) h1 = fmaxf(1e-6f, h0 * 1e-3f);
-        else h1 = powf(0.01f / fmaxf(d1, d2), 1.0f / (order + 1.f));
-        dt = fminf(100.f * h0, h1);
-    }
+    rc = ode_init_step(f, n, t, tsign, atol, rtol, w, s, &dt);
+    if (rc) return rc;
 
     // small vector fields: the whole step attempt in one kernel, controller on the device
     if (ode_small_enabled() && n_layers == 4 && dims[1] <= SM_WMAX && dims[2] <= SM_WMAX && dims[3] <= SM_WMAX &&
         d + 1 <= SM_WMAX && n >= (size_t)n_t)
-        return ode_dopri5_small(W, b, dims, B, d, t_span, n_t, atol, rtol, traj, n_steps, nfe, w.x, w.k[0], w.xt,
-                                (void*)(w.red + 16), w.sync, t, dt, evals, s);
+        return ode_dopri5_small<0>(W, b, dims, B, d, t_span, n_t, tsign, nullptr, atol, rtol, traj, n_steps, nfe, w.x,
+                                   w.k[0], w.xt, (void*)(w.red + 16), w.sync, t, dt, evals, s);
 
     int ckpt = 1;  // next t_span index to land on
     const int max_attempts = 1000000;
@@ -286,7 +330,7 @@ extern "C" int cfm_ode_dopri5_mlp_f32(const float* const* W, const float* const*
             Stages st{}; st.n = sIdx + 1;
             for (int q = 0; q < 7; ++q) { st.k[q] = w.k[q < 7 ? q : 0]; st.c[q] = q <= sIdx ? (float)DP_A[sIdx][q] : 0.f; }
             float* dst = (sIdx == 5) ? w.xn : w.xt;
-            hipLaunchKernelGGL(ode_combine, dim3(nb), dim3(256), 0, s, n, w.x, dt, st, dst, (float*)nullptr);
+            hipLaunchKernelGGL(ode_combine, dim3(nb), dim3(256), 0, s, n, w.x, tsign * dt, st, dst, (float*)nullptr);
             rc = f(t + DP_C[sIdx] * dt, dst, w.k[sIdx + 1]);
             if (rc) return rc;
         }
@@ -389,6 +433,8 @@ __device__ __forceinline__ double DP_E_dev(int q) {
 }
 
 struct SmState { float t, dt; int ckpt, steps, evals, par, done, pad; };
+// One persistent solve at a time per process, whatever its augmentation mode (see ode_dopri5_small)
+static std::mutex g_persistent_mu;
 struct SmArgs { const float* W[4]; const float* b[4]; int dims[5]; };
 
 // the step-size clipping the host loop does before every attempt
@@ -471,6 +517,133 @@ __device__ __forceinline__ SmTile sm_field(const SmTile& y, float t, const SmArg
     return acc;
 }
 
+// ---- CNF augmentation: v = f(t, x) and its divergence on the tile ----------------------------------------------
+// J = W3 diag(s3) W2 diag(s2) W1 diag(s1) W0[:, :d],  s_l = selu'(z_l) at the layer's pre-activation.
+//   AUG_EXACT: tr J = sum_k (J e_k)_k.  T1 = s1 * W0[:, k] needs no product; T2 = s2 * (W1 T1), T3 = s3 * (W2 T2);
+//              only row k of W3 is needed, so the last product is a dot product: 2 GEMMs per direction.
+//   AUG_HUTCH: eps^T J eps (eps fixed per solve): T1 = s1 * (W0 eps), T2, T3, Ju = W3 T3: 4 GEMMs.
+// The lane that owns (row, col) of z_l owns (row, col) of every tangent tile, so s_l stays in its registers; the
+// tangent tiles take the primal's LDS staging buffers in the same strict alternation (a barrier after every write).
+enum { AUG_NONE = 0, AUG_EXACT = 1, AUG_HUTCH = 2 };
+
+// selu'(z) as PyTorch's elu_backward takes it: scale for z > 0, scale * alpha * exp(z) otherwise (z = 0 included)
+__device__ __forceinline__ float selu_slope(float z) {
+    return z > 0.f ? 1.0507009873554805f : (1.0507009873554805f * 1.6732632423543772f) * expf(z);
+}
+
+// per-row sum of a C-layout tile over its 64 columns: 16 lanes of a wave (butterfly: every lane gets the same bits),
+// then the 4 waves in a fixed order through red[4][SM_ROWS]; every lane gets the sums of its SM_V rows
+__device__ __forceinline__ SmTile sm_rowsum(SmTile p, float* red, int wv, int lane) {
+#pragma unroll
+    for (int i = 0; i < SM_V; ++i) {
+#pragma unroll
+        for (int o = 1; o < 16; o <<= 1) p.v[i] += __shfl_xor(p.v[i], o, 64);
+    }
+    if ((lane & 15) == 0) {
+#pragma unroll
+        for (int i = 0; i < SM_V; ++i) red[wv * SM_ROWS + sm_row(i, lane)] = p.v[i];
+    }
+    sm_lds_barrier();
+    SmTile r;
+#pragma unroll
+    for (int i = 0; i < SM_V; ++i) {
+        const int row = sm_row(i, lane);
+        r.v[i] = ((red[row] + red[SM_ROWS + row]) + red[2 * SM_ROWS + row]) + red[3 * SM_ROWS + row];
+    }
+    return r;
+}
+
+// f(t, y) exactly as sm_field (bitwise the same v), plus div (per row, in every lane holding the row).
+// eps: the probe tile (C layout, zero outside [rows, d]); nrows: rows of the tile below B (the rest stay zero in
+// every tangent tile).
+template <int MODE>
+__device__ __forceinline__ SmTile sm_field_aug(const SmTile& y, float t, const SmArgs& A, int d, float* Abuf0,
+                                               float* Abuf1, const float* Wl, const float* bl, const float* wt,
+                                               const SmTile& eps, int nrows, float* red, int wv, int lane,
+                                               SmTile& div) {
+    const int col = wv * 16 + (lane & 15);
+#pragma unroll
+    for (int i = 0; i < SM_V; ++i) Abuf0[sm_row(i, lane) * SM_LD + col] = (col < d) ? y.v[i] : 0.f;
+    sm_lds_barrier();
+    SmTile acc, sl[3];
+    float* src = Abuf0; float* dst = Abuf1;
+#pragma unroll
+    for (int l = 0; l < 4; ++l) {
+        const int K = (l == 0) ? d : A.dims[l];
+        const int N = A.dims[l + 1];
+        f32x4 c[SM_MB];
+        sm_gemm(src, Wl + l * SM_W * SM_LD, K, wv, lane, c);
+        const float bv = (col < N) ? bl[l * SM_W + col] : 0.f;
+        const float wtc = (l == 0 && col < N) ? wt[col] : 0.f;
+#pragma unroll
+        for (int i = 0; i < SM_V; ++i) {
+            float v = c[i >> 2][i & 3] + bv;
+            if (l == 0) v = fmaf(t, wtc, v);
+            if (l < 3) {
+                sl[l].v[i] = (col < N && sm_row(i, lane) < nrows) ? selu_slope(v) : 0.f;
+                v = selu_f(v);
+            }
+            acc.v[i] = (col < N) ? v : 0.f;
+        }
+        if (l < 3) {
+#pragma unroll
+            for (int i = 0; i < SM_V; ++i) dst[sm_row(i, lane) * SM_LD + col] = acc.v[i];
+            sm_lds_barrier();
+            float* tmp = src; src = dst; dst = tmp;
+        }
+    }
+    SmTile q;
+    if constexpr (MODE == AUG_HUTCH) {
+#pragma unroll
+        for (int i = 0; i < SM_V; ++i) Abuf0[sm_row(i, lane) * SM_LD + col] = (col < d) ? eps.v[i] : 0.f;
+        sm_lds_barrier();
+        src = Abuf0; dst = Abuf1;
+        SmTile tg;
+#pragma unroll
+        for (int l = 0; l < 4; ++l) {
+            const int N = A.dims[l + 1];
+            f32x4 c[SM_MB];
+            sm_gemm(src, Wl + l * SM_W * SM_LD, N, wv, lane, c);
+#pragma unroll
+            for (int i = 0; i < SM_V; ++i) {
+                float u = c[i >> 2][i & 3];
+                if (l < 3) u = sl[l].v[i] * u;
+                tg.v[i] = (col < N) ? u : 0.f;
+            }
+            if (l < 3) {
+#pragma unroll
+                for (int i = 0; i < SM_V; ++i) dst[sm_row(i, lane) * SM_LD + col] = tg.v[i];
+                sm_lds_barrier();
+                float* tmp = src; src = dst; dst = tmp;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < SM_V; ++i) q.v[i] = (col < d) ? eps.v[i] * tg.v[i] : 0.f;
+    } else {
+        (void)eps;
+        const int N1 = A.dims[1], N2 = A.dims[2], N3 = A.dims[3];
+#pragma unroll
+        for (int i = 0; i < SM_V; ++i) q.v[i] = 0.f;
+        for (int k = 0; k < d; ++k) {
+            const float w0 = (col < N1) ? Wl[col * SM_LD + k] : 0.f;                      // W0[col][k]
+#pragma unroll
+            for (int i = 0; i < SM_V; ++i) Abuf0[sm_row(i, lane) * SM_LD + col] = sl[0].v[i] * w0;
+            sm_lds_barrier();
+            f32x4 c[SM_MB];
+            sm_gemm(Abuf0, Wl + 1 * SM_W * SM_LD, N1, wv, lane, c);
+#pragma unroll
+            for (int i = 0; i < SM_V; ++i) Abuf1[sm_row(i, lane) * SM_LD + col] = (col < N2) ? sl[1].v[i] * c[i >> 2][i & 3] : 0.f;
+            sm_lds_barrier();
+            sm_gemm(Abuf1, Wl + 2 * SM_W * SM_LD, N2, wv, lane, c);
+            const float w3 = (col < N3) ? Wl[3 * SM_W * SM_LD + k * SM_LD + col] : 0.f;  // W3[k][col]
+#pragma unroll
+            for (int i = 0; i < SM_V; ++i) q.v[i] = fmaf(w3, (col < N3) ? sl[2].v[i] * c[i >> 2][i & 3] : 0.f, q.v[i]);
+        }
+    }
+    div = sm_rowsum(q, red, wv, lane);
+    return acc;
+}
+
 // weights -> LDS, zero padded to [4][64][SM_LD]; biases; the time column of layer 0
 __device__ __forceinline__ void sm_stage_weights(const SmArgs& A, int d, float* Wl, float* bl, float* wt, int tid) {
     for (int l = 0; l < 4; ++l) {
@@ -538,35 +711,49 @@ __device__ __forceinline__ bool sm_grid_allsum(double* __restrict__ row, double 
 // the same fixed order (so the solve is reproducible bit for bit), derives the same accept / reject
 // decision and next step size from that sum (the fp32 controller of the host loop above).  `lines` is only
 // touched by SM_PROF builds (phase stamps).
-template <bool RESIDENT>
+template <bool RESIDENT, int MODE>
 __global__ __launch_bounds__(256) void ode_small_dopri(SmArgs A, int B, int d, SmState* __restrict__ st_io,
                                                     float* __restrict__ xbuf, float* __restrict__ kbuf,
                                                     const float* __restrict__ tspan, int n_t, float atol, float rtol,
                                                     float* __restrict__ traj, double* __restrict__ partial,
-                                                    unsigned long long* __restrict__ lines, int max_attempts) {
+                                                    unsigned long long* __restrict__ lines, int max_attempts,
+                                                    float tsign, const float* __restrict__ eps) {
+    // MODE != AUG_NONE: the state is [B, 1 + d] (column 0 = l, the log-density accumulator, d l / dt = -div); each
+    // row's l and its stage values sit in the registers of every lane that holds the row
+    constexpr bool AUG = MODE != AUG_NONE;
     extern __shared__ __attribute__((aligned(16))) float small_lds[];
     float* Wl = small_lds;                           // [4][64][SM_LD]
     float* bl = Wl + 4 * SM_W * SM_LD;               // [4][64]
     float* wt = bl + 4 * SM_W;                       // [64] time column of layer 0
     float* Ab0 = wt + SM_W;                          // [SM_ROWS][SM_LD]
     float* Ab1 = Ab0 + SM_ROWS * SM_LD;
+    float* red = Ab1 + SM_ROWS * SM_LD;              // AUG: [4][SM_ROWS] row sums
     __shared__ double redw[4];
     __shared__ double sh_total;
     __shared__ int sh_ok;
     SmState st = st_io[0];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     sm_stage_weights(A, d, Wl, bl, wt, tid);
-    const size_t n = (size_t)B * d;
+    const int D = AUG ? d + 1 : d;                   // row stride of the state, trajectory and stage buffers
+    const int c0 = AUG ? 1 : 0;                      // column of x[.., 0]
+    const size_t n = (size_t)B * D;
     const int col = wv * 16 + (lane & 15);
+    const bool lw = wv == 0 && (lane & 15) == 0;     // AUG: the lanes that store / count a row's l
     const float T = tspan[n_t - 1];
     SmTile x, k0, k1, k2, k3, k4, k5, k6, y;
+    SmTile xl, l0, l1, l2, l3, l4, l5, l6, yl, ep;   // AUG: l, its stage derivatives (-div), the probe tile
     if (RESIDENT) {
 #pragma unroll
         for (int i = 0; i < SM_V; ++i) {
             const int gr = blockIdx.x * SM_ROWS + sm_row(i, lane);
             const bool ok = gr < B && col < d;
-            x.v[i] = ok ? xbuf[(size_t)gr * d + col] : 0.f;
-            k0.v[i] = ok ? kbuf[(size_t)gr * d + col] : 0.f;
+            x.v[i] = ok ? xbuf[(size_t)gr * D + c0 + col] : 0.f;
+            k0.v[i] = ok ? kbuf[(size_t)gr * D + c0 + col] : 0.f;
+            if constexpr (AUG) {
+                xl.v[i] = gr < B ? xbuf[(size_t)gr * D] : 0.f;
+                l0.v[i] = gr < B ? kbuf[(size_t)gr * D] : 0.f;
+                ep.v[i] = (MODE == AUG_HUTCH && ok) ? eps[(size_t)gr * d + col] : 0.f;
+            }
         }
     }
     __syncthreads();                                  // weights staged
@@ -578,6 +765,7 @@ __global__ __launch_bounds__(256) void ode_small_dopri(SmArgs A, int B, int d, S
                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         float dt, dt_old; bool flag, lands;
         sm_prestep(st, tspan, n_t, dt, dt_old, flag, lands);
+        const float hdt = tsign * dt;                 // stage coefficient sign (reverse time: g = -f(-s, y))
         const float* x_in = xbuf + (size_t)st.par * n;
         const float* k1_in = kbuf + (size_t)st.par * n;
         float* x_out = xbuf + (size_t)(st.par ^ 1) * n;
@@ -589,27 +777,44 @@ __global__ __launch_bounds__(256) void ode_small_dopri(SmArgs A, int B, int d, S
                 for (int i = 0; i < SM_V; ++i) {
                     const int gr = row0 + sm_row(i, lane);
                     const bool ok = gr < B && col < d;
-                    x.v[i] = ok ? x_in[(size_t)gr * d + col] : 0.f;
-                    k0.v[i] = ok ? k1_in[(size_t)gr * d + col] : 0.f;
+                    x.v[i] = ok ? x_in[(size_t)gr * D + c0 + col] : 0.f;
+                    k0.v[i] = ok ? k1_in[(size_t)gr * D + c0 + col] : 0.f;
+                    if constexpr (AUG) {
+                        xl.v[i] = gr < B ? x_in[(size_t)gr * D] : 0.f;
+                        l0.v[i] = gr < B ? k1_in[(size_t)gr * D] : 0.f;
+                        ep.v[i] = (MODE == AUG_HUTCH && ok) ? eps[(size_t)gr * d + col] : 0.f;
+                    }
                 }
                 sm_lds_barrier();                     // previous tile done with the activation buffers
             }
             // stage S (a literal): y = x + dt * sum_{q<=S} a[S][q] k_q ; KOUT = f(t + c[S] dt, y)
-#define SM_STAGE(S, KOUT)                                                                            \
-            {                                                                                        \
-                _Pragma("unroll") for (int i = 0; i < SM_V; ++i) {                                   \
-                    float acc = (float)DP_A_dev(S, 0) * k0.v[i];                                     \
-                    if (S >= 1) acc = fmaf((float)DP_A_dev(S, 1), k1.v[i], acc);                     \
-                    if (S >= 2) acc = fmaf((float)DP_A_dev(S, 2), k2.v[i], acc);                     \
-                    if (S >= 3) acc = fmaf((float)DP_A_dev(S, 3), k3.v[i], acc);                     \
-                    if (S >= 4) acc = fmaf((float)DP_A_dev(S, 4), k4.v[i], acc);                     \
-                    if (S >= 5) acc = fmaf((float)DP_A_dev(S, 5), k5.v[i], acc);                     \
-                    y.v[i] = fmaf(dt, acc, x.v[i]);                                                  \
-                }                                                                                    \
-                KOUT = sm_field(y, st.t + DP_C_dev(S) * dt, A, d, Ab0, Ab1, Wl, bl, wt, wv, lane);   \
+#define SM_COMBINE(S, Y, X, K0, K1, K2, K3, K4, K5)                                                  \
+            _Pragma("unroll") for (int i = 0; i < SM_V; ++i) {                                       \
+                float acc = (float)DP_A_dev(S, 0) * K0.v[i];                                         \
+                if (S >= 1) acc = fmaf((float)DP_A_dev(S, 1), K1.v[i], acc);                         \
+                if (S >= 2) acc = fmaf((float)DP_A_dev(S, 2), K2.v[i], acc);                         \
+                if (S >= 3) acc = fmaf((float)DP_A_dev(S, 3), K3.v[i], acc);                         \
+                if (S >= 4) acc = fmaf((float)DP_A_dev(S, 4), K4.v[i], acc);                         \
+                if (S >= 5) acc = fmaf((float)DP_A_dev(S, 5), K5.v[i], acc);                         \
+                Y.v[i] = fmaf(hdt, acc, X.v[i]);                                                     \
             }
-            SM_STAGE(0, k1) SM_STAGE(1, k2) SM_STAGE(2, k3) SM_STAGE(3, k4) SM_STAGE(4, k5) SM_STAGE(5, k6)
+#define SM_STAGE(S, KOUT, LOUT)                                                                      \
+            {                                                                                        \
+                SM_COMBINE(S, y, x, k0, k1, k2, k3, k4, k5)                                          \
+                const float tf = tsign * (st.t + DP_C_dev(S) * dt);                                  \
+                if constexpr (AUG) {                                                                 \
+                    SM_COMBINE(S, yl, xl, l0, l1, l2, l3, l4, l5)                                    \
+                    SmTile dv;                                                                       \
+                    KOUT = sm_field_aug<MODE>(y, tf, A, d, Ab0, Ab1, Wl, bl, wt, ep, B - row0, red, wv, lane, dv); \
+                    _Pragma("unroll") for (int i = 0; i < SM_V; ++i) LOUT.v[i] = -dv.v[i];         \
+                } else {                                                                             \
+                    KOUT = sm_field(y, tf, A, d, Ab0, Ab1, Wl, bl, wt, wv, lane);                    \
+                }                                                                                    \
+            }
+            SM_STAGE(0, k1, l1) SM_STAGE(1, k2, l2) SM_STAGE(2, k3, l3) SM_STAGE(3, k4, l4) SM_STAGE(4, k5, l5)
+            SM_STAGE(5, k6, l6)
 #undef SM_STAGE
+#undef SM_COMBINE
             // y is x_new (the 5th-order solution), k6 = f(t + dt, x_new): error + outputs
 #pragma unroll
             for (int i = 0; i < SM_V; ++i) {
@@ -627,8 +832,27 @@ __global__ __launch_bounds__(256) void ode_small_dopri(SmArgs A, int B, int d, S
                     const float rr = e / sc;
                     esum += (double)rr * (double)rr;
                     if (!RESIDENT) {
-                        x_out[(size_t)gr * d + col] = y.v[i];
-                        k7_out[(size_t)gr * d + col] = k6.v[i];
+                        x_out[(size_t)gr * D + c0 + col] = y.v[i];
+                        k7_out[(size_t)gr * D + c0 + col] = k6.v[i];
+                    }
+                }
+                if constexpr (AUG) {
+                    if (gr < B && lw) {               // each row's l counts once in the norm
+                        float e = (float)DP_E_dev(0) * l0.v[i];
+                        e = fmaf((float)DP_E_dev(1), l1.v[i], e);
+                        e = fmaf((float)DP_E_dev(2), l2.v[i], e);
+                        e = fmaf((float)DP_E_dev(3), l3.v[i], e);
+                        e = fmaf((float)DP_E_dev(4), l4.v[i], e);
+                        e = fmaf((float)DP_E_dev(5), l5.v[i], e);
+                        e = fmaf((float)DP_E_dev(6), l6.v[i], e);
+                        e *= dt;
+                        const float sc = atol + rtol * fmaxf(fabsf(xl.v[i]), fabsf(yl.v[i]));
+                        const float rr = e / sc;
+                        esum += (double)rr * (double)rr;
+                        if (!RESIDENT) {
+                            x_out[(size_t)gr * D] = yl.v[i];
+                            k7_out[(size_t)gr * D] = l6.v[i];
+                        }
                     }
                 }
             }
@@ -648,18 +872,22 @@ __global__ __launch_bounds__(256) void ode_small_dopri(SmArgs A, int B, int d, S
 #pragma unroll
                     for (int i = 0; i < SM_V; ++i) {
                         const int gr = blockIdx.x * SM_ROWS + sm_row(i, lane);
-                        if (gr < B && col < d) dst[(size_t)gr * d + col] = y.v[i];
+                        if (gr < B && col < d) dst[(size_t)gr * D + c0 + col] = y.v[i];
+                        if constexpr (AUG) {
+                            if (gr < B && lw) dst[(size_t)gr * D] = yl.v[i];
+                        }
                     }
                 }
                 x = y; k0 = k6;                       // FSAL
+                if constexpr (AUG) { xl = yl; l0 = l6; }
             }
         } else if (accept && lands) {
             const float* xn = xbuf + (size_t)(st.par ^ 1) * n;
             float* dst = traj + (size_t)st.ckpt * n;
             for (int row0 = blockIdx.x * SM_ROWS; row0 < B; row0 += gridDim.x * SM_ROWS) {
                 const int rows = (B - row0 < SM_ROWS) ? B - row0 : SM_ROWS;
-                const size_t base = (size_t)row0 * d;
-                for (int e = tid; e < rows * d; e += 256) dst[base + e] = xn[base + e];   // own rows, written above
+                const size_t base = (size_t)row0 * D;
+                for (int e = tid; e < rows * D; e += 256) dst[base + e] = xn[base + e];   // own rows, written above
             }
         }
         SmState nx = st;
@@ -686,28 +914,34 @@ __global__ __launch_bounds__(256) void ode_small_dopri(SmArgs A, int B, int d, S
     if (blockIdx.x == 0 && tid == 0) { st.pad = err; st_io[1] = st; }
 }
 
+static size_t sm_lds_bytes(int mode) {
+    return sizeof(float) * (4 * SM_W * SM_LD + 4 * SM_W + SM_W + 2 * SM_ROWS * SM_LD + (mode ? 4 * SM_ROWS : 0));
+}
+
+template <int MODE>
 static int ode_dopri5_small(const float* const* W, const float* const* b, const int* dims, int B, int d,
-                            const float* t_span, int n_t, float atol, float rtol, float* traj,
-                            int* n_steps, int* nfe, float* xbuf, float* kbuf, float* tspan_dev,
+                            const float* t_span, int n_t, float tsign, const float* eps, float atol, float rtol,
+                            float* traj, int* n_steps, int* nfe, float* xbuf, float* kbuf, float* tspan_dev,
                             void* state_dev, char* sync_dev, float t0, float dt0, int evals0, hipStream_t s) {
     SmArgs A;
     for (int l = 0; l < 4; ++l) { A.W[l] = W[l]; A.b[l] = b[l]; }
     for (int l = 0; l < 5; ++l) A.dims[l] = dims[l];
-    const size_t lds = sizeof(float) * (4 * SM_W * SM_LD + 4 * SM_W + SM_W + 2 * SM_ROWS * SM_LD);
+    const size_t lds = sm_lds_bytes(MODE);
     static int raised_d[CFM_MAX_DEVICES], resident_d[CFM_MAX_DEVICES];
     static std::once_flag once_d[CFM_MAX_DEVICES];
     const int dvi = cfm_device_index();
     int& raised = raised_d[dvi]; int& resident = resident_d[dvi];
+    // (one set per MODE: the grid is sized from the occupancy of the instantiation that is launched)
     std::call_once(once_d[dvi], [lds, &raised, &resident] {
-        hipError_t e = hipFuncSetAttribute((const void*)ode_small_dopri<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-        hipError_t e2 = hipFuncSetAttribute((const void*)ode_small_dopri<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+        hipError_t e = hipFuncSetAttribute((const void*)ode_small_dopri<true, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+        hipError_t e2 = hipFuncSetAttribute((const void*)ode_small_dopri<false, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
         int ok = (e == hipSuccess && e2 == hipSuccess) ? 1 : -1;
         // workgroups that can be resident at once: the grid rendezvous needs grid <= this
         int dev = 0, cus = 0, pa = 0, pb = 0;
         if (ok > 0 && hipGetDevice(&dev) == hipSuccess &&
             hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&pa, (const void*)ode_small_dopri<true>, 256, lds) == hipSuccess &&
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&pb, (const void*)ode_small_dopri<false>, 256, lds) == hipSuccess &&
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&pa, (const void*)ode_small_dopri<true, MODE>, 256, lds) == hipSuccess &&
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&pb, (const void*)ode_small_dopri<false, MODE>, 256, lds) == hipSuccess &&
             cus > 0 && pa > 0 && pb > 0)
             resident = cus * (pa < pb ? pa : pb);
         else
@@ -734,14 +968,13 @@ static int ode_dopri5_small(const float* const* W, const float* const* b, const 
     // One persistent solve at a time per process: two of them launched from two streams could each get only part
     // of their workgroups resident and wait for the rest forever (the bounded wait would turn that into
     // CFM_ETIMEOUT after 4 s).  The call is synchronous anyway: the lock is held until the solve has finished.
-    static std::mutex persistent_mu;
-    std::lock_guard<std::mutex> persistent_lock(persistent_mu);
+    std::lock_guard<std::mutex> persistent_lock(g_persistent_mu);
     if (tiles <= grid)
-        hipLaunchKernelGGL(ode_small_dopri<true>, dim3(grid), dim3(256), lds, s, A, B, d, st, xbuf, kbuf, tspan_dev, n_t, atol,
-                           rtol, traj, partial, lines, 1000000);
+        hipLaunchKernelGGL((ode_small_dopri<true, MODE>), dim3(grid), dim3(256), lds, s, A, B, d, st, xbuf, kbuf, tspan_dev, n_t,
+                           atol, rtol, traj, partial, lines, 1000000, tsign, eps);
     else
-        hipLaunchKernelGGL(ode_small_dopri<false>, dim3(grid), dim3(256), lds, s, A, B, d, st, xbuf, kbuf, tspan_dev, n_t, atol,
-                           rtol, traj, partial, lines, 1000000);
+        hipLaunchKernelGGL((ode_small_dopri<false, MODE>), dim3(grid), dim3(256), lds, s, A, B, d, st, xbuf, kbuf, tspan_dev, n_t,
+                           atol, rtol, traj, partial, lines, 1000000, tsign, eps);
     rc = cfm_status();
     if (rc) return rc;
     SmState cur;
@@ -877,52 +1110,73 @@ extern "C" int cfm_sde_em_mlp_f32(const float* const* Wf, const float* const* bf
 }
 
 // Fixed-step Euler for the same small fields: x_{k+1} = x_k + dt_k f(t_k, x_k), every step of the
-// tile inside one launch (same arithmetic as ode_combine: fmaf(dt, 1.f * k, x)).
+// tile inside one launch (same arithmetic as ode_combine: fmaf(dt, 1.f * k, x)).  A decreasing t_span needs nothing
+// else: dt < 0 steps it, bit for bit the forward solve of -f(-s, x) on s = -t_span.  MODE != AUG_NONE: the
+// trajectory is [n_t, B, 1 + d] with column 0 = l, l_{k+1} = l_k + dt_k (-div f(t_k, x_k)); the x columns are bitwise
+// those of the plain solve.
+template <int MODE>
 __global__ __launch_bounds__(256) void ode_small_euler(SmArgs A, int B, int d, const float* __restrict__ tspan, int n_t,
-                                                    float* __restrict__ traj) {
+                                                    float* __restrict__ traj, const float* __restrict__ eps) {
+    constexpr bool AUG = MODE != AUG_NONE;
     extern __shared__ __attribute__((aligned(16))) float small_lds[];
     float* Wl = small_lds;
     float* bl = Wl + 4 * SM_W * SM_LD;
     float* wt = bl + 4 * SM_W;
     float* Ab0 = wt + SM_W;
     float* Ab1 = Ab0 + SM_ROWS * SM_LD;
+    float* red = Ab1 + SM_ROWS * SM_LD;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     sm_stage_weights(A, d, Wl, bl, wt, tid);
-    const size_t n = (size_t)B * d;
+    const int D = AUG ? d + 1 : d;
+    const int c0 = AUG ? 1 : 0;
+    const size_t n = (size_t)B * D;
     const int col = wv * 16 + (lane & 15);
+    const bool lw = wv == 0 && (lane & 15) == 0;
     for (int row0 = blockIdx.x * SM_ROWS; row0 < B; row0 += gridDim.x * SM_ROWS) {
-        SmTile x;
+        SmTile x, xl, ep;
 #pragma unroll
         for (int i = 0; i < SM_V; ++i) {
             const int gr = row0 + sm_row(i, lane);
-            x.v[i] = (gr < B && col < d) ? traj[(size_t)gr * d + col] : 0.f;
+            x.v[i] = (gr < B && col < d) ? traj[(size_t)gr * D + c0 + col] : 0.f;
+            if constexpr (AUG) {
+                xl.v[i] = gr < B ? traj[(size_t)gr * D] : 0.f;
+                ep.v[i] = (MODE == AUG_HUTCH && gr < B && col < d) ? eps[(size_t)gr * d + col] : 0.f;
+            }
         }
         __syncthreads();
         for (int k = 0; k + 1 < n_t; ++k) {
             const float t = tspan[k], dt = tspan[k + 1] - tspan[k];
-            const SmTile f = sm_field(x, t, A, d, Ab0, Ab1, Wl, bl, wt, wv, lane);
+            SmTile f, dv;
+            if constexpr (AUG) f = sm_field_aug<MODE>(x, t, A, d, Ab0, Ab1, Wl, bl, wt, ep, B - row0, red, wv, lane, dv);
+            else f = sm_field(x, t, A, d, Ab0, Ab1, Wl, bl, wt, wv, lane);
 #pragma unroll
             for (int i = 0; i < SM_V; ++i) {
                 x.v[i] = fmaf(dt, 1.f * f.v[i], x.v[i]);
                 const int gr = row0 + sm_row(i, lane);
-                if (gr < B && col < d) traj[(size_t)(k + 1) * n + (size_t)gr * d + col] = x.v[i];
+                if (gr < B && col < d) traj[(size_t)(k + 1) * n + (size_t)gr * D + c0 + col] = x.v[i];
+                if constexpr (AUG) {
+                    xl.v[i] = fmaf(dt, -dv.v[i], xl.v[i]);
+                    if (gr < B && lw) traj[(size_t)(k + 1) * n + (size_t)gr * D] = xl.v[i];
+                }
             }
         }
     }
 }
 
-static int ode_euler_small(const float* const* W, const float* const* b, const int* dims, int B, int d,
-                           const float* t_span, int n_t, float* traj, float* tspan_dev, hipStream_t s) {
+template <int MODE>
+static int ode_euler_small_t(const float* const* W, const float* const* b, const int* dims, int B, int d,
+                             const float* t_span, int n_t, float* traj, float* tspan_dev, const float* eps,
+                             hipStream_t s) {
     SmArgs A;
     for (int l = 0; l < 4; ++l) { A.W[l] = W[l]; A.b[l] = b[l]; }
     for (int l = 0; l < 5; ++l) A.dims[l] = dims[l];
-    const size_t lds = sizeof(float) * (4 * SM_W * SM_LD + 4 * SM_W + SM_W + 2 * SM_ROWS * SM_LD);
+    const size_t lds = sm_lds_bytes(MODE);
     static int raised_d[CFM_MAX_DEVICES];
     static std::once_flag once_d[CFM_MAX_DEVICES];
     const int dvi = cfm_device_index();
     int& raised = raised_d[dvi];
     std::call_once(once_d[dvi], [&raised] {
-        hipError_t e = hipFuncSetAttribute((const void*)ode_small_euler, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+        hipError_t e = hipFuncSetAttribute((const void*)ode_small_euler<MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
         (void)hipGetLastError();
         raised = (e == hipSuccess) ? 1 : -1;
     });
@@ -930,6 +1184,172 @@ static int ode_euler_small(const float* const* W, const float* const* b, const i
     int rc = cfm_hip(hipMemcpyAsync(tspan_dev, t_span, sizeof(float) * n_t, hipMemcpyHostToDevice, s));
     if (rc) return rc;
     const int tiles = (B + SM_ROWS - 1) / SM_ROWS;
-    hipLaunchKernelGGL(ode_small_euler, dim3(tiles < 4096 ? tiles : 4096), dim3(256), lds, s, A, B, d, tspan_dev, n_t, traj);
+    hipLaunchKernelGGL(ode_small_euler<MODE>, dim3(tiles < 4096 ? tiles : 4096), dim3(256), lds, s, A, B, d, tspan_dev, n_t,
+                       traj, eps);
     return cfm_status();
+}
+
+static int ode_euler_small(const float* const* W, const float* const* b, const int* dims, int B, int d,
+                           const float* t_span, int n_t, float* traj, float* tspan_dev, hipStream_t s) {
+    return ode_euler_small_t<AUG_NONE>(W, b, dims, B, d, t_span, n_t, traj, tspan_dev, nullptr, s);
+}
+
+// ---- CNF: one evaluation of [v, div] (the tile kernel of the augmented solves, once) --------------------------
+// x: rows of stride ldx (d values each); v: rows of stride ldv; div[row * lddiv] = dsign * div.
+template <int MODE>
+__global__ __launch_bounds__(256) void ode_small_div(SmArgs A, int B, int d, const float* __restrict__ x, int ldx,
+                                                  float t, const float* __restrict__ eps, float* __restrict__ v,
+                                                  int ldv, float* __restrict__ div, int lddiv, float dsign) {
+    extern __shared__ __attribute__((aligned(16))) float small_lds[];
+    float* Wl = small_lds;
+    float* bl = Wl + 4 * SM_W * SM_LD;
+    float* wt = bl + 4 * SM_W;
+    float* Ab0 = wt + SM_W;
+    float* Ab1 = Ab0 + SM_ROWS * SM_LD;
+    float* red = Ab1 + SM_ROWS * SM_LD;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    sm_stage_weights(A, d, Wl, bl, wt, tid);
+    const int col = wv * 16 + (lane & 15);
+    for (int row0 = blockIdx.x * SM_ROWS; row0 < B; row0 += gridDim.x * SM_ROWS) {
+        SmTile y, ep;
+#pragma unroll
+        for (int i = 0; i < SM_V; ++i) {
+            const int gr = row0 + sm_row(i, lane);
+            const bool ok = gr < B && col < d;
+            y.v[i] = ok ? x[(size_t)gr * ldx + col] : 0.f;
+            ep.v[i] = (MODE == AUG_HUTCH && ok) ? eps[(size_t)gr * d + col] : 0.f;
+        }
+        __syncthreads();
+        SmTile dv;
+        const SmTile f = sm_field_aug<MODE>(y, t, A, d, Ab0, Ab1, Wl, bl, wt, ep, B - row0, red, wv, lane, dv);
+#pragma unroll
+        for (int i = 0; i < SM_V; ++i) {
+            const int gr = row0 + sm_row(i, lane);
+            if (gr < B && col < d) v[(size_t)gr * ldv + col] = f.v[i];
+            if (gr < B && wv == 0 && (lane & 15) == 0) div[(size_t)gr * lddiv] = dsign * dv.v[i];
+        }
+    }
+}
+
+template <int MODE>
+static int cnf_eval(const SmArgs& A, int B, int d, const float* x, int ldx, float t, const float* eps, float* v, int ldv,
+                    float* div, int lddiv, float dsign, hipStream_t s) {
+    static int raised_d[CFM_MAX_DEVICES];
+    static std::once_flag once_d[CFM_MAX_DEVICES];
+    const int dvi = cfm_device_index();
+    int& raised = raised_d[dvi];
+    std::call_once(once_d[dvi], [&raised] {
+        hipError_t e = hipFuncSetAttribute((const void*)ode_small_div<MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+        (void)hipGetLastError();
+        raised = (e == hipSuccess) ? 1 : -1;
+    });
+    if (raised < 0) return CFM_EINVAL;
+    const int tiles = (B + SM_ROWS - 1) / SM_ROWS;
+    hipLaunchKernelGGL(ode_small_div<MODE>, dim3(tiles < 4096 ? tiles : 4096), dim3(256), sm_lds_bytes(MODE), s, A, B, d, x,
+                       ldx, t, eps, v, ldv, div, lddiv, dsign);
+    return cfm_status();
+}
+
+// the envelope of the CNF entries: the small-field kernels (4 layers, widths <= 64, [x, t] -> dx), fused path on,
+// mode 0 (exact trace) or 1 (Hutchinson, eps given)
+static int cnf_check(const float* const* W, const float* const* b, const int* dims, int n_layers, int B, int mode,
+                     const float* eps, int* d_out, SmArgs* A) {
+    int d;
+    if (!W || !b || B <= 0 || (mode != 0 && mode != 1) || (mode == 1 && !eps)) return CFM_EINVAL;
+    if (n_layers != 4 || check_mlp(dims, n_layers, &d)) return CFM_EINVAL;
+    for (int l = 1; l <= 3; ++l) if (dims[l] < 1 || dims[l] > SM_WMAX) return CFM_EINVAL;
+    if (d < 1 || d + 1 > SM_WMAX || !ode_small_enabled()) return CFM_EINVAL;
+    for (int l = 0; l < 4; ++l) { A->W[l] = W[l]; A->b[l] = b[l]; }
+    for (int l = 0; l < 5; ++l) A->dims[l] = dims[l];
+    *d_out = d;
+    return 0;
+}
+
+extern "C" int cfm_mlp_divergence_f32(const float* const* W, const float* const* b, const int* dims, int n_layers,
+                                      const float* x, int B, float t, int mode, const float* eps, float* v, float* div,
+                                      void* ws, void* stream) {
+    int d; SmArgs A;
+    (void)ws;
+    if (!x || !v || !div) return CFM_EINVAL;
+    int rc = cnf_check(W, b, dims, n_layers, B, mode, eps, &d, &A);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    return mode == 0 ? cnf_eval<AUG_EXACT>(A, B, d, x, d, t, eps, v, d, div, 1, 1.f, s)
+                     : cnf_eval<AUG_HUTCH>(A, B, d, x, d, t, eps, v, d, div, 1, 1.f, s);
+}
+
+extern "C" int cfm_ode_euler_cnf_mlp_f32(const float* const* W, const float* const* b, const int* dims, int n_layers,
+                                         const float* x0, int B, const float* t_span, int n_t, int mode,
+                                         const float* eps, float* traj, int* nfe, void* ws, void* stream) {
+    int d; SmArgs A;
+    if (!x0 || !t_span || !traj || !ws || n_t < 1) return CFM_EINVAL;
+    int rc = cnf_check(W, b, dims, n_layers, B, mode, eps, &d, &A);
+    if (rc) return rc;
+    for (int k = 0; k + 1 < n_t; ++k)                  // strictly monotone, either way
+        if (!(t_span[k + 1] > t_span[k]) && !(t_span[k + 1] < t_span[k])) return CFM_EINVAL;
+    if (n_t > 2) {
+        const int up = t_span[1] > t_span[0];
+        for (int k = 1; k + 1 < n_t; ++k) if ((t_span[k + 1] > t_span[k]) != up) return CFM_EINVAL;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const int width = maxwidth(dims, n_layers);
+    OdeWs w = ode_carve(ws, B, width, d + 1);          // workspace of CFM_OP_ODE at d + 1
+    const size_t n = (size_t)B * (d + 1);
+    if ((size_t)n_t > 3 * n) return CFM_EINVAL;        // t_span copy: w.x .. w.xt
+    rc = cfm_hip(hipMemcpyAsync(traj, x0, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (rc) return rc;
+    if (nfe) *nfe = n_t - 1;
+    if (n_t < 2) return 0;
+    return mode == 0 ? ode_euler_small_t<AUG_EXACT>(W, b, dims, B, d, t_span, n_t, traj, w.x, eps, s)
+                     : ode_euler_small_t<AUG_HUTCH>(W, b, dims, B, d, t_span, n_t, traj, w.x, eps, s);
+}
+
+template <int MODE>
+static int cnf_dopri5(const SmArgs& A, const float* const* W, const float* const* b, const int* dims, int d,
+                      const float* x0, int B, const float* ts, int n_t, float tsign, const float* eps, float atol,
+                      float rtol, float* traj, int* n_steps, int* nfe, void* ws, hipStream_t s) {
+    const int D = d + 1;
+    OdeWs w = ode_carve(ws, B, maxwidth(dims, 4), D);  // workspace of CFM_OP_ODE at d + 1: every buffer is [B, 1 + d]
+    const size_t n = (size_t)B * D;
+    if (n < (size_t)n_t) return CFM_EINVAL;            // t_span copy: w.xt
+    int evals = 0;
+    // augmented field in solver time: k = [-div, v] at tsign * t (the sign of g = -f(-s, .) rides on the coefficients)
+    auto f = [&](float t, const float* xin, float* kout) -> int {
+        ++evals;
+        return cnf_eval<MODE>(A, B, d, xin + 1, D, tsign * t, eps, kout + 1, D, kout, D, -1.f, s);
+    };
+    int rc = cfm_hip(hipMemcpyAsync(w.x, x0, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (rc) return rc;
+    rc = cfm_hip(hipMemcpyAsync(traj, x0, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (rc) return rc;
+    const float t = ts[0];
+    rc = f(t, w.x, w.k[0]);
+    if (rc) return rc;
+    float dt;
+    rc = ode_init_step(f, n, t, tsign, atol, rtol, w, s, &dt);   // d0, d1, d2 over all B (1 + d) elements
+    if (rc) return rc;
+    return ode_dopri5_small<MODE>(W, b, dims, B, d, ts, n_t, tsign, eps, atol, rtol, traj, n_steps, nfe, w.x, w.k[0], w.xt,
+                                  (void*)(w.red + 16), w.sync, t, dt, evals, s);
+}
+
+extern "C" int cfm_ode_dopri5_cnf_mlp_f32(const float* const* W, const float* const* b, const int* dims, int n_layers,
+                                          const float* x0, int B, const float* t_span, int n_t, int mode,
+                                          const float* eps, float atol, float rtol, float* traj, int* n_steps,
+                                          int* nfe, void* ws, void* stream) {
+    int d; SmArgs A;
+    if (!x0 || !t_span || !traj || !ws || n_t < 2) return CFM_EINVAL;
+    int rc = cnf_check(W, b, dims, n_layers, B, mode, eps, &d, &A);
+    if (rc) return rc;
+    float* ts = (float*)malloc(sizeof(float) * (size_t)n_t);
+    if (!ts) return CFM_EINVAL;
+    const float tsign = ode_direction(t_span, n_t, ts);
+    if (tsign == 0.f) rc = CFM_EINVAL;
+    else if (mode == 0)
+        rc = cnf_dopri5<AUG_EXACT>(A, W, b, dims, d, x0, B, ts, n_t, tsign, eps, atol, rtol, traj, n_steps, nfe, ws,
+                                   (hipStream_t)stream);
+    else
+        rc = cnf_dopri5<AUG_HUTCH>(A, W, b, dims, d, x0, B, ts, n_t, tsign, eps, atol, rtol, traj, n_steps, nfe, ws,
+                                   (hipStream_t)stream);
+    free(ts);
+    return rc;
 }

@@ -4,9 +4,14 @@
 examples/images/cifar10/utils_cifar.py:63-68).
 
 When the vector field is ``torch_wrapper(MLP(time_varying=True))`` the whole solve runs in
-the HIP drivers (``cfm_ode_euler_mlp_f32`` / ``cfm_ode_dopri5_mlp_f32``).  Any other
-vector field (e.g. a UNet) is stepped by the same algorithm at the tensor level — host
-control flow only, the field itself runs wherever the user's module runs.
+the HIP drivers (``cfm_ode_euler_mlp_f32`` / ``cfm_ode_dopri5_mlp_f32``); ``CNF(MLP)`` (cnf.py) of
+the small-kernel envelope on fp32 ``[B, 1 + d]`` states runs in ``cfm_ode_*_cnf_mlp_f32``.  Any
+other vector field (e.g. a UNet) is stepped by the same algorithm at the tensor level — host
+control flow only, the field itself runs wherever the user's module runs.  ``last_path`` says
+which of the two ran ("hip" / "generic").
+
+``t_span`` is strictly monotone.  A decreasing one integrates backward in time as torchdyn does
+(SURVEY.md A.4): ``g(s, x) = -f(-s, x)`` on ``s = -t_span``.
 """
 import ctypes
 
@@ -35,6 +40,20 @@ def _hairer_norm(x):
     return x.abs().pow(2).mean().sqrt()
 
 
+def _check_t_span(ts):
+    """Strictly monotone (either way); returns +1 / -1."""
+    if ts.dim() != 1 or ts.numel() < 1:
+        raise ValueError("t_span must be a 1-D grid")
+    if ts.numel() < 2:
+        return 1
+    dts = ts[1:] - ts[:-1]
+    if bool((dts > 0).all()):
+        return 1
+    if bool((dts < 0).all()):
+        return -1
+    raise ValueError("t_span must be strictly increasing or strictly decreasing")
+
+
 class NeuralODE(torch.nn.Module):
     def __init__(self, vector_field, solver="dopri5", order=1, atol=1e-3, rtol=1e-3,
                  sensitivity="autograd", return_t_eval=True, **kwargs):
@@ -47,6 +66,7 @@ class NeuralODE(torch.nn.Module):
         self.return_t_eval = return_t_eval
         self.nfe = 0
         self.n_steps = 0
+        self.last_path = None     # "hip" / "generic": which path the last trajectory() took
 
     # ---- dispatch ----
     def _hip_mlp(self):
@@ -60,10 +80,70 @@ class NeuralODE(torch.nn.Module):
 
     @torch.no_grad()
     def trajectory(self, x, t_span):
+        _check_t_span(torch.as_tensor(t_span, dtype=torch.float32).cpu())
+        from .cnf import CNF
+        if isinstance(self.vf, CNF):
+            return self._trajectory_cnf(self.vf, x, t_span)
         m = self._hip_mlp()
         if m is not None and x.dim() == 2:
+            self.last_path = "hip"
             return self._trajectory_hip(m, x, t_span)
+        self.last_path = "generic"
         return self._trajectory_generic(x, t_span)
+
+    def _trajectory_cnf(self, cnf, x, t_span):
+        # one probe for the whole solve (cnf.noise, else a fresh draw exposed as cnf.last_noise)
+        eps = None
+        if cnf.estimator != "exact":
+            eps = cnf.checked_noise(x[:, 1:]) if cnf.noise is not None else cnf.draw_noise(x[:, 1:])
+        cnf._solve_noise = eps
+        try:
+            if x.dim() == 2 and x.dtype == torch.float32 and torch.cuda.is_available():
+                m = cnf.hip_mlp(x.shape[1] - 1)
+                if m is not None and all(p.dtype == torch.float32 for p in m.parameters()):
+                    traj = self._trajectory_cnf_hip(m, x, t_span, eps)
+                    if traj is not None:
+                        self.last_path = "hip"
+                        return traj
+            self.last_path = "generic"
+            return self._trajectory_generic(x, t_span)
+        finally:
+            cnf._solve_noise = None
+
+    def _trajectory_cnf_hip(self, m, x, t_span, eps):
+        """Augmented solve in cfm_ode_{euler,dopri5}_cnf_mlp_f32; None when the library declines it (CFM_EINVAL:
+        the fused small-field path is switched off) so the caller steps it generically."""
+        lib = _lib.load()
+        dev = _lib.require_gpu()
+        Wp, bp, dims, keep = m.hip_params(dev)
+        xd = _lib.to_dev_f32(x, dev)
+        B, D = xd.shape
+        ts = np.ascontiguousarray(torch.as_tensor(t_span, dtype=torch.float32).cpu().numpy())
+        n_t = ts.shape[0]
+        traj = torch.empty((n_t, B, D), dtype=torch.float32, device=dev)
+        ws = _lib.workspace(_lib.OP_ODE, B, max(dims[1:4]), D, dev)
+        mode = 0 if eps is None else 1
+        if eps is not None and tuple(eps.shape) != (B, D - 1):
+            raise ValueError(f"probe of shape {tuple(eps.shape)} for a state of {B} rows and {D - 1} columns")
+        ed = _lib.to_dev_f32(eps, dev) if eps is not None else None
+        nfe = ctypes.c_int(0)
+        steps = ctypes.c_int(0)
+        tsp = ts.ctypes.data_as(ctypes.c_void_p)
+        if self.solver == "euler":
+            rc = lib.cfm_ode_euler_cnf_mlp_f32(Wp, bp, dims, 4, ptr(xd), B, tsp, n_t, mode, ptr(ed), ptr(traj),
+                                               ctypes.byref(nfe), ptr(ws), stream_ptr())
+            steps.value = n_t - 1
+            what = "cfm_ode_euler_cnf_mlp_f32"
+        else:
+            rc = lib.cfm_ode_dopri5_cnf_mlp_f32(Wp, bp, dims, 4, ptr(xd), B, tsp, n_t, mode, ptr(ed), self.atol,
+                                                self.rtol, ptr(traj), ctypes.byref(steps), ctypes.byref(nfe),
+                                                ptr(ws), stream_ptr())
+            what = "cfm_ode_dopri5_cnf_mlp_f32"
+        if rc == -1:
+            return None
+        check(rc, what)
+        self.nfe, self.n_steps = nfe.value, steps.value
+        return traj.to(x.device)
 
     def forward(self, x, t_span):
         sol = self.trajectory(x, t_span)
@@ -104,9 +184,16 @@ class NeuralODE(torch.nn.Module):
         ts = torch.as_tensor(t_span, dtype=torch.float32)
         sol = [x]
         self.nfe = 0
+        # a decreasing grid: dopri5 solves g(s, y) = -f(-s, y) on s = -t_span (Euler steps dt < 0 as it is: the
+        # same numbers in fp32)
+        sign = -1.0 if (self.solver == "dopri5" and len(ts) > 1 and float(ts[1]) < float(ts[0])) else 1.0
+        if sign < 0:
+            ts = -ts
 
         def ev(t, y):
             self.nfe += 1
+            if sign < 0:
+                return -f(torch.as_tensor(-np.float32(t), dtype=torch.float32, device=y.device), y)
             return f(torch.as_tensor(t, dtype=torch.float32, device=y.device), y)
 
         if self.solver == "euler":
@@ -121,10 +208,10 @@ class NeuralODE(torch.nn.Module):
         t, T = f32(ts[0]), f32(ts[-1])
         k1 = ev(t, x)
         scale = atol + x.abs() * rtol
-        d0, d1 = f32(_hairer_norm(x / scale)), f32(_hairer_norm(k1 / scale))
+        d0, d1 = f32(float(_hairer_norm(x / scale))), f32(float(_hairer_norm(k1 / scale)))
         h0 = f32(1e-6) if (d0 < 1e-5 or d1 < 1e-5) else f32(0.01) * d0 / d1
         f1 = ev(t + h0, x + h0 * k1)
-        d2 = f32(_hairer_norm((f1 - k1) / scale)) / h0
+        d2 = f32(float(_hairer_norm((f1 - k1) / scale))) / h0
         if d1 <= 1e-15 and d2 <= 1e-15:
             h1 = max(f32(1e-6), h0 * f32(1e-3))
         else:
@@ -144,7 +231,7 @@ class NeuralODE(torch.nn.Module):
                 ks.append(ev(t + f32(_DP_C[s]) * dt, y))
             x_new = y
             err = float(dt) * sum(float(bs - ba) * k for bs, ba, k in zip(_DP_BSOL, _DP_BALT, ks))
-            ratio = f32(_hairer_norm(err / (atol + rtol * torch.max(x.abs(), x_new.abs()))))
+            ratio = f32(float(_hairer_norm(err / (atol + rtol * torch.max(x.abs(), x_new.abs())))))
             steps += 1
             if ratio <= 1:
                 if lands:

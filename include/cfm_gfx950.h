@@ -383,7 +383,8 @@ int cfm_rbf_mix_sum_f32(const float* D, size_t n, const float* gammas, int n_gam
  * Replaces NeuralODE(torch_wrapper(model), solver=...).trajectory(x, t_span)
  *   call sites: examples/2D_tutorials/Flow_matching_tutorial.ipynb cells 11/16,
  *   examples/images/cifar10/utils_cifar.py:63-68.
- * t_span: host float[n_t].  traj: device [n_t,B,d].
+ * t_span: host float[n_t], strictly monotone (a decreasing grid integrates -f(-s, x) on s = -t_span, as
+ * torchdyn does: runner/src/models/components/solver.py:184-216).  traj: device [n_t,B,d].
  * euler: fixed steps on t_span.  dopri5: adaptive Dormand-Prince 5(4), one
  * global RMS error norm over the batch, every t_span point is a step end.
  * n_steps/nfe: host ints (accepted+rejected steps, function evaluations). */
@@ -394,6 +395,26 @@ int cfm_ode_dopri5_mlp_f32(const float* const* W, const float* const* b, const i
                            int n_layers, const float* x0, int B, const float* t_span,
                            int n_t, float atol, float rtol, float* traj, int* n_steps,
                            int* nfe, void* ws, void* stream);
+
+/* K12 — continuous normalising flow of an MLP field v = MLP([x, t]) (4 linear layers, widths <= 64, dims[0] = d + 1).
+ * mode 0: div = tr(dv/dx) (exact); mode 1: div = eps^T (dv/dx) eps (Hutchinson; eps device [B,d], fixed for a solve).
+ * Replaces CNF + autograd_trace of examples/2D_tutorials/model-comparison-plotting.ipynb cells 2, 4 and 7, and
+ * cnf_wrapper (exact / hutch_*) of examples/2D_tutorials/Maximum_likelihood_CNF_tutorial.ipynb cells 3 and 4.
+ * Return CFM_EINVAL outside that envelope or with the fused small-field path disabled (cfm_ode_set_fused(0)).
+ * One evaluation: x, v device [B,d], div device [B]; ws may be NULL. */
+int cfm_mlp_divergence_f32(const float* const* W, const float* const* b, const int* dims, int n_layers,
+                           const float* x, int B, float t, int mode, const float* eps,
+                           float* v, float* div, void* ws, void* stream);
+/* Augmented solves of d[l, x]/dt = [-div, v]: x0 device [B,1+d], traj device [n_t,B,1+d], column 0 = l.
+ * t_span: host float[n_t], strictly monotone either way.  ws: cfm_workspace_bytes(CFM_OP_ODE, B, max width, d + 1).
+ * dopri5: the error and init-step norms run over all B (1 + d) elements. */
+int cfm_ode_euler_cnf_mlp_f32(const float* const* W, const float* const* b, const int* dims, int n_layers,
+                              const float* x0, int B, const float* t_span, int n_t, int mode,
+                              const float* eps, float* traj, int* nfe, void* ws, void* stream);
+int cfm_ode_dopri5_cnf_mlp_f32(const float* const* W, const float* const* b, const int* dims, int n_layers,
+                               const float* x0, int B, const float* t_span, int n_t, int mode,
+                               const float* eps, float atol, float rtol, float* traj, int* n_steps,
+                               int* nfe, void* ws, void* stream);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop
