@@ -109,10 +109,23 @@ struct Glds64 {
     }
     // The MFMAs are INLINE ASSEMBLY with the accumulator tied to its own VGPRs ("+v"): with the builtin the register
     // allocator un-ties the destination of a step's last MFMAs and rotates the accumulators back at the loop head — 24
-    // v_accvgpr read / mov / write per K step, each waiting for the matrix pipe to drain (tools/isa_report.py).  What the
-    // compiler's hazard recogniser no longer sees is covered by hand: an accumulator comes round again after three other
-    // 8-pass MFMAs (no wait states needed), fragments come from ds_reads (s_waitcnt is placed on the asm's operands as on any
-    // instruction), and run() ends with s_nop 15 x 2 in front of the first VALU read of an accumulator.
+    // v_accvgpr read / mov / write per K step, each waiting for the matrix pipe to drain (tools/isa_report.py).  The
+    // compiler pads no hazard of an instruction inside an asm string, so what its hazard recogniser no longer sees is
+    // covered by hand and CHECKED on the compiled code by tools/isa_hazards.py (tests/test_isa_hazards.py, rule H1):
+    //   * MFMA -> the next MFMA on the same accumulator: an accumulate chain (D taken whole as C), no wait states;
+    //   * fragments come from ds_reads: s_waitcnt is placed on the asm's operands as on any instruction;
+    //   * MFMA -> anything else that touches the accumulator (the epilogue's reads, but also the v_mov copies the
+    //     register allocator makes wherever accumulators reach a point over two paths: the loop exit, the has_tail
+    //     split, the merge in front of the epilogue): acc_guard(), a nop statement TIED to the four accumulators ("+v":
+    //     no consumer of them, compiler-made or not, is scheduled above it), on every path right behind the last MFMA
+    //     in front of a branch or a merge.  A nop that is not tied (the `s_nop 15 x 2` that stood at the end of run())
+    //     protects nothing: the copies were scheduled 3 to 7 states behind the MFMAs, in front of it.
+    // The compiler leaves 10 states behind its own 16x16x4 f32 MFMAs (8 passes + 2; measured over every builtin site by
+    // the checker); the guard takes 12, the figure the kernel-programming literature gives for an 8-pass MFMA.  It runs
+    // three times per TILE (not per K step) and overlaps with the matrix pipe draining.
+    __device__ __forceinline__ void acc_guard() {
+        asm volatile("s_nop 11" : "+v"(acc[0][0]), "+v"(acc[0][1]), "+v"(acc[1][0]), "+v"(acc[1][1]));
+    }
     __device__ __forceinline__ void mfma16(const Frag& t) {
 #define G6_MFMA(ACC_, A_, B_) asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+v"(ACC_) : "v"(A_), "v"(B_))
 #define G6_MM(C_) \
@@ -163,10 +176,12 @@ struct Glds64 {
             __builtin_amdgcn_sched_barrier(0);
             mfma16(t1);
         }
+        acc_guard();                                               // loop exit: paths merge (and split again) here
         if (nfull > 0) {                                           // the last full step (t0 holds its first group)
             const Frag t1 = read_frag(lds, st, 1);
             __builtin_amdgcn_sched_barrier(0);
             mfma16(t0);
+            acc_guard();                                           // in front of the has_tail split
             if (has_tail) {                                        // (uniform) 16 more k: one group of the next stage
                 st = (st + 1 == NST) ? 0 : st + 1;
                 sf = (sf + 1 == NST) ? 0 : sf + 1;
@@ -175,13 +190,16 @@ struct Glds64 {
                 __builtin_amdgcn_sched_barrier(0);
                 mfma16(t1);
                 mfma16(t0);
-            } else {
+                acc_guard();                                       // end of every path: MFMA -> the merge copies and
+            } else {                                               // the epilogue's reads
                 mfma16(t1);
+                acc_guard();
             }
         } else {
             mfma16(t0);                                            // K = 16: the tail is the only step
+            acc_guard();
         }
 #undef G6_STEP_HEAD
-        asm volatile("s_waitcnt vmcnt(0)\n\ts_nop 15\n\ts_nop 15" ::: "memory");    // no DMA may outlive the workgroup's LDS allocation; MFMA -> VALU read
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // no DMA may outlive the workgroup's LDS allocation
     }
 };
