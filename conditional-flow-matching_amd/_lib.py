@@ -86,7 +86,15 @@ SIGNATURES = {
     "cfm_ode_euler_cnf_mlp_f32": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "cfm_ode_dopri5_cnf_mlp_f32": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _f, _f, _vp, _vp, _vp,
                                        _vp, _vp]),
+    "cfm_ode_adaptive_mlp_f32": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp]),
+    "cfm_ode_fixed_mlp_f32": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "cfm_ode_adaptive_cnf_mlp_f32": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _f, _f, _vp, _vp, _vp,
+                                         _vp, _vp]),
+    "cfm_ode_fixed_cnf_mlp_f32": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
 }
+# solver selectors of the cfm_ode_adaptive_* / cfm_ode_fixed_* entries (include/cfm_gfx950.h)
+ODE_TABLEAU = {"dopri5": 0, "tsit5": 1}
+ODE_SCHEME = {"euler": 0, "midpoint": 1, "rk4": 2}
 # helpers that are not part of the documented ABI (tuning / replace=False bookkeeping)
 EXTRA_SIGNATURES = {
     "cfm_assign_set_params": (None, [_d, _d, _d, _d, _i, _i, _i]),

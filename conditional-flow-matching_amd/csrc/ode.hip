@@ -6,7 +6,9 @@
 // line for line, by oracle/cfm_oracle.py::dopri5_trajectory — "torchdyn-style
 // dopri5", parity unpinned by the reference itself).
 //
-//  euler  : fixed steps on t_span, fully asynchronous (no host sync).
+//  euler, midpoint, rk4 : fixed steps on t_span (explicit tableaus of 1, 2 and 4 stages; rk4 is the 3/8 rule,
+//           "torchdyn-style rk4", unpinned like dopri5), fully asynchronous (no host sync).
+//  tsit5  : Tsitouras 5(4): the same driver as dopri5 with another tableau (7 stages, FSAL, last row of a = b).
 //  dopri5 : Dormand-Prince 5(4), FSAL, one global RMS error norm over the batch
 //           (hairer_norm over all B*d elements), every t_span point is a step
 //           end.  Stage combinations and the scaled error norm are fused
@@ -80,6 +82,26 @@ __global__ __launch_bounds__(256) void ode_sqnorm(size_t n, const float* __restr
     if (threadIdx.x == 0) atomicAdd(out, red[0] + red[1] + red[2] + red[3]);
 }
 
+// adapt_step(dt, ratio, safety=0.9, min_factor=0.2, max_factor=10, order=5): the factor of the next step size
+__device__ __forceinline__ float ode_step_factor(float ratio) {
+    float factor;
+    if (ratio == 0.f) factor = 10.f;
+    else {
+        const float minf = ratio < 1.f ? 1.f : 0.2f;
+        factor = fminf(10.f, fmaxf(0.9f / powf(ratio, 1.f / 5.f), minf));
+    }
+    return factor;
+}
+
+// The controller's scalars of the layer-per-kernel driver, taken where the fused kernel takes them (one lane): the
+// device's powf and the host's differ in the last bit on some inputs, and a step size must not depend on the path.
+// out[0] = error ratio (RMS over n elements), out[1] = step factor.
+__global__ void ode_controller(const double* __restrict__ e2, double n, float* __restrict__ out) {
+    const float ratio = (float)sqrt(e2[0] / n);
+    out[0] = ratio;
+    out[1] = ode_step_factor(ratio);
+}
+
 static inline int ode_blocks(size_t n) {
     size_t b = (n + 255) / 256;
     return (int)(b < 2048 ? (b ? b : 1) : 2048);
@@ -134,39 +156,151 @@ static int ode_small_enabled() {
     if (g_ode_fused < 0) { const char* e = getenv("CFM_ODE_FUSED"); g_ode_fused = (e && e[0] == '0') ? 0 : 1; }
     return g_ode_fused;
 }
-static int ode_euler_small(const float* const* W, const float* const* b, const int* dims, int B, int d,
+// ---- tableaus ----------------------------------------------------------------------------------------------------
+// Entries as compile-time constants: in the kernels every index is a constant after unrolling, the host drivers
+// read the same tables.  Every use casts the fp64 constant: (float)rk_a<TAB>(s, q), (float)rk_e<TAB>(q).
+// Adaptive pairs (7 stages, FSAL, row 6 of a = b, so stage 6's y is x_new; e = b - b_alt):
+//   CFM_ODE_DOPRI5: Dormand-Prince 5(4);  CFM_ODE_TSIT5: Tsitouras 5(4) (Tsitouras 2011, the
+//   coefficients torchdyn's default solver carries).
+template <int TAB>
+__host__ __device__ __forceinline__ double rk_a(int s, int q) {
+    if constexpr (TAB == CFM_ODE_TSIT5) {
+        constexpr double A[6][6] = {
+            {0.161, 0, 0, 0, 0, 0},
+            {-0.008480655492356989, 0.335480655492357, 0, 0, 0, 0},
+            {2.8971530571054935, -6.359448489975075, 4.3622954328695815, 0, 0, 0},
+            {5.325864828439257, -11.748883564062828, 7.4955393428898365, -0.09249506636175525, 0, 0},
+            {5.86145544294642, -12.92096931784711, 8.159367898576159, -0.071584973281401, -0.028269050394068383, 0},
+            {0.09646076681806523, 0.01, 0.4798896504144996, 1.379008574103742, -3.290069515436081, 2.324710524099774}};
+        return A[s][q];
+    } else {
+        constexpr double A[6][6] = {
+            {1.0 / 5, 0, 0, 0, 0, 0},
+            {3.0 / 40, 9.0 / 40, 0, 0, 0, 0},
+            {44.0 / 45, -56.0 / 15, 32.0 / 9, 0, 0, 0},
+            {19372.0 / 6561, -25360.0 / 2187, 64448.0 / 6561, -212.0 / 729, 0, 0},
+            {9017.0 / 3168, -355.0 / 33, 46732.0 / 5247, 49.0 / 176, -5103.0 / 18656, 0},
+            {35.0 / 384, 0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784, 11.0 / 84}};
+        return A[s][q];
+    }
+}
+template <int TAB>
+__host__ __device__ __forceinline__ float rk_c(int s) {
+    if constexpr (TAB == CFM_ODE_TSIT5) {
+        constexpr float C[6] = {(float)0.161, (float)0.327, (float)0.9, (float)0.9800255409045097, 1.f, 1.f};
+        return C[s];
+    } else {
+        constexpr float C[6] = {1.f / 5, 3.f / 10, 4.f / 5, 8.f / 9, 1.f, 1.f};
+        return C[s];
+    }
+}
+template <int TAB>
+__host__ __device__ __forceinline__ double rk_e(int q) {
+    if constexpr (TAB == CFM_ODE_TSIT5) {
+        constexpr double E[7] = {0.001780011052226, 0.000816434459657, -0.007880878010262, 0.144711007173263,
+                                 -0.582357165452555, 0.458082105929187, -1.0 / 66};
+        return E[q];
+    } else {
+        constexpr double BS[7] = {35.0 / 384, 0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784, 11.0 / 84, 0};
+        constexpr double BA[7] = {1951.0 / 21600, 0, 22642.0 / 50085, 451.0 / 720, -12231.0 / 42400, 649.0 / 6300, 1.0 / 60};
+        return BS[q] - BA[q];
+    }
+}
+static double rk_a_host(int tab, int s, int q) { return tab == CFM_ODE_TSIT5 ? rk_a<CFM_ODE_TSIT5>(s, q) : rk_a<CFM_ODE_DOPRI5>(s, q); }
+static float rk_c_host(int tab, int s) { return tab == CFM_ODE_TSIT5 ? rk_c<CFM_ODE_TSIT5>(s) : rk_c<CFM_ODE_DOPRI5>(s); }
+static double rk_e_host(int tab, int q) { return tab == CFM_ODE_TSIT5 ? rk_e<CFM_ODE_TSIT5>(q) : rk_e<CFM_ODE_DOPRI5>(q); }
+static int rk_adaptive_known(int tab) { return tab == CFM_ODE_DOPRI5 || tab == CFM_ODE_TSIT5; }
+
+// Fixed-step schemes: stage s >= 1 is y = x + dt * sum_{q<s} a[s-1][q] k_q at t + c[s-1] dt; x_new = x + dt * sum b k.
+//   CFM_ODE_EULER;  CFM_ODE_MIDPOINT: x + dt f(t + dt/2, x + dt/2 k1);  CFM_ODE_RK4: the 3/8 rule.
+template <int SCHEME>
+__host__ __device__ __forceinline__ constexpr int fx_stages() { return SCHEME == CFM_ODE_RK4 ? 4 : SCHEME == CFM_ODE_MIDPOINT ? 2 : 1; }
+template <int SCHEME>
+__host__ __device__ __forceinline__ double fx_a(int s, int q) {
+    if constexpr (SCHEME == CFM_ODE_RK4) {
+        constexpr double A[3][3] = {{1.0 / 3, 0, 0}, {-1.0 / 3, 1, 0}, {1, -1, 1}};
+        return A[s][q];
+    } else {
+        constexpr double A[3][3] = {{1.0 / 2, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+        return A[s][q];
+    }
+}
+template <int SCHEME>
+__host__ __device__ __forceinline__ double fx_c(int s) {
+    if constexpr (SCHEME == CFM_ODE_RK4) {
+        constexpr double C[3] = {1.0 / 3, 2.0 / 3, 1};
+        return C[s];
+    } else {
+        constexpr double C[3] = {1.0 / 2, 0, 0};
+        return C[s];
+    }
+}
+template <int SCHEME>
+__host__ __device__ __forceinline__ double fx_b(int q) {
+    if constexpr (SCHEME == CFM_ODE_RK4) {
+        constexpr double Bv[4] = {1.0 / 8, 3.0 / 8, 3.0 / 8, 1.0 / 8};
+        return Bv[q];
+    } else if constexpr (SCHEME == CFM_ODE_MIDPOINT) {
+        constexpr double Bv[4] = {0, 1, 0, 0};
+        return Bv[q];
+    } else {
+        constexpr double Bv[4] = {1, 0, 0, 0};
+        return Bv[q];
+    }
+}
+static int fx_known(int scheme) { return scheme == CFM_ODE_EULER || scheme == CFM_ODE_MIDPOINT || scheme == CFM_ODE_RK4; }
+static int fx_stages_host(int scheme) { return scheme == CFM_ODE_RK4 ? 4 : scheme == CFM_ODE_MIDPOINT ? 2 : 1; }
+static double fx_a_host(int sc, int s, int q) { return sc == CFM_ODE_RK4 ? fx_a<CFM_ODE_RK4>(s, q) : fx_a<CFM_ODE_MIDPOINT>(s, q); }
+static double fx_c_host(int sc, int s) { return sc == CFM_ODE_RK4 ? fx_c<CFM_ODE_RK4>(s) : fx_c<CFM_ODE_MIDPOINT>(s); }
+static double fx_b_host(int sc, int q) {
+    return sc == CFM_ODE_RK4 ? fx_b<CFM_ODE_RK4>(q) : sc == CFM_ODE_MIDPOINT ? fx_b<CFM_ODE_MIDPOINT>(q) : fx_b<CFM_ODE_EULER>(q);
+}
+
+static int ode_fixed_small(int scheme, const float* const* W, const float* const* b, const int* dims, int B, int d,
                            const float* t_span, int n_t, float* traj, float* tspan_dev, hipStream_t s);
 
-extern "C" int cfm_ode_euler_mlp_f32(const float* const* W, const float* const* b, const int* dims,
+extern "C" int cfm_ode_fixed_mlp_f32(const float* const* W, const float* const* b, const int* dims,
                                      int n_layers, const float* x0, int B, const float* t_span,
-                                     int n_t, float* traj, int* nfe, void* ws, void* stream) {
+                                     int n_t, int scheme, float* traj, int* nfe, void* ws, void* stream) {
     int d;
-    if (!W || !b || !x0 || !t_span || !traj || !ws || B <= 0 || n_t < 1) return CFM_EINVAL;
+    if (!W || !b || !x0 || !t_span || !traj || !ws || B <= 0 || n_t < 1 || !fx_known(scheme)) return CFM_EINVAL;
     int rc = check_mlp(dims, n_layers, &d);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int width = maxwidth(dims, n_layers);
     OdeWs w = ode_carve(ws, B, width, d);
     const size_t n = (size_t)B * d;
+    const int ns = fx_stages_host(scheme);
     rc = cfm_hip(hipMemcpyAsync(traj, x0, n * sizeof(float), hipMemcpyDeviceToDevice, s));
     if (rc) return rc;
     // small vector fields: rows are independent and the steps are fixed, so ONE launch integrates the
     // whole t_span (a workgroup walks its 64-row tile through every step, weights resident in LDS)
     if (ode_small_enabled() && n_layers == 4 && dims[1] <= SM_WMAX && dims[2] <= SM_WMAX && dims[3] <= SM_WMAX &&
         d + 1 <= SM_WMAX && n >= (size_t)n_t && n_t >= 2) {
-        rc = ode_euler_small(W, b, dims, B, d, t_span, n_t, traj, w.xt, s);
-        if (nfe) *nfe = n_t - 1;
+        rc = ode_fixed_small(scheme, W, b, dims, B, d, t_span, n_t, traj, w.xt, s);
+        if (nfe) *nfe = ns * (n_t - 1);
         return rc;
     }
     int evals = 0;
     for (int k = 0; k + 1 < n_t; ++k) {
         const float t = t_span[k], dt = t_span[k + 1] - t_span[k];
         const float* xk = traj + (size_t)k * n;
-        rc = cfm_mlp_forward_impl(xk, nullptr, t, 1, 0, W, b, dims, n_layers, B, w.k[0], w.act, s);
-        if (rc) return rc;
-        ++evals;
-        Stages st{}; st.k[0] = w.k[0]; st.c[0] = 1.f; st.n = 1;
-        for (int q = 1; q < 7; ++q) { st.k[q] = w.k[0]; st.c[q] = 0.f; }
+        for (int sg = 0; sg < ns; ++sg) {
+            const float* yin = xk;
+            float tsg = t;
+            if (sg > 0) {
+                Stages st{}; st.n = sg;
+                for (int q = 0; q < 7; ++q) { st.k[q] = w.k[q < sg ? q : 0]; st.c[q] = q < sg ? (float)fx_a_host(scheme, sg - 1, q) : 0.f; }
+                hipLaunchKernelGGL(ode_combine, dim3(ode_blocks(n)), dim3(256), 0, s, n, xk, dt, st, w.xt, (float*)nullptr);
+                yin = w.xt;
+                tsg = t + (float)fx_c_host(scheme, sg - 1) * dt;
+            }
+            rc = cfm_mlp_forward_impl(yin, nullptr, tsg, 1, 0, W, b, dims, n_layers, B, w.k[sg], w.act, s);
+            if (rc) return rc;
+            ++evals;
+        }
+        Stages st{}; st.n = ns;
+        for (int q = 0; q < 7; ++q) { st.k[q] = w.k[q < ns ? q : 0]; st.c[q] = q < ns ? (float)fx_b_host(scheme, q) : 0.f; }
         hipLaunchKernelGGL(ode_combine, dim3(ode_blocks(n)), dim3(256), 0, s, n, xk, dt, st,
                            traj + (size_t)(k + 1) * n, (float*)nullptr);
     }
@@ -174,18 +308,11 @@ extern "C" int cfm_ode_euler_mlp_f32(const float* const* W, const float* const* 
     return cfm_status();
 }
 
-// Dormand-Prince 5(4) tableau
-static const float DP_C[6] = {1.f / 5, 3.f / 10, 4.f / 5, 8.f / 9, 1.f, 1.f};
-static const double DP_A[6][6] = {
-    {1.0 / 5, 0, 0, 0, 0, 0},
-    {3.0 / 40, 9.0 / 40, 0, 0, 0, 0},
-    {44.0 / 45, -56.0 / 15, 32.0 / 9, 0, 0, 0},
-    {19372.0 / 6561, -25360.0 / 2187, 64448.0 / 6561, -212.0 / 729, 0, 0},
-    {9017.0 / 3168, -355.0 / 33, 46732.0 / 5247, 49.0 / 176, -5103.0 / 18656, 0},
-    {35.0 / 384, 0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784, 11.0 / 84}};
-static const double DP_BSOL[7] = {35.0 / 384, 0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784, 11.0 / 84, 0};
-static const double DP_BALT[7] = {1951.0 / 21600, 0, 22642.0 / 50085, 451.0 / 720, -12231.0 / 42400,
-                                  649.0 / 6300, 1.0 / 60};
+extern "C" int cfm_ode_euler_mlp_f32(const float* const* W, const float* const* b, const int* dims,
+                                     int n_layers, const float* x0, int B, const float* t_span,
+                                     int n_t, float* traj, int* nfe, void* ws, void* stream) {
+    return cfm_ode_fixed_mlp_f32(W, b, dims, n_layers, x0, B, t_span, n_t, CFM_ODE_EULER, traj, nfe, ws, stream);
+}
 
 static double* g_ode_pinned = nullptr;
 
@@ -202,11 +329,17 @@ static int read_red(hipStream_t s, const double* dev, int count, double* host) {
     return 0;
 }
 
-template <int MODE>
+template <int TAB, int MODE>
 static int ode_dopri5_small(const float* const* W, const float* const* b, const int* dims, int B, int d,
                             const float* t_span, int n_t, float tsign, const float* eps, float atol, float rtol,
                             float* traj, int* n_steps, int* nfe, float* xbuf, float* kbuf, float* tspan_dev,
                             void* state_dev, char* sync_dev, float t0, float dt0, int evals0, hipStream_t s);
+
+// the tableau selector (validated by the entry points) picks the instantiation
+template <int MODE, class... Args>
+static int ode_adaptive_small(int tab, Args... args) {
+    return tab == CFM_ODE_TSIT5 ? ode_dopri5_small<CFM_ODE_TSIT5, MODE>(args...) : ode_dopri5_small<CFM_ODE_DOPRI5, MODE>(args...);
+}
 
 // Time direction of a t_span (torchdyn's rule): a strictly decreasing grid is integrated as
 // g(s, y) = -f(-s, y) on s = -t_span.  ts receives the (increasing) grid the solver steps on; the returned sign
@@ -258,28 +391,35 @@ static int ode_init_step(F&& f, size_t n, float t, float hsign, float atol, floa
     return 0;
 }
 
-static int ode_dopri5_layers(const float* const* W, const float* const* b, const int* dims, int n_layers, int d,
+static int ode_dopri5_layers(int tab, const float* const* W, const float* const* b, const int* dims, int n_layers, int d,
                              const float* x0, int B, const float* t_span, int n_t, float tsign, float atol,
                              float rtol, float* traj, int* n_steps, int* nfe, void* ws, void* stream);
 
-extern "C" int cfm_ode_dopri5_mlp_f32(const float* const* W, const float* const* b, const int* dims,
-                                      int n_layers, const float* x0, int B, const float* t_span,
-                                      int n_t, float atol, float rtol, float* traj, int* n_steps,
-                                      int* nfe, void* ws, void* stream) {
+extern "C" int cfm_ode_adaptive_mlp_f32(const float* const* W, const float* const* b, const int* dims,
+                                        int n_layers, const float* x0, int B, const float* t_span,
+                                        int n_t, int tableau, float atol, float rtol, float* traj, int* n_steps,
+                                        int* nfe, void* ws, void* stream) {
     int d;
-    if (!W || !b || !x0 || !t_span || !traj || !ws || B <= 0 || n_t < 2) return CFM_EINVAL;
+    if (!W || !b || !x0 || !t_span || !traj || !ws || B <= 0 || n_t < 2 || !rk_adaptive_known(tableau)) return CFM_EINVAL;
     int rc = check_mlp(dims, n_layers, &d);
     if (rc) return rc;
     float* ts = (float*)malloc(sizeof(float) * (size_t)n_t);   // the grid in solver time (s = sign * t)
     if (!ts) return CFM_EINVAL;
     const float tsign = ode_direction(t_span, n_t, ts);
     if (tsign == 0.f) { free(ts); return CFM_EINVAL; }          // strictly monotone t_span only
-    rc = ode_dopri5_layers(W, b, dims, n_layers, d, x0, B, ts, n_t, tsign, atol, rtol, traj, n_steps, nfe, ws, stream);
+    rc = ode_dopri5_layers(tableau, W, b, dims, n_layers, d, x0, B, ts, n_t, tsign, atol, rtol, traj, n_steps, nfe, ws, stream);
     free(ts);
     return rc;
 }
 
-static int ode_dopri5_layers(const float* const* W, const float* const* b, const int* dims, int n_layers, int d,
+extern "C" int cfm_ode_dopri5_mlp_f32(const float* const* W, const float* const* b, const int* dims,
+                                      int n_layers, const float* x0, int B, const float* t_span,
+                                      int n_t, float atol, float rtol, float* traj, int* n_steps,
+                                      int* nfe, void* ws, void* stream) {
+    return cfm_ode_adaptive_mlp_f32(W, b, dims, n_layers, x0, B, t_span, n_t, CFM_ODE_DOPRI5, atol, rtol, traj, n_steps, nfe, ws, stream);
+}
+
+static int ode_dopri5_layers(int tab, const float* const* W, const float* const* b, const int* dims, int n_layers, int d,
                              const float* x0, int B, const float* t_span, int n_t, float tsign, float atol,
                              float rtol, float* traj, int* n_steps, int* nfe, void* ws, void* stream) {
     int rc;
@@ -288,14 +428,12 @@ static int ode_dopri5_layers(const float* const* W, const float* const* b, const
     OdeWs w = ode_carve(ws, B, width, d);
     const size_t n = (size_t)B * d;
     const int nb = ode_blocks(n);
-    const float order = 5.f;
     int evals = 0, steps = 0;
 
     auto f = [&](float t, const float* xin, float* kout) -> int {
         ++evals;
         return cfm_mlp_forward_impl(xin, nullptr, tsign * t, 1, 0, W, b, dims, n_layers, B, kout, w.act, s);
     };
-    auto rms = [&](double sumsq) -> float { return (float)sqrt(sumsq / (double)n); };
 
     rc = cfm_hip(hipMemcpyAsync(w.x, x0, n * sizeof(float), hipMemcpyDeviceToDevice, s));
     if (rc) return rc;
@@ -315,7 +453,7 @@ static int ode_dopri5_layers(const float* const* W, const float* const* b, const
     // small vector fields: the whole step attempt in one kernel, controller on the device
     if (ode_small_enabled() && n_layers == 4 && dims[1] <= SM_WMAX && dims[2] <= SM_WMAX && dims[3] <= SM_WMAX &&
         d + 1 <= SM_WMAX && n >= (size_t)n_t)
-        return ode_dopri5_small<0>(W, b, dims, B, d, t_span, n_t, tsign, nullptr, atol, rtol, traj, n_steps, nfe, w.x,
+        return ode_adaptive_small<0>(tab, W, b, dims, B, d, t_span, n_t, tsign, nullptr, atol, rtol, traj, n_steps, nfe, w.x,
                                    w.k[0], w.xt, (void*)(w.red + 16), w.sync, t, dt, evals, s);
 
     int ckpt = 1;  // next t_span index to land on
@@ -328,24 +466,26 @@ static int ode_dopri5_layers(const float* const* W, const float* const* b, const
         // stages k2..k6, then x_new and k7 (FSAL)
         for (int sIdx = 0; sIdx < 6; ++sIdx) {
             Stages st{}; st.n = sIdx + 1;
-            for (int q = 0; q < 7; ++q) { st.k[q] = w.k[q < 7 ? q : 0]; st.c[q] = q <= sIdx ? (float)DP_A[sIdx][q] : 0.f; }
+            for (int q = 0; q < 7; ++q) { st.k[q] = w.k[q < 7 ? q : 0]; st.c[q] = q <= sIdx ? (float)rk_a_host(tab, sIdx, q) : 0.f; }
             float* dst = (sIdx == 5) ? w.xn : w.xt;
             hipLaunchKernelGGL(ode_combine, dim3(nb), dim3(256), 0, s, n, w.x, tsign * dt, st, dst, (float*)nullptr);
-            rc = f(t + DP_C[sIdx] * dt, dst, w.k[sIdx + 1]);
+            rc = f(t + rk_c_host(tab, sIdx) * dt, dst, w.k[sIdx + 1]);
             if (rc) return rc;
         }
         {
             Stages st{}; st.n = 7;
-            for (int q = 0; q < 7; ++q) { st.k[q] = w.k[q]; st.c[q] = (float)(DP_BSOL[q] - DP_BALT[q]); }
+            for (int q = 0; q < 7; ++q) { st.k[q] = w.k[q]; st.c[q] = (float)rk_e_host(tab, q); }
             rc = cfm_hip(hipMemsetAsync(w.red + 4, 0, 8, s));
             if (rc) return rc;
             hipLaunchKernelGGL(ode_error, dim3(nb), dim3(256), 0, s, n, w.x, w.xn, dt, st, atol, rtol, w.red + 4);
         }
-        double e2;
-        rc = read_red(s, w.red + 4, 1, &e2);
+        hipLaunchKernelGGL(ode_controller, dim3(1), dim3(1), 0, s, w.red + 4, (double)n, (float*)(w.red + 6));
+        double ctl;
+        rc = read_red(s, w.red + 6, 1, &ctl);
         if (rc) return rc;
         ++steps;
-        const float ratio = rms(e2);
+        float ratio, factor;
+        memcpy(&ratio, (const char*)&ctl, 4); memcpy(&factor, (const char*)&ctl + 4, 4);
         const bool accept = ratio <= 1.f;
         if (accept) {
             if (lands) {
@@ -360,14 +500,7 @@ static int ode_dopri5_layers(const float* const* W, const float* const* b, const
             tmp = w.k[0]; w.k[0] = w.k[6]; w.k[6] = tmp;        // k1 <- k7 (FSAL)
         }
         if (flag) dt = dt_old - dt;
-        // adapt_step(dt, ratio, safety=0.9, min_factor=0.2, max_factor=10, order=5)
-        float factor;
-        if (ratio == 0.f) factor = 10.f;
-        else {
-            const float minf = ratio < 1.f ? 1.f : 0.2f;
-            factor = fminf(10.f, fmaxf(0.9f / powf(ratio, 1.f / order), minf));
-        }
-        dt = dt * factor;
+        dt = dt * factor;                  // (ode_step_factor on the device, see ode_controller)
         if (!(dt > 1e-12f)) dt = 1e-12f;   // guard (documented deviation)
     }
     if (n_steps) *n_steps = steps;
@@ -410,28 +543,6 @@ __device__ __forceinline__ int sm_row(int i, int lane) { return 16 * (i >> 2) + 
 __device__ __forceinline__ float selu_f(float x) {
     return x > 0.f ? 1.0507009873554805f * x : (1.0507009873554805f * 1.6732632423543772f) * expm1f(x);
 }
-// tableau entries as compile-time constants (indices are constants after unrolling); the casts
-// mirror the host driver: (float)DP_A[s][q], (float)(DP_BSOL[q] - DP_BALT[q])
-__device__ __forceinline__ double DP_A_dev(int s, int q) {
-    constexpr double A[6][6] = {
-        {1.0 / 5, 0, 0, 0, 0, 0},
-        {3.0 / 40, 9.0 / 40, 0, 0, 0, 0},
-        {44.0 / 45, -56.0 / 15, 32.0 / 9, 0, 0, 0},
-        {19372.0 / 6561, -25360.0 / 2187, 64448.0 / 6561, -212.0 / 729, 0, 0},
-        {9017.0 / 3168, -355.0 / 33, 46732.0 / 5247, 49.0 / 176, -5103.0 / 18656, 0},
-        {35.0 / 384, 0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784, 11.0 / 84}};
-    return A[s][q];
-}
-__device__ __forceinline__ float DP_C_dev(int s) {
-    constexpr float C[6] = {1.f / 5, 3.f / 10, 4.f / 5, 8.f / 9, 1.f, 1.f};
-    return C[s];
-}
-__device__ __forceinline__ double DP_E_dev(int q) {
-    constexpr double BS[7] = {35.0 / 384, 0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784, 11.0 / 84, 0};
-    constexpr double BA[7] = {1951.0 / 21600, 0, 22642.0 / 50085, 451.0 / 720, -12231.0 / 42400, 649.0 / 6300, 1.0 / 60};
-    return BS[q] - BA[q];
-}
-
 struct SmState { float t, dt; int ckpt, steps, evals, par, done, pad; };
 // One persistent solve at a time per process, whatever its augmentation mode (see ode_dopri5_small)
 static std::mutex g_persistent_mu;
@@ -711,7 +822,7 @@ __device__ __forceinline__ bool sm_grid_allsum(double* __restrict__ row, double 
 // the same fixed order (so the solve is reproducible bit for bit), derives the same accept / reject
 // decision and next step size from that sum (the fp32 controller of the host loop above).  `lines` is only
 // touched by SM_PROF builds (phase stamps).
-template <bool RESIDENT, int MODE>
+template <int TAB, bool RESIDENT, int MODE>
 __global__ __launch_bounds__(256) void ode_small_dopri(SmArgs A, int B, int d, SmState* __restrict__ st_io,
                                                     float* __restrict__ xbuf, float* __restrict__ kbuf,
                                                     const float* __restrict__ tspan, int n_t, float atol, float rtol,
@@ -790,18 +901,18 @@ __global__ __launch_bounds__(256) void ode_small_dopri(SmArgs A, int B, int d, S
             // stage S (a literal): y = x + dt * sum_{q<=S} a[S][q] k_q ; KOUT = f(t + c[S] dt, y)
 #define SM_COMBINE(S, Y, X, K0, K1, K2, K3, K4, K5)                                                  \
             _Pragma("unroll") for (int i = 0; i < SM_V; ++i) {                                       \
-                float acc = (float)DP_A_dev(S, 0) * K0.v[i];                                         \
-                if (S >= 1) acc = fmaf((float)DP_A_dev(S, 1), K1.v[i], acc);                         \
-                if (S >= 2) acc = fmaf((float)DP_A_dev(S, 2), K2.v[i], acc);                         \
-                if (S >= 3) acc = fmaf((float)DP_A_dev(S, 3), K3.v[i], acc);                         \
-                if (S >= 4) acc = fmaf((float)DP_A_dev(S, 4), K4.v[i], acc);                         \
-                if (S >= 5) acc = fmaf((float)DP_A_dev(S, 5), K5.v[i], acc);                         \
+                float acc = (float)rk_a<TAB>(S, 0) * K0.v[i];                                         \
+                if (S >= 1) acc = fmaf((float)rk_a<TAB>(S, 1), K1.v[i], acc);                         \
+                if (S >= 2) acc = fmaf((float)rk_a<TAB>(S, 2), K2.v[i], acc);                         \
+                if (S >= 3) acc = fmaf((float)rk_a<TAB>(S, 3), K3.v[i], acc);                         \
+                if (S >= 4) acc = fmaf((float)rk_a<TAB>(S, 4), K4.v[i], acc);                         \
+                if (S >= 5) acc = fmaf((float)rk_a<TAB>(S, 5), K5.v[i], acc);                         \
                 Y.v[i] = fmaf(hdt, acc, X.v[i]);                                                     \
             }
 #define SM_STAGE(S, KOUT, LOUT)                                                                      \
             {                                                                                        \
                 SM_COMBINE(S, y, x, k0, k1, k2, k3, k4, k5)                                          \
-                const float tf = tsign * (st.t + DP_C_dev(S) * dt);                                  \
+                const float tf = tsign * (st.t + rk_c<TAB>(S) * dt);                                  \
                 if constexpr (AUG) {                                                                 \
                     SM_COMBINE(S, yl, xl, l0, l1, l2, l3, l4, l5)                                    \
                     SmTile dv;                                                                       \
@@ -820,13 +931,13 @@ __global__ __launch_bounds__(256) void ode_small_dopri(SmArgs A, int B, int d, S
             for (int i = 0; i < SM_V; ++i) {
                 const int gr = row0 + sm_row(i, lane);
                 if (gr < B && col < d) {
-                    float e = (float)DP_E_dev(0) * k0.v[i];
-                    e = fmaf((float)DP_E_dev(1), k1.v[i], e);
-                    e = fmaf((float)DP_E_dev(2), k2.v[i], e);
-                    e = fmaf((float)DP_E_dev(3), k3.v[i], e);
-                    e = fmaf((float)DP_E_dev(4), k4.v[i], e);
-                    e = fmaf((float)DP_E_dev(5), k5.v[i], e);
-                    e = fmaf((float)DP_E_dev(6), k6.v[i], e);
+                    float e = (float)rk_e<TAB>(0) * k0.v[i];
+                    e = fmaf((float)rk_e<TAB>(1), k1.v[i], e);
+                    e = fmaf((float)rk_e<TAB>(2), k2.v[i], e);
+                    e = fmaf((float)rk_e<TAB>(3), k3.v[i], e);
+                    e = fmaf((float)rk_e<TAB>(4), k4.v[i], e);
+                    e = fmaf((float)rk_e<TAB>(5), k5.v[i], e);
+                    e = fmaf((float)rk_e<TAB>(6), k6.v[i], e);
                     e *= dt;
                     const float sc = atol + rtol * fmaxf(fabsf(x.v[i]), fabsf(y.v[i]));
                     const float rr = e / sc;
@@ -838,13 +949,13 @@ __global__ __launch_bounds__(256) void ode_small_dopri(SmArgs A, int B, int d, S
                 }
                 if constexpr (AUG) {
                     if (gr < B && lw) {               // each row's l counts once in the norm
-                        float e = (float)DP_E_dev(0) * l0.v[i];
-                        e = fmaf((float)DP_E_dev(1), l1.v[i], e);
-                        e = fmaf((float)DP_E_dev(2), l2.v[i], e);
-                        e = fmaf((float)DP_E_dev(3), l3.v[i], e);
-                        e = fmaf((float)DP_E_dev(4), l4.v[i], e);
-                        e = fmaf((float)DP_E_dev(5), l5.v[i], e);
-                        e = fmaf((float)DP_E_dev(6), l6.v[i], e);
+                        float e = (float)rk_e<TAB>(0) * l0.v[i];
+                        e = fmaf((float)rk_e<TAB>(1), l1.v[i], e);
+                        e = fmaf((float)rk_e<TAB>(2), l2.v[i], e);
+                        e = fmaf((float)rk_e<TAB>(3), l3.v[i], e);
+                        e = fmaf((float)rk_e<TAB>(4), l4.v[i], e);
+                        e = fmaf((float)rk_e<TAB>(5), l5.v[i], e);
+                        e = fmaf((float)rk_e<TAB>(6), l6.v[i], e);
                         e *= dt;
                         const float sc = atol + rtol * fmaxf(fabsf(xl.v[i]), fabsf(yl.v[i]));
                         const float rr = e / sc;
@@ -899,13 +1010,7 @@ __global__ __launch_bounds__(256) void ode_small_dopri(SmArgs A, int B, int d, S
         }
         float ndt = dt;
         if (flag) ndt = dt_old - dt;
-        float factor;
-        if (ratio == 0.f) factor = 10.f;
-        else {
-            const float minf = ratio < 1.f ? 1.f : 0.2f;
-            factor = fminf(10.f, fmaxf(0.9f / powf(ratio, 1.f / 5.f), minf));
-        }
-        ndt = ndt * factor;
+        ndt = ndt * ode_step_factor(ratio);
         if (!(ndt > 1e-12f)) ndt = 1e-12f;
         nx.dt = ndt;
         nx.done = (nx.t < T) ? 0 : 1;
@@ -918,7 +1023,7 @@ static size_t sm_lds_bytes(int mode) {
     return sizeof(float) * (4 * SM_W * SM_LD + 4 * SM_W + SM_W + 2 * SM_ROWS * SM_LD + (mode ? 4 * SM_ROWS : 0));
 }
 
-template <int MODE>
+template <int TAB, int MODE>
 static int ode_dopri5_small(const float* const* W, const float* const* b, const int* dims, int B, int d,
                             const float* t_span, int n_t, float tsign, const float* eps, float atol, float rtol,
                             float* traj, int* n_steps, int* nfe, float* xbuf, float* kbuf, float* tspan_dev,
@@ -931,17 +1036,17 @@ static int ode_dopri5_small(const float* const* W, const float* const* b, const 
     static std::once_flag once_d[CFM_MAX_DEVICES];
     const int dvi = cfm_device_index();
     int& raised = raised_d[dvi]; int& resident = resident_d[dvi];
-    // (one set per MODE: the grid is sized from the occupancy of the instantiation that is launched)
+    // (one set per TAB and MODE: the grid is sized from the occupancy of the instantiation that is launched)
     std::call_once(once_d[dvi], [lds, &raised, &resident] {
-        hipError_t e = hipFuncSetAttribute((const void*)ode_small_dopri<true, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-        hipError_t e2 = hipFuncSetAttribute((const void*)ode_small_dopri<false, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+        hipError_t e = hipFuncSetAttribute((const void*)ode_small_dopri<TAB, true, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+        hipError_t e2 = hipFuncSetAttribute((const void*)ode_small_dopri<TAB, false, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
         int ok = (e == hipSuccess && e2 == hipSuccess) ? 1 : -1;
         // workgroups that can be resident at once: the grid rendezvous needs grid <= this
         int dev = 0, cus = 0, pa = 0, pb = 0;
         if (ok > 0 && hipGetDevice(&dev) == hipSuccess &&
             hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&pa, (const void*)ode_small_dopri<true, MODE>, 256, lds) == hipSuccess &&
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&pb, (const void*)ode_small_dopri<false, MODE>, 256, lds) == hipSuccess &&
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&pa, (const void*)ode_small_dopri<TAB, true, MODE>, 256, lds) == hipSuccess &&
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&pb, (const void*)ode_small_dopri<TAB, false, MODE>, 256, lds) == hipSuccess &&
             cus > 0 && pa > 0 && pb > 0)
             resident = cus * (pa < pb ? pa : pb);
         else
@@ -970,10 +1075,10 @@ static int ode_dopri5_small(const float* const* W, const float* const* b, const 
     // CFM_ETIMEOUT after 4 s).  The call is synchronous anyway: the lock is held until the solve has finished.
     std::lock_guard<std::mutex> persistent_lock(g_persistent_mu);
     if (tiles <= grid)
-        hipLaunchKernelGGL((ode_small_dopri<true, MODE>), dim3(grid), dim3(256), lds, s, A, B, d, st, xbuf, kbuf, tspan_dev, n_t,
+        hipLaunchKernelGGL((ode_small_dopri<TAB, true, MODE>), dim3(grid), dim3(256), lds, s, A, B, d, st, xbuf, kbuf, tspan_dev, n_t,
                            atol, rtol, traj, partial, lines, 1000000, tsign, eps);
     else
-        hipLaunchKernelGGL((ode_small_dopri<false, MODE>), dim3(grid), dim3(256), lds, s, A, B, d, st, xbuf, kbuf, tspan_dev, n_t,
+        hipLaunchKernelGGL((ode_small_dopri<TAB, false, MODE>), dim3(grid), dim3(256), lds, s, A, B, d, st, xbuf, kbuf, tspan_dev, n_t,
                            atol, rtol, traj, partial, lines, 1000000, tsign, eps);
     rc = cfm_status();
     if (rc) return rc;
@@ -1109,15 +1214,18 @@ extern "C" int cfm_sde_em_mlp_f32(const float* const* Wf, const float* const* bf
     return cfm_status();
 }
 
-// Fixed-step Euler for the same small fields: x_{k+1} = x_k + dt_k f(t_k, x_k), every step of the
-// tile inside one launch (same arithmetic as ode_combine: fmaf(dt, 1.f * k, x)).  A decreasing t_span needs nothing
-// else: dt < 0 steps it, bit for bit the forward solve of -f(-s, x) on s = -t_span.  MODE != AUG_NONE: the
-// trajectory is [n_t, B, 1 + d] with column 0 = l, l_{k+1} = l_k + dt_k (-div f(t_k, x_k)); the x columns are bitwise
-// those of the plain solve.
-template <int MODE>
-__global__ __launch_bounds__(256) void ode_small_euler(SmArgs A, int B, int d, const float* __restrict__ tspan, int n_t,
+// Fixed-step explicit Runge-Kutta (euler / midpoint / rk4: fx_stages<SCHEME>() = 1, 2 or 4 stages) for the same small
+// fields: every step of the tile inside one launch, the stage tiles in registers.  Same arithmetic as the layer driver's
+// ode_combine calls: stage y = fmaf(dt, a0 k0 (+ fma chain), x), x_{k+1} = fmaf(dt, b0 k0 (+ fma chain), x_k); for
+// euler that is fmaf(dt, 1.f * k, x).  A decreasing t_span needs nothing else: dt < 0 steps it, bit for bit the forward
+// solve of -f(-s, x) on s = -t_span.  MODE != AUG_NONE: the trajectory is [n_t, B, 1 + d] with column 0 = l, whose
+// stage derivatives are -div f at the stage points (the field does not read l, so l has no stage states); the x columns
+// are bitwise those of the plain solve.
+template <int SCHEME, int MODE>
+__global__ __launch_bounds__(256) void ode_small_fixed(SmArgs A, int B, int d, const float* __restrict__ tspan, int n_t,
                                                     float* __restrict__ traj, const float* __restrict__ eps) {
     constexpr bool AUG = MODE != AUG_NONE;
+    constexpr int NS = fx_stages<SCHEME>();
     extern __shared__ __attribute__((aligned(16))) float small_lds[];
     float* Wl = small_lds;
     float* bl = Wl + 4 * SM_W * SM_LD;
@@ -1146,16 +1254,44 @@ __global__ __launch_bounds__(256) void ode_small_euler(SmArgs A, int B, int d, c
         __syncthreads();
         for (int k = 0; k + 1 < n_t; ++k) {
             const float t = tspan[k], dt = tspan[k + 1] - tspan[k];
-            SmTile f, dv;
-            if constexpr (AUG) f = sm_field_aug<MODE>(x, t, A, d, Ab0, Ab1, Wl, bl, wt, ep, B - row0, red, wv, lane, dv);
-            else f = sm_field(x, t, A, d, Ab0, Ab1, Wl, bl, wt, wv, lane);
+            SmTile f[NS], lf[NS];
+#pragma unroll
+            for (int sg = 0; sg < NS; ++sg) {
+                SmTile y = x;
+                float tsg = t;
+                if (sg > 0) {
+#pragma unroll
+                    for (int i = 0; i < SM_V; ++i) {
+                        float acc = (float)fx_a<SCHEME>(sg - 1, 0) * f[0].v[i];
+#pragma unroll
+                        for (int q = 1; q < NS - 1; ++q)
+                            if (q < sg) acc = fmaf((float)fx_a<SCHEME>(sg - 1, q), f[q].v[i], acc);
+                        y.v[i] = fmaf(dt, acc, x.v[i]);
+                    }
+                    tsg = t + (float)fx_c<SCHEME>(sg - 1) * dt;
+                }
+                if constexpr (AUG) {
+                    SmTile dv;
+                    f[sg] = sm_field_aug<MODE>(y, tsg, A, d, Ab0, Ab1, Wl, bl, wt, ep, B - row0, red, wv, lane, dv);
+#pragma unroll
+                    for (int i = 0; i < SM_V; ++i) lf[sg].v[i] = -dv.v[i];
+                } else {
+                    f[sg] = sm_field(y, tsg, A, d, Ab0, Ab1, Wl, bl, wt, wv, lane);
+                }
+            }
 #pragma unroll
             for (int i = 0; i < SM_V; ++i) {
-                x.v[i] = fmaf(dt, 1.f * f.v[i], x.v[i]);
+                float acc = (float)fx_b<SCHEME>(0) * f[0].v[i];
+#pragma unroll
+                for (int q = 1; q < NS; ++q) acc = fmaf((float)fx_b<SCHEME>(q), f[q].v[i], acc);
+                x.v[i] = fmaf(dt, acc, x.v[i]);
                 const int gr = row0 + sm_row(i, lane);
                 if (gr < B && col < d) traj[(size_t)(k + 1) * n + (size_t)gr * D + c0 + col] = x.v[i];
                 if constexpr (AUG) {
-                    xl.v[i] = fmaf(dt, -dv.v[i], xl.v[i]);
+                    float lacc = (float)fx_b<SCHEME>(0) * lf[0].v[i];
+#pragma unroll
+                    for (int q = 1; q < NS; ++q) lacc = fmaf((float)fx_b<SCHEME>(q), lf[q].v[i], lacc);
+                    xl.v[i] = fmaf(dt, lacc, xl.v[i]);
                     if (gr < B && lw) traj[(size_t)(k + 1) * n + (size_t)gr * D] = xl.v[i];
                 }
             }
@@ -1163,8 +1299,8 @@ __global__ __launch_bounds__(256) void ode_small_euler(SmArgs A, int B, int d, c
     }
 }
 
-template <int MODE>
-static int ode_euler_small_t(const float* const* W, const float* const* b, const int* dims, int B, int d,
+template <int SCHEME, int MODE>
+static int ode_fixed_small_t(const float* const* W, const float* const* b, const int* dims, int B, int d,
                              const float* t_span, int n_t, float* traj, float* tspan_dev, const float* eps,
                              hipStream_t s) {
     SmArgs A;
@@ -1176,7 +1312,7 @@ static int ode_euler_small_t(const float* const* W, const float* const* b, const
     const int dvi = cfm_device_index();
     int& raised = raised_d[dvi];
     std::call_once(once_d[dvi], [&raised] {
-        hipError_t e = hipFuncSetAttribute((const void*)ode_small_euler<MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+        hipError_t e = hipFuncSetAttribute((const void*)ode_small_fixed<SCHEME, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
         (void)hipGetLastError();
         raised = (e == hipSuccess) ? 1 : -1;
     });
@@ -1184,14 +1320,23 @@ static int ode_euler_small_t(const float* const* W, const float* const* b, const
     int rc = cfm_hip(hipMemcpyAsync(tspan_dev, t_span, sizeof(float) * n_t, hipMemcpyHostToDevice, s));
     if (rc) return rc;
     const int tiles = (B + SM_ROWS - 1) / SM_ROWS;
-    hipLaunchKernelGGL(ode_small_euler<MODE>, dim3(tiles < 4096 ? tiles : 4096), dim3(256), lds, s, A, B, d, tspan_dev, n_t,
-                       traj, eps);
+    hipLaunchKernelGGL((ode_small_fixed<SCHEME, MODE>), dim3(tiles < 4096 ? tiles : 4096), dim3(256), lds, s, A, B, d, tspan_dev,
+                       n_t, traj, eps);
     return cfm_status();
 }
 
-static int ode_euler_small(const float* const* W, const float* const* b, const int* dims, int B, int d,
+// the scheme selector (validated by the entry points) picks the instantiation
+template <int MODE>
+static int ode_fixed_small_m(int scheme, const float* const* W, const float* const* b, const int* dims, int B, int d,
+                             const float* t_span, int n_t, float* traj, float* tspan_dev, const float* eps, hipStream_t s) {
+    if (scheme == CFM_ODE_RK4) return ode_fixed_small_t<CFM_ODE_RK4, MODE>(W, b, dims, B, d, t_span, n_t, traj, tspan_dev, eps, s);
+    if (scheme == CFM_ODE_MIDPOINT) return ode_fixed_small_t<CFM_ODE_MIDPOINT, MODE>(W, b, dims, B, d, t_span, n_t, traj, tspan_dev, eps, s);
+    return ode_fixed_small_t<CFM_ODE_EULER, MODE>(W, b, dims, B, d, t_span, n_t, traj, tspan_dev, eps, s);
+}
+
+static int ode_fixed_small(int scheme, const float* const* W, const float* const* b, const int* dims, int B, int d,
                            const float* t_span, int n_t, float* traj, float* tspan_dev, hipStream_t s) {
-    return ode_euler_small_t<AUG_NONE>(W, b, dims, B, d, t_span, n_t, traj, tspan_dev, nullptr, s);
+    return ode_fixed_small_m<AUG_NONE>(scheme, W, b, dims, B, d, t_span, n_t, traj, tspan_dev, nullptr, s);
 }
 
 // ---- CNF: one evaluation of [v, div] (the tile kernel of the augmented solves, once) --------------------------
@@ -1278,11 +1423,11 @@ extern "C" int cfm_mlp_divergence_f32(const float* const* W, const float* const*
                      : cnf_eval<AUG_HUTCH>(A, B, d, x, d, t, eps, v, d, div, 1, 1.f, s);
 }
 
-extern "C" int cfm_ode_euler_cnf_mlp_f32(const float* const* W, const float* const* b, const int* dims, int n_layers,
+extern "C" int cfm_ode_fixed_cnf_mlp_f32(const float* const* W, const float* const* b, const int* dims, int n_layers,
                                          const float* x0, int B, const float* t_span, int n_t, int mode,
-                                         const float* eps, float* traj, int* nfe, void* ws, void* stream) {
+                                         const float* eps, int scheme, float* traj, int* nfe, void* ws, void* stream) {
     int d; SmArgs A;
-    if (!x0 || !t_span || !traj || !ws || n_t < 1) return CFM_EINVAL;
+    if (!x0 || !t_span || !traj || !ws || n_t < 1 || !fx_known(scheme)) return CFM_EINVAL;
     int rc = cnf_check(W, b, dims, n_layers, B, mode, eps, &d, &A);
     if (rc) return rc;
     for (int k = 0; k + 1 < n_t; ++k)                  // strictly monotone, either way
@@ -1298,14 +1443,20 @@ extern "C" int cfm_ode_euler_cnf_mlp_f32(const float* const* W, const float* con
     if ((size_t)n_t > 3 * n) return CFM_EINVAL;        // t_span copy: w.x .. w.xt
     rc = cfm_hip(hipMemcpyAsync(traj, x0, n * sizeof(float), hipMemcpyDeviceToDevice, s));
     if (rc) return rc;
-    if (nfe) *nfe = n_t - 1;
+    if (nfe) *nfe = fx_stages_host(scheme) * (n_t - 1);
     if (n_t < 2) return 0;
-    return mode == 0 ? ode_euler_small_t<AUG_EXACT>(W, b, dims, B, d, t_span, n_t, traj, w.x, eps, s)
-                     : ode_euler_small_t<AUG_HUTCH>(W, b, dims, B, d, t_span, n_t, traj, w.x, eps, s);
+    return mode == 0 ? ode_fixed_small_m<AUG_EXACT>(scheme, W, b, dims, B, d, t_span, n_t, traj, w.x, eps, s)
+                     : ode_fixed_small_m<AUG_HUTCH>(scheme, W, b, dims, B, d, t_span, n_t, traj, w.x, eps, s);
+}
+
+extern "C" int cfm_ode_euler_cnf_mlp_f32(const float* const* W, const float* const* b, const int* dims, int n_layers,
+                                         const float* x0, int B, const float* t_span, int n_t, int mode,
+                                         const float* eps, float* traj, int* nfe, void* ws, void* stream) {
+    return cfm_ode_fixed_cnf_mlp_f32(W, b, dims, n_layers, x0, B, t_span, n_t, mode, eps, CFM_ODE_EULER, traj, nfe, ws, stream);
 }
 
 template <int MODE>
-static int cnf_dopri5(const SmArgs& A, const float* const* W, const float* const* b, const int* dims, int d,
+static int cnf_dopri5(int tab, const SmArgs& A, const float* const* W, const float* const* b, const int* dims, int d,
                       const float* x0, int B, const float* ts, int n_t, float tsign, const float* eps, float atol,
                       float rtol, float* traj, int* n_steps, int* nfe, void* ws, hipStream_t s) {
     const int D = d + 1;
@@ -1328,16 +1479,16 @@ static int cnf_dopri5(const SmArgs& A, const float* const* W, const float* const
     float dt;
     rc = ode_init_step(f, n, t, tsign, atol, rtol, w, s, &dt);   // d0, d1, d2 over all B (1 + d) elements
     if (rc) return rc;
-    return ode_dopri5_small<MODE>(W, b, dims, B, d, ts, n_t, tsign, eps, atol, rtol, traj, n_steps, nfe, w.x, w.k[0], w.xt,
+    return ode_adaptive_small<MODE>(tab, W, b, dims, B, d, ts, n_t, tsign, eps, atol, rtol, traj, n_steps, nfe, w.x, w.k[0], w.xt,
                                   (void*)(w.red + 16), w.sync, t, dt, evals, s);
 }
 
-extern "C" int cfm_ode_dopri5_cnf_mlp_f32(const float* const* W, const float* const* b, const int* dims, int n_layers,
-                                          const float* x0, int B, const float* t_span, int n_t, int mode,
-                                          const float* eps, float atol, float rtol, float* traj, int* n_steps,
-                                          int* nfe, void* ws, void* stream) {
+extern "C" int cfm_ode_adaptive_cnf_mlp_f32(const float* const* W, const float* const* b, const int* dims, int n_layers,
+                                            const float* x0, int B, const float* t_span, int n_t, int mode,
+                                            const float* eps, int tableau, float atol, float rtol, float* traj,
+                                            int* n_steps, int* nfe, void* ws, void* stream) {
     int d; SmArgs A;
-    if (!x0 || !t_span || !traj || !ws || n_t < 2) return CFM_EINVAL;
+    if (!x0 || !t_span || !traj || !ws || n_t < 2 || !rk_adaptive_known(tableau)) return CFM_EINVAL;
     int rc = cnf_check(W, b, dims, n_layers, B, mode, eps, &d, &A);
     if (rc) return rc;
     float* ts = (float*)malloc(sizeof(float) * (size_t)n_t);
@@ -1345,11 +1496,19 @@ extern "C" int cfm_ode_dopri5_cnf_mlp_f32(const float* const* W, const float* co
     const float tsign = ode_direction(t_span, n_t, ts);
     if (tsign == 0.f) rc = CFM_EINVAL;
     else if (mode == 0)
-        rc = cnf_dopri5<AUG_EXACT>(A, W, b, dims, d, x0, B, ts, n_t, tsign, eps, atol, rtol, traj, n_steps, nfe, ws,
+        rc = cnf_dopri5<AUG_EXACT>(tableau, A, W, b, dims, d, x0, B, ts, n_t, tsign, eps, atol, rtol, traj, n_steps, nfe, ws,
                                    (hipStream_t)stream);
     else
-        rc = cnf_dopri5<AUG_HUTCH>(A, W, b, dims, d, x0, B, ts, n_t, tsign, eps, atol, rtol, traj, n_steps, nfe, ws,
+        rc = cnf_dopri5<AUG_HUTCH>(tableau, A, W, b, dims, d, x0, B, ts, n_t, tsign, eps, atol, rtol, traj, n_steps, nfe, ws,
                                    (hipStream_t)stream);
     free(ts);
     return rc;
+}
+
+extern "C" int cfm_ode_dopri5_cnf_mlp_f32(const float* const* W, const float* const* b, const int* dims, int n_layers,
+                                          const float* x0, int B, const float* t_span, int n_t, int mode,
+                                          const float* eps, float atol, float rtol, float* traj, int* n_steps,
+                                          int* nfe, void* ws, void* stream) {
+    return cfm_ode_adaptive_cnf_mlp_f32(W, b, dims, n_layers, x0, B, t_span, n_t, mode, eps, CFM_ODE_DOPRI5, atol, rtol, traj,
+                                        n_steps, nfe, ws, stream);
 }

@@ -4,11 +4,18 @@
 examples/images/cifar10/utils_cifar.py:63-68).
 
 When the vector field is ``torch_wrapper(MLP(time_varying=True))`` the whole solve runs in
-the HIP drivers (``cfm_ode_euler_mlp_f32`` / ``cfm_ode_dopri5_mlp_f32``); ``CNF(MLP)`` (cnf.py) of
+the HIP drivers (``cfm_ode_fixed_mlp_f32`` / ``cfm_ode_adaptive_mlp_f32``); ``CNF(MLP)`` (cnf.py) of
 the small-kernel envelope on fp32 ``[B, 1 + d]`` states runs in ``cfm_ode_*_cnf_mlp_f32``.  Any
 other vector field (e.g. a UNet) is stepped by the same algorithm at the tensor level — host
 control flow only, the field itself runs wherever the user's module runs.  ``last_path`` says
 which of the two ran ("hip" / "generic").
+
+Solvers: torchdyn's fixed-step set ``euler``, ``midpoint``, ``rk4`` (steps exactly on ``t_span``; ``atol`` / ``rtol``
+are ignored, as torchdyn does) and the adaptive 5(4) pairs ``dopri5`` and ``tsit5`` (one driver, two tableaus: 7 stages,
+FSAL, order-5 controller and initial step, every ``t_span`` point is a step end).  torchdyn's own default is ``tsit5``;
+the default here stays ``dopri5``.  ``rk4`` is the 3/8 rule ("torchdyn-style rk4": torchdyn is absent from the reference
+tree, so like ``dopri5`` its parity is unpinned).  ``nfe``: stages * (n_t - 1) for the fixed-step solvers, 2 + 6 * step
+attempts for the adaptive ones.
 
 ``t_span`` is strictly monotone.  A decreasing one integrates backward in time as torchdyn does
 (SURVEY.md A.4): ``g(s, x) = -f(-s, x)`` on ``s = -t_span``.
@@ -23,17 +30,37 @@ from ._lib import check, ptr, stream_ptr
 from .models import MLP
 from .utils import torch_wrapper
 
-_DP_C = [1 / 5, 3 / 10, 4 / 5, 8 / 9, 1.0, 1.0]
-_DP_A = [
-    [1 / 5],
-    [3 / 40, 9 / 40],
-    [44 / 45, -56 / 15, 32 / 9],
-    [19372 / 6561, -25360 / 2187, 64448 / 6561, -212 / 729],
-    [9017 / 3168, -355 / 33, 46732 / 5247, 49 / 176, -5103 / 18656],
-    [35 / 384, 0, 500 / 1113, 125 / 192, -2187 / 6784, 11 / 84],
-]
+# Adaptive pairs: c, a (rows 2..7; row 7 = b, so stage 7's state is the solution), e (x_err = dt * sum e_i k_i).
 _DP_BSOL = [35 / 384, 0, 500 / 1113, 125 / 192, -2187 / 6784, 11 / 84, 0]
 _DP_BALT = [1951 / 21600, 0, 22642 / 50085, 451 / 720, -12231 / 42400, 649 / 6300, 1 / 60]
+ADAPTIVE_TABLEAUS = {
+    "dopri5": dict(
+        c=[1 / 5, 3 / 10, 4 / 5, 8 / 9, 1.0, 1.0],
+        a=[[1 / 5],
+           [3 / 40, 9 / 40],
+           [44 / 45, -56 / 15, 32 / 9],
+           [19372 / 6561, -25360 / 2187, 64448 / 6561, -212 / 729],
+           [9017 / 3168, -355 / 33, 46732 / 5247, 49 / 176, -5103 / 18656],
+           [35 / 384, 0, 500 / 1113, 125 / 192, -2187 / 6784, 11 / 84]],
+        e=[bs - ba for bs, ba in zip(_DP_BSOL, _DP_BALT)], order=5),
+    "tsit5": dict(
+        c=[0.161, 0.327, 0.9, 0.9800255409045097, 1.0, 1.0],
+        a=[[0.161],
+           [-0.008480655492356989, 0.335480655492357],
+           [2.8971530571054935, -6.359448489975075, 4.3622954328695815],
+           [5.325864828439257, -11.748883564062828, 7.4955393428898365, -0.09249506636175525],
+           [5.86145544294642, -12.92096931784711, 8.159367898576159, -0.071584973281401, -0.028269050394068383],
+           [0.09646076681806523, 0.01, 0.4798896504144996, 1.379008574103742, -3.290069515436081, 2.324710524099774]],
+        e=[0.001780011052226, 0.000816434459657, -0.007880878010262, 0.144711007173263, -0.582357165452555,
+           0.458082105929187, -1 / 66], order=5),
+}
+# Fixed-step schemes: stage s >= 2 sits at t + c[s-2] dt on x + dt * sum a[s-2][q] k_q; x_new = x + dt * sum b k.
+FIXED_TABLEAUS = {
+    "euler": dict(c=[], a=[], b=[1.0], order=1),
+    "midpoint": dict(c=[1 / 2], a=[[1 / 2]], b=[0.0, 1.0], order=2),
+    "rk4": dict(c=[1 / 3, 2 / 3, 1.0], a=[[1 / 3], [-1 / 3, 1.0], [1.0, -1.0, 1.0]], b=[1 / 8, 3 / 8, 3 / 8, 1 / 8], order=4),
+}
+SOLVERS = ("euler", "midpoint", "rk4", "dopri5", "tsit5")
 
 
 def _hairer_norm(x):
@@ -58,8 +85,8 @@ class NeuralODE(torch.nn.Module):
     def __init__(self, vector_field, solver="dopri5", order=1, atol=1e-3, rtol=1e-3,
                  sensitivity="autograd", return_t_eval=True, **kwargs):
         super().__init__()
-        if solver not in ("euler", "dopri5"):
-            raise NotImplementedError(f"solver {solver!r}: only 'euler' and 'dopri5' are built")
+        if solver not in SOLVERS:
+            raise NotImplementedError(f"solver {solver!r}: one of {SOLVERS}")
         self.vf = vector_field
         self.solver, self.atol, self.rtol = solver, float(atol), float(rtol)
         self.sensitivity = sensitivity          # inert without autograd through the solve
@@ -111,7 +138,7 @@ class NeuralODE(torch.nn.Module):
             cnf._solve_noise = None
 
     def _trajectory_cnf_hip(self, m, x, t_span, eps):
-        """Augmented solve in cfm_ode_{euler,dopri5}_cnf_mlp_f32; None when the library declines it (CFM_EINVAL:
+        """Augmented solve in cfm_ode_{fixed,adaptive}_cnf_mlp_f32; None when the library declines it (CFM_EINVAL:
         the fused small-field path is switched off) so the caller steps it generically."""
         lib = _lib.load()
         dev = _lib.require_gpu()
@@ -129,16 +156,17 @@ class NeuralODE(torch.nn.Module):
         nfe = ctypes.c_int(0)
         steps = ctypes.c_int(0)
         tsp = ts.ctypes.data_as(ctypes.c_void_p)
-        if self.solver == "euler":
-            rc = lib.cfm_ode_euler_cnf_mlp_f32(Wp, bp, dims, 4, ptr(xd), B, tsp, n_t, mode, ptr(ed), ptr(traj),
-                                               ctypes.byref(nfe), ptr(ws), stream_ptr())
+        if self.solver in _lib.ODE_SCHEME:
+            rc = lib.cfm_ode_fixed_cnf_mlp_f32(Wp, bp, dims, 4, ptr(xd), B, tsp, n_t, mode, ptr(ed),
+                                               _lib.ODE_SCHEME[self.solver], ptr(traj), ctypes.byref(nfe), ptr(ws),
+                                               stream_ptr())
             steps.value = n_t - 1
-            what = "cfm_ode_euler_cnf_mlp_f32"
+            what = "cfm_ode_fixed_cnf_mlp_f32"
         else:
-            rc = lib.cfm_ode_dopri5_cnf_mlp_f32(Wp, bp, dims, 4, ptr(xd), B, tsp, n_t, mode, ptr(ed), self.atol,
-                                                self.rtol, ptr(traj), ctypes.byref(steps), ctypes.byref(nfe),
-                                                ptr(ws), stream_ptr())
-            what = "cfm_ode_dopri5_cnf_mlp_f32"
+            rc = lib.cfm_ode_adaptive_cnf_mlp_f32(Wp, bp, dims, 4, ptr(xd), B, tsp, n_t, mode, ptr(ed),
+                                                  _lib.ODE_TABLEAU[self.solver], self.atol, self.rtol, ptr(traj),
+                                                  ctypes.byref(steps), ctypes.byref(nfe), ptr(ws), stream_ptr())
+            what = "cfm_ode_adaptive_cnf_mlp_f32"
         if rc == -1:
             return None
         check(rc, what)
@@ -165,16 +193,16 @@ class NeuralODE(torch.nn.Module):
         nfe = ctypes.c_int(0)
         steps = ctypes.c_int(0)
         tsp = ts.ctypes.data_as(ctypes.c_void_p)
-        if self.solver == "euler":
-            check(lib.cfm_ode_euler_mlp_f32(Wp, bp, dims, n, ptr(xd), B, tsp, n_t, ptr(traj),
-                                            ctypes.byref(nfe), ptr(ws), stream_ptr()),
-                  "cfm_ode_euler_mlp_f32")
+        if self.solver in _lib.ODE_SCHEME:
+            check(lib.cfm_ode_fixed_mlp_f32(Wp, bp, dims, n, ptr(xd), B, tsp, n_t, _lib.ODE_SCHEME[self.solver],
+                                            ptr(traj), ctypes.byref(nfe), ptr(ws), stream_ptr()),
+                  "cfm_ode_fixed_mlp_f32")
             steps.value = n_t - 1
         else:
-            check(lib.cfm_ode_dopri5_mlp_f32(Wp, bp, dims, n, ptr(xd), B, tsp, n_t, self.atol,
-                                             self.rtol, ptr(traj), ctypes.byref(steps),
-                                             ctypes.byref(nfe), ptr(ws), stream_ptr()),
-                  "cfm_ode_dopri5_mlp_f32")
+            check(lib.cfm_ode_adaptive_mlp_f32(Wp, bp, dims, n, ptr(xd), B, tsp, n_t, _lib.ODE_TABLEAU[self.solver],
+                                               self.atol, self.rtol, ptr(traj), ctypes.byref(steps),
+                                               ctypes.byref(nfe), ptr(ws), stream_ptr()),
+                  "cfm_ode_adaptive_mlp_f32")
         self.nfe, self.n_steps = nfe.value, steps.value
         return traj.to(x.device)
 
@@ -184,9 +212,10 @@ class NeuralODE(torch.nn.Module):
         ts = torch.as_tensor(t_span, dtype=torch.float32)
         sol = [x]
         self.nfe = 0
-        # a decreasing grid: dopri5 solves g(s, y) = -f(-s, y) on s = -t_span (Euler steps dt < 0 as it is: the
-        # same numbers in fp32)
-        sign = -1.0 if (self.solver == "dopri5" and len(ts) > 1 and float(ts[1]) < float(ts[0])) else 1.0
+        # a decreasing grid: the adaptive solvers integrate g(s, y) = -f(-s, y) on s = -t_span (the fixed-step ones
+        # step dt < 0 as it is: the same numbers in fp32)
+        adaptive = self.solver in ADAPTIVE_TABLEAUS
+        sign = -1.0 if (adaptive and len(ts) > 1 and float(ts[1]) < float(ts[0])) else 1.0
         if sign < 0:
             ts = -ts
 
@@ -203,6 +232,21 @@ class NeuralODE(torch.nn.Module):
                 sol.append(x)
             self.n_steps = len(ts) - 1
             return torch.stack(sol)
+        if not adaptive:
+            tab = FIXED_TABLEAUS[self.solver]
+            for k in range(len(ts) - 1):
+                t, dt = np.float32(ts[k]), np.float32(ts[k + 1] - ts[k])
+                ks = [ev(float(t), x)]
+                for c, row in zip(tab["c"], tab["a"]):
+                    y = x + float(dt) * sum(float(a) * kq for a, kq in zip(row, ks))
+                    ks.append(ev(float(t + np.float32(c) * dt), y))
+                x = x + float(dt) * sum(float(b) * kq for b, kq in zip(tab["b"], ks))
+                sol.append(x)
+            self.n_steps = len(ts) - 1
+            return torch.stack(sol)
+        tab = ADAPTIVE_TABLEAUS[self.solver]
+        tab_a, tab_c, tab_e = tab["a"], tab["c"], tab["e"]
+        order = np.float32(tab["order"])
         atol, rtol = self.atol, self.rtol
         f32 = np.float32
         t, T = f32(ts[0]), f32(ts[-1])
@@ -215,7 +259,7 @@ class NeuralODE(torch.nn.Module):
         if d1 <= 1e-15 and d2 <= 1e-15:
             h1 = max(f32(1e-6), h0 * f32(1e-3))
         else:
-            h1 = f32(f32(0.01) / max(d1, d2)) ** f32(1.0 / 6.0)
+            h1 = f32(f32(0.01) / max(d1, d2)) ** (f32(1.0) / (order + f32(1.0)))
         dt = f32(min(f32(100) * h0, h1))
         ckpt, steps = 1, 0
         while t < T:
@@ -227,10 +271,10 @@ class NeuralODE(torch.nn.Module):
             lands = ckpt < len(ts) and (flag or t + dt == f32(ts[ckpt]))
             ks = [k1]
             for s in range(6):
-                y = x + float(dt) * sum(float(a) * k for a, k in zip(_DP_A[s], ks))
-                ks.append(ev(t + f32(_DP_C[s]) * dt, y))
+                y = x + float(dt) * sum(float(a) * k for a, k in zip(tab_a[s], ks))
+                ks.append(ev(t + f32(tab_c[s]) * dt, y))
             x_new = y
-            err = float(dt) * sum(float(bs - ba) * k for bs, ba, k in zip(_DP_BSOL, _DP_BALT, ks))
+            err = float(dt) * sum(float(e) * k for e, k in zip(tab_e, ks))
             ratio = f32(float(_hairer_norm(err / (atol + rtol * torch.max(x.abs(), x_new.abs())))))
             steps += 1
             if ratio <= 1:
@@ -245,7 +289,7 @@ class NeuralODE(torch.nn.Module):
                 factor = f32(10)
             else:
                 minf = f32(1.0) if ratio < 1 else f32(0.2)
-                factor = min(f32(10), max(f32(0.9) / ratio ** f32(0.2), minf))
+                factor = min(f32(10), max(f32(0.9) / ratio ** (f32(1.0) / order), minf))
             dt = f32(dt * factor)
             if not dt > 1e-12:
                 dt = f32(1e-12)

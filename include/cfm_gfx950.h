@@ -396,6 +396,23 @@ int cfm_ode_dopri5_mlp_f32(const float* const* W, const float* const* b, const i
                            int n_t, float atol, float rtol, float* traj, int* n_steps,
                            int* nfe, void* ws, void* stream);
 
+/* The solver set of torchdyn's odeint behind one selector each.  Replaces NeuralODE(..., solver="tsit5") — torchdyn's
+ * default, and what the runner switches to for every adaptive test-time rollout (runner/src/models/cfm_module.py:313 and
+ * :1055 via FlowSolver.ode_solver) — and torchdyn's fixed-step set "euler" / "midpoint" / "rk4" (torchdyn odeint;
+ * rk4 = the 3/8 rule, "torchdyn-style", unpinned).  tableau: an adaptive 5(4) FSAL pair stepped by the dopri5 driver
+ * above (same controller, order 5); scheme: explicit fixed steps on t_span, nfe = stages * (n_t - 1).
+ * CFM_EINVAL for an unknown selector.  Everything else as cfm_ode_dopri5_mlp_f32 / cfm_ode_euler_mlp_f32, which are
+ * these entries at CFM_ODE_DOPRI5 / CFM_ODE_EULER. */
+enum { CFM_ODE_DOPRI5 = 0, CFM_ODE_TSIT5 = 1 };                          /* tableau */
+enum { CFM_ODE_EULER = 0, CFM_ODE_MIDPOINT = 1, CFM_ODE_RK4 = 2 };       /* scheme */
+int cfm_ode_adaptive_mlp_f32(const float* const* W, const float* const* b, const int* dims,
+                             int n_layers, const float* x0, int B, const float* t_span,
+                             int n_t, int tableau, float atol, float rtol, float* traj, int* n_steps,
+                             int* nfe, void* ws, void* stream);
+int cfm_ode_fixed_mlp_f32(const float* const* W, const float* const* b, const int* dims,
+                          int n_layers, const float* x0, int B, const float* t_span,
+                          int n_t, int scheme, float* traj, int* nfe, void* ws, void* stream);
+
 /* K12 — continuous normalising flow of an MLP field v = MLP([x, t]) (4 linear layers, widths <= 64, dims[0] = d + 1).
  * mode 0: div = tr(dv/dx) (exact); mode 1: div = eps^T (dv/dx) eps (Hutchinson; eps device [B,d], fixed for a solve).
  * Replaces CNF + autograd_trace of examples/2D_tutorials/model-comparison-plotting.ipynb cells 2, 4 and 7, and
@@ -415,6 +432,17 @@ int cfm_ode_dopri5_cnf_mlp_f32(const float* const* W, const float* const* b, con
                                const float* x0, int B, const float* t_span, int n_t, int mode,
                                const float* eps, float atol, float rtol, float* traj, int* n_steps,
                                int* nfe, void* ws, void* stream);
+
+/* The augmented solves with the solver selectors of cfm_ode_adaptive_mlp_f32 / cfm_ode_fixed_mlp_f32 (log-likelihood
+ * under torchdyn's default "tsit5", runner/src/models/cfm_module.py:313, or a fixed-step torchdyn odeint scheme);
+ * cfm_ode_dopri5_cnf_mlp_f32 / cfm_ode_euler_cnf_mlp_f32 are these at CFM_ODE_DOPRI5 / CFM_ODE_EULER. */
+int cfm_ode_adaptive_cnf_mlp_f32(const float* const* W, const float* const* b, const int* dims, int n_layers,
+                                 const float* x0, int B, const float* t_span, int n_t, int mode,
+                                 const float* eps, int tableau, float atol, float rtol, float* traj, int* n_steps,
+                                 int* nfe, void* ws, void* stream);
+int cfm_ode_fixed_cnf_mlp_f32(const float* const* W, const float* const* b, const int* dims, int n_layers,
+                              const float* x0, int B, const float* t_span, int n_t, int mode,
+                              const float* eps, int scheme, float* traj, int* nfe, void* ws, void* stream);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

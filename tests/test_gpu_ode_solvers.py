@@ -1,0 +1,325 @@
+"""GPU (-m gpu): tsit5, midpoint and rk4 on the HIP drivers — against the float64 restatements of tests/ode_rk_ref.py
+(fixtures: tests/golden/ode_solvers_cases.npz), fused kernel against layer-per-kernel path bit for bit, reverse time,
+the augmented (CNF) solves, the wide-field layer driver and the selector entries of the C ABI."""
+import ctypes
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import cfm_oracle as oracle
+import cnf_restate as R
+import ode_rk_ref as rk
+
+pytestmark = pytest.mark.gpu
+
+STAGES = {"euler": 1, "midpoint": 2, "rk4": 4}
+
+
+@pytest.fixture(scope="module")
+def dev():
+    import cfm_amd  # noqa: F401
+    from cfm_amd import _lib
+    _lib.load()
+    d = torch.device("cuda:0")
+    torch.cuda.set_device(d)
+    return d
+
+
+@pytest.fixture(scope="module")
+def cases(golden_dir):
+    g = np.load(os.path.join(golden_dir, "ode_solvers_cases.npz"))
+    for k in ("g", "c", "l"):           # the condition on the fixture: no accept can legitimately flip in fp32
+        assert rk.ratios_clear_of_one(g[f"{k}_tsit5_log"]), k
+    return g
+
+
+def _seeded_mlp(d, w, seed):
+    torch.manual_seed(seed)
+    lins = [torch.nn.Linear(d + 1, w), torch.nn.Linear(w, w), torch.nn.Linear(w, w), torch.nn.Linear(w, d)]
+    return [l.weight.detach().numpy().copy() for l in lins], [l.bias.detach().numpy().copy() for l in lins]
+
+
+def _node(Ws, bs, solver, tol, dev, cnf=False, **kw):
+    import cfm_amd
+    from cfm_amd.ode import NeuralODE
+    from cfm_amd.utils import torch_wrapper
+    m = R.make_mlp(Ws, bs, dev)
+    vf = cfm_amd.CNF(m, **kw) if cnf else torch_wrapper(m)
+    return NeuralODE(vf, solver=solver, atol=tol, rtol=tol)
+
+
+def _aug0(x):
+    return torch.cat([torch.zeros(x.shape[0], 1), x], 1)
+
+
+def _close(tr, ref, what):
+    err, scale = np.abs(tr - ref).max(), np.abs(ref).max()
+    print(what, "max |diff| / max |ref| =", err / scale)
+    assert err <= 1e-5 * scale, (what, err / scale)
+
+
+# ---------------------------------------------------------------------------------------- against the restatement
+def test_golden_mlp_vs_restatement(dev, cases, golden_dir):
+    d = np.load(os.path.join(golden_dir, "ode_cases.npz"))
+    Ws, bs = [d[f"W{k}"] for k in range(4)], [d[f"b{k}"] for k in range(4)]
+    x, ts = torch.from_numpy(d["x"]), torch.from_numpy(d["t_span"])
+    node = _node(Ws, bs, "tsit5", 1e-4, dev)
+    tr = node.trajectory(x, ts).cpu().numpy()
+    assert node.last_path == "hip"
+    assert (node.n_steps, node.nfe) == (int(cases["g_tsit5_steps"]), int(cases["g_tsit5_nfe"])), (node.n_steps, node.nfe)
+    _close(tr, cases["g_tsit5"], "tsit5")
+    np.testing.assert_array_equal(tr[0], d["x"])
+    for solver in ("midpoint", "rk4"):
+        node = _node(Ws, bs, solver, 1e-4, dev)
+        tr = node.trajectory(x, ts).cpu().numpy()
+        assert node.last_path == "hip" and (node.n_steps, node.nfe) == (len(ts) - 1, STAGES[solver] * (len(ts) - 1))
+        _close(tr, cases[f"g_{solver}"], solver)
+
+
+@pytest.mark.parametrize("solver", ["tsit5", "midpoint", "rk4"])
+def test_c5_shape_vs_restatement(dev, cases, solver):
+    """B = 8192, 51-64-64-64-50, linspace(0, 1, 100), atol = rtol = 1e-4: the restatement is integrated here (the
+    full trajectory is too large to record) and must reproduce the recorded log / last-frame rows."""
+    Ws, bs = _seeded_mlp(50, 64, 0)
+    x0, _ = oracle.config_inputs("C5")
+    ts = torch.from_numpy(np.linspace(0, 1, 100).astype(np.float32))     # the generator's grid, to the bit
+    f = lambda t, y: oracle.mlp_forward_f64(Ws, bs, y, t)
+    node = _node(Ws, bs, solver, 1e-4, dev)
+    tr = node.trajectory(x0, ts).cpu().numpy()
+    assert node.last_path == "hip" and tr.shape == (100, 8192, 50)
+    if solver == "tsit5":
+        ref, info = rk.adaptive_trajectory(f, x0.numpy(), ts.numpy(), 1e-4, 1e-4, "tsit5", return_log=True)
+        rk.assert_same_log(info["log"], cases["c_tsit5_log"])
+        assert (info["steps"], info["nfe"]) == (int(cases["c_tsit5_steps"]), int(cases["c_tsit5_nfe"]))
+        assert (node.n_steps, node.nfe) == (info["steps"], info["nfe"]), (node.n_steps, node.nfe, info["steps"], info["nfe"])
+    else:
+        ref = rk.fixed_trajectory(f, x0.numpy(), ts.numpy(), solver)
+        assert (node.n_steps, node.nfe) == (99, STAGES[solver] * 99)
+    assert np.abs(ref[-1, :256] - cases[f"c_{solver}_last"]).max() <= 1e-10 * np.abs(ref[-1]).max()
+    _close(tr, ref, solver)
+
+
+def test_wide_field_tsit5_vs_restatement(dev, cases):
+    """d = 784, w = 512: the layer-per-kernel driver (weights regenerated from the seed, guarded by a checksum)."""
+    Ws, bs = _seeded_mlp(784, 512, 5)
+    assert abs(float(np.abs(Ws[0]).sum()) - float(cases["l_W0_checksum"])) <= 1e-6 * float(cases["l_W0_checksum"])
+    g = torch.Generator().manual_seed(17)
+    x = torch.randn(24, 784, generator=g)
+    ts = torch.from_numpy(np.linspace(0, 1, 4).astype(np.float32))
+    node = _node(Ws, bs, "tsit5", 1e-4, dev)
+    tr = node.trajectory(x, ts).cpu().numpy()
+    assert node.last_path == "hip"
+    assert (node.n_steps, node.nfe) == (int(cases["l_tsit5_steps"]), int(cases["l_tsit5_nfe"])), (node.n_steps, node.nfe)
+    _close(tr, cases["l_tsit5"].astype(np.float64), "wide tsit5")
+
+
+# ---------------------------------------------------------------------------------------- fused == layer path
+@pytest.mark.parametrize("B,d,w,n_t", [(300, 2, 64, 25), (257, 50, 64, 12), (64, 63, 33, 4), (8192, 50, 64, 6),
+                                        (8231, 3, 48, 5), (20000, 2, 64, 4)])
+def test_fused_small_field_equals_layer_path(dev, B, d, w, n_t):
+    """The shapes of test_ode_fused_small_field_equals_layer_path (x / k1 resident in registers up to B = 8192, streamed
+    above: the last two cases).  On the register-staged layer core (cfm_mlp_set_glds(0)) the fused kernels and the
+    layer-per-kernel drivers run the same fp32 arithmetic in the same order: trajectories, nfe and n_steps are equal bit
+    for bit, for tsit5, midpoint and rk4 (and still for euler through the generalised kernel)."""
+    import cfm_amd
+    from cfm_amd import _lib
+    from cfm_amd.ode import NeuralODE
+    from cfm_amd.utils import torch_wrapper
+    lib = _lib.load()
+    torch.manual_seed(3)
+    model = cfm_amd.MLP(dim=d, time_varying=True, w=w).to(dev)
+    x = torch.randn(B, d, generator=torch.Generator().manual_seed(9)).to(dev)
+    ts = torch.linspace(0, 1, n_t, device=dev)
+    out = {}
+    glds0 = lib.cfm_mlp_get_glds()
+    try:
+        lib.cfm_mlp_set_glds(0)
+        for fused in (1, 0):
+            lib.cfm_ode_set_fused(fused)
+            for solver in ("tsit5", "midpoint", "rk4", "euler"):
+                node = NeuralODE(torch_wrapper(model), solver=solver, atol=1e-4, rtol=1e-4)
+                out[(fused, solver)] = (node.trajectory(x, ts).cpu(), node.nfe, node.n_steps)
+                assert node.last_path == "hip"
+    finally:
+        lib.cfm_ode_set_fused(1); lib.cfm_mlp_set_glds(glds0)
+    for solver in ("tsit5", "midpoint", "rk4", "euler"):
+        a, b = out[(1, solver)], out[(0, solver)]
+        assert a[1] == b[1] and a[2] == b[2], (solver, a[1:], b[1:])
+        assert torch.equal(a[0], b[0]), (solver, float((a[0] - b[0]).abs().max()))
+        assert bool(torch.isfinite(a[0]).all())
+
+
+# ---------------------------------------------------------------------------------------- reverse time
+@pytest.mark.parametrize("fused", [True, False])
+@pytest.mark.parametrize("d,w", [(2, 64), (5, 32)])
+def test_reverse_tsit5_is_the_negated_mlp_forward_solve(dev, d, w, fused):
+    from cfm_amd import _lib
+    lib = _lib.load()
+    Ws, bs = R.mlp_params(d, w, seed=7 + d)
+    Wn, bn = R.negated_mlp_params(Ws, bs)
+    torch.manual_seed(3)
+    x = torch.randn(300, d)
+    ts = torch.tensor([1.0, 0.7, 0.25, 0.0])
+    lib.cfm_ode_set_fused(1 if fused else 0)
+    try:
+        a = _node(Ws, bs, "tsit5", 1e-5, dev)
+        ta = a.trajectory(x, ts).cpu()
+        b = _node(Wn, bn, "tsit5", 1e-5, dev)
+        tb = b.trajectory(x, -ts).cpu()
+        fixed = {}
+        for solver in ("midpoint", "rk4"):
+            fixed[solver] = (_node(Ws, bs, solver, 1e-5, dev).trajectory(x, ts).cpu(),
+                             _node(Wn, bn, solver, 1e-5, dev).trajectory(x, -ts).cpu())
+    finally:
+        lib.cfm_ode_set_fused(1)
+    assert a.last_path == "hip" and ta.shape == (4, 300, d)
+    assert torch.equal(ta, tb) and (a.n_steps, a.nfe) == (b.n_steps, b.nfe)
+    # The controller is free here (8 attempts for 3 intervals, one rejected at d = 2): same attempts as the restatement,
+    # whose log keeps clear of 1.  The step sizes come from an error estimate that is a cancellation, so fp32 and float64
+    # stage values give slightly different dt, and two solves with different dt differ by their integration errors:
+    # the bound is the parity bar plus the restatement's own distance from a converged solve (the form of the bound on l
+    # in tests/test_gpu_cnf.py).
+    G = R.reverse(R.mlp_field_np(Ws, bs))
+    ref, info = rk.adaptive_trajectory(G, x.numpy(), -ts.numpy(), 1e-5, 1e-5, "tsit5", return_log=True)
+    assert rk.ratios_clear_of_one(info["log"])
+    assert (a.n_steps, a.nfe) == (info["steps"], info["nfe"]), (a.n_steps, a.nfe, info["steps"], info["nfe"])
+    own = np.abs(ref - rk.adaptive_trajectory(G, x.numpy(), -ts.numpy(), 1e-10, 1e-10, "tsit5")).max()
+    err = np.abs(ta.numpy() - ref).max()
+    print("reverse tsit5: |diff| / max|ref| =", err / np.abs(ref).max(), "restatement's own error:", own / np.abs(ref).max())
+    assert err <= 1e-5 * np.abs(ref).max() + own
+    for solver, (fa, fb) in fixed.items():          # dt < 0 steps backward: the same numbers
+        assert torch.equal(fa, fb), solver
+        _close(fa.numpy(), rk.fixed_trajectory(R.mlp_field_np(Ws, bs), x.numpy(), ts.numpy(), solver), "reverse " + solver)
+
+
+# ---------------------------------------------------------------------------------------- CNF
+@pytest.mark.parametrize("estimator", ["exact", "hutch_rademacher"])
+@pytest.mark.parametrize("solver", ["tsit5", "rk4"])
+@pytest.mark.parametrize("d,w,B", [(2, 64, 700), (3, 64, 9000)])
+def test_log_likelihood_on_the_hip_path_vs_generic(dev, monkeypatch, solver, estimator, d, w, B):
+    """log_likelihood(solver=...) runs in the augmented HIP drivers and agrees with the torch.func generic path under
+    the same solver within the CNF tests' tolerance (test_augmented_dopri5_smooth_field_l_to_1e5: x and l to 1e-5, on a
+    field whose SELUs stay on their smooth branch).  B = 9000: the streamed form of the adaptive kernel."""
+    import cfm_amd
+    from cfm_amd import _lib
+    from cfm_amd.ode import NeuralODE
+    lib = _lib.load()
+    Ws, bs = R.smooth_mlp_params(d, w, seed=90 + d + w)
+    m = R.make_mlp(Ws, bs, dev)
+    torch.manual_seed(9)
+    x = 0.5 * torch.randn(B, d)
+    eps = torch.randint(0, 2, (B, d)).float() * 2 - 1 if estimator != "exact" else None
+    ts = torch.linspace(1, 0, 9) if solver == "rk4" else torch.tensor([1.0, 0.0])
+    paths = []
+    orig = NeuralODE.trajectory
+
+    def spy(self, *a, **k):
+        out = orig(self, *a, **k)
+        paths.append((self.solver, self.last_path, self.nfe, self.n_steps))
+        return out
+    monkeypatch.setattr(NeuralODE, "trajectory", spy)
+    lp, z = cfm_amd.log_likelihood(m, x.to(dev), t_span=ts, solver=solver, atol=1e-5, rtol=1e-5, estimator=estimator,
+                                   noise=eps, return_z=True)
+    assert paths[-1][:2] == (solver, "hip"), paths
+    if solver == "rk4":
+        assert paths[-1][2:] == (4 * 8, 8)
+    else:
+        assert paths[-1][2] == 2 + 6 * paths[-1][3]
+    node = _node(Ws, bs, solver, 1e-5, dev, cnf=True, estimator=estimator, noise=eps)
+    tr = node.trajectory(_aug0(x), ts).cpu()
+    assert node.last_path == "hip"
+    assert torch.equal(tr[-1][:, 1:], z.cpu())
+    last = tr[-1].to(dev)                                       # (the prior's sum where log_likelihood takes it)
+    assert torch.equal(cfm_amd.cnf.standard_normal_log_prob(last[:, 1:]) - last[:, 0], lp)
+    assert float(tr[..., 1:].abs().max()) < 3.0                 # inside the box where every pre-activation is < 0
+    lib.cfm_ode_set_fused(0)
+    try:
+        gen = _node(Ws, bs, solver, 1e-5, dev, cnf=True, estimator=estimator, noise=eps)
+        g = gen.trajectory(_aug0(x), ts).cpu()
+    finally:
+        lib.cfm_ode_set_fused(1)
+    assert gen.last_path == "generic"
+    tr, g = tr.numpy(), g.numpy()
+    sl = np.abs(tr[..., 0]).max()
+    ex, el = np.abs(g[..., 1:] - tr[..., 1:]).max() / np.abs(tr[..., 1:]).max(), np.abs(g[..., 0] - tr[..., 0]).max() / sl
+    print(solver, estimator, B, "x:", ex, "l:", el, "steps hip / generic:", node.n_steps, gen.n_steps)
+    assert sl > 1e-3 and ex <= 1e-5 and el <= 1e-5, (ex, el)
+
+
+# ---------------------------------------------------------------------------------------- C ABI
+def _abi_args(dev, B=64, d=2, w=64, n_t=5):
+    import cfm_amd
+    from cfm_amd import _lib
+    torch.manual_seed(1)
+    m = cfm_amd.MLP(dim=d, time_varying=True, w=w).to(dev)
+    Wp, bp, dims, keep = m.hip_params(dev)
+    x = torch.randn(B, d, device=dev)
+    ts = np.linspace(0, 1, n_t).astype(np.float32)
+    ws = _lib.workspace(_lib.OP_ODE, B, w, d + 1, dev)
+    return m, Wp, bp, dims, keep, x, ts, ws
+
+
+def test_abi_unknown_selector_is_einval(dev):
+    from cfm_amd import _lib
+    from cfm_amd._lib import ptr, stream_ptr
+    lib = _lib.load()
+    m, Wp, bp, dims, keep, x, ts, ws = _abi_args(dev)
+    B, d = x.shape
+    tsp = ts.ctypes.data_as(ctypes.c_void_p)
+    traj = torch.zeros((len(ts), B, d + 1), device=dev)
+    xa = torch.cat([torch.zeros(B, 1, device=dev), x], 1).contiguous()
+    nfe, steps = ctypes.c_int(0), ctypes.c_int(0)
+    for bad in (-1, 2, 7):
+        assert lib.cfm_ode_adaptive_mlp_f32(Wp, bp, dims, 4, ptr(x), B, tsp, len(ts), bad, 1e-4, 1e-4, ptr(traj),
+                                            ctypes.byref(steps), ctypes.byref(nfe), ptr(ws), stream_ptr()) == -1
+        assert lib.cfm_ode_adaptive_cnf_mlp_f32(Wp, bp, dims, 4, ptr(xa), B, tsp, len(ts), 0, None, bad, 1e-4, 1e-4,
+                                                ptr(traj), ctypes.byref(steps), ctypes.byref(nfe), ptr(ws),
+                                                stream_ptr()) == -1
+    for bad in (-1, 3, 9):
+        assert lib.cfm_ode_fixed_mlp_f32(Wp, bp, dims, 4, ptr(x), B, tsp, len(ts), bad, ptr(traj), ctypes.byref(nfe),
+                                         ptr(ws), stream_ptr()) == -1
+        assert lib.cfm_ode_fixed_cnf_mlp_f32(Wp, bp, dims, 4, ptr(xa), B, tsp, len(ts), 0, None, bad, ptr(traj),
+                                             ctypes.byref(nfe), ptr(ws), stream_ptr()) == -1
+    torch.cuda.synchronize()
+    assert float(traj.abs().max()) == 0.0                       # refused before anything was written
+
+
+def test_abi_old_entries_are_the_new_ones_at_dopri5_and_euler(dev):
+    from cfm_amd import _lib
+    from cfm_amd._lib import ptr, stream_ptr
+    lib = _lib.load()
+    assert _lib.ODE_TABLEAU == {"dopri5": 0, "tsit5": 1} and _lib.ODE_SCHEME == {"euler": 0, "midpoint": 1, "rk4": 2}
+    m, Wp, bp, dims, keep, x, ts, ws = _abi_args(dev, B=500, d=5, w=48, n_t=6)
+    B, d = x.shape
+    tsp = ts.ctypes.data_as(ctypes.c_void_p)
+    a, b = torch.zeros((len(ts), B, d), device=dev), torch.zeros((len(ts), B, d), device=dev)
+    na, nb, sa, sb = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    assert lib.cfm_ode_dopri5_mlp_f32(Wp, bp, dims, 4, ptr(x), B, tsp, len(ts), 1e-5, 1e-5, ptr(a), ctypes.byref(sa),
+                                      ctypes.byref(na), ptr(ws), stream_ptr()) == 0
+    assert lib.cfm_ode_adaptive_mlp_f32(Wp, bp, dims, 4, ptr(x), B, tsp, len(ts), 0, 1e-5, 1e-5, ptr(b), ctypes.byref(sb),
+                                        ctypes.byref(nb), ptr(ws), stream_ptr()) == 0
+    torch.cuda.synchronize()
+    assert torch.equal(a, b) and (sa.value, na.value) == (sb.value, nb.value) and na.value == 2 + 6 * sa.value
+    assert lib.cfm_ode_euler_mlp_f32(Wp, bp, dims, 4, ptr(x), B, tsp, len(ts), ptr(a), ctypes.byref(na), ptr(ws),
+                                     stream_ptr()) == 0
+    assert lib.cfm_ode_fixed_mlp_f32(Wp, bp, dims, 4, ptr(x), B, tsp, len(ts), 0, ptr(b), ctypes.byref(nb), ptr(ws),
+                                     stream_ptr()) == 0
+    torch.cuda.synchronize()
+    assert torch.equal(a, b) and na.value == nb.value == len(ts) - 1
+    # the augmented pair
+    xa = torch.cat([torch.zeros(B, 1, device=dev), x], 1).contiguous()
+    a, b = torch.zeros((len(ts), B, d + 1), device=dev), torch.zeros((len(ts), B, d + 1), device=dev)
+    assert lib.cfm_ode_dopri5_cnf_mlp_f32(Wp, bp, dims, 4, ptr(xa), B, tsp, len(ts), 0, None, 1e-5, 1e-5, ptr(a),
+                                          ctypes.byref(sa), ctypes.byref(na), ptr(ws), stream_ptr()) == 0
+    assert lib.cfm_ode_adaptive_cnf_mlp_f32(Wp, bp, dims, 4, ptr(xa), B, tsp, len(ts), 0, None, 0, 1e-5, 1e-5, ptr(b),
+                                            ctypes.byref(sb), ctypes.byref(nb), ptr(ws), stream_ptr()) == 0
+    torch.cuda.synchronize()
+    assert torch.equal(a, b) and (sa.value, na.value) == (sb.value, nb.value)
+    assert lib.cfm_ode_euler_cnf_mlp_f32(Wp, bp, dims, 4, ptr(xa), B, tsp, len(ts), 0, None, ptr(a), ctypes.byref(na),
+                                         ptr(ws), stream_ptr()) == 0
+    assert lib.cfm_ode_fixed_cnf_mlp_f32(Wp, bp, dims, 4, ptr(xa), B, tsp, len(ts), 0, None, 0, ptr(b), ctypes.byref(nb),
+                                         ptr(ws), stream_ptr()) == 0
+    torch.cuda.synchronize()
+    assert torch.equal(a, b) and na.value == nb.value == len(ts) - 1
