@@ -152,7 +152,7 @@ extern "C" void cfm_assign_set_async(int on, int blocks, int last_div) {
     std::lock_guard<std::mutex> lk(g_params_mu);
     g_params.async_auction = on < 0 ? 0 : (on > 2 ? 2 : on);        // 1: the epsilon > 0 phases; 2: the epsilon = 0 rounds too
     if (blocks >= 0) g_params.async_blocks = blocks;
-    if (last_div > 0) g_params.async_last_div = last_div;      // (bits 8+: see asg_run)
+    if (last_div > 0) g_params.async_last_div = last_div;      // (bits 8+: see asg_pack_pad0)
 }
 extern "C" void cfm_assign_set_async_min_n(int n) { std::lock_guard<std::mutex> lk(g_params_mu); if (n >= 64) g_params.async_min_n = n; }
 extern "C" void cfm_assign_get_async(int* out3) {
@@ -1602,7 +1602,7 @@ __global__ __launch_bounds__(WT) void asg_step(AsgWs w0, int n_host, int par, si
 // The only products of this kernel are the keys (prices), the bid lists and a few counters.
 // Residency: the phases wait for workgroups that have not started yet (a slot never written counts as "all rows
 // unmatched") — but only for ASG_ASYNC_GRACE looks of the controller, so two auction grids from different streams that
-// each hold a part of the chip cannot stall each other for long; the grid is capped at the CU count (asg_run).  Every
+// each hold a part of the chip cannot stall each other for long; the grid is capped at the CU count (asg_size).  Every
 // loop is capped.
 #define ASG_ASYNC_ITER_CAP 60000
 // Looks of the controller during which a workgroup that has not started counts as "all rows unmatched".  Its only purpose
@@ -1613,7 +1613,7 @@ __global__ __launch_bounds__(WT) void asg_step(AsgWs w0, int n_host, int par, si
 // fallback, 10-20 ms.  Measured (profiles/r5_async_sweep.txt): 64 looks: one region in three at 1.3-2.05 ms per step;
 // 8192 looks: none above 1.1 in 33 regions but one (1.32).
 #define ASG_ASYNC_GRACE 8192
-#define ASG_GROUPS_MAX 512     // row groups of an auction grid (= its gridDim.x: <= 512, asg_run)
+#define ASG_GROUPS_MAX 512     // row groups of an auction grid (= its gridDim.x: <= 512, asg_size)
 #define ASG_ADOPT_AFTER 8      // iterations (~5 us each) after which a running workgroup starts adopting unclaimed groups, one per iteration
 // wave-uniform values that came out of vector loads: into scalar registers (the loop carries a dozen of them)
 __device__ __forceinline__ double asg_uni_d(double v) {
@@ -1862,482 +1862,11 @@ __global__ void asg_trivial(const float* M, int n, int* perm, int* certified, do
     }
 }
 
-// ------------------------------------------------------------------ host -----
-// The kernels take only workspace-derived arguments, so the launch programs are captured once per
-// host thread / workspace into hipGraphs and replayed (a solve is ~200 launches; with several
-// couplings in flight on different streams the host launch rate would be the limit).  Falls back
-// to plain launches when the stream cannot be captured (the legacy default stream) or CFM_ASG_GRAPH=0.
-//   PRG_BULK   `bulk` x asg_step                                  (unpolled head of a solve)
-//   PRG_CHUNK  `chunk` x asg_step, asg_build, asg_solve, 2 x asg_step   (polled; progresses from any state)
-enum { PRG_CHUNK = 0, PRG_BULK = 1, PRG_COUNT = 2 };
-struct AsgGraph {
-    void* ws = nullptr; int n = 0, nb = 0, chunk = 0, bulk = 0, blocks = 0, sparse = 0;
-    hipGraphExec_t exec[PRG_COUNT] = {nullptr, nullptr};
-    hipStream_t stream = nullptr; int disabled = 0;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    int ev_blocking = -1;          // how ev[] were created (this thread's g_blocking_sync at the time)
-};
-// A host thread keeps the programs of its last few (workspace, size, batch, stream) combinations: a training loop
-// alternates between a few of them (groups of couplings and a shorter last group, single solves), and capturing +
-// instantiating the two programs costs milliseconds.
-#define ASG_GRAPH_SLOTS 4
-static thread_local AsgGraph g_graphs[ASG_GRAPH_SLOTS];
-static thread_local unsigned g_graph_use[ASG_GRAPH_SLOTS];
-static thread_local unsigned g_graph_clock = 0;
-static thread_local int g_graph_off = 0;      // this thread's streams cannot be captured: plain launches from now on
-// The host wait of a solve (ONE per solve since round 5): with HIP's default an event wait SPINS on a host core; a
-// coupling worker of a training loop (cfm_amd.prefetch: 3 per rank, 8 ranks per node) burns a core each for the whole
-// solve.  cfm_set_blocking_sync(1) makes this THREAD's solver waits yield: its events carry hipEventBlockingSync AND the
-// wait itself is a poll (hipEventQuery) with a 20 us sleep in between — on this stack (ROCm 7, torch 2.10) a
-// "blocking" event wait was measured to spin exactly like the default (tools/probe/blocking_sync_probe.py: thread CPU
-// time == wall time for torch.cuda.Event(blocking=True) and for hipEventBlockingSync alike), so the flag alone buys
-// nothing.  The poll notices completion up to one sleep (~60 us with the kernel's timer slack) late — once per job of
-// several couplings, not per step.  Thread-local: a latency-critical lone solve on the caller's own thread keeps the spin.
-static thread_local int g_blocking_sync = 0;
-extern "C" void cfm_set_blocking_sync(int on) { g_blocking_sync = on ? 1 : 0; }
-static hipError_t asg_wait(hipEvent_t ev) {
-    if (!g_blocking_sync) return hipEventSynchronize(ev);
-    for (;;) {
-        const hipError_t e = hipEventQuery(ev);
-        if (e != hipErrorNotReady) return e;
-        (void)hipGetLastError();                  // (hipErrorNotReady is sticky in hipGetLastError otherwise)
-        struct timespec ts = {0, 20000};
-        nanosleep(&ts, nullptr);
-    }
-}
-static hipError_t asg_events(AsgGraph& G) {
-    if (G.ev_blocking != g_blocking_sync) {
-        for (int q = 0; q < 2; ++q) if (G.ev[q]) { (void)hipEventDestroy(G.ev[q]); G.ev[q] = nullptr; }
-        G.ev_blocking = g_blocking_sync;
-    }
-    const unsigned flags = hipEventDisableTiming | (g_blocking_sync ? hipEventBlockingSync : 0u);
-    for (int q = 0; q < 2; ++q)
-        if (!G.ev[q]) { hipError_t e = hipEventCreateWithFlags(&G.ev[q], flags); if (e != hipSuccess) return e; }
-    return hipSuccess;
-}
-static AsgGraph& asg_graph_slot(void* ws, int n, int nb, hipStream_t s) {
-    int hit = -1, lru = 0;
-    for (int q = 0; q < ASG_GRAPH_SLOTS; ++q) {
-        const AsgGraph& G = g_graphs[q];
-        if (G.exec[0] && G.ws == ws && G.n == n && G.nb == nb && G.stream == s) hit = q;
-        if (g_graph_use[q] < g_graph_use[lru]) lru = q;
-    }
-    const int q = hit >= 0 ? hit : lru;
-    g_graph_use[q] = ++g_graph_clock;
-    return g_graphs[q];
-}
-
-static int asg_graph_enabled() {
-    static const int v = [] { const char* e = getenv("CFM_ASG_GRAPH"); return (e && e[0] == '0') ? 0 : 1; }();
-    return v;
-}
-
-// dynamic LDS above the 64 KiB default needs the attribute: once per device
-static int asg_raise_lds() {
-    static std::once_flag once[16];
-    static int ok[16];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = 0;
-    std::call_once(once[dev], [dev] {
-        hipError_t e1 = hipFuncSetAttribute((const void*)asg_step, hipFuncAttributeMaxDynamicSharedMemorySize, 112 * 1024);
-        if (e1 == hipSuccess) e1 = hipFuncSetAttribute((const void*)asg_auction, hipFuncAttributeMaxDynamicSharedMemorySize, 112 * 1024);
-        hipError_t e2 = hipFuncSetAttribute((const void*)asg_build, hipFuncAttributeMaxDynamicSharedMemorySize, 136 * 1024);
-        hipError_t e3 = hipFuncSetAttribute((const void*)asg_solve, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        ok[dev] = (e1 == hipSuccess ? 1 : 0) | (e2 == hipSuccess && e3 == hipSuccess ? 2 : 0);
-        (void)hipGetLastError();
-    });
-    return ok[dev];
-}
-
-// poll buffer (pinned host memory): one per host thread, concurrent solves on different streams
-// must not share it
-static thread_local int* g_pinned = nullptr;
-static thread_local int g_small_last[16];      // status block of this thread's last one-workgroup solve (phase times)
-// tuning aid: {solves of this PROCESS that the dense state machine had to redo, last device error code} — process-wide
-// since round 6: the couplings of a training loop run on prefetch worker threads, and the bench line reports the count
-struct AsgFallback {
-    std::atomic<int> v[2];
-    struct Ref { std::atomic<int>& a; Ref& operator=(int x) { a.store(x, std::memory_order_relaxed); return *this; }
-                 Ref& operator++() { a.fetch_add(1, std::memory_order_relaxed); return *this; } };
-    Ref operator[](int q) { return Ref{v[q]}; }
-};
-static AsgFallback g_fallback;
-extern "C" void cfm_assign_debug_fallback(int* out2) { out2[0] = g_fallback.v[0].load(); out2[1] = g_fallback.v[1].load(); }
-extern "C" void cfm_assign_debug_small(int* out16) { for (int q = 0; q < 16; ++q) out16[q] = g_small_last[q]; }
-
-// CUs the stream may use: the device's count, or the population of its CU mask (hipExtStreamCreateWithCUMask streams).
-// Cached per host thread for its last few streams (the query is a host-side lookup, but it sits on every solve's path).
-static int asg_stream_cus(hipStream_t s) {
-    static int cus[CFM_MAX_DEVICES];
-    const int di = cfm_device_index();
-    int& c = cus[di];
-    if (c <= 0 && (hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, di) != hipSuccess || c <= 0)) c = 256;
-    if (!s) return c;
-    static thread_local struct { hipStream_t s; int dev, n; } cache[4];
-    static thread_local unsigned clock_ = 0;
-    for (auto& e : cache) if (e.s == s && e.dev == di && e.n > 0) return e.n;
-    uint32_t mask[16] = {0};
-    int n = c;
-    if (hipExtStreamGetCUMask(s, 16, mask) == hipSuccess) {
-        int pop = 0;
-        for (int q = 0; q < 16; ++q) pop += __builtin_popcount(mask[q]);
-        if (pop > 0 && pop < n) n = pop;
-    } else (void)hipGetLastError();
-    auto& e = cache[clock_++ & 3];
-    e.s = s; e.dev = di; e.n = n;
-    return n;
-}
-
-struct AsgLaunch {
-    AsgWs w; int n, blocks, blocks_build, nb; size_t stride; size_t lds_step, lds_build, lds_solve; int sparse; hipStream_t s;
-    int async_auction = 0, blocks_auction = 0;
-    // every program holds an EVEN number of asg_step launches and starts on an even launch count, so the parity
-    // argument (which control record a bid round reads, see AucCtl) is the position inside the program.
-    // grid.y = the problems of a batch (one carving each, `stride` bytes apart)
-    void step(int par) const { hipLaunchKernelGGL(asg_step, dim3(blocks, nb), dim3(WT), lds_step, s, w, n, par & 1, stride); }
-    void program(int prg, int chunk, int bulk) const {
-        int k = 0;
-        // asynchronous phase A: ONE launch behind the two init steps (a no-op in any other state, like every kernel here)
-        auto auction = [&]() { if (async_auction) hipLaunchKernelGGL(asg_auction, dim3(blocks_auction, nb), dim3(WT), lds_step, s, w, n, stride); };
-        if (prg == PRG_BULK) {
-            if (async_auction >= 2 && sparse) {
-                // The WHOLE solve as the unpolled head when the bid rounds (epsilon > 0 and epsilon = 0) are the one auction
-                // launch and the list solver closes the search: 2 init steps, the auction, convert / row minima / column
-                // reduction (+ one spare step: an even count), list build, list solver, certificate (+ one spare).  A solve
-                // that takes this road — every C3 instance seen so far — is finished when the head is; the others are
-                // picked up by the polled chunks.  (Round 4's head was 96 steps, then chunks of 10 steps + the pair + 2: a
-                // lone solve paid ~35 no-op launches, 0.15 ms, around its list build and behind its last step.)
-                step(k++); step(k++);
-                auction();
-                step(k++); step(k++); step(k++); step(k++);
-                hipLaunchKernelGGL(asg_build, dim3(blocks_build, nb), dim3(SP_BUILD_WAVES * 64), lds_build, s, w, n, stride);
-                hipLaunchKernelGGL(asg_solve, dim3(1, nb), dim3(SP_T), lds_solve, s, w, n, stride);
-                step(k++); step(k++);
-                return;
-            }
-            for (int c = 0; c < bulk; ++c) { if (c == 2) auction(); step(k++); }
-            return;
-        }
-        auction();
-        for (int c = 0; c < chunk; ++c) step(k++);
-        if (sparse) {
-            hipLaunchKernelGGL(asg_build, dim3(blocks_build, nb), dim3(SP_BUILD_WAVES * 64), lds_build, s, w, n, stride);
-            hipLaunchKernelGGL(asg_solve, dim3(1, nb), dim3(SP_T), lds_solve, s, w, n, stride);
-            step(k++); step(k++);      // certificate + whatever the guess missed
-        }
-    }
-    int count(int prg, int chunk, int bulk) const {
-        if (prg == PRG_BULK && async_auction >= 2 && sparse) return bulk > 0 ? 11 : 0;
-        return (prg == PRG_BULK ? bulk : chunk + (sparse ? 4 : 0)) + ((async_auction && (prg != PRG_BULK || bulk > 2)) ? 1 : 0);
-    }
-};
-
 // the first 64 bytes of every problem's state block, gathered for ONE copy to the host
 __global__ void asg_collect(const AsgState* st0, size_t stride, int nb, int* out) {
     const int b = threadIdx.x >> 4, q = threadIdx.x & 15;
     if (b < nb) out[16 * b + q] = reinterpret_cast<const int*>(reinterpret_cast<const char*>(st0) + stride * b)[q];
 }
 
-struct AsgProblem { const float* M; int* perm; int* certified; double* total_cost; int* stats; };
-#define ASG_BATCH_MAX 16
-#define ASG_PINNED_INTS (2 * ASG_BATCH_MAX * 16)
-
-static int asg_pinned() {
-    if (g_pinned) return 0;
-    return cfm_hip(hipHostMalloc((void**)&g_pinned, ASG_PINNED_INTS * sizeof(int), hipHostMallocDefault));
-}
-
-// Solves nb problems of the same size on one chain of launches (grid.y = problem).  cert_out[b] / err_out[b]: the
-// certificate and the device error code of problem b (0 = none).  nb == 1: the plain solve.
-static int asg_run(const AsgProblem* pr, int nb, int B, void* ws, size_t stride, void* stream, const AsgParams& P,
-                   int use_sparse, int* cert_out, int* err_out) {
-    if (!pr || nb < 1 || nb > ASG_BATCH_MAX || B < 0 || (B > 1 && !ws)) return CFM_EINVAL;
-    for (int b = 0; b < nb; ++b) if (!pr[b].M || !pr[b].perm) return CFM_EINVAL;
-    if (B > (1 << 20)) return CFM_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    for (int b = 0; b < nb; ++b) { cert_out[b] = 1; err_out[b] = 0; }
-    if (B == 0) return 0;
-    if (B == 1) {
-        for (int b = 0; b < nb; ++b)
-            hipLaunchKernelGGL(asg_trivial, dim3(1), dim3(64), 0, s, pr[b].M, B, pr[b].perm, pr[b].certified, pr[b].total_cost, pr[b].stats);
-        return cfm_status();
-    }
-    if (((uintptr_t)ws & 15) != 0 || (stride & 15) != 0) return CFM_EALIGN;
-    for (int b = 0; b < nb; ++b) if (((uintptr_t)pr[b].M & 15) != 0) return CFM_EALIGN;
-    const int n = B;
-    AsgLaunch L;
-    L.w = asg_carve(ws, n); L.n = n; L.s = s; L.nb = nb; L.stride = nb > 1 ? stride : 0;
-    int rc = asg_pinned();
-    if (rc) return rc;
-    int wide_blocks = (n + 15) / 16;        // one wave per row when everything bids
-    if (wide_blocks > 512) wide_blocks = 512;
-    if (P.wide_blocks_cap > 0 && wide_blocks > P.wide_blocks_cap) wide_blocks = P.wide_blocks_cap;
-    L.blocks_build = wide_blocks < (n + 63) / 64 ? (n + 63) / 64 : wide_blocks;     // the list build streams the matrix once: its own grid
-    // a batch shares the chip: ASG_BATCH_WGS workgroups in all (every workgroup of a bid round stages the prices whether
-    // its rows bid or not; measured at n = 4096: 8 problems 9.1 ms with 256 workgroups each, 6.5 ms with 64); the rounds
-    // then take the queue form (wide_bid_queue)
-    const int floor_blocks = nb > 1 ? (n + ASG_BQ - 1) / ASG_BQ : (n + 63) / 64;
-#define ASG_BATCH_WGS 256
-    if (nb > 1 && wide_blocks > ASG_BATCH_WGS / nb) wide_blocks = ASG_BATCH_WGS / nb;
-    if (wide_blocks < floor_blocks) wide_blocks = floor_blocks;      // (the queue form takes ASG_BQ rows per workgroup)
-    if (wide_blocks < 1) wide_blocks = 1;
-    L.blocks = wide_blocks;
-    const int raised = asg_raise_lds();
-    L.lds_step = sizeof(double) * WT + 2 * sizeof(int) * WT;                      // relax merge buffers
-    if (n <= WIDE_PLDS_MAX) {                                            // bid rounds: prices + owner rows
-        const size_t need = (size_t)((n + 1) & ~1) * sizeof(double) + (size_t)(n + 2) * sizeof(int);
-        if (need > L.lds_step) L.lds_step = need;
-    }
-    if (n <= 6144 && (size_t)2 * n * sizeof(int) > L.lds_step) L.lds_step = (size_t)2 * n * sizeof(int);   // path walks of MS_FINISH
-    L.lds_step = (L.lds_step + 15) & ~(size_t)15;
-    if (L.lds_step > 64 * 1024 && !(raised & 1)) return CFM_EINVAL;
-    L.sparse = (use_sparse && n <= SP_NMAX && (raised & 2)) ? 1 : 0;
-    L.lds_build = sp_build_lds_bytes(n); L.lds_solve = sp_solver_lds_bytes(n);
-
-    // asynchronous phase A: the keys must fit the LDS snapshot and the grid must give every workgroup at most ASG_BQ rows
-    L.blocks_auction = wide_blocks;
-    if (nb > 1 && P.async_blocks > 0 && P.async_blocks < wide_blocks) L.blocks_auction = P.async_blocks;
-    if ((long)L.blocks_auction * ASG_BQ < n) L.blocks_auction = (n + ASG_BQ - 1) / ASG_BQ;      // (a workgroup takes at most ASG_BQ rows)
-    {   // its workgroups (16 waves, the whole register file of a CU each) must be able to be resident TOGETHER: a phase ends
-        // when the whole grid has reported, and a workgroup that has not started counts as "all rows unmatched"
-        // — on the CUs THIS STREAM may use: a CU-masked stream (cfm_stream_create_cu_mask, ChipPartition) gives the grid
-        // fewer than the device has, and workgroups that cannot start before others exit would be counted as "all rows
-        // unmatched" for the whole grace (~40 ms) and then left out: > 64 free rows, the dense fallback
-        int c = asg_stream_cus(s);
-        if ((long)L.blocks_auction * nb > c) L.blocks_auction = c / nb > 0 ? c / nb : 1;
-    }
-    L.async_auction = (P.async_auction && n >= P.async_min_n && n <= WIDE_PLDS_MAX && (raised & 1) && (long)L.blocks_auction * ASG_BQ >= n) ? P.async_auction : 0;
-    for (int b = 0; b < nb; ++b) {
-        AsgState h;
-        memset(&h, 0, sizeof(h));
-        h.wide_blocks = wide_blocks;
-        h.mode = MODE_UMIN0; h.n = n; h.Mptr = pr[b].M;
-        h.out_perm = pr[b].perm; h.out_cert = pr[b].certified; h.out_cost = pr[b].total_cost; h.out_stats = pr[b].stats;
-        h.eps = P.eps0_frac; h.eps_last = P.eps_last_frac; h.theta = L.async_auction ? P.async_theta : P.theta;
-        h.stop_frac = P.stop_frac; h.round_cap = P.round_cap; h.arr_cap = P.arr_cap;
-        h.cmin_bits = 0xffffffffu; h.cmax_bits = 0u; h.minslack_ord = ~0ull;
-        h.fr_min = ~0ull; h.fr_max = 0ull;
-        h.sparse = L.sparse; h.handoff = P.handoff; h.stop_early = P.stop_early;
-        h.tag = 1; h.pad0 = (P.async_last_div & 0xff) | ((P.async_auction >= 2 ? 1 : 0) << 8) | ((P.async_last_div >> 8) << 16);   // (bits 16+: experiment — grace of unstarted workgroups / 64)
-        { int rb = 1; while ((1 << rb) <= n) ++rb; h.rb = rb; }     // row ids 0 .. n-1 and the all-ones "none"
-        hipLaunchKernelGGL(asg_init, dim3(1), dim3(64), 0, s, asg_carve((char*)ws + (size_t)b * L.stride, n), h);
-    }
-    rc = cfm_status();
-    if (rc) return rc;
-
-    int chunk = ((P.chunk > 0 ? P.chunk : 10) + 1) & ~1;        // even: see AsgLaunch::step
-    // A batch pays for every problem that is not yet at its list build when the first build + solver pair comes by: it
-    // is built and solved by the NEXT chunk, behind the others' solver (~1.9 ms at n = 4096).  The steps before the
-    // build vary by ~+-6 between problems: 24 instead of 10 steps in front of the pair (a no-op step costs 3-5 us).
-#define ASG_BATCH_CHUNK 24
-    if (nb > 1 && chunk < ASG_BATCH_CHUNK) chunk = ASG_BATCH_CHUNK;
-    // ... the unpolled head then is: 2 init steps, the auction launch, ~10 epsilon = 0 rounds + convert / row minima / column
-    // reduction (the synchronous rounds needed ~96 launches here)
-    int bulk = ((n >= P.bulk_min_n) ? P.bulk : 0) & ~1;
-    if (L.async_auction && bulk > 16) bulk = 16;
-    AsgGraph& G = asg_graph_slot(ws, n, nb, s);
-    bool use_graph = asg_graph_enabled() && !g_graph_off && n >= 256;
-    if (use_graph && !(G.exec[0] && G.ws == ws && G.n == n && G.nb == nb && G.chunk == chunk && G.bulk == bulk &&
-                       G.blocks == wide_blocks + 1024 * L.blocks_auction && G.sparse == L.sparse + 2 * L.async_auction && G.stream == s)) {
-        for (int q = 0; q < PRG_COUNT; ++q) if (G.exec[q]) { (void)hipGraphExecDestroy(G.exec[q]); G.exec[q] = nullptr; }
-        hipError_t e = hipSuccess;
-        // The programs are captured on a PRIVATE stream of this host thread, not on the caller's: while a stream captures,
-        // HIP refuses any other stream's wait on an event that was recorded on it EARLIER (hipErrorStreamCaptureIsolation) —
-        // a prefetch worker that starts a job of a new size while the training thread waits for the worker's previous job
-        // (cfm_amd.prefetch: _Handle.result) raised exactly that, once in five runs of tests/test_gpu_prefetch.py.  The
-        // kernels take workspace-derived arguments only, so where they are captured does not matter.
-        static thread_local hipStream_t cap_stream = nullptr;
-        if (!cap_stream) e = hipStreamCreateWithFlags(&cap_stream, hipStreamNonBlocking);
-        AsgLaunch Lc = L; Lc.s = cap_stream;
-        for (int prg = 0; prg < PRG_COUNT && e == hipSuccess; ++prg) {
-            if (L.count(prg, chunk, bulk) == 0) continue;
-            hipGraph_t graph = nullptr;
-            e = hipStreamBeginCapture(cap_stream, hipStreamCaptureModeThreadLocal);
-            if (e != hipSuccess) break;
-            Lc.program(prg, chunk, bulk);
-            e = hipStreamEndCapture(cap_stream, &graph);
-            if (e == hipSuccess && graph) e = hipGraphInstantiate(&G.exec[prg], graph, nullptr, nullptr, 0);
-            if (graph) (void)hipGraphDestroy(graph);
-        }
-        if (e == hipSuccess) e = asg_events(G);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            for (int q = 0; q < PRG_COUNT; ++q) if (G.exec[q]) { (void)hipGraphExecDestroy(G.exec[q]); G.exec[q] = nullptr; }
-            g_graph_off = 1; use_graph = false;     // e.g. the legacy default stream
-        } else {
-            G.ws = ws; G.n = n; G.nb = nb; G.chunk = chunk; G.bulk = bulk; G.blocks = wide_blocks + 1024 * L.blocks_auction;
-            G.sparse = L.sparse + 2 * L.async_auction; G.stream = s;
-        }
-    }
-    rc = cfm_hip(asg_events(G)); if (rc) return rc;      // (also: the thread's blocking-sync choice changed since they were made)
-
-    long launched = 0;
-    auto run = [&](int prg) -> int {
-        const int cnt = L.count(prg, chunk, bulk);
-        if (cnt == 0) return 0;
-        launched += cnt;
-        if (use_graph) return cfm_hip(hipGraphLaunch(G.exec[prg], s));
-        L.program(prg, chunk, bulk);
-        return cfm_status();
-    };
-    // The head goes out unpolled (a solve at n = 4096 takes ~100 steps before the list solver); the rest
-    // in chunks that make progress from any state, each followed by a copy of the first 64 bytes of every
-    // problem's state into its own pinned slot and an event, with the NEXT chunk already queued when the host
-    // waits for a slot: no idle gap.  A kernel that does not own the current mode is a ~2 us no-op.
-    rc = run(PRG_BULK); if (rc) return rc;
-    int cur = 0;
-    int* stage = reinterpret_cast<int*>((char*)ws + (size_t)nb * stride);      // batches: 2 x nb x 64 bytes behind the carvings
-    auto issue = [&](int slot, bool with_chunk = true) -> int {
-        int r2 = with_chunk ? run(PRG_CHUNK) : 0; if (r2) return r2;
-        int* host = g_pinned + 16 * ASG_BATCH_MAX * slot;
-        if (nb == 1) r2 = cfm_hip(hipMemcpyAsync(host, L.w.st, 64, hipMemcpyDeviceToHost, s));
-        else {
-            hipLaunchKernelGGL(asg_collect, dim3(1), dim3(16 * ASG_BATCH_MAX), 0, s, L.w.st, L.stride, nb, stage + 16 * nb * slot);
-            r2 = cfm_status();
-            if (!r2) r2 = cfm_hip(hipMemcpyAsync(host, stage + 16 * nb * slot, 64 * (size_t)nb, hipMemcpyDeviceToHost, s));
-        }
-        if (r2) return r2;
-        return cfm_hip(hipEventRecord(G.ev[slot], s));
-    };
-    // the head holds the whole solve (see AsgLaunch::program): look at the state behind it BEFORE queueing anything else —
-    // a finished solve returns here, with no look-ahead chunk of no-ops to wait for
-    const bool head_is_whole = L.async_auction >= 2 && L.sparse && bulk > 0;
-    if (head_is_whole) {
-        rc = issue(0, false); if (rc) return rc;
-        rc = cfm_hip(asg_wait(G.ev[0])); if (rc) return rc;
-        const int* hs = g_pinned;
-        int open_ = 0;
-        for (int b = 0; b < nb; ++b) {
-            const int mode = hs[16 * b + 0], err = hs[16 * b + 2];
-            if (err) err_out[b] = err;
-            else if (mode == MODE_DONE) cert_out[b] = hs[16 * b + 3];
-            else ++open_;
-        }
-        if (!open_) return 0;
-        for (int b = 0; b < nb; ++b) { err_out[b] = 0; cert_out[b] = 1; }      // (re-read by the chunk loop)
-    }
-    rc = issue(0); if (rc) return rc;
-    int result = 0;
-    for (;;) {
-        rc = issue(cur ^ 1); if (rc) return rc;
-        rc = cfm_hip(asg_wait(G.ev[cur])); if (rc) return rc;
-        const int* hs = g_pinned + 16 * ASG_BATCH_MAX * cur;
-        int open_ = 0;
-        for (int b = 0; b < nb; ++b) {
-            const int mode = hs[16 * b + 0], err = hs[16 * b + 2];
-            if (err) err_out[b] = err;                        // this problem stopped (its launches are no-ops now)
-            else if (mode == MODE_DONE) cert_out[b] = hs[16 * b + 3];
-            else ++open_;
-        }
-        if (!open_) break;
-        if (launched >= P.max_launches) { result = CFM_ETIMEOUT; break; }
-        cur ^= 1;
-    }
-    // the look-ahead chunk is still in flight: it is a string of no-ops on a finished state, but the
-    // workspace (and the pinned slot it copies into) must not be reused under it
-    rc = cfm_hip(asg_wait(G.ev[cur ^ 1]));
-    return rc ? rc : result;
-}
-
-// one problem through the candidate-list machine, the dense state machine deciding should its certificate ever fail
-static int asg_solve_one(const AsgProblem& pr, int B, void* ws, void* stream, const AsgParams& P, int first_sparse) {
-    int cert = 1, err = 0;
-    int rc = asg_run(&pr, 1, B, ws, 0, stream, P, first_sparse, &cert, &err);
-    if (rc) return rc;
-    if (err) { g_fallback[1] = err; rc = CFM_ENOCONV; }
-    if (first_sparse && B > 1 && B <= SP_NMAX && (rc == CFM_ENOCONV || !cert)) {
-        ++g_fallback[0];
-        if (rc == 0) g_fallback[1] = -1;          // uncertified
-        rc = asg_run(&pr, 1, B, ws, 0, stream, P, 0, &cert, &err);
-        if (rc == 0 && err) { g_fallback[1] = err; rc = CFM_ENOCONV; }
-    }
-    if (rc == 0 && B > 1 && !cert) rc = CFM_ENOCONV;     // never hand back an uncertified permutation silently
-    return rc;
-}
-
-extern "C" int cfm_assign_exact_f32(const float* M, int B, int* perm, int* certified,
-                                    double* total_cost, int* stats, void* ws, void* stream) {
-    const AsgParams P = asg_params_snapshot();
-    if (P.small && B >= 2 && B <= SMA_N) {
-        // one workgroup, one launch; a solve that hits its round caps or fails its certificate reports it and
-        // the chip-wide state machine below takes over
-        if (!M || !perm || !ws) return CFM_EINVAL;
-        if (((uintptr_t)ws & 15) != 0) return CFM_EALIGN;
-        hipStream_t s = (hipStream_t)stream;
-        int rc0 = asg_pinned();
-        if (rc0) return rc0;
-        SmaParams Q;
-        Q.theta = P.async_theta;            // (its epsilon phases are asynchronous since round 6: theta 2-3 measured 10 % ahead of 5, tools/asg_small_sweep.py)
-        Q.eps0_frac = P.eps0_frac; Q.eps_last_frac = P.eps_last_frac;
-        Q.stop_frac = P.stop_frac;
-        Q.round_cap = P.round_cap; Q.arr_cap = P.arr_cap > 15 ? P.arr_cap : 15; Q.total_cap = 20000;   // (the one-workgroup solver was tuned with 15)
-        Q.reserved = 0;
-        int* status = (int*)ws;            // (the kernel clears `certified` and writes every word of the status block itself)
-        hipLaunchKernelGGL(asg_small, dim3(1), dim3(SMA_T), 0, s, M, B, Q, perm, certified, total_cost, stats, status);
-        rc0 = cfm_status();
-        if (rc0) return rc0;
-        rc0 = cfm_hip(hipMemcpyAsync(g_pinned, status, 64, hipMemcpyDeviceToHost, s));
-        if (rc0) return rc0;
-        rc0 = cfm_hip(hipStreamSynchronize(s));
-        if (rc0) return rc0;
-        for (int q = 0; q < 16; ++q) g_small_last[q] = g_pinned[q];
-        if (g_pinned[0] == 1) return 0;
-    }
-    if (!M || !perm) return CFM_EINVAL;
-    const AsgProblem pr = {M, perm, certified, total_cost, stats};
-    return asg_solve_one(pr, B, ws, stream, P, P.sparse);
-}
-
-// nb problems of the same size in ONE chain of launches: every launch carries all problems (grid.y), so the
-// latency-bound chain — ~110 launch boundaries, a one-workgroup list solver — is paid once per batch.  A problem
-// whose candidate-list path stops or ends uncertified is redone alone on the dense state machine, like a single solve.
-extern "C" size_t cfm_assign_batch_ws_bytes_internal(int n, int nb) {
-    if (nb > ASG_BATCH_MAX) nb = ASG_BATCH_MAX;       // longer lists go through in groups of ASG_BATCH_MAX
-    return (size_t)nb * cfm_align_up(asg_ws_bytes(n), 256) + 2 * 64 * (size_t)ASG_BATCH_MAX + 256;
-}
-
-extern "C" int cfm_assign_exact_batch_f32(const float* const* M, int nb, int B, int* const* perm, int* certified,
-                                          double* total_cost, int* stats, void* ws, void* stream) {
-    if (!M || !perm || nb < 0) return CFM_EINVAL;
-    if (nb == 0) return 0;
-    AsgParams P = asg_params_snapshot();
-    // The batch entry is the THROUGHPUT form of the solve (couplings prefetched beside a model step): its launches are
-    // capped at ASG_TP_WGS workgroups per problem whatever the batch size — also for a batch of one, two or three
-    // (the first, small job of a prefetch run; the remainder of a run).  A bid round occupies the chip for as long as
-    // its slowest workgroup whatever it does, and every workgroup stages the prices: fewer, fuller workgroups take
-    // less of the chip from the other jobs and the dense products.  Measured in the C3 pipelined loop (round 4,
-    // CFM_ASG_BLOCKS sweep, same box): 256 / 64 / 32 / 16 per problem for the odd-sized jobs: 1.201 / 1.163 / 1.162 /
-    // 1.276 ms per step; a lone solve prefers the wide grid (3.30 vs 3.68 ms sequential): cfm_assign_exact_f32 keeps it.
-#define ASG_TP_WGS 64
-    if (P.wide_blocks_cap == 0) P.wide_blocks_cap = ASG_TP_WGS;      // (an explicit cfm_assign_set_wide_blocks cap is the caller's: never overridden)
-    const size_t stride = cfm_align_up(asg_ws_bytes(B), 256);
-    int rc = 0;
-    for (int b0 = 0; b0 < nb && rc == 0; b0 += ASG_BATCH_MAX) {
-        const int k = nb - b0 < ASG_BATCH_MAX ? nb - b0 : ASG_BATCH_MAX;
-        AsgProblem pr[ASG_BATCH_MAX];
-        int cert[ASG_BATCH_MAX], err[ASG_BATCH_MAX];
-        for (int b = 0; b < k; ++b) {
-            if (!M[b0 + b] || !perm[b0 + b]) return CFM_EINVAL;
-            pr[b] = {M[b0 + b], perm[b0 + b], certified ? certified + b0 + b : nullptr,
-                     total_cost ? total_cost + b0 + b : nullptr, stats ? stats + 8 * (size_t)(b0 + b) : nullptr};
-        }
-        const bool machine = !(P.small && B >= 2 && B <= SMA_N) && B > 1 && k > 1;
-        if (!machine) {               // single problems and the one-workgroup sizes: one after the other
-            for (int b = 0; b < k && rc == 0; ++b) {
-                if (P.small && B >= 2 && B <= SMA_N || B <= 1)
-                    rc = cfm_assign_exact_f32(pr[b].M, B, pr[b].perm, pr[b].certified, pr[b].total_cost, pr[b].stats, ws, stream);
-                else
-                    rc = asg_solve_one(pr[b], B, ws, stream, P, P.sparse);      // the chip-wide machine on the throughput grid
-            }
-            continue;
-        }
-        rc = asg_run(pr, k, B, ws, stride, stream, P, P.sparse, cert, err);
-        for (int b = 0; b < k && rc == 0; ++b) {
-            if (!err[b] && cert[b]) continue;
-            if (!(P.sparse && B <= SP_NMAX)) { rc = CFM_ENOCONV; break; }
-            ++g_fallback[0]; g_fallback[1] = err[b] ? err[b] : -1;
-            rc = asg_solve_one(pr[b], B, (char*)ws + (size_t)b * stride, stream, P, 0);
-        }
-    }
-    return rc;
-}
+// ------------------------------------------------------------------ host -----
+#include "assign_driver.h"

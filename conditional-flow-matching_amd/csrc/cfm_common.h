@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <mutex>
 #include "../../include/cfm_gfx950.h"
 #include "../../include/cfm_gfx950_tuning.h"   // every export is declared in one of the two headers (-fvisibility=hidden)
 
@@ -22,6 +23,24 @@ static inline int cfm_device_index() {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= CFM_MAX_DEVICES) dev = 0;
     return dev;
+}
+// Host only: setup() runs once per device and its int result is handed back from then on; a HIP error it left behind is
+// swallowed (its result says what failed).  Every lambda has its own type: one set of statics per call site and per
+// instantiation of a templated caller.
+template <class F>
+static inline int cfm_once_per_device(F setup) {
+    static std::once_flag once[CFM_MAX_DEVICES];
+    static int result[CFM_MAX_DEVICES];
+    const int dvi = cfm_device_index();
+    std::call_once(once[dvi], [&] { result[dvi] = setup(); (void)hipGetLastError(); });
+    return result[dvi];
+}
+// compute units of the current device (256 when the query fails)
+static inline int cfm_device_cus() {
+    return cfm_once_per_device([] {
+        int c = 0;
+        return (hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, cfm_device_index()) == hipSuccess && c > 0) ? c : 256;
+    });
 }
 
 // XCD-aware block remap: the dispatcher places block b on XCD b % 8; give each

@@ -1032,29 +1032,20 @@ static int ode_dopri5_small(const float* const* W, const float* const* b, const 
     for (int l = 0; l < 4; ++l) { A.W[l] = W[l]; A.b[l] = b[l]; }
     for (int l = 0; l < 5; ++l) A.dims[l] = dims[l];
     const size_t lds = sm_lds_bytes(MODE);
-    static int raised_d[CFM_MAX_DEVICES], resident_d[CFM_MAX_DEVICES];
-    static std::once_flag once_d[CFM_MAX_DEVICES];
-    const int dvi = cfm_device_index();
-    int& raised = raised_d[dvi]; int& resident = resident_d[dvi];
-    // (one set per TAB and MODE: the grid is sized from the occupancy of the instantiation that is launched)
-    std::call_once(once_d[dvi], [lds, &raised, &resident] {
+    // (one result per TAB and MODE: the grid is sized from the occupancy of the instantiation that is launched)
+    const int resident = cfm_once_per_device([lds] {
         hipError_t e = hipFuncSetAttribute((const void*)ode_small_dopri<TAB, true, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
         hipError_t e2 = hipFuncSetAttribute((const void*)ode_small_dopri<TAB, false, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-        int ok = (e == hipSuccess && e2 == hipSuccess) ? 1 : -1;
         // workgroups that can be resident at once: the grid rendezvous needs grid <= this
-        int dev = 0, cus = 0, pa = 0, pb = 0;
-        if (ok > 0 && hipGetDevice(&dev) == hipSuccess &&
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
+        int pa = 0, pb = 0;
+        if (e == hipSuccess && e2 == hipSuccess &&
             hipOccupancyMaxActiveBlocksPerMultiprocessor(&pa, (const void*)ode_small_dopri<TAB, true, MODE>, 256, lds) == hipSuccess &&
             hipOccupancyMaxActiveBlocksPerMultiprocessor(&pb, (const void*)ode_small_dopri<TAB, false, MODE>, 256, lds) == hipSuccess &&
-            cus > 0 && pa > 0 && pb > 0)
-            resident = cus * (pa < pb ? pa : pb);
-        else
-            ok = -1;
-        (void)hipGetLastError();
-        raised = ok;
+            pa > 0 && pb > 0)
+            return cfm_device_cus() * (pa < pb ? pa : pb);
+        return -1;
     });
-    if (raised < 0) return CFM_EINVAL;
+    if (resident < 0) return CFM_EINVAL;
     int rc = cfm_hip(hipMemcpyAsync(tspan_dev, t_span, sizeof(float) * n_t, hipMemcpyHostToDevice, s));
     if (rc) return rc;
     SmState h[2];
@@ -1196,14 +1187,9 @@ extern "C" int cfm_sde_em_mlp_f32(const float* const* Wf, const float* const* bf
     for (int l = 0; l < 4; ++l) { F.W[l] = Wf[l]; F.b[l] = bf[l]; S.W[l] = Ws ? Ws[l] : Wf[l]; S.b[l] = bs ? bs[l] : bf[l]; }
     for (int l = 0; l < 5; ++l) { F.dims[l] = dims[l]; S.dims[l] = dims[l]; }
     const size_t lds = sizeof(float) * (2 * (4 * SM_W * SM_LD + 4 * SM_W + SM_W) + 2 * SM_ROWS * SM_LD);
-    static int raised_d[CFM_MAX_DEVICES];
-    static std::once_flag once_d[CFM_MAX_DEVICES];
-    const int dvi = cfm_device_index();
-    int& raised = raised_d[dvi];
-    std::call_once(once_d[dvi], [&raised] {
+    const int raised = cfm_once_per_device([] {
         hipError_t e = hipFuncSetAttribute((const void*)ode_small_em, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipGetLastError();
-        raised = (e == hipSuccess) ? 1 : -1;
+        return (e == hipSuccess) ? 1 : -1;
     });
     if (raised < 0) return CFM_EINVAL;
     int rc = cfm_hip(hipMemcpyAsync(ws, steps_host, sizeof(EmStep) * (size_t)n_steps, hipMemcpyHostToDevice, s));
@@ -1307,14 +1293,9 @@ static int ode_fixed_small_t(const float* const* W, const float* const* b, const
     for (int l = 0; l < 4; ++l) { A.W[l] = W[l]; A.b[l] = b[l]; }
     for (int l = 0; l < 5; ++l) A.dims[l] = dims[l];
     const size_t lds = sm_lds_bytes(MODE);
-    static int raised_d[CFM_MAX_DEVICES];
-    static std::once_flag once_d[CFM_MAX_DEVICES];
-    const int dvi = cfm_device_index();
-    int& raised = raised_d[dvi];
-    std::call_once(once_d[dvi], [&raised] {
+    const int raised = cfm_once_per_device([] {
         hipError_t e = hipFuncSetAttribute((const void*)ode_small_fixed<SCHEME, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-        (void)hipGetLastError();
-        raised = (e == hipSuccess) ? 1 : -1;
+        return (e == hipSuccess) ? 1 : -1;
     });
     if (raised < 0) return CFM_EINVAL;
     int rc = cfm_hip(hipMemcpyAsync(tspan_dev, t_span, sizeof(float) * n_t, hipMemcpyHostToDevice, s));
@@ -1379,14 +1360,9 @@ __global__ __launch_bounds__(256) void ode_small_div(SmArgs A, int B, int d, con
 template <int MODE>
 static int cnf_eval(const SmArgs& A, int B, int d, const float* x, int ldx, float t, const float* eps, float* v, int ldv,
                     float* div, int lddiv, float dsign, hipStream_t s) {
-    static int raised_d[CFM_MAX_DEVICES];
-    static std::once_flag once_d[CFM_MAX_DEVICES];
-    const int dvi = cfm_device_index();
-    int& raised = raised_d[dvi];
-    std::call_once(once_d[dvi], [&raised] {
+    const int raised = cfm_once_per_device([] {
         hipError_t e = hipFuncSetAttribute((const void*)ode_small_div<MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-        (void)hipGetLastError();
-        raised = (e == hipSuccess) ? 1 : -1;
+        return (e == hipSuccess) ? 1 : -1;
     });
     if (raised < 0) return CFM_EINVAL;
     const int tiles = (B + SM_ROWS - 1) / SM_ROWS;

@@ -645,16 +645,10 @@ extern "C" int cfm_sinkhorn_log_f32(const float* M, int B0, int B1, double reg, 
     const int row_wgs = (B0 + rows_per_wg - 1) / rows_per_wg;
     int v_in_lds = ((size_t)B1 * 8 <= 128 * 1024) ? 1 : 0;
     if (v_in_lds && (size_t)B1 * 8 > 48 * 1024) {
-        static int raised_d[CFM_MAX_DEVICES];   // dynamic LDS above the 64 KiB default needs the attribute (per device)
-        static std::once_flag once_d[CFM_MAX_DEVICES];
-        int& raised = raised_d[cfm_device_index()];
-        std::call_once(once_d[cfm_device_index()], [&raised] {
-            hipError_t e = hipFuncSetAttribute((const void*)sk_row_pass<true>,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-            hipError_t e2 = hipFuncSetAttribute((const void*)sk_row_pass<false>,
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-            (void)hipGetLastError();
-            raised = (e == hipSuccess && e2 == hipSuccess) ? 1 : -1;
+        const int raised = cfm_once_per_device([] {   // dynamic LDS above the 64 KiB default needs the attribute (per device)
+            hipError_t e = hipFuncSetAttribute((const void*)sk_row_pass<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+            hipError_t e2 = hipFuncSetAttribute((const void*)sk_row_pass<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+            return (e == hipSuccess && e2 == hipSuccess) ? 1 : -1;
         });
         if (raised < 0) v_in_lds = 0;
     }
@@ -662,23 +656,15 @@ extern "C" int cfm_sinkhorn_log_f32(const float* M, int B0, int B1, double reg, 
     // streaming row pass: a persistent grid of SK_STREAM_WAVES-wave workgroups
     int stream_grid = 0, stream_nf4 = 0;
     if (row_fast && v_in_lds) {
-        static int per_cu_d[CFM_MAX_DEVICES], cus_d[CFM_MAX_DEVICES];
-        static std::once_flag once_stream_d[CFM_MAX_DEVICES];
-        const int dvi = cfm_device_index();
-        int& per_cu = per_cu_d[dvi]; int& cus = cus_d[dvi];
-        std::call_once(once_stream_d[dvi], [&per_cu, &cus] {
+        const int cus = cfm_device_cus();
+        const int per_cu = cfm_once_per_device([] {
             const char* e = getenv("CFM_SK_STREAM");       // workgroups per CU; 0 = one-shot row pass
             int pc = e ? atoi(e) : 1;
-            int dev = 0, c = 0;
-            if (hipGetDevice(&dev) != hipSuccess ||
-                hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || c <= 0) c = 256;
             const void* fns[4] = {(const void*)sk_row_stream<4>, (const void*)sk_row_stream<8>,
                                   (const void*)sk_row_stream<12>, (const void*)sk_row_stream<16>};
             for (int q = 0; q < 4; ++q)
-                if (hipFuncSetAttribute(fns[q], hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess)
-                    pc = 0;
-            (void)hipGetLastError();
-            cus = c; per_cu = pc < 0 ? 0 : pc;
+                if (hipFuncSetAttribute(fns[q], hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess) pc = 0;
+            return pc < 0 ? 0 : pc;
         });
         // units of 256 * nf4 columns: the largest of 4, 8, 12, 16 float4 per lane that divides the row
         for (int q = 4; q <= SK_STREAM_UNIT; q += 4)

@@ -275,16 +275,13 @@ extern "C" int cfm_sinkhorn_log_points_f32(const float* x0, const float* x1, int
     stage_cap = stage_cap / (PTS_STRIDE * PTS_U) * (PTS_STRIDE * PTS_U);          // whole trips
     if (stage_cap > n_max) stage_cap = (n_max + PTS_STRIDE * PTS_U - 1) / (PTS_STRIDE * PTS_U) * (PTS_STRIDE * PTS_U);
     const size_t lds = (size_t)stage_cap * (8 + 4 * d);
-    {
-        static std::once_flag once_d[CFM_MAX_DEVICES];          // the attribute is per device
-        std::call_once(once_d[cfm_device_index()], [] {
-            const void* fns[8] = {(const void*)sk_pts_pass<1>, (const void*)sk_pts_pass<2>, (const void*)sk_pts_pass<3>,
-                                  (const void*)sk_pts_pass<4>, (const void*)sk_pts_pass<5>, (const void*)sk_pts_pass<6>,
-                                  (const void*)sk_pts_pass<7>, (const void*)sk_pts_pass<8>};
-            for (int q = 0; q < 8; ++q) (void)hipFuncSetAttribute(fns[q], hipFuncAttributeMaxDynamicSharedMemorySize, 136 * 1024);
-            (void)hipGetLastError();
-        });
-    }
+    (void)cfm_once_per_device([] {          // the attribute is per device
+        const void* fns[8] = {(const void*)sk_pts_pass<1>, (const void*)sk_pts_pass<2>, (const void*)sk_pts_pass<3>,
+                              (const void*)sk_pts_pass<4>, (const void*)sk_pts_pass<5>, (const void*)sk_pts_pass<6>,
+                              (const void*)sk_pts_pass<7>, (const void*)sk_pts_pass<8>};
+        for (int q = 0; q < 8; ++q) (void)hipFuncSetAttribute(fns[q], hipFuncAttributeMaxDynamicSharedMemorySize, 136 * 1024);
+        return 0;
+    });
     const int n = n_max;
     hipLaunchKernelGGL(sk_pts_init, dim3((n + 255) / 256), dim3(256), 0, s, st, u, v[0], v[1], B0, B1, max_iter);
     const int col_grid = (B1 + PTS_OWN - 1) / PTS_OWN, row_grid = (B0 + PTS_OWN - 1) / PTS_OWN;

@@ -627,15 +627,10 @@ extern "C" int cfm_transport_exact_f32(const float* M, int B0, int B1, const int
     if (B0 + B1 > TP_NMAX) return CFM_EINVAL;
     if (((uintptr_t)ws & 15) != 0) return CFM_EALIGN;
     hipStream_t s = (hipStream_t)stream;
-    static int raised_d[CFM_MAX_DEVICES];
-    static std::once_flag once_d[CFM_MAX_DEVICES];
-    const int dvi = cfm_device_index();
-    int& raised = raised_d[dvi];
-    std::call_once(once_d[dvi], [&raised] {
+    const int raised = cfm_once_per_device([] {
         hipError_t e = hipFuncSetAttribute((const void*)tp_pd_solve<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);
         if (e == hipSuccess) e = hipFuncSetAttribute((const void*)tp_pd_solve<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);
-        (void)hipGetLastError();
-        raised = (e == hipSuccess) ? 1 : -1;
+        return (e == hipSuccess) ? 1 : -1;
     });
     if (raised < 0) return CFM_EINVAL;
     const int transposed = B0 > B1 ? 1 : 0;
