@@ -43,6 +43,12 @@ static inline int cfm_device_cus() {
     });
 }
 
+// one net's operands of a layer launch that serves two nets (mlp.hip: cfm_mlp_launch_layer_two; mlp_train.hip)
+struct MlpNetLayer {
+    const float* X; const float* W; const float* bias; float* out; float* zout;
+    const float* target; const float* lam; float scale; float* partial;      // last layer: loss target, row weights, seed scale, loss partials
+};
+
 // XCD-aware block remap: the dispatcher places block b on XCD b % 8; give each
 // XCD a contiguous range of logical ids so neighbouring tiles share its L2.
 // Bijective for any grid size (speed only, never correctness).

@@ -34,12 +34,14 @@ __device__ __forceinline__ float selu_f(float x) {
 struct LayerEpi {
     const float* W; int ldw; const float* bias; const float* tptr; float tval; int t_per_row, tcol, B, N;
     float* out; float* zout; const float* mse_u; float mse_scale, mse_inv_n; float* mse_partial;
+    const float* lam;      // weighted residual (the score loss of the SF2M step): r = lam[row] * v + mse_u, seed (r * mse_scale) * lam[row]
 };
+// wg: the workgroup's index inside its net's grid (blockIdx.x when one net runs alone) — the slot of its loss partial
 template <bool ACT, typename G>
-__device__ __forceinline__ void layer_epilogue(const G& g, int row0, int col0, const LayerEpi& E) {
+__device__ __forceinline__ void layer_epilogue(const G& g, int row0, int col0, const LayerEpi& E, unsigned wg) {
     constexpr int EU = G::EU, EM = G::EM, ER = G::ER;
     const float* __restrict__ W = E.W; const float* __restrict__ tptr = E.tptr; const float* __restrict__ mse_u = E.mse_u;
-    float* __restrict__ out = E.out; float* __restrict__ zout = E.zout;
+    float* __restrict__ out = E.out; float* __restrict__ zout = E.zout; const float* __restrict__ lam = E.lam;
     const int tcol = E.tcol, t_per_row = E.t_per_row, B = E.B, N = E.N, ldw = E.ldw;
     const float tsc = (tcol >= 0 && !t_per_row) ? (tptr ? tptr[0] : E.tval) : 0.f;
     const int gc = col0 + G::col_lo();
@@ -60,6 +62,7 @@ __device__ __forceinline__ void layer_epilogue(const G& g, int row0, int col0, c
             const int gr = row0 + G::row_of(m, r);
             if (gr >= B || gc >= N) continue;
             const float tv = (tcol >= 0) ? (t_per_row ? tptr[gr] : tsc) : 0.f;
+            const float lw = (!ACT && lam != nullptr) ? lam[gr] : 0.f;
             float v[2], z[2];
 #pragma unroll
             for (int u = 0; u < EU; ++u) {
@@ -68,9 +71,16 @@ __device__ __forceinline__ void layer_epilogue(const G& g, int row0, int col0, c
                 z[u] = x;
                 v[u] = ACT ? selu_f(x) : x;
                 if (!ACT && mse_u != nullptr && gc + u < N) {
-                    const float dlt = v[u] - mse_u[(size_t)gr * N + gc + u];
-                    lsum = fmaf(dlt, dlt, lsum);
-                    v[u] = dlt * E.mse_scale;
+                    const float tgt = mse_u[(size_t)gr * N + gc + u];
+                    if (lam != nullptr) {       // (lam = 1: fmaf(1, v, e) = v - (-e) and (r * scale) * 1 — the bits of the plain mode on u = -e)
+                        const float rr = fmaf(lw, v[u], tgt);
+                        lsum = fmaf(rr, rr, lsum);
+                        v[u] = (rr * E.mse_scale) * lw;
+                    } else {
+                        const float dlt = v[u] - tgt;
+                        lsum = fmaf(dlt, dlt, lsum);
+                        v[u] = dlt * E.mse_scale;
+                    }
                 }
             }
             float* po = out + (size_t)gr * N + gc;
@@ -89,7 +99,7 @@ __device__ __forceinline__ void layer_epilogue(const G& g, int row0, int col0, c
         lsum = wave_sum_f(lsum);
         if ((threadIdx.x & 63) == 0) msh[threadIdx.x >> 6] = lsum;
         __syncthreads();
-        if (threadIdx.x == 0) E.mse_partial[blockIdx.x] = ((msh[0] + msh[1]) + (msh[2] + msh[3])) * E.mse_inv_n;
+        if (threadIdx.x == 0) E.mse_partial[wg] = ((msh[0] + msh[1]) + (msh[2] + msh[3])) * E.mse_inv_n;
     }
 }
 
@@ -112,8 +122,29 @@ __global__ __launch_bounds__(256) void mlp_layer(const float* __restrict__ X, in
     Core g;
     g.zero();
     g.run(lds, X, lda, row0, B, W, ldw, col0, N, 0, K, GcNoPost());
-    const LayerEpi E = {W, ldw, bias, tptr, tval, t_per_row, tcol, B, N, out, zout, mse_u, mse_scale, mse_inv_n, mse_partial};
-    layer_epilogue<ACT>(g, row0, col0, E);
+    const LayerEpi E = {W, ldw, bias, tptr, tval, t_per_row, tcol, B, N, out, zout, mse_u, mse_scale, mse_inv_n, mse_partial, nullptr};
+    layer_epilogue<ACT>(g, row0, col0, E, blockIdx.x);
+}
+
+// The same layer of TWO nets of equal sizes in one launch (the flow and the score net of the SF2M step,
+// cfm_mlp_sf2m_step_f32): workgroups [0, per_net) are net 0's grid, [per_net, 2 per_net) net 1's, each in the order
+// and with the tile it has when that net runs alone — the same bits as two launches.
+struct LayerArgs { const float* X; int lda, K, tiles_n; LayerEpi E; };
+struct LayerArgs2 { LayerArgs net[2]; };
+template <int BM, int BN, int BK, bool ACT, bool VECA, bool VECB>
+__global__ __launch_bounds__(256) void mlp_layer_two(LayerArgs2 T, unsigned per_net) {
+    using Core = GemmCore<BM, BN, BK, false, false, VECA, VECB>;
+    __shared__ __attribute__((aligned(16))) float lds[Core::LDS_FLOATS];
+    const unsigned second = blockIdx.x >= per_net ? 1u : 0u;
+    const LayerArgs P = T.net[second];
+    const unsigned wg = blockIdx.x - second * per_net;
+    const unsigned lid = cfm_xcd_remap(wg, per_net);
+    const int tm = lid / P.tiles_n, tn = lid % P.tiles_n;
+    const int row0 = tm * BM, col0 = tn * BN;
+    Core g;
+    g.zero();
+    g.run(lds, P.X, P.lda, row0, P.E.B, P.E.W, P.E.ldw, col0, P.E.N, 0, P.K, GcNoPost());
+    layer_epilogue<ACT>(g, row0, col0, P.E, wg);
 }
 
 // The same layer on the direct-to-LDS engine (gemm_glds64.h): 64 x 64 tiles, operands DMA'd row-major into LDS, one
@@ -130,7 +161,22 @@ __global__ __launch_bounds__(256) void mlp_layer_glds(const float* __restrict__ 
     Glds64<MLP_GLDS_NST> g;
     g.zero();
     g.run(glds, X, lda, row0, E.B, W, ldw, col0, E.N, K);
-    layer_epilogue<ACT>(g, row0, col0, E);
+    layer_epilogue<ACT>(g, row0, col0, E, blockIdx.x);
+}
+// (two nets per launch, as mlp_layer_two)
+template <bool ACT>
+__global__ __launch_bounds__(256) void mlp_layer_glds_two(LayerArgs2 T, unsigned per_net) {
+    extern __shared__ __attribute__((aligned(16))) float glds[];
+    const unsigned second = blockIdx.x >= per_net ? 1u : 0u;
+    const LayerArgs P = T.net[second];
+    const unsigned wg = blockIdx.x - second * per_net;
+    const unsigned lid = cfm_xcd_remap(wg, per_net);
+    const int tm = lid / P.tiles_n, tn = lid % P.tiles_n;
+    const int row0 = tm * G6_BM, col0 = tn * G6_BN;
+    Glds64<MLP_GLDS_NST> g;
+    g.zero();
+    g.run(glds, P.X, P.lda, row0, P.E.B, P.E.W, P.E.ldw, col0, P.E.N, P.K);
+    layer_epilogue<ACT>(g, row0, col0, P.E, wg);
 }
 
 extern "C" size_t cfm_mlp_ws_bytes_internal(int B, int width) {
@@ -174,35 +220,92 @@ static void launch_layer_t(int tile, const float* X, int lda, const float* W, in
     }
 }
 
-// one layer launch; picks the tile so the grid covers the chip.  16-byte loads per operand when its rows allow it
-// (K % 4 == 0, row pitch % 4 == 0, aligned base): the 785-wide rows of a time-varying first layer do not.
+// Which kernel a layer runs on: the tile so the grid covers the chip; 16-byte loads per operand when its rows allow it
+// (K % 4 == 0, row pitch % 4 == 0, aligned base): the 785-wide rows of a time-varying first layer do not; the
+// direct-to-LDS form of the 64 x 64 tile (round 6) where its preconditions hold.
+struct LayerPlan { int tile; bool va, vb, glds; int tm, tn; };
+static LayerPlan plan_layer(const float* X, int lda, const float* W, int ldw, int B, int K, int N) {
+    LayerPlan P;
+    P.tile = cfm_gemm_pick_tile(B, N, 1);
+    P.tm = (P.tile == 0) ? (B + 127) / 128 : (B + 63) / 64;
+    P.tn = (P.tile == 0) ? (N + 127) / 128 : (N + 63) / 64;
+    P.va = (K % 4 == 0) && (lda % 4 == 0) && ((uintptr_t)X & 15) == 0;
+    P.vb = (K % 4 == 0) && (ldw % 4 == 0) && ((uintptr_t)W & 15) == 0;
+    const int gmode = mlp_glds_mode();
+    const bool ga = gmode == 2 ? (((uintptr_t)X & 3) == 0) : P.va, gb = gmode == 2 ? (((uintptr_t)W & 3) == 0) : P.vb;
+    P.glds = gmode && P.tile == 2 && K >= 16 && K % 16 == 0 && ga && gb &&
+             (size_t)B * (size_t)lda * 4 < 0xffff0000ull && (size_t)N * (size_t)ldw * 4 < 0xffff0000ull;
+    return P;
+}
+
+// one layer launch
 static int launch_layer(const float* X, int lda, const float* W, int ldw, const float* bias,
                         const float* t, float tval, int t_per_row, int tcol, int B, int K, int N, float* out,
                         bool act, hipStream_t s, float* zout = nullptr, const float* mse_u = nullptr, float mse_scale = 0.f,
                         float mse_inv_n = 0.f, float* mse_partial = nullptr, int* mse_blocks = nullptr) {
-    const int tile = cfm_gemm_pick_tile(B, N, 1);
-    if (mse_blocks) *mse_blocks = (tile == 0) ? ((B + 127) / 128) * ((N + 127) / 128) : ((B + 63) / 64) * ((N + 63) / 64);
-    const bool va = (K % 4 == 0) && (lda % 4 == 0) && ((uintptr_t)X & 15) == 0;
-    const bool vb = (K % 4 == 0) && (ldw % 4 == 0) && ((uintptr_t)W & 15) == 0;
-    // the direct-to-LDS form of the 64 x 64 tile (round 6)
-    const int gmode = mlp_glds_mode();
-    const bool ga = gmode == 2 ? (((uintptr_t)X & 3) == 0) : va, gb = gmode == 2 ? (((uintptr_t)W & 3) == 0) : vb;
-    if (gmode && tile == 2 && K >= 16 && K % 16 == 0 && ga && gb &&
-        (size_t)B * (size_t)lda * 4 < 0xffff0000ull && (size_t)N * (size_t)ldw * 4 < 0xffff0000ull) {
-        const int tm = (B + 63) / 64, tn = (N + 63) / 64;
-        const LayerEpi E = {W, ldw, bias, t, tval, t_per_row, tcol, B, N, out, zout, mse_u, mse_scale, mse_inv_n, mse_partial};
+    const LayerPlan P = plan_layer(X, lda, W, ldw, B, K, N);
+    const int tile = P.tile;
+    if (mse_blocks) *mse_blocks = P.tm * P.tn;
+    if (P.glds) {
+        const LayerEpi E = {W, ldw, bias, t, tval, t_per_row, tcol, B, N, out, zout, mse_u, mse_scale, mse_inv_n, mse_partial, nullptr};
         constexpr int lds_bytes = Glds64<MLP_GLDS_NST>::LDS_BYTES;
-        if (act) hipLaunchKernelGGL(mlp_layer_glds<true>, dim3(tm * tn), dim3(256), lds_bytes, s, X, lda, W, ldw, K, tn, E);
-        else hipLaunchKernelGGL(mlp_layer_glds<false>, dim3(tm * tn), dim3(256), lds_bytes, s, X, lda, W, ldw, K, tn, E);
+        if (act) hipLaunchKernelGGL(mlp_layer_glds<true>, dim3(P.tm * P.tn), dim3(256), lds_bytes, s, X, lda, W, ldw, K, P.tn, E);
+        else hipLaunchKernelGGL(mlp_layer_glds<false>, dim3(P.tm * P.tn), dim3(256), lds_bytes, s, X, lda, W, ldw, K, P.tn, E);
         return cfm_status();
     }
 #define CFM_LL(ACT_, VA_, VB_) launch_layer_t<ACT_, VA_, VB_>(tile, X, lda, W, ldw, bias, t, tval, t_per_row, tcol, B, K, N, out, s, zout, mse_u, mse_scale, mse_inv_n, mse_partial)
-    if (act) { if (va) { if (vb) CFM_LL(true, true, true); else CFM_LL(true, true, false); }
-               else    { if (vb) CFM_LL(true, false, true); else CFM_LL(true, false, false); } }
-    else     { if (va) { if (vb) CFM_LL(false, true, true); else CFM_LL(false, true, false); }
-               else    { if (vb) CFM_LL(false, false, true); else CFM_LL(false, false, false); } }
+    if (act) { if (P.va) { if (P.vb) CFM_LL(true, true, true); else CFM_LL(true, true, false); }
+               else      { if (P.vb) CFM_LL(true, false, true); else CFM_LL(true, false, false); } }
+    else     { if (P.va) { if (P.vb) CFM_LL(false, true, true); else CFM_LL(false, true, false); }
+               else      { if (P.vb) CFM_LL(false, false, true); else CFM_LL(false, false, false); } }
 #undef CFM_LL
     return cfm_status();
+}
+
+template <bool ACT, bool VECA, bool VECB>
+static void launch_layer_two_t(int tile, const LayerArgs2& T, unsigned per_net, unsigned nets, hipStream_t s) {
+    if (tile == 0) hipLaunchKernelGGL((mlp_layer_two<128, 128, 16, ACT, VECA, VECB>), dim3(nets * per_net), dim3(256), 0, s, T, per_net);
+    else hipLaunchKernelGGL((mlp_layer_two<64, 64, 32, ACT, VECA, VECB>), dim3(nets * per_net), dim3(256), 0, s, T, per_net);
+}
+// nets = 2: both nets of the table on one grid; nets = 1: net 0 alone (no workgroup reaches the second half)
+static int launch_layer_two(const LayerPlan& P, const LayerArgs2& T, unsigned nets, bool act, hipStream_t s) {
+    const unsigned per_net = (unsigned)(P.tm * P.tn);
+    if (P.glds) {
+        constexpr int lds_bytes = Glds64<MLP_GLDS_NST>::LDS_BYTES;
+        if (act) hipLaunchKernelGGL(mlp_layer_glds_two<true>, dim3(nets * per_net), dim3(256), lds_bytes, s, T, per_net);
+        else hipLaunchKernelGGL(mlp_layer_glds_two<false>, dim3(nets * per_net), dim3(256), lds_bytes, s, T, per_net);
+        return cfm_status();
+    }
+#define CFM_LL(ACT_, VA_, VB_) launch_layer_two_t<ACT_, VA_, VB_>(P.tile, T, per_net, nets, s)
+    if (act) { if (P.va) { if (P.vb) CFM_LL(true, true, true); else CFM_LL(true, true, false); }
+               else      { if (P.vb) CFM_LL(true, false, true); else CFM_LL(true, false, false); } }
+    else     { if (P.va) { if (P.vb) CFM_LL(false, true, true); else CFM_LL(false, true, false); }
+               else      { if (P.vb) CFM_LL(false, false, true); else CFM_LL(false, false, false); } }
+#undef CFM_LL
+    return cfm_status();
+}
+
+// One layer of the two nets of cfm_mlp_sf2m_step_f32 (mlp_train.hip): equal sizes, one time vector, per-net operands.
+// The kernel is chosen PER NET by plan_layer, as if that net ran alone; equal choices (the sizes are equal, so only an
+// operand's alignment can make them differ) share one launch of 2 x the grid, unequal ones take one launch each.
+// Last layer (act = false, target != NULL): the loss epilogue, plain (lam == NULL) or weighted.
+int cfm_mlp_launch_layer_two(const MlpNetLayer* net, int lda, int ldw, const float* t, int tcol, int B, int K, int N,
+                             bool act, float inv_n, hipStream_t s, int* n_partials) {
+    LayerPlan P[2]; LayerArgs2 T;
+    for (int q = 0; q < 2; ++q) {
+        P[q] = plan_layer(net[q].X, lda, net[q].W, ldw, B, K, N);
+        const LayerEpi E = {net[q].W, ldw, net[q].bias, t, 0.f, tcol >= 0 ? 1 : 0, tcol, B, N, net[q].out, net[q].zout,
+                            net[q].target, net[q].scale, inv_n, net[q].partial, net[q].lam};
+        T.net[q] = LayerArgs{net[q].X, lda, K, P[q].tn, E};
+    }
+    if (n_partials) *n_partials = P[0].tm * P[0].tn;      // (the tile follows from the sizes alone: equal for both nets)
+    if (P[0].va == P[1].va && P[0].vb == P[1].vb && P[0].glds == P[1].glds) return launch_layer_two(P[0], T, 2, act, s);
+    for (int q = 0; q < 2; ++q) {
+        LayerArgs2 T1; T1.net[0] = T.net[q]; T1.net[1] = T.net[q];
+        const int rc = launch_layer_two(P[q], T1, 1, act, s);
+        if (rc) return rc;
+    }
+    return 0;
 }
 
 // (mlp_train.hip: the fused regression step runs its forward through the same launcher)

@@ -154,6 +154,36 @@ __global__ __launch_bounds__(256) void gemm_pair_f32_mfma(GemmArgs D, int tiles_
     }
 }
 
+// The same launches for TWO nets of equal sizes (the flow and the score net of cfm_mlp_sf2m_step_f32): x-blocks
+// [0, per_net) are net 0's grid, [per_net, 2 per_net) net 1's, each net's workgroups in the order, on the tile and
+// with the split they have when that net runs alone — the same tile routine, the same bits as one launch per net.
+struct GemmArgs2 { GemmArgs net[2]; };
+template <int BM, int BN, int BK, bool A_KMAJOR, bool B_KMAJOR, int EPI, bool VECA, bool VECB>
+__global__ __launch_bounds__(256) void gemm_f32_mfma_two(GemmArgs2 T, unsigned per_net) {
+    using Core = GemmCore<BM, BN, BK, A_KMAJOR, B_KMAJOR, VECA, VECB>;
+    __shared__ __attribute__((aligned(16))) float lds[Core::LDS_FLOATS];
+    const unsigned second = blockIdx.x >= per_net ? 1u : 0u;
+    const GemmArgs G = T.net[second];
+    gemm_tile<BM, BN, BK, A_KMAJOR, B_KMAJOR, EPI, VECA, VECB>(lds, cfm_xcd_remap(blockIdx.x - second * per_net, per_net), (int)blockIdx.y, G);
+}
+__global__ __launch_bounds__(256) void gemm_pair_f32_mfma_two(GemmArgs2 D, int tiles_d, GemmArgs2 Wg, int tiles_w, int splits_w) {
+    using CoreD = GemmCore<64, 64, 32, false, true, true, true>;
+    using CoreW = GemmCore<64, 64, 32, true, true, true, true>;
+    constexpr int LDSF = CoreD::LDS_FLOATS > CoreW::LDS_FLOATS ? CoreD::LDS_FLOATS : CoreW::LDS_FLOATS;
+    __shared__ __attribute__((aligned(16))) float lds[LDSF];
+    const int per_net = tiles_d + tiles_w * splits_w;
+    const int second = (int)blockIdx.x >= per_net ? 1 : 0;
+    const int b = (int)blockIdx.x - second * per_net;
+    if (b < tiles_d) {
+        const GemmArgs G = D.net[second];
+        gemm_tile<64, 64, 32, false, true, EPI_SELU_GRAD, true, true>(lds, cfm_xcd_remap((unsigned)b, (unsigned)tiles_d), 0, G);
+    } else {
+        const int q = b - tiles_d;
+        const GemmArgs G = Wg.net[second];
+        gemm_tile<64, 64, 32, true, true, EPI_PLAIN, true, true>(lds, cfm_xcd_remap((unsigned)(q % tiles_w), (unsigned)tiles_w), q / tiles_w, G);
+    }
+}
+
 // out[e] = sum_s partial[s * stride + e] in split order (deterministic), for every tensor of the table
 // (all weight and bias gradients of a backward pass in ONE launch)
 struct ReduceJob { const float* partial; float* out; unsigned long long stride, n; int S, cols, ld_out, pad; };   // cols > 0: out[(e / cols) * ld_out + e % cols]
@@ -207,6 +237,9 @@ int cfm_mlp_launch_layer_mse(const float* X, int lda, const float* W, int ldw, c
                              int t_per_row, int tcol, int B, int K, int N, float* out, hipStream_t s, const float* u,
                              float scale, float inv_n, float* partial, int* n_partials);
 
+int cfm_mlp_launch_layer_two(const MlpNetLayer* net, int lda, int ldw, const float* t, int tcol, int B, int K, int N,
+                             bool act, float inv_n, hipStream_t s, int* n_partials);
+
 static GemmArgs gemm_args(const float* A, int lda, const float* Bm, int ldb, float* C, int ldc, size_t split_stride,
                           const float* H, int M, int N, int Kc, int k_chunk, int tiles_n, float* colsum, const float* tvec,
                           float* tsum) {
@@ -251,6 +284,16 @@ static int launch_gemm(const float* A, int lda, const float* Bm, int ldb, float*
     return cfm_status();
 }
 
+// batch splits of a weight gradient dW[N, K]: enough workgroups to fill the chip, at least 64 rows per split
+// (round 6, forced split counts at C3: S = 4 / 8 / 16 (this rule) / 32: forward + MSE + backward 444 / 413 / 410 / 477 us —
+//  profiles/r6_experiments.txt)
+static int wgrad_splits(int N, int K, int B) {
+    const long tiles = (long)((N + 127) / 128) * ((K + 127) / 128);
+    int S = 1;
+    while (S < MLP_MAX_SPLITS && tiles * S < 256 && B / (2 * S) >= 64) S *= 2;
+    return S;
+}
+
 // Backward through all layers.  acts[l] = h_l (l = 0: the network input [B, dims[0]]; l = 1 .. n-1: the
 // saved hidden activations), preact[l] = z_l for l = 1 .. n-1 (preact[0] unused); dout [B, dims[n]].
 // Writes dW[l] ([dims[l+1], dims[l]]), db[l] and, if dx is not NULL, the input gradient [B, dims[0]].
@@ -277,11 +320,7 @@ static int mlp_backward_impl(const float* const* acts, const float* const* preac
         const int Kfull = dims[l], N = dims[l + 1];
         const int K = split_t ? Kfull - 1 : Kfull;            // columns of the GEMM operand
         // wgrad: dW[N,K] = dz^T[N,B] . h[B,K], contraction over the batch, S splits; db partials ride along
-        const long tiles = (long)((N + 127) / 128) * ((K + 127) / 128);
-        int S = 1;
-        while (S < MLP_MAX_SPLITS && tiles * S < 256 && B / (2 * S) >= 64) S *= 2;
-        // (round 6, forced split counts at C3: S = 4 / 8 / 16 (this rule) / 32: forward + MSE + backward 444 / 413 / 410 / 477 us —
-        //  profiles/r6_experiments.txt)
+        const int S = wgrad_splits(N, K, B);
         const size_t np = (size_t)N * K;
         if (used + (size_t)S * (np + 2 * (size_t)N) > pool_floats) return CFM_EINVAL;      // more layers than the workspace was sized for
         float* part = pool + used; used += (size_t)S * np;
@@ -433,6 +472,191 @@ extern "C" int cfm_mlp_regression_step_f32(const float* xt, const float* t, cons
     for (int l = 1; l < n_layers; ++l) { acts[l] = hidden[l - 1]; zs[l] = preact[l - 1]; }
     const ReduceJob lj = ReduceJob{lpart, loss, 1ull, 1ull, n_lpart, 0, 0, 1};      // (pad = 1: one number out of n_lpart partials)
     return mlp_backward_impl(acts, zs, W, dims, n_layers, B, g, dW, db, nullptr, ws, s, has_t ? t : nullptr, &lj, layer_done);
+}
+
+// ------------------------------------------------------------ the SF2M step: two nets ----
+// one product of each of two nets: per-net operands, shared sizes
+struct GemmOps { const float* A; const float* Bm; float* C; const float* H; float* colsum; float* tsum; };
+
+template <bool AK, bool BK_, int EPI, bool VA, bool VB>
+static void launch_gemm_two_t(int tile, const GemmOps* op, unsigned nets, int lda, int ldb, int ldc, size_t split_stride, int M, int N,
+                              int Kc, int k_chunk, int S, hipStream_t s, const float* tvec) {
+    const int bm = tile == 0 ? 128 : 64;
+    const int tm = (M + bm - 1) / bm, tn = (N + bm - 1) / bm;
+    GemmArgs2 T;
+    for (unsigned q = 0; q < 2; ++q) {
+        const GemmOps& o = op[q < nets ? q : 0];
+        T.net[q] = gemm_args(o.A, lda, o.Bm, ldb, o.C, ldc, split_stride, o.H, M, N, Kc, k_chunk, tn, o.colsum, tvec, o.tsum);
+    }
+    if (tile == 0)
+        hipLaunchKernelGGL((gemm_f32_mfma_two<128, 128, 16, AK, BK_, EPI, VA, VB>), dim3(nets * tm * tn, S), dim3(256), 0, s, T, (unsigned)(tm * tn));
+    else
+        hipLaunchKernelGGL((gemm_f32_mfma_two<64, 64, 32, AK, BK_, EPI, VA, VB>), dim3(nets * tm * tn, S), dim3(256), 0, s, T, (unsigned)(tm * tn));
+}
+
+// launch_gemm for two nets: tile and split from the sizes (equal for both), 16-byte loads per net from its own operands;
+// equal choices share one launch, unequal ones (an operand of one net off the 16-byte grid) take one launch each
+template <bool AK, bool BK_, int EPI>
+static int launch_gemm_two(const GemmOps* op, int lda, int ldb, int ldc, size_t split_stride, int M, int N, int Kc, int S,
+                           hipStream_t s, const float* tvec = nullptr) {
+    int k_chunk = (Kc + S - 1) / S;
+    k_chunk = (k_chunk + 31) / 32 * 32;
+    const int tile = cfm_gemm_pick_tile(M, N, S);
+    bool va[2], vb[2];
+    for (int q = 0; q < 2; ++q) { va[q] = gemm_vec_ok(op[q].A, lda, AK ? M : Kc); vb[q] = gemm_vec_ok(op[q].Bm, ldb, BK_ ? N : Kc); }
+    const bool same = va[0] == va[1] && vb[0] == vb[1];
+    for (int q = 0; q < (same ? 1 : 2); ++q) {
+        const GemmOps* o = op + q; const unsigned nets = same ? 2u : 1u;
+#define CFM_LG(VA_, VB_) launch_gemm_two_t<AK, BK_, EPI, VA_, VB_>(tile, o, nets, lda, ldb, ldc, split_stride, M, N, Kc, k_chunk, S, s, tvec)
+        if (va[q]) { if (vb[q]) CFM_LG(true, true); else CFM_LG(true, false); }
+        else       { if (vb[q]) CFM_LG(false, true); else CFM_LG(false, false); }
+#undef CFM_LG
+        const int rc = cfm_status();
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+// what mlp_backward_impl needs of one net
+struct NetBackward {
+    const float* acts[MLP_MAX_LAYERS]; const float* zs[MLP_MAX_LAYERS]; const float* const* W; float* const* dW; float* const* db;
+    const float* dout; void* ws; ReduceJob loss;
+};
+
+// mlp_backward_impl for two nets of equal sizes: layer by layer the same launches, each on twice the grid (tile, split
+// and pairing decided per net exactly as above), and ONE reduction of both nets' partials and loss partials.
+static int mlp_backward_two_impl(const NetBackward* nb, const int* dims, int n_layers, int B, hipStream_t s, const float* tvec) {
+    int maxw = 0; size_t maxp = 0;
+    for (int l = 0; l <= n_layers; ++l) maxw = dims[l] > maxw ? dims[l] : maxw;
+    for (int l = 0; l < n_layers; ++l) { const size_t p = (size_t)dims[l] * dims[l + 1]; maxp = p > maxp ? p : maxp; }
+    float* gbuf[2][2]; float* pool[2];
+    for (int q = 0; q < 2; ++q) {
+        gbuf[q][0] = (float*)nb[q].ws; gbuf[q][1] = gbuf[q][0] + (size_t)B * maxw;
+        pool[q] = gbuf[q][1] + (size_t)B * maxw;
+    }
+    const size_t pool_floats = (size_t)MLP_MAX_SPLITS * (maxp + maxw) * 4;
+    size_t used = 0;
+    ReduceTable T; T.count = 0;
+    const float* dz[2] = {nb[0].dout, nb[1].dout};
+    for (int l = n_layers - 1; l >= 0; --l) {
+        const bool split_t = (l == 0 && tvec != nullptr);
+        const int Kfull = dims[l], N = dims[l + 1];
+        const int K = split_t ? Kfull - 1 : Kfull;
+        const int S = wgrad_splits(N, K, B);
+        const size_t np = (size_t)N * K;
+        if (used + (size_t)S * (np + 2 * (size_t)N) > pool_floats) return CFM_EINVAL;
+        const size_t o_part = used; used += (size_t)S * np;
+        const size_t o_bpart = used; used += (size_t)S * N;
+        const size_t o_tpart = used; if (split_t) used += (size_t)S * N;
+        bool pair_ok[2];
+        GemmOps wop[2], dop[2];
+        for (int q = 0; q < 2; ++q) {
+            float* dprev = (l > 0) ? gbuf[q][l & 1] : nullptr;
+            wop[q] = GemmOps{dz[q], nb[q].acts[l], pool[q] + o_part, nullptr, pool[q] + o_bpart, split_t ? pool[q] + o_tpart : nullptr};
+            dop[q] = GemmOps{dz[q], nb[q].W[l], dprev, nb[q].zs[l], nullptr, nullptr};
+            pair_ok[q] = l > 0 && cfm_gemm_pick_tile(N, K, S) == 2 && cfm_gemm_pick_tile(B, K, 1) == 2 &&
+                         gemm_vec_ok(dz[q], N, N) && gemm_vec_ok(nb[q].acts[l], K, K) && gemm_vec_ok(nb[q].W[l], K, K);
+        }
+        int rc = 0;
+        const bool paired = pair_ok[0] && pair_ok[1];
+        if (paired) {
+            int k_chunk_w = (B + S - 1) / S; k_chunk_w = (k_chunk_w + 31) / 32 * 32;
+            const int k_chunk_d = (N + 31) / 32 * 32;
+            const int tnw = (K + 63) / 64, tiles_w = ((N + 63) / 64) * tnw;
+            const int tnd = (K + 63) / 64, tiles_d = ((B + 63) / 64) * tnd;
+            GemmArgs2 Ga, Gw;
+            for (int q = 0; q < 2; ++q) {
+                Ga.net[q] = gemm_args(dz[q], N, nb[q].W[l], K, dop[q].C, K, 0, nb[q].zs[l], B, K, N, k_chunk_d, tnd, nullptr, nullptr, nullptr);
+                Gw.net[q] = gemm_args(dz[q], N, nb[q].acts[l], K, wop[q].C, K, np, nullptr, N, K, B, k_chunk_w, tnw, wop[q].colsum, nullptr, nullptr);
+            }
+            hipLaunchKernelGGL(gemm_pair_f32_mfma_two, dim3(2 * (tiles_d + tiles_w * S)), dim3(256), 0, s, Ga, tiles_d, Gw, tiles_w, S);
+            rc = cfm_status();
+        } else {
+            rc = launch_gemm_two<true, true, EPI_PLAIN>(wop, N, K, K, np, N, K, B, S, s, split_t ? tvec : nullptr);
+        }
+        if (rc) return rc;
+        for (int q = 0; q < 2; ++q) {
+            T.job[T.count++] = ReduceJob{wop[q].C, nb[q].dW[l], np, np, S, split_t ? K : 0, Kfull, 0};
+            T.job[T.count++] = ReduceJob{wop[q].colsum, nb[q].db[l], (unsigned long long)N, (unsigned long long)N, S, 0, 0, 0};
+            if (split_t) T.job[T.count++] = ReduceJob{wop[q].tsum, nb[q].dW[l] + K, (unsigned long long)N, (unsigned long long)N, S, 1, Kfull, 0};
+        }
+        if (l > 0) {
+            if (!paired) {
+                rc = launch_gemm_two<false, true, EPI_SELU_GRAD>(dop, N, K, K, 0, B, K, N, 1, s);
+                if (rc) return rc;
+            }
+            dz[0] = dop[0].C; dz[1] = dop[1].C;
+        }
+    }
+    T.job[T.count++] = nb[0].loss; T.job[T.count++] = nb[1].loss;
+    hipLaunchKernelGGL(reduce_splits_multi, dim3(256, T.count), dim3(256), 0, s, T);
+    return cfm_status();
+}
+
+// the deepest pair of nets whose reduction jobs fit ONE ReduceTable: 2 nets x (2 per layer + the time column + the loss)
+#define SF2M_MAX_LAYERS ((2 * MLP_MAX_LAYERS + 2 - 4) / 4)
+
+// One [SF]2M training step for a flow net and a score net of equal layer sizes, everything but the optimizer update:
+//     v = flow([xt, t]);  s = score([xt, t]);  losses = {mean((v - ut)^2), mean((lam[:, None] * s + eps)^2)}
+//     dW, db of both nets = d (losses[0] + score_weight * losses[1]) / d parameters
+// — examples/2D_tutorials/SF2M_tutorial.ipynb cell 3, runner/src/models/cfm_module.py:896-909.  Every launch of
+// cfm_mlp_regression_step_f32 serves both nets (see gemm_f32_mfma_two), so the step has the launch count of ONE
+// regression step; the kernel choices are made per net, so each net's gradients are the bits that step gives it alone
+// (the flow net on ut; the score net, with lam = 1, on -eps).
+extern "C" int cfm_mlp_sf2m_step_f32(const float* xt, const float* t, const float* ut, const float* eps, const float* lam,
+                                     const float* const* W, const float* const* b, float* const* hidden,
+                                     float* const* preact, float* const* dW, float* const* db, const int* dims,
+                                     int n_layers, int B, float* g_flow, float* g_score, float* losses,
+                                     float score_weight, void* ws, void* stream) {
+    if (!xt || !ut || !eps || !lam || !W || !b || !dims || !g_flow || !g_score || !dW || !db || !losses || !ws || n_layers < 1 || B < 1)
+        return CFM_EINVAL;
+    if (n_layers > SF2M_MAX_LAYERS) return CFM_EINVAL;      // the one reduction's table is full at two nets of 7 layers
+    if (n_layers > 1 && (!hidden || !preact)) return CFM_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const int has_t = t != nullptr;
+    if (has_t && dims[0] < 2) return CFM_EINVAL;
+    int maxw = 0; size_t maxp = 0;
+    for (int l = 0; l <= n_layers; ++l) maxw = dims[l] > maxw ? dims[l] : maxw;
+    for (int l = 0; l < n_layers; ++l) { const size_t p = (size_t)dims[l] * dims[l + 1]; maxp = p > maxp ? p : maxp; }
+    // one loss partial per workgroup of the last layer (this step has no separate loss launch to fall back on)
+    if ((long)((B + 63) / 64) * ((dims[n_layers] + 63) / 64) > MLP_LOSS_PARTIALS) return CFM_EINVAL;
+    // two CFM_OP_MLP_TRAIN workspaces back to back: the flow net's, then the score net's
+    const size_t ws_one = cfm_mlp_train_ws_bytes_internal(B, maxw, (int)maxp), ws_pitch = cfm_align_up(ws_one, 256);
+    NetBackward nb[2];
+    float* lpart[2];
+    for (int q = 0; q < 2; ++q) {
+        nb[q].ws = (char*)ws + q * ws_pitch;
+        lpart[q] = (float*)((char*)nb[q].ws + ws_one - 4 * MLP_LOSS_PARTIALS);
+        nb[q].W = W + q * n_layers; nb[q].dW = dW + q * n_layers; nb[q].db = db + q * n_layers;
+        nb[q].acts[0] = xt; nb[q].zs[0] = nullptr;
+        for (int l = 1; l < n_layers; ++l) { nb[q].acts[l] = hidden[q * (n_layers - 1) + l - 1]; nb[q].zs[l] = preact[q * (n_layers - 1) + l - 1]; }
+    }
+    nb[0].dout = g_flow; nb[1].dout = g_score;
+    const size_t nel = (size_t)B * dims[n_layers];
+    const float inv_n = 1.0f / (float)nel;
+    const float* cur[2] = {xt, xt};
+    int n_lpart = 0;
+    for (int l = 0; l < n_layers; ++l) {
+        const bool last = (l == n_layers - 1);
+        const bool first_t = (l == 0 && has_t);
+        const int K = first_t ? dims[0] - 1 : dims[l];
+        MlpNetLayer net[2];
+        for (int q = 0; q < 2; ++q) {
+            float* dst = last ? (q ? g_score : g_flow) : hidden[q * (n_layers - 1) + l];
+            net[q] = MlpNetLayer{cur[q], W[q * n_layers + l], b[q * n_layers + l], dst, last ? nullptr : preact[q * (n_layers - 1) + l],
+                                 nullptr, nullptr, 0.f, nullptr};
+            if (last) {
+                net[q].target = q ? eps : ut; net[q].lam = q ? lam : nullptr; net[q].partial = lpart[q];
+                net[q].scale = q ? (2.0f * inv_n) * score_weight : 2.0f * inv_n;
+            }
+            cur[q] = dst;
+        }
+        const int rc = cfm_mlp_launch_layer_two(net, K, dims[l], first_t ? t : nullptr, first_t ? K : -1, B, K, dims[l + 1], !last, inv_n, s,
+                                                last ? &n_lpart : nullptr);
+        if (rc) return rc;
+    }
+    for (int q = 0; q < 2; ++q) nb[q].loss = ReduceJob{lpart[q], losses + q, 1ull, 1ull, n_lpart, 0, 0, 1};
+    return mlp_backward_two_impl(nb, dims, n_layers, B, s, has_t ? t : nullptr);
 }
 
 // ------------------------------------------------------------------- Adam ----

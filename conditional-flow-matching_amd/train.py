@@ -21,6 +21,11 @@ the reference's DDP wrapper does it (train_cifar10_ddp.py:92,167-180): one bucke
 communication stream as soon as that layer's gradient is final (``layer_done`` events recorded by the C call between
 its launches) while the remaining layers' products still run; the compute stream waits for the buckets, and the
 ``1 / world`` of the mean is a factor inside the Adam launch (``grad_scale``) — no eager op in the step for N > 1 either.
+
+``SF2MStep(model, score_model, optimizer)(t, xt, ut, eps, lambda_t)`` is the same for the [SF]2M loops
+(examples/2D_tutorials/SF2M_tutorial.ipynb cell 3, single-cell_example.ipynb, runner/src/models/cfm_module.py:896-909):
+a flow net and a score net of equal layer sizes under one optimizer, ``cfm_mlp_sf2m_step_f32`` — every launch of the
+regression step serving both nets — followed by one ``cfm_adam_step_f32`` over all parameters of both.
 """
 import ctypes
 
@@ -149,3 +154,129 @@ class RegressionStep:
             self.flat_grad.mul_(1.0 / world)
             self.opt.step()
         return loss
+
+
+def _as_mlp(net, who, what):
+    net = net.module if hasattr(net, "module") and isinstance(net.module, MLP) else net
+    if not isinstance(net, MLP):
+        raise TypeError(f"{who}: {what} is a {type(net).__name__}, not a cfm_amd.MLP")
+    return net
+
+
+def _need_fp32_gpu(who, nets):
+    """nets: (Linear layers, what to call them) per net; biases first, then the dtype, then the device"""
+    for lins, what in nets:
+        if any(l.bias is None for l in lins):
+            raise TypeError(f"{who}: {what} has a Linear layer without bias")
+    for lins, what in nets:
+        if any(l.weight.dtype != torch.float32 or l.bias.dtype != torch.float32 for l in lins):
+            raise TypeError(f"{who}: {what} is not fp32")
+    for lins, what in nets:
+        if any(l.weight.device.type != "cuda" or l.bias.device != l.weight.device for l in lins):
+            raise TypeError(f"{who}: {what} is not on the GPU")
+
+
+class SF2MStep:
+    """The [SF]2M training step for a flow ``MLP`` and a score ``MLP`` of equal layer sizes:
+
+        vt = model(torch.cat([xt, t[:, None]], dim=-1)); st = score_model(torch.cat([xt, t[:, None]], dim=-1))
+        flow_loss = torch.mean((vt - ut) ** 2); score_loss = torch.mean((lambda_t[:, None] * st + eps) ** 2)
+        (flow_loss + score_weight * score_loss).backward(); optimizer.step()
+
+    ``step(t, xt, ut, eps, lambda_t)`` returns the device tensor ``[flow_loss, score_loss]`` (both unweighted, overwritten
+    by the next call); ``lambda_t`` is the caller's ``FM.compute_lambda(...)``, one value per row."""
+
+    MAX_LAYERS = 7      # cfm_mlp_sf2m_step_f32: the one final reduction holds the jobs of two 7-layer nets
+
+    def __init__(self, model, score_model, optimizer, score_weight=1.0):
+        who = "SF2MStep"
+        self.net, self.score_net = _as_mlp(model, who, "the flow model"), _as_mlp(score_model, who, "the score model")
+        flins, slins = self.net._linears(), self.score_net._linears()
+        dims = [flins[0].in_features] + [l.out_features for l in flins]
+        sdims = [slins[0].in_features] + [l.out_features for l in slins]
+        if dims != sdims or bool(self.net.time_varying) != bool(self.score_net.time_varying):
+            raise TypeError(f"{who}: the nets' layer sizes differ (flow {dims}, score {sdims}): one launch serves both "
+                            "nets only when their layers have equal sizes")
+        _need_fp32_gpu(who, ((flins, "the flow model"), (slins, "the score model")))
+        if slins[0].weight.device != flins[0].weight.device:
+            raise TypeError(f"{who}: the score model is not on the GPU of the flow model")
+        if self.net is self.score_net:
+            raise TypeError(f"{who}: the flow and the score model are the same module")
+        self.opt, self.score_weight = optimizer, float(score_weight)
+        self.dims, self.n, self.dev = dims, len(flins), flins[0].weight.device
+        self.lins = flins + slins                                     # flow first, score second: the order of every table
+        # ONE flat gradient buffer for both nets; every parameter's .grad is a view of it
+        self.flat_grad = torch.zeros(sum(l.weight.numel() + l.bias.numel() for l in self.lins), dtype=torch.float32, device=self.dev)
+        self._gviews, off = [], 0
+        for l in self.lins:
+            for p in (l.weight, l.bias):
+                v = self.flat_grad[off:off + p.numel()].view_as(p); off += p.numel()
+                p.grad = v
+                self._gviews.append(v)
+        self._B = None
+        self.losses = torch.zeros(2, dtype=torch.float32, device=self.dev)
+
+    def _buffers(self, B):
+        if self._B != B:
+            d, n, dev = self.dims, self.n, self.dev
+            self.hidden = [torch.empty((B, d[l + 1]), dtype=torch.float32, device=dev) for _ in range(2) for l in range(n - 1)]
+            self.preact = [torch.empty((B, d[l + 1]), dtype=torch.float32, device=dev) for _ in range(2) for l in range(n - 1)]
+            self.g = [torch.empty((B, d[n]), dtype=torch.float32, device=dev) for _ in range(2)]      # own allocations: aligned as RegressionStep's
+            one = _lib.load().cfm_workspace_bytes(_lib.OP_MLP_TRAIN, B, max(d), max(d[l] * d[l + 1] for l in range(n)))
+            self.ws = torch.empty(2 * one, dtype=torch.uint8, device=dev)      # two workspaces back to back
+            m = max(1, 2 * (n - 1))
+            self.hp = (ctypes.c_void_p * m)(*([h.data_ptr() for h in self.hidden] or [0]))
+            self.zp = (ctypes.c_void_p * m)(*([z.data_ptr() for z in self.preact] or [0]))
+            self.cd = (ctypes.c_int * (n + 1))(*d)
+            self._B = B
+
+    def backward_only(self, t, xt, ut, eps, lambda_t):
+        """forward + both losses + backward of both nets; returns ``[flow_loss, score_loss]`` (device tensor)"""
+        if self.n > self.MAX_LAYERS:
+            raise RuntimeError(f"SF2MStep: the nets have {self.n} Linear layers; the fused step takes at most "
+                               f"{self.MAX_LAYERS} (two nets' reduction jobs fill its one table)")
+        lib = _lib.load()
+        xt = xt.detach().reshape(xt.shape[0], -1)
+        ut = ut.detach().reshape(ut.shape[0], -1)
+        B, n = xt.shape[0], self.n
+        tv = self.net.time_varying
+        if xt.shape[1] != self.dims[0] - int(bool(tv)) or ut.shape[1] != self.dims[n] or ut.shape[0] != B:
+            raise RuntimeError(f"SF2MStep: xt has {xt.shape[1]} / ut has {ut.shape[1]} columns, the nets map "
+                               f"{self.dims[0] - int(bool(tv))} (+ time) -> {self.dims[n]}")
+        if eps.numel() != ut.numel() or eps.shape[0] != B:
+            raise RuntimeError(f"SF2MStep: eps has shape {tuple(eps.shape)}, ut {tuple(ut.shape)}")
+        if lambda_t.numel() != B:
+            raise RuntimeError(f"SF2MStep: lambda_t has {lambda_t.numel()} values for {B} rows (one per row is required)")
+        xt = _lib.to_dev_f32(xt, self.dev); ut = _lib.to_dev_f32(ut, self.dev)
+        eps = _lib.to_dev_f32(eps.reshape(B, -1), self.dev); lam = _lib.to_dev_f32(lambda_t.reshape(-1), self.dev)
+        tt = _lib.to_dev_f32(t.detach().reshape(-1), self.dev) if tv else None
+        if tv and tt.numel() != B:
+            raise RuntimeError("SF2MStep: one time per row is required")
+        self._buffers(B)
+        params = [q for l in self.lins for q in (l.weight, l.bias)]
+        for v, p in zip(self._gviews, params):
+            if p.grad is not v:
+                p.grad = v
+        N2 = 2 * n
+        Wp = (ctypes.c_void_p * N2)(*[l.weight.data_ptr() for l in self.lins])
+        bp = (ctypes.c_void_p * N2)(*[l.bias.data_ptr() for l in self.lins])
+        dWp = (ctypes.c_void_p * N2)(*[self._gviews[2 * l].data_ptr() for l in range(N2)])
+        dbp = (ctypes.c_void_p * N2)(*[self._gviews[2 * l + 1].data_ptr() for l in range(N2)])
+        check(lib.cfm_mlp_sf2m_step_f32(ptr(xt), ptr(tt), ptr(ut), ptr(eps), ptr(lam), Wp, bp, self.hp, self.zp, dWp, dbp,
+                                        self.cd, n, B, ptr(self.g[0]), ptr(self.g[1]), ptr(self.losses),
+                                        self.score_weight, ptr(self.ws), stream_ptr()),
+              "cfm_mlp_sf2m_step_f32")
+        return self.losses
+
+    def loss(self):
+        """``flow_loss + score_weight * score_loss`` of the last call (logging: not part of the step)"""
+        return self.losses[0] + self.score_weight * self.losses[1]
+
+    def __call__(self, t, xt, ut, eps, lambda_t):
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise NotImplementedError("SF2MStep is not built for data parallel runs (its gradients would be stepped on "
+                                      "unreduced); use one process, or RegressionStep for the flow net alone")
+        losses = self.backward_only(t, xt, ut, eps, lambda_t)
+        self.opt.step()
+        return losses

@@ -345,6 +345,31 @@ int cfm_mlp_regression_step_f32(const float* xt, const float* t, const float* ut
                                 int B, float* const* hidden, float* const* preact, float* g,
                                 float* const* dW, float* const* db, float* loss, void* const* layer_done,
                                 void* ws, void* stream);
+/* One [SF]2M training step — a flow net and a score net of EQUAL layer sizes on one coupled batch, everything but the
+ * optimizer update, in the launch count of ONE cfm_mlp_regression_step_f32 (every launch serves both nets):
+ *     v = flow([xt, t]);  s = score([xt, t])
+ *     losses[0] = mean((v - ut)^2);  losses[1] = mean((lam[:, None] * s + eps)^2)
+ *     dW, db = d (losses[0] + score_weight * losses[1]) / d parameters
+ * Replaces, of the reference's [SF]2M loops (examples/2D_tutorials/SF2M_tutorial.ipynb cell 3,
+ * examples/single_cell/single-cell_example.ipynb, runner/src/models/cfm_module.py:896-909 with its score_weight),
+ *     vt = model(torch.cat([xt, t[:, None]], dim=-1)); st = score_model(torch.cat([xt, t[:, None]], dim=-1))
+ *     flow_loss = torch.mean((vt - ut) ** 2); score_loss = torch.mean((lambda_t[:, None] * st + eps) ** 2)
+ *     loss = flow_loss + score_loss; loss.backward()
+ * xt, t, ut, dims, n_layers, B as in cfm_mlp_regression_step_f32 (t == NULL: the nets are not time varying); eps
+ * [B, dims[n_layers]]; lam [B] (the caller's FM.compute_lambda(t): not recomputed here).  W, b, dW, db: HOST tables
+ * of 2 * n_layers device pointers, the flow net's layers first, then the score net's; hidden, preact: 2 * (n_layers - 1)
+ * in the same order.  g_flow, g_score [B, dims[n_layers]] receive d loss / d v and d loss / d s.  losses: two device
+ * floats, flow and score, both UNweighted (score_weight scales the score net's gradient seed, 2 * score_weight / (B * N),
+ * not the reported loss).  The kernel of every product is chosen per net exactly as the one-net step chooses it, so
+ * the flow net's gradients are the bits of cfm_mlp_regression_step_f32 on ut, and the score net's, with lam = 1 and
+ * score_weight = 1, its bits on -eps.  Deterministic.  n_layers <= 7 (the one reduction's table holds the jobs of two
+ * 7-layer nets) and at most 4096 output tiles of 64 x 64 in the last layer; beyond either: CFM_EINVAL.
+ * ws: TWO workspaces of cfm_workspace_bytes(CFM_OP_MLP_TRAIN, B, widest layer, largest dims[l]*dims[l+1]) bytes back to
+ * back (the second starts at that byte count, a multiple of 256). */
+int cfm_mlp_sf2m_step_f32(const float* xt, const float* t, const float* ut, const float* eps, const float* lam,
+                          const float* const* W, const float* const* b, float* const* hidden, float* const* preact,
+                          float* const* dW, float* const* db, const int* dims, int n_layers, int B,
+                          float* g_flow, float* g_score, float* losses, float score_weight, void* ws, void* stream);
 /* One torch.optim.Adam step (amsgrad=False, maximize=False) on n_tensors fp32 tensors in ONE launch.
  * table: DEVICE array of n_tensors records {float* param; const float* grad; float* exp_avg;
  * float* exp_avg_sq; uint64 numel} (40 bytes each).  step >= 1 is the step count AFTER this update
