@@ -79,6 +79,8 @@ SIGNATURES = {
     "cfm_mlp_sf2m_step_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _f, _vp, _vp]),
     "cfm_adam_step_f32": (_i, [_vp, _i, _d, _d, _d, _d, _d, _i, _d, _vp]),
     "cfm_sde_em_step_f32": (_i, [_vp, _vp, _vp, _vp, _d, _d, _d, _sz, _vp]),
+    "cfm_sde_srk_mlp_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _vp, ctypes.c_ulonglong, _vp, _vp, _vp]),
+    "cfm_sde_srk_step_f32": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _d, _d, _sz, _vp]),
     "cfm_rbf_mix_sum_f32": (_i, [_vp, _sz, _vp, _i, _vp, _vp]),
     "cfm_ode_euler_mlp_f32": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "cfm_ode_dopri5_mlp_f32": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _i, _f, _f, _vp, _vp, _vp,

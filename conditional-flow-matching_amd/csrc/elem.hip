@@ -16,6 +16,7 @@
 // native approximations) — measured 1-ulp mismatches on gfx950 — so they are not used.  HBM-bound: reads x0[i], x1[j],
 // eps once, writes xt, ut once (16-byte accesses when rows allow it).
 #include "cfm_common.h"
+#include "sde_srk.h"
 #pragma clang fp contract(off)
 
 __device__ __forceinline__ float f_mul(float a, float b) { return a * b; }
@@ -203,9 +204,9 @@ extern "C" int cfm_gather_rows(const void* src, const int64_t* idx, int n, size_
 }
 
 // ---------------------------------------------------------------- SDE step ----
-// One Euler-Maruyama step of dy = (v + s) dt + g dW (SF2M sampling: the reference integrates
-// f = drift(x) + score(x), g = sigma with torchsde.sdeint(..., method="euler"),
-// examples/2D_tutorials/SF2M_tutorial.ipynb cell 5; runner/src/models/components/solver.py:157-182):
+// One Euler-Maruyama step of dy = (v + s) dt + g dW (SF2M sampling: f = drift(x) + score(x), g = sigma under
+// torchsde.sdeint(..., method="euler"): runner/src/models/components/solver.py:157-182 at sde_solver: euler.  The
+// notebooks run torchsde's default "srk" instead — sde_srk_step_kernel below):
 //   y <- y + dt * (v [+ s]) + g * sqrt_dt * xi
 // v, s: drift and score network outputs, xi ~ N(0, 1) drawn by the caller's generator.  In place.
 __global__ __launch_bounds__(256) void sde_em_step_kernel(float* __restrict__ y, const float* __restrict__ v,
@@ -228,6 +229,50 @@ extern "C" int cfm_sde_em_step_f32(float* y, const float* v, const float* s, con
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(sde_em_step_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, y, v, s, xi, (float)dt,
                        (float)(g * sqrt(fabs(dt))), (float)score_sign, n);
+    return cfm_status();
+}
+
+// One stage of an `srk` step (sde_srk.h: SRI2W1 with constant g, torchsde's default method for the reference's
+// SDE classes: the default-method torchsde.sdeint calls of single-cell_example.ipynb / mnist_example.ipynb /
+// conditional_mnist.ipynb / SF2M_tutorial.ipynb cell 5, and runner/src/models/components/solver.py:169-179 at
+// sde_solver: srk) for fields that do not fit the one-launch sampler.  f_i = v_i + ssign * s_i as above.
+//   stage 1: ys = y + h f1          stage 2: ys = y + (h/4)(f1 + f2) + c3 (xi1 + xi2 / sqrt(3))
+//   stage 3: y <- y + (h/6)(f1 + f2 + 4 f3) + gs xi1      (in place)
+template <int STAGE>
+__global__ __launch_bounds__(256) void sde_srk_step_kernel(float* __restrict__ y, float* __restrict__ ys,
+                                                           const float* __restrict__ v1, const float* __restrict__ s1,
+                                                           const float* __restrict__ v2, const float* __restrict__ s2,
+                                                           const float* __restrict__ v3, const float* __restrict__ s3,
+                                                           const float* __restrict__ xi1, const float* __restrict__ xi2,
+                                                           float h, float gs, float c3, float ssign, size_t n) {
+    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (size_t)gridDim.x * 256) {
+        const float k1 = srk_drift(v1[e], s1 ? s1[e] : 0.f, s1 != nullptr, ssign);
+        if (STAGE == 1) { ys[e] = srk_stage2(y[e], k1, h); continue; }
+        const float k2 = srk_drift(v2[e], s2 ? s2[e] : 0.f, s2 != nullptr, ssign);
+        const float z1 = xi1 ? xi1[e] : 0.f;
+        if (STAGE == 2) { ys[e] = srk_stage3(y[e], k1, k2, h, c3, z1, xi2 ? xi2[e] : 0.f); continue; }
+        const float k3 = srk_drift(v3[e], s3 ? s3[e] : 0.f, s3 != nullptr, ssign);
+        y[e] = srk_final(y[e], k1, k2, k3, h, gs, z1);
+    }
+}
+
+extern "C" int cfm_sde_srk_step_f32(int stage, float* y, float* ys, const float* v1, const float* s1, const float* v2,
+                                    const float* s2, const float* v3, const float* s3, const float* xi1,
+                                    const float* xi2, double h, double g, double score_sign, size_t n, void* stream) {
+    if (stage < 1 || stage > 3 || !y || !v1) return CFM_EINVAL;
+    if (stage < 3 && (!ys || ys == y)) return CFM_EINVAL;
+    if (stage >= 2 && !v2) return CFM_EINVAL;
+    if (stage == 3 && !v3) return CFM_EINVAL;
+    if (n == 0) return 0;
+    int blocks = (int)((n + 255) / 256);
+    if (blocks > 4096) blocks = 4096;
+    const float gs = (float)(g * sqrt(fabs(h))), c3 = (float)(0.75 * g * sqrt(fabs(h)));
+    hipStream_t st = (hipStream_t)stream;
+#define CFM_SRK_STAGE(K)                                                                                              \
+    hipLaunchKernelGGL(sde_srk_step_kernel<K>, dim3(blocks), dim3(256), 0, st, y, ys, v1, s1, v2, s2, v3, s3, xi1, xi2, \
+                       (float)h, gs, c3, (float)score_sign, n)
+    if (stage == 1) CFM_SRK_STAGE(1); else if (stage == 2) CFM_SRK_STAGE(2); else CFM_SRK_STAGE(3);
+#undef CFM_SRK_STAGE
     return cfm_status();
 }
 

@@ -1,12 +1,17 @@
 """SDE sampling for SF2M — counterpart of how the reference draws stochastic trajectories:
-``torchsde.sdeint(SDE(model, score_model, sigma), x0, ts, method="euler")``
-(examples/2D_tutorials/SF2M_tutorial.ipynb cell 5) and ``FlowSolver.sdeint`` / ``forward_sde_drift`` /
-``backward_sde_drift`` (runner/src/models/components/solver.py:129-139,157-182).
+``torchsde.sdeint(SDE(model, score_model, sigma), x0, ts)`` (examples/2D_tutorials/SF2M_tutorial.ipynb cell 5,
+single-cell_example.ipynb, mnist_example.ipynb, conditional_mnist.ipynb) and ``FlowSolver.sdeint`` /
+``forward_sde_drift`` / ``backward_sde_drift`` (runner/src/models/components/solver.py:129-139,157-182).
 
-``sdeint`` is fixed-step Euler-Maruyama on the ``ts`` grid refined to steps of at most ``dt``
-(torchsde's Euler scheme).  When the drift and the score are ``cfm_amd.MLP`` fields the network
-evaluations run on the HIP inference kernels and the state update is one fused HIP kernel per step
-(``cfm_sde_em_step_f32``); any other callable pair is stepped by the same scheme in eager torch.
+The notebooks name no method (the tutorial's ``solver="euler"`` is a keyword torchsde ignores with a warning), so for
+their ``noise_type = "diagonal"``, ``sde_type = "ito"`` classes torchsde runs its default ``srk`` (Roessler's SRI2W1,
+strong order 1.5); the runner passes ``method=self.sde_solver``.  Both are built here: ``method="euler"`` (this
+package's default) is fixed-step Euler-Maruyama on the ``ts`` grid refined to steps of at most ``dt`` (torchsde's
+Euler scheme), ``method="srk"`` is SRI2W1 for the constant diagonal noise all of the reference's SDE classes have.
+A script that relied on torchsde's default passes ``method="srk"`` explicitly.  When the drift and the score are
+``cfm_amd.MLP`` fields the network evaluations run on the HIP inference kernels and the state update is one fused HIP
+kernel per step (``cfm_sde_em_step_f32``) or stage (``cfm_sde_srk_step_f32``); any other callable pair is stepped by
+the same scheme in eager torch.
 The Brownian increments come from ``torch.randn`` on the state's device (torchsde's BrownianInterval
 stream is not reproducible without torchsde: the noise stream is NOT bit-compatible, the scheme is).
 """
@@ -70,21 +75,55 @@ def _fused_fields(sde):
     return f, s, df
 
 
+_SRK_SCOPE = ("sdeint method 'srk' is built for FlowScoreSDE with a constant (non-callable) sigma: for constant diagonal "
+              "noise every diffusion-derivative term of the SRI2W1 tableau vanishes; a state- or time-dependent g needs "
+              "the full tableau, which is not built")
+
+
+def _noise_arg(noise, method, n_steps, y0):
+    """None for the named modes, else the caller's standard normals checked against the refined grid."""
+    if isinstance(noise, str):
+        if noise not in ("philox", "torch"):
+            raise ValueError("noise must be 'philox', 'torch' or a tensor of standard normals")
+        return None
+    if not torch.is_tensor(noise):
+        raise ValueError("noise must be 'philox', 'torch' or a tensor of standard normals")
+    want = (n_steps, 2) + tuple(y0.shape) if method == "srk" else (n_steps,) + tuple(y0.shape)
+    if tuple(noise.shape) != want:
+        raise ValueError(f"sdeint(method={method!r}): the noise tensor must have shape {list(want)} "
+                         f"([n_steps{', 2' if method == 'srk' else ''}, B, d] on the grid refined to dt), got {list(noise.shape)}")
+    return noise
+
+
 @torch.no_grad()
 def sdeint(sde, y0, ts, method="euler", dt=1e-3, generator=None, noise="philox", fused=None, **unused):
-    """Euler-Maruyama trajectory [len(ts), B, d] of ``sde`` (an object with f(t, y), g(t, y)) from y0.
+    """Trajectory [len(ts), B, d] of ``sde`` (an object with f(t, y), g(t, y)) from y0 on the ``ts`` grid refined to
+    steps of at most ``dt``.  ``method="euler"`` (default): Euler-Maruyama.  ``method="srk"``: torchsde's default
+    scheme for diagonal Ito noise (SRI2W1, strong order 1.5), built for ``FlowScoreSDE`` with a constant ``sigma`` and
+    strictly increasing ``ts`` (backward integration is ``reverse=True``); three drift evaluations per step.
 
     Two small ``cfm_amd.MLP`` fields (4 layers, widths <= 64: the SF2M tutorial's and the single-cell models) run the
-    WHOLE trajectory in one launch (``cfm_sde_em_mlp_f32``: weights of both fields in LDS, state in registers).
+    WHOLE trajectory in one launch (``cfm_sde_em_mlp_f32`` / ``cfm_sde_srk_mlp_f32``: weights of both fields in LDS,
+    state in registers).
     ``noise="philox"`` (default): N(0, 1) from Philox4x32-10 inside the kernel, seeded from ``generator`` (or torch's
     default CUDA generator), so ``torch.manual_seed`` makes runs repeatable; ``noise="torch"``: the increments are
-    drawn with ``torch.randn`` step by step exactly as the launch-per-step scheme draws them — same trajectory, bit for
-    bit, as that scheme.  ``fused=False`` forces the launch-per-step scheme (measurement / test switch)."""
-    if method != "euler":
-        raise NotImplementedError(f"sdeint method {method!r}: only 'euler' (Euler-Maruyama) is built")
-    if noise not in ("philox", "torch"):
-        raise ValueError("noise must be 'philox' or 'torch'")
+    drawn with ``torch.randn`` step by step exactly as the launch-per-step scheme draws them (``(B, d)`` per step for
+    ``euler``, ``(2, B, d)`` = (xi1, xi2) for ``srk``) — same trajectory, bit for bit, as that scheme; a tensor: the
+    caller's standard normals, ``[n_steps, B, d]`` for ``euler`` and ``[n_steps, 2, B, d]`` for ``srk`` with
+    ``n_steps`` the length of the refined grid.  ``fused=False`` forces the launch-per-step scheme (measurement /
+    test switch)."""
+    if method not in ("euler", "srk"):
+        raise NotImplementedError(f"sdeint method {method!r}: 'euler' (Euler-Maruyama) and 'srk' (SRI2W1) are built")
+    srk = method == "srk"
+    if srk:
+        if not isinstance(sde, FlowScoreSDE) or callable(sde.sigma):
+            raise NotImplementedError(_SRK_SCOPE)
+        pts = [float(x) for x in ts]
+        if any(b <= a for a, b in zip(pts[:-1], pts[1:])):
+            raise ValueError("sdeint(method='srk'): ts must be strictly increasing (integrate backwards with "
+                             "FlowScoreSDE(..., reverse=True))")
     steps = _grid(ts, float(dt))
+    given = _noise_arg(noise, method, len(steps), y0)
     fast = (isinstance(sde, FlowScoreSDE) and isinstance(sde.drift, MLP) and isinstance(sde.score, MLP)
             and not callable(sde.sigma) and y0.dim() == 2 and torch.cuda.is_available())
     out = [y0]
@@ -92,6 +131,8 @@ def sdeint(sde, y0, ts, method="euler", dt=1e-3, generator=None, noise="philox",
         lib = _lib.load()
         dev = _lib.require_gpu()
         y = _lib.to_dev_f32(y0, dev).clone()
+        if given is not None:
+            given = _lib.to_dev_f32(given, dev).contiguous()
         fields = _fused_fields(sde) if (y.shape[1] <= 64 and fused is not False) else None
         if fields is not None and y.shape[1] != fields[2][4]:
             # the one-launch kernel reads y0 with the fields' output width as its pitch: a state of another width
@@ -101,6 +142,7 @@ def sdeint(sde, y0, ts, method="euler", dt=1e-3, generator=None, noise="philox",
             fields = None
         if fused is True and fields is None:
             raise ValueError("sdeint(fused=True): needs two 4-layer time-varying cfm_amd.MLP fields of widths <= 64")
+        sigma = float(sde.sigma)
         if fields is not None:
             import ctypes
             import struct
@@ -108,44 +150,87 @@ def sdeint(sde, y0, ts, method="euler", dt=1e-3, generator=None, noise="philox",
             B, d = y.shape
             recs, n_out = [], 0
             for t, h, is_out in steps:
-                te = (1.0 - t) if sde.reverse else t
                 # the casts of the launch-per-step path: float32 time, float32 step, float32 (g sqrt|h|)
-                recs.append(struct.pack("<fffi", te, h, float(sde.sigma) * math.sqrt(abs(h)), 1 if is_out else 0))
+                gs = sigma * math.sqrt(abs(h))
+                if srk:
+                    te = [(1.0 - u) if sde.reverse else u for u in (t, t + h, t + 0.5 * h)]
+                    recs.append(struct.pack("<ffffffii", te[0], te[1], te[2], h, gs, 0.75 * sigma * math.sqrt(abs(h)),
+                                            1 if is_out else 0, 0))
+                else:
+                    recs.append(struct.pack("<fffi", (1.0 - t) if sde.reverse else t, h, gs, 1 if is_out else 0))
                 n_out += 1 if is_out else 0
-            host = (ctypes.c_char * (16 * len(steps))).from_buffer_copy(b"".join(recs))
-            xi = None
+            rec = 32 if srk else 16
+            host = (ctypes.c_char * (rec * len(steps))).from_buffer_copy(b"".join(recs))
+            xi = given
             seed = 0
-            if noise == "torch":
-                xi = torch.stack([torch.randn((B, d), device=dev, dtype=torch.float32, generator=generator) for _ in steps])
-            else:
+            if xi is None and noise == "torch":
+                shape = (2, B, d) if srk else (B, d)
+                xi = torch.stack([torch.randn(shape, device=dev, dtype=torch.float32, generator=generator) for _ in steps])
+            elif xi is None:
                 seed = int(torch.randint(0, 2 ** 62, (1,), device=dev, generator=generator).item())
             Wf, bf, _, keep_f = f.hip_params(dev)
             Ws, bs, _, keep_s = s.hip_params(dev)
             cd = (ctypes.c_int * 5)(*dims)
             traj = torch.empty((n_out, B, d), dtype=torch.float32, device=dev)
-            ws = torch.empty(16 * len(steps) + 256, dtype=torch.uint8, device=dev)
-            check(lib.cfm_sde_em_mlp_f32(Wf, bf, Ws, bs, cd, 4, ptr(y), B, host, len(steps), 1 if sde.reverse else 0,
-                                         ptr(xi), seed, ptr(traj), ptr(ws), stream_ptr()), "cfm_sde_em_mlp_f32")
+            ws = torch.empty(rec * len(steps) + 256, dtype=torch.uint8, device=dev)
+            entry, name = (lib.cfm_sde_srk_mlp_f32, "cfm_sde_srk_mlp_f32") if srk else (lib.cfm_sde_em_mlp_f32, "cfm_sde_em_mlp_f32")
+            check(entry(Wf, bf, Ws, bs, cd, 4, ptr(y), B, host, len(steps), 1 if sde.reverse else 0,
+                        ptr(xi), seed, ptr(traj), ptr(ws), stream_ptr()), name)
             torch.cuda.current_stream().synchronize()          # `host` (pageable) must outlive the copy
             return torch.cat([y0.to(torch.float32)[None].to(y0.device), traj.to(y0.device)])
         sign = 1.0
-        for t, h, is_out in steps:
+        if srk:
+            def pair(yy, u):
+                te = (1.0 - u) if sde.reverse else u
+                v = sde.drift.forward_hip(yy, te)
+                return (-v if sde.reverse else v), sde.score.forward_hip(yy, te)
+            ys = torch.empty_like(y)
+            for k, (t, h, is_out) in enumerate(steps):
+                xi = given[k] if given is not None else torch.randn((2,) + tuple(y.shape), device=dev, dtype=torch.float32,
+                                                                    generator=generator)
+                xi1, xi2 = xi[0], xi[1]
+                v1, s1 = pair(y, t)
+                v2 = s2 = v3 = s3 = None
+                for stage in (1, 2, 3):
+                    check(lib.cfm_sde_srk_step_f32(stage, ptr(y), ptr(ys), ptr(v1), ptr(s1), ptr(v2), ptr(s2), ptr(v3),
+                                                   ptr(s3), ptr(xi1), ptr(xi2), float(h), sigma, sign, y.numel(),
+                                                   stream_ptr()), "cfm_sde_srk_step_f32")
+                    if stage == 1:
+                        v2, s2 = pair(ys, t + h)
+                    elif stage == 2:
+                        v3, s3 = pair(ys, t + 0.5 * h)
+                if is_out:
+                    out.append(y.clone().to(y0.device))
+            return torch.stack([o.to(torch.float32) for o in out])
+        for k, (t, h, is_out) in enumerate(steps):
             te = (1.0 - t) if sde.reverse else t
             v = sde.drift.forward_hip(y, te)
             s = sde.score.forward_hip(y, te)
             if sde.reverse:
                 v = -v
-            xi = torch.randn(y.shape, device=dev, dtype=torch.float32, generator=generator)
-            check(lib.cfm_sde_em_step_f32(ptr(y), ptr(v), ptr(s), ptr(xi), float(h), float(sde.sigma), sign,
+            xi = given[k] if given is not None else torch.randn(y.shape, device=dev, dtype=torch.float32, generator=generator)
+            check(lib.cfm_sde_em_step_f32(ptr(y), ptr(v), ptr(s), ptr(xi), float(h), sigma, sign,
                                           y.numel(), stream_ptr()), "cfm_sde_em_step_f32")
             if is_out:
                 out.append(y.clone().to(y0.device))
         return torch.stack([o.to(torch.float32) for o in out])
     y = y0
-    for t, h, is_out in steps:
+    if given is not None:
+        given = given.to(device=y.device, dtype=y.dtype)
+    for k, (t, h, is_out) in enumerate(steps):
         tt = torch.as_tensor(t, dtype=y.dtype, device=y.device)
-        xi = torch.randn(y.shape, device=y.device, dtype=y.dtype, generator=generator)
-        y = y + h * sde.f(tt, y) + sde.g(tt, y) * math.sqrt(abs(h)) * xi
+        if srk:
+            # the scheme of csrc/sde_srk.h in the caller's dtype
+            xi = given[k] if given is not None else torch.randn((2,) + tuple(y.shape), device=y.device, dtype=y.dtype,
+                                                                generator=generator)
+            gs = float(sde.sigma) * math.sqrt(abs(h))
+            k1 = sde.f(tt, y)
+            k2 = sde.f(tt + h, y + h * k1)
+            k3 = sde.f(tt + 0.5 * h, y + (0.25 * h) * (k1 + k2) + (0.75 * gs) * (xi[0] + xi[1] / math.sqrt(3.0)))
+            y = y + (h / 6.0) * ((k1 + k2) + 4.0 * k3) + gs * xi[0]
+        else:
+            xi = given[k] if given is not None else torch.randn(y.shape, device=y.device, dtype=y.dtype, generator=generator)
+            y = y + h * sde.f(tt, y) + sde.g(tt, y) * math.sqrt(abs(h)) * xi
         if is_out:
             out.append(y)
     return torch.stack(out)
@@ -154,7 +239,7 @@ def sdeint(sde, y0, ts, method="euler", dt=1e-3, generator=None, noise="philox",
 class FlowSolver(torch.nn.Module):
     """Subset of runner/src/models/components/solver.py:44-230 on this backend: a flow field and an
     optional score field (separate networks, or one network whose output is [flow, score]) behind
-    ``odeint`` (NeuralODE) and ``sdeint`` (Euler-Maruyama).  vector_field / score_field are called as
+    ``odeint`` (NeuralODE) and ``sdeint`` (Euler-Maruyama; ``srk`` needs a constant sigma: ``sde.sdeint``).  vector_field / score_field are called as
     f(t, x) like torchdyn vector fields."""
 
     def __init__(self, vector_field, dim, score_field=None, sigma=None, ode_solver="euler", sde_solver="euler",
@@ -198,6 +283,9 @@ class FlowSolver(torch.nn.Module):
         return node(x0, t_span)
 
     def sdeint(self, x0, t_span, reverse=False, generator=None):
+        if self.sde_solver == "srk":
+            raise NotImplementedError("FlowSolver(sde_solver='srk'): sigma is a schedule sigma(t) here, and 'srk' is built "
+                                      "for constant diagonal noise only (the full SRI2W1 tableau is not built)")
         self.nfe = 0
         outer = self
 

@@ -382,15 +382,16 @@ int cfm_adam_step_f32(const void* table, int n_tensors, double lr, double beta1,
 
 /* SF2M sampling — one Euler-Maruyama step  y <- y + dt (v + score_sign * s) + g sqrt(|dt|) xi,  in place.
  * Replaces the step torchsde.sdeint(sde, x0, ts, method="euler") takes for the reference's SDE
- * (f = drift + score, g = sigma): examples/2D_tutorials/SF2M_tutorial.ipynb cell 5,
- * runner/src/models/components/solver.py:129-139,157-182.  s and xi may be NULL. */
+ * (f = drift + score, g = sigma): runner/src/models/components/solver.py:129-139,157-182 at sde_solver: euler.
+ * (The notebooks run torchsde's default method "srk": cfm_sde_srk_step_f32 / cfm_sde_srk_mlp_f32.)  s and xi may be
+ * NULL. */
 int cfm_sde_em_step_f32(float* y, const float* v, const float* s, const float* xi, double dt, double g,
                         double score_sign, size_t n, void* stream);
 /* SF2M sampling — the WHOLE Euler-Maruyama trajectory of a batch in one launch, for two small MLP fields (flow v and
  * score s: 4 layers, widths <= 64, time column last; Ws = bs = NULL: no score):
  *     y <- y + h (+-v(te, y) + s(te, y)) + g sqrt|h| xi        (reverse: -v, fields evaluated at te = 1 - t)
- * Replaces torchsde.sdeint(SDE(model, score_model, ...), x0, ts, method="euler", dt=...): SF2M_tutorial.ipynb cell 5,
- * runner/src/models/components/solver.py:129-139,157-182.  steps_host: n_steps records {float te, h, g_sqrt_h;
+ * Replaces torchsde.sdeint(SDE(model, score_model, ...), x0, ts, method="euler", dt=...):
+ * runner/src/models/components/solver.py:129-139,157-182 at sde_solver: euler.  steps_host: n_steps records {float te, h, g_sqrt_h;
  * int is_out} on the HOST (copied into ws: >= 16 n_steps bytes of device scratch); out [n_out, B, d] receives the
  * state after every step with is_out != 0.  xi: caller's N(0,1) noise [n_steps, B, d] (then the trajectory is
  * bit-equal to stepping with cfm_mlp_forward_f32 + cfm_sde_em_step_f32), or NULL: Philox4x32-10 noise from `seed`
@@ -399,6 +400,32 @@ int cfm_sde_em_mlp_f32(const float* const* Wf, const float* const* bf, const flo
                        const float* const* bs, const int* dims, int n_layers, const float* y0, int B,
                        const void* steps_host, int n_steps, int reverse, const float* xi,
                        unsigned long long seed, float* out, void* ws, void* stream);
+/* SF2M sampling — one stage of an `srk` step: Roessler's SRI2W1 (strong order 1.5) for CONSTANT diagonal noise
+ * g = sigma, the scheme torchsde.sdeint runs when no method is given (noise_type "diagonal", sde_type "ito").
+ * Replaces the steps of the default-method calls torchsde.sdeint(sde, x0, ts=...) in
+ * examples/2D_tutorials/SF2M_tutorial.ipynb cell 5 (its solver="euler" is an ignored keyword),
+ * examples/single_cell/single-cell_example.ipynb, examples/images/mnist_example.ipynb and
+ * examples/images/conditional_mnist.ipynb, and runner/src/models/components/solver.py:169-179 at sde_solver: srk.
+ *   f_i = v_i + score_sign * s_i  (s_i may be NULL), gs = g sqrt|h|, xi1, xi2 ~ N(0, 1) (NULL: no noise)
+ *   stage 1: ys = y + h f1
+ *   stage 2: ys = y + (h/4)(f1 + f2) + 0.75 gs (xi1 + xi2 / sqrt(3))
+ *   stage 3: y <- y + (h/6)(f1 + f2 + 4 f3) + gs xi1                    (in place; ys unused)
+ * f1 = field at (t, y), f2 at (t + h, ys of stage 1), f3 at (t + h/2, ys of stage 2).  Arguments a stage does not
+ * read may be NULL; ys must not alias y.  CFM_EINVAL for another stage or a missing operand. */
+int cfm_sde_srk_step_f32(int stage, float* y, float* ys, const float* v1, const float* s1, const float* v2,
+                         const float* s2, const float* v3, const float* s3, const float* xi1, const float* xi2,
+                         double h, double g, double score_sign, size_t n, void* stream);
+/* SF2M sampling — the WHOLE `srk` trajectory of a batch in one launch, for the small field pairs of
+ * cfm_sde_em_mlp_f32 (same arguments and return codes).  Replaces the same default-method torchsde.sdeint calls and
+ * runner/src/models/components/solver.py:169-179 as cfm_sde_srk_step_f32.  steps_host: n_steps records {float te1,
+ * te2, te3 (field times of the stages at t, t + h, t + h/2; reverse: 1 - them), h, g sqrt|h|, 0.75 g sqrt|h|; int
+ * is_out, pad} on the HOST (copied into ws: >= 32 n_steps bytes of device scratch).  xi: caller's N(0,1) noise
+ * [n_steps, 2, B, d] (plane 0: xi1, plane 1: xi2; then the trajectory is bit-equal to stepping with
+ * cfm_mlp_forward_f32 + cfm_sde_srk_step_f32), or NULL: two Philox4x32-10 streams from `seed` in the kernel. */
+int cfm_sde_srk_mlp_f32(const float* const* Wf, const float* const* bf, const float* const* Ws,
+                        const float* const* bs, const int* dims, int n_layers, const float* y0, int B,
+                        const void* steps_host, int n_steps, int reverse, const float* xi,
+                        unsigned long long seed, float* out, void* ws, void* stream);
 /* Mixture-RBF kernel sum  out[0] += sum_e sum_q exp(-gammas[q] * D[e])  over a squared-distance matrix D
  * (n elements, device fp32; gammas device fp32[n_gamma]; out device double, zeroed by the caller).
  * Replaces the K_XX / K_XY / K_YY matrices of mix_rbf_mmd2: runner/src/models/components/mmd.py:43-63,80-110. */
