@@ -224,8 +224,11 @@ __global__ __launch_bounds__(256) void reduce_splits_multi(ReduceTable T) {
 #define MLP_MAX_SPLITS 32
 #define MLP_LOSS_PARTIALS 4096
 extern "C" size_t cfm_mlp_train_ws_bytes_internal(int B, int maxw, int max_params) {
-    // two [B, maxw] gradient buffers + per-layer split-K partials (weights and biases; <= MLP_MAX_LAYERS layers
-    // are sized here by the largest one: callers pass the largest dims[l] * dims[l+1])
+    // two [B, maxw] gradient buffers + a pool of split-K partials (weights, biases, the time column) that holds FOUR
+    // layers of the largest size at MLP_MAX_SPLITS splits (callers pass the largest dims[l] * dims[l+1]): every layer of
+    // a net of up to four, so such a net is reduced by one launch at the end.  A deeper net at a batch that splits every
+    // layer 32 ways fills it: the backward then reduces what it has collected and reuses the pool from its start
+    // (one more small launch per refill, the same bits).
     // (+ MLP_LOSS_PARTIALS loss partials for cfm_mlp_regression_step_f32: one per workgroup of the last layer)
     return sizeof(float) * ((size_t)2 * B * maxw + (size_t)MLP_MAX_SPLITS * ((size_t)max_params + maxw) * 4) + 4 * MLP_LOSS_PARTIALS;
 }
@@ -298,7 +301,8 @@ static int wgrad_splits(int N, int K, int B) {
 // saved hidden activations), preact[l] = z_l for l = 1 .. n-1 (preact[0] unused); dout [B, dims[n]].
 // Writes dW[l] ([dims[l+1], dims[l]]), db[l] and, if dx is not NULL, the input gradient [B, dims[0]].
 // Launches: per layer ONE launch for wgrad (bias column sums ride along) + dgrad (round 6; two where the shapes do not allow
-// the pair), then ONE reduction of every split-K partial (weights and biases of all layers).
+// the pair), then ONE reduction of every split-K partial (weights and biases of all layers).  The workspace's pool holds
+// four layers' partials at 32 splits: a deeper net that fills it gets one more reduction per refill (see the loop).
 // tvec != NULL: the network input is [acts[0] (B x dims[0] - 1, pitch dims[0] - 1), tvec (B)] — the time column is
 // kept apart (the fused regression step never concatenates it); its weight gradient is the weighted column sum.
 // extra: one more job for the final reduction (the loss partials of the fused step), or NULL.
@@ -322,7 +326,17 @@ static int mlp_backward_impl(const float* const* acts, const float* const* preac
         // wgrad: dW[N,K] = dz^T[N,B] . h[B,K], contraction over the batch, S splits; db partials ride along
         const int S = wgrad_splits(N, K, B);
         const size_t np = (size_t)N * K;
-        if (used + (size_t)S * (np + 2 * (size_t)N) > pool_floats) return CFM_EINVAL;      // more layers than the workspace was sized for
+        const size_t need = (size_t)S * (np + (size_t)N * (split_t ? 2 : 1));
+        // (cannot happen with a workspace of cfm_mlp_train_ws_bytes_internal: np + 2 N <= maxp + maxw even with the time
+        //  column apart and S <= MLP_MAX_SPLITS, a quarter of the pool — kept for a caller that passes other dims there)
+        if (need > pool_floats) return CFM_EINVAL;
+        if (used + need > pool_floats) {
+            // the pool is full (a fifth layer at S = 32): reduce what has been collected and start it again at offset zero.
+            // Stream order puts the reduction in front of the next product, so no slot is rewritten before it is read;
+            // every job keeps its partials and its split order: bit-equal to an unbounded pool.
+            if (T.count) { hipLaunchKernelGGL(reduce_splits_multi, dim3(256, T.count), dim3(256), 0, s, T); T.count = 0; }
+            used = 0;
+        }
         float* part = pool + used; used += (size_t)S * np;
         float* bpart = pool + used; used += (size_t)S * N;
         float* tpart = nullptr;
@@ -357,7 +371,7 @@ static int mlp_backward_impl(const float* const* acts, const float* const* preac
             // layers' products run.  Same jobs, same order of the partial sums: bit-equal to the one-reduction form.
             if (l == 0 && extra) T.job[T.count++] = *extra;
             hipLaunchKernelGGL(reduce_splits_multi, dim3(256, T.count), dim3(256), 0, s, T);
-            T.count = 0;
+            T.count = 0; used = 0;      // (the next layer's partials go where these were: its product runs behind this reduction)
             if (layer_done[l]) { const hipError_t e = hipEventRecord((hipEvent_t)layer_done[l], s); if (e != hipSuccess) return (int)e; }
         }
         // dgrad: dz_prev[B,K] = (dz[B,N] . W[N,K]) * selu'(z_prev)
@@ -524,7 +538,8 @@ struct NetBackward {
 };
 
 // mlp_backward_impl for two nets of equal sizes: layer by layer the same launches, each on twice the grid (tile, split
-// and pairing decided per net exactly as above), and ONE reduction of both nets' partials and loss partials.
+// and pairing decided per net exactly as above), and ONE reduction of both nets' partials and loss partials (one more
+// per refill of the pool for nets deeper than four layers at 32 splits, as above).
 static int mlp_backward_two_impl(const NetBackward* nb, const int* dims, int n_layers, int B, hipStream_t s, const float* tvec) {
     int maxw = 0; size_t maxp = 0;
     for (int l = 0; l <= n_layers; ++l) maxw = dims[l] > maxw ? dims[l] : maxw;
@@ -544,7 +559,14 @@ static int mlp_backward_two_impl(const NetBackward* nb, const int* dims, int n_l
         const int K = split_t ? Kfull - 1 : Kfull;
         const int S = wgrad_splits(N, K, B);
         const size_t np = (size_t)N * K;
-        if (used + (size_t)S * (np + 2 * (size_t)N) > pool_floats) return CFM_EINVAL;
+        const size_t need = (size_t)S * (np + (size_t)N * (split_t ? 2 : 1));
+        if (need > pool_floats) return CFM_EINVAL;      // (cannot happen with the documented workspace: see mlp_backward_impl)
+        if (used + need > pool_floats) {
+            // both pools are full: reduce both nets' jobs so far and start again at offset zero (see mlp_backward_impl);
+            // the loss jobs stay in the final launch
+            if (T.count) { hipLaunchKernelGGL(reduce_splits_multi, dim3(256, T.count), dim3(256), 0, s, T); T.count = 0; }
+            used = 0;
+        }
         const size_t o_part = used; used += (size_t)S * np;
         const size_t o_bpart = used; used += (size_t)S * N;
         const size_t o_tpart = used; if (split_t) used += (size_t)S * N;

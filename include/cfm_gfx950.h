@@ -318,7 +318,11 @@ int cfm_mlp_forward_f32(const float* x, const float* t, int t_per_row,
  * preact[l] = the forward's preact[l-1], preact[0] unused);
  * dout [B, dims[n_layers]]; writes dW[l] [dims[l+1], dims[l]], db[l] [dims[l+1]] and, when dx is not
  * NULL, dx [B, dims[0]].  Split-K partial sums are reduced in a fixed order (deterministic).
- * ws: cfm_workspace_bytes(CFM_OP_MLP_TRAIN, B, widest layer incl. input/output, largest dims[l]*dims[l+1]). */
+ * ws: cfm_workspace_bytes(CFM_OP_MLP_TRAIN, B, widest layer incl. input/output, largest dims[l]*dims[l+1]): two
+ * [B, widest] gradient buffers, a pool for the split-K partials of four layers of the largest size at 32 splits, and
+ * 4096 loss partials.  Nets of up to four layers are reduced by one launch at the end; a deeper net (n_layers <= 15)
+ * whose partials outgrow the pool is reduced in several launches, the pool reused in between: the same bits, the same
+ * workspace size, never a refusal. */
 int cfm_mlp_forward_train_f32(const float* x, const float* const* W, const float* const* b,
                               const int* dims, int n_layers, int B, float* const* hidden,
                               float* const* preact, float* out, void* stream);
@@ -339,7 +343,8 @@ int cfm_mlp_backward_f32(const float* const* acts, const float* const* preact, c
  * layer l's split partials are reduced right after its weight-gradient product (one small launch per layer instead of
  * one at the end; same sums in the same order, bit-equal gradients) and layer_done[l] is recorded on `stream`, so the
  * caller's communication stream can all-reduce dW[l], db[l] under the remaining layers' products.
- * ws: cfm_workspace_bytes(CFM_OP_MLP_TRAIN, B, widest layer incl. input/output, largest dims[l]*dims[l+1]). */
+ * ws: cfm_workspace_bytes(CFM_OP_MLP_TRAIN, B, widest layer incl. input/output, largest dims[l]*dims[l+1]), as for
+ * cfm_mlp_backward_f32 (any depth up to 15 layers at any batch; with layer_done every layer reuses the pool's start). */
 int cfm_mlp_regression_step_f32(const float* xt, const float* t, const float* ut,
                                 const float* const* W, const float* const* b, const int* dims, int n_layers,
                                 int B, float* const* hidden, float* const* preact, float* g,
@@ -365,7 +370,8 @@ int cfm_mlp_regression_step_f32(const float* xt, const float* t, const float* ut
  * score_weight = 1, its bits on -eps.  Deterministic.  n_layers <= 7 (the one reduction's table holds the jobs of two
  * 7-layer nets) and at most 4096 output tiles of 64 x 64 in the last layer; beyond either: CFM_EINVAL.
  * ws: TWO workspaces of cfm_workspace_bytes(CFM_OP_MLP_TRAIN, B, widest layer, largest dims[l]*dims[l+1]) bytes back to
- * back (the second starts at that byte count, a multiple of 256). */
+ * back (the second starts at that byte count, a multiple of 256); nets deeper than four layers reuse each pool as
+ * cfm_mlp_backward_f32 does, the two loss reductions staying in the last launch. */
 int cfm_mlp_sf2m_step_f32(const float* xt, const float* t, const float* ut, const float* eps, const float* lam,
                           const float* const* W, const float* const* b, float* const* hidden, float* const* preact,
                           float* const* dW, float* const* db, const int* dims, int n_layers, int B,

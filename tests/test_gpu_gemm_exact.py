@@ -13,9 +13,10 @@ import ctypes
 import pytest
 import torch
 
-pytestmark = pytest.mark.gpu
+from exact_util import LIMIT, _Mode, _arr, _first_diff, _ints, _layer_data, _nan, _nan_ws
+from exact_util import lib_ as _lib_
 
-LIMIT = 2 ** 24
+pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
@@ -24,70 +25,6 @@ def dev():
     from cfm_amd import _lib
     _lib.load()
     return _lib.require_gpu()
-
-
-def _lib_():
-    from cfm_amd import _lib
-    return _lib, _lib.load()
-
-
-def _arr(ts):
-    return (ctypes.c_void_p * len(ts))(*[t.data_ptr() if t is not None else 0 for t in ts])
-
-
-def _ints(gen, shape, lo, hi):
-    """int64 tensor, uniform in {lo .. hi}"""
-    return torch.randint(lo, hi + 1, shape, generator=gen, dtype=torch.int64)
-
-
-def _nan(shape, dev):
-    """an output buffer no kernel has written yet: an element the kernel skips stays NaN and fails torch.equal"""
-    return torch.full(shape, float("nan"), device=dev, dtype=torch.float32)
-
-
-def _first_diff(got, ref):
-    """(index, got, expected) of the first differing element and the number of them (for the failure message)"""
-    g, r = got.detach().cpu().double(), ref.detach().cpu().double()
-    bad = ~(g == r)
-    n = int(bad.sum())
-    if n == 0:
-        return "equal"
-    idx = tuple(int(v) for v in bad.nonzero()[0])
-    rows = sorted(set(int(v) for v in bad.nonzero()[:, 0][:2000]))[:8]
-    return f"{n} of {g.numel()} differ; first at {idx}: got {float(g[idx])}, expected {float(r[idx])}; rows {rows}"
-
-
-class _Mode:
-    """cfm_mlp_set_glds(mode) for the body, the previous mode back in every case"""
-
-    def __init__(self, lib, mode):
-        self.lib, self.mode = lib, mode
-
-    def __enter__(self):
-        self.prev = self.lib.cfm_mlp_get_glds()
-        self.lib.cfm_mlp_set_glds(self.mode)
-
-    def __exit__(self, *exc):
-        self.lib.cfm_mlp_set_glds(self.prev)
-        return False
-
-
-def _layer_data(B, K, N, time, seed, lo=-3, hi=3):
-    """One Linear layer's integer data and its int64 result.  time: None | "scalar" | "row"; with a time the weight has
-    K + 1 columns (the time column last: rows of 4 (K + 1) bytes, 4-byte aligned only when K + 1 is odd)."""
-    g = torch.Generator().manual_seed(seed)
-    x = _ints(g, (B, K), lo, hi)
-    w = _ints(g, (N, K + (time is not None)), lo, hi)
-    b = _ints(g, (N,), -50, 50)
-    t = None if time is None else (_ints(g, (B,), lo, hi) if time == "row" else torch.tensor([2], dtype=torch.int64))
-    ref = x @ w[:, :K].T + b
-    mag = x.abs() @ w[:, :K].abs().T + b.abs()
-    if t is not None:
-        tt = t.reshape(-1, 1) if time == "row" else t.reshape(1, 1).expand(B, 1)
-        ref = ref + tt * w[:, K].reshape(1, N)
-        mag = mag + tt.abs() * w[:, K].abs().reshape(1, N)
-    assert int(mag.max()) < LIMIT, "premise: every partial sum is an exact fp32 integer"
-    return x, w, b, t, ref
 
 
 def _forward1(lib, _lib, dev, xd, wd, bd, td, t_per_row, dims, B):
@@ -211,7 +148,8 @@ def test_activated_layer_preact_exact_and_selu_close(dev, B, K, H, N):
                                    (4096, 784, 512), (4096, 512, 784), (4096, 512, 512)])
 def test_backward_one_layer_is_exact(dev, B, K, N):
     """cfm_mlp_backward_f32 with one layer: dW = dout^T x, db = sum dout, dx = dout W on gemm_core.h (B = 4096: split-K
-    partials and their fixed-order reduction).  Values in {-2 .. 2}."""
+    partials and their fixed-order reduction).  Values in {-2 .. 2}.  The workspace starts as NaN: a partial that the
+    reduction reads and no workgroup wrote shows.  (Split-K edges: test_gpu_backward_exact.py.)"""
     _lib, lib = _lib_()
     g = torch.Generator().manual_seed(B * 7 + K + N)
     x, w, dout = _ints(g, (B, K), -2, 2), _ints(g, (N, K), -2, 2), _ints(g, (B, N), -2, 2)
@@ -220,7 +158,7 @@ def test_backward_one_layer_is_exact(dev, B, K, N):
     assert int((dout.abs() @ w.abs()).max()) < LIMIT
     xd, wd, dd = x.float().to(dev), w.float().to(dev), dout.float().to(dev)
     dWd, dbd, dxd = _nan((N, K), dev), _nan((N,), dev), _nan((B, K), dev)
-    ws = torch.zeros(lib.cfm_workspace_bytes(_lib.OP_MLP_TRAIN, B, max(K, N), K * N), dtype=torch.uint8, device=dev)
+    ws = _nan_ws(lib.cfm_workspace_bytes(_lib.OP_MLP_TRAIN, B, max(K, N), K * N), dev)
     cd = (ctypes.c_int * 2)(K, N)
     _lib.check(lib.cfm_mlp_backward_f32(_arr([xd]), _arr([None]), _arr([wd]), cd, 1, B, _lib.ptr(dd), _arr([dWd]),
                                         _arr([dbd]), _lib.ptr(dxd), _lib.ptr(ws), _lib.stream_ptr()), "cfm_mlp_backward_f32")
