@@ -16,7 +16,7 @@ from .conditional_flow_matching import (  # noqa: F401
     pad_t_like_x,
 )
 from .models import MLP  # noqa: F401
-from .cnf import CNF, log_likelihood  # noqa: F401
+from .cnf import CNF, DifferentiableCNF, log_likelihood  # noqa: F401
 from .optim import FusedAdam  # noqa: F401
 from .train import RegressionStep, SF2MStep  # noqa: F401
 from .optimal_transport import OTPlanSampler, wasserstein  # noqa: F401

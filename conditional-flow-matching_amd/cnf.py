@@ -13,6 +13,14 @@ inputs the divergence runs in the HIP kernel ``cfm_mlp_divergence_f32``, and ``N
 integrates the augmented state in one persistent launch (``cfm_ode_euler_cnf_mlp_f32`` /
 ``cfm_ode_dopri5_cnf_mlp_f32``).  Anything else is evaluated with ``torch.func`` in the input's dtype.
 
+Training by maximum likelihood (the tutorial's cell 5: ``NeuralODE(cnf_wrapper(model, "exact"), solver="euler",
+sensitivity="adjoint")``, ``loss.backward()``) is ``DifferentiableCNF``: the Euler solve of the augmented state with a
+gradient.  On the HIP path the forward is ``cfm_ode_fixed_cnf_mlp_f32`` at Euler and the backward is one launch of
+``cfm_cnf_euler_grad_f32`` over the saved trajectory: the exact gradient of the recurrence the forward ran
+(discretise-then-optimise).  torchdyn's ``sensitivity="adjoint"`` integrates the continuous adjoint with the same
+solver instead, which differs from this by O(h); torchdyn is absent from the reference tree, so that variant is
+unpinned, as the forward solvers are.
+
 Hutchinson probes are fixed for a whole solve (FFJORD's convention, model-comparison's ``CNF.noise``
 slot): ``cnf.noise`` if set, else one draw per ``NeuralODE.trajectory`` call, kept as
 ``cnf.last_noise``.  The ML-CNF tutorial redraws the probe at every evaluation; that is not replicated.
@@ -168,3 +176,147 @@ def log_likelihood(model, x, t_span=None, solver="dopri5", atol=1e-5, rtol=1e-5,
     logp0 = prior_log_prob(z) if prior_log_prob is not None else standard_normal_log_prob(z)
     out = logp0 - ell
     return (out, z) if return_z else out
+
+
+class _Declined(Exception):
+    """The forward solve answered CFM_EINVAL inside the envelope: the fused small-field path is switched off, or the
+    grid has more points than the solve's workspace holds (n_t > 3 B (1 + d))."""
+
+
+class _CNFEulerFunction(torch.autograd.Function):
+    """[l_N, y_N] of the Euler augmented solve (cfm_ode_fixed_cnf_mlp_f32); backward: cfm_cnf_euler_grad_f32."""
+
+    @staticmethod
+    def forward(ctx, x_aug, ts, eps, dims, *params):
+        lib = _lib.load()
+        dev = x_aug.device
+        Ws = [_lib.to_dev_f32(p, dev) for p in params[0::2]]
+        bs = [_lib.to_dev_f32(p, dev) for p in params[1::2]]
+        Wp = (ctypes.c_void_p * 4)(*[w.data_ptr() for w in Ws])
+        bp = (ctypes.c_void_p * 4)(*[b.data_ptr() for b in bs])
+        cdims = (ctypes.c_int * 5)(*dims)
+        xd = _lib.to_dev_f32(x_aug, dev)
+        B, D = xd.shape
+        n_t = ts.shape[0]
+        traj = torch.empty((n_t, B, D), dtype=torch.float32, device=dev)
+        ws = _lib.workspace(_lib.OP_ODE, B, max(dims[1:4]), D, dev)
+        ed = _lib.to_dev_f32(eps, dev) if eps is not None else None
+        nfe = ctypes.c_int(0)
+        rc = lib.cfm_ode_fixed_cnf_mlp_f32(Wp, bp, cdims, 4, ptr(xd), B, ts.ctypes.data_as(ctypes.c_void_p), n_t,
+                                           0 if eps is None else 1, ptr(ed), _lib.ODE_SCHEME["euler"], ptr(traj),
+                                           ctypes.byref(nfe), ptr(ws), stream_ptr())
+        if rc == -1:
+            raise _Declined()
+        _lib.check(rc, "cfm_ode_fixed_cnf_mlp_f32")
+        ctx.ts, ctx.dims, ctx.eps = ts, dims, ed
+        ctx.save_for_backward(traj, *params)
+        return traj[-1].clone()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        lib = _lib.load()
+        traj, *params = ctx.saved_tensors
+        dev = traj.device
+        Ws = [_lib.to_dev_f32(p, dev) for p in params[0::2]]
+        bs = [_lib.to_dev_f32(p, dev) for p in params[1::2]]
+        dWs = [torch.empty_like(w) for w in Ws]
+        dbs = [torch.empty_like(b) for b in bs]
+        Wp = (ctypes.c_void_p * 4)(*[w.data_ptr() for w in Ws])
+        bp = (ctypes.c_void_p * 4)(*[b.data_ptr() for b in bs])
+        dWp = (ctypes.c_void_p * 4)(*[w.data_ptr() for w in dWs])
+        dbp = (ctypes.c_void_p * 4)(*[b.data_ptr() for b in dbs])
+        cdims = (ctypes.c_int * 5)(*ctx.dims)
+        n_t, B, D = traj.shape
+        gd = _lib.to_dev_f32(g, dev)
+        g0 = torch.empty((B, D), dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
+        ws = _lib.workspace(_lib.OP_CNF_GRAD, B, n_t, 0, dev)
+        rc = lib.cfm_cnf_euler_grad_f32(Wp, bp, cdims, 4, ptr(traj), B, ctx.ts.ctypes.data_as(ctypes.c_void_p), n_t,
+                                        0 if ctx.eps is None else 1, ptr(ctx.eps), ptr(gd), dWp, dbp, ptr(g0), ptr(ws),
+                                        stream_ptr())
+        _lib.check(rc, "cfm_cnf_euler_grad_f32")
+        grads = [None] * len(params)
+        grads[0::2] = dWs
+        grads[1::2] = dbs
+        return (g0, None, None, None, *grads)
+
+
+class DifferentiableCNF(CNF):
+    """The Euler solve of the augmented state [l, y] with a gradient: maximum-likelihood training of a CNF.
+
+    ``solve(x_aug, t_span)`` returns the final state [B, 1 + d], differentiable with respect to the field's parameters
+    and ``x_aug``; ``nll(x)`` is the tutorial's loss.  fp32 CUDA states of a small-envelope ``MLP(time_varying=True)``
+    (or ``torch_wrapper`` of one) with fp32 parameters run on the HIP kernels (``last_path == "hip"``; the value is
+    bit-equal to ``NeuralODE(CNF(m), solver="euler").trajectory(...)[-1]``, the gradient is that of the recurrence,
+    once differentiable).  Everything else runs the same recurrence in differentiable torch ops (``"generic"``): CPU,
+    float64, other fields, the fused path switched off, and a grid of more than 3 B (1 + d) points, which
+    ``cfm_ode_fixed_cnf_mlp_f32`` refuses because its workspace keeps the device copy of ``t_span`` in three state-sized
+    buffers (B = 1, d = 2 with the default 100 steps is such a case).  Nothing is printed: ``last_path`` says which path
+    ran.  The Hutchinson probe follows ``CNF``: ``noise`` if given, else one draw per solve (``last_noise``)."""
+
+    def __init__(self, model, estimator="exact", noise=None, solver="euler"):
+        super().__init__(model, estimator=estimator, noise=noise)
+        if solver != "euler":
+            raise NotImplementedError(f"solver {solver!r}: the gradient is that of the Euler recurrence "
+                                      "y += h v, l -= h div (discretise-then-optimise); no other scheme has one")
+        self.solver = solver
+        self.last_path = None
+
+    def solve(self, x_aug, t_span):
+        from .ode import _check_t_span
+        if x_aug.dim() != 2 or x_aug.shape[1] < 2:
+            raise ValueError(f"the state is [B, 1 + d]; got {tuple(x_aug.shape)}")
+        ts = torch.as_tensor(t_span).detach().to(dtype=x_aug.dtype).cpu()
+        _check_t_span(ts)
+        y = x_aug[:, 1:]
+        eps = None
+        if self.estimator != "exact":
+            eps = self.checked_noise(y) if self.noise is not None else self.draw_noise(y)
+        m = self.hip_mlp(y.shape[1])
+        if (m is not None and x_aug.is_cuda and x_aug.dtype == torch.float32
+                and all(p.dtype == torch.float32 and p.device == x_aug.device for p in m.parameters())):
+            lins = m._linears()
+            params = [p for l in lins for p in (l.weight, l.bias)]
+            dims = [lins[0].in_features] + [l.out_features for l in lins]
+            try:
+                out = _CNFEulerFunction.apply(x_aug, ts.numpy().copy(), eps, dims, *params)
+                self.last_path = "hip"
+                return out
+            except _Declined:
+                pass
+        self.last_path = "generic"
+        return self._solve_generic(x_aug, ts, eps)
+
+    def _solve_generic(self, x_aug, ts, eps):
+        """The recurrence in differentiable torch ops, through the module graph (MLP.net, never MLP.forward: see
+        CNF._func_field), with the parameters cast to the state's dtype."""
+        m = self.model
+        net = m.net if isinstance(m, MLP) else m
+        l, y = x_aug[:, 0], x_aug[:, 1:]
+        params = {k: p.to(device=y.device, dtype=y.dtype) for k, p in net.named_parameters()}
+        buffers = {k: b.to(device=y.device) for k, b in net.named_buffers()}
+        for n in range(ts.numel() - 1):
+            h = float(ts[n + 1] - ts[n])
+            tt = ts[n].to(device=y.device).reshape(1)
+
+            def f(yy):
+                return torch.func.functional_call(net, (params, buffers), (torch.cat([yy, tt])[None],))[0]
+            if eps is None:
+                v = torch.func.vmap(f)(y)
+                jac = torch.func.vmap(torch.func.jacrev(f))(y)
+                div = torch.diagonal(jac, dim1=-2, dim2=-1).sum(-1)
+            else:
+                v, jv = torch.func.vmap(lambda yy, ee: torch.func.jvp(f, (yy,), (ee,)))(y, eps)
+                div = (eps * jv).sum(-1)
+            y = y + h * v
+            l = l - h * div
+        return torch.cat([l[:, None], y], 1)
+
+    def nll(self, x, t_span=None, steps=100, prior_log_prob=None):
+        """-mean(log p_0(z) - l) of the solve of [0, x] from t = 1 to t = 0 on `steps` uniform Euler steps (or on
+        `t_span`); the prior term (default: the standard normal) goes through ordinary autograd."""
+        ts = torch.linspace(1.0, 0.0, int(steps) + 1, dtype=x.dtype) if t_span is None else t_span
+        out = self.solve(torch.cat([torch.zeros_like(x[:, :1]), x], 1), ts)
+        z, ell = out[:, 1:], out[:, 0]
+        logp0 = prior_log_prob(z) if prior_log_prob is not None else standard_normal_log_prob(z)
+        return -(logp0 - ell).mean()

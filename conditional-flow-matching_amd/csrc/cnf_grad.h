@@ -1,0 +1,400 @@
+// cnf_grad.h — gradient of the Euler solve of the augmented CNF state (included by ode.hip after the small-field tile
+// code: SmTile, sm_gemm, sm_stage_weights, selu_f, selu_slope, cnf_check).
+//
+// Forward (ode_small_fixed<CFM_ODE_EULER, MODE>):  y_{n+1} = y_n + h_n v(y_n, t_n),  l_{n+1} = l_n - h_n div(y_n, t_n).
+// Given G = dL/d[l_N, y_N]:  c = G[:, 0] never changes (l enters linearly), a_N = G[:, 1:], and for n = N-1 .. 0
+//   g_n(y, theta) = a_{n+1} . v - c div        a_n = a_{n+1} + h_n grad_y g_n(y_n)        theta_bar += h_n sum_rows grad_theta g_n
+// h_n is folded into the seeds: the step runs the reverse pass of g with (h a, h c) in place of (a, c).
+//
+// One reverse step on a 16-row tile (z_l pre-activations, s_l = selu'(z_l), q_l = selu''(z_l), U_l^k = W_{l-1} T_{l-1}^k,
+// T_l^k = s_l * U_l^k, div = sum_k w_k^T W_3 T_3^k; exact: (T_0^k, w_k) = (e_k, e_k), k < d; Hutchinson: one pair (eps, eps)):
+//   primal forward from y_n (the forward pass's code: same z bits, so the same side of every kink): s_l, q_l, h_l in registers
+//   per direction k:   T_1..T_3 forward;   Tb_3 = -c w_k^T W_3;   for l = 3..1:  sb_l += Tb_l * U_l,  Ub_l = s_l * Tb_l,
+//                      dW_{l-1} += Ub_l^T T_{l-1},  Tb_{l-1} = Ub_l W_{l-1};   dW_3 += w_k^T (-c T_3)
+//   primal reverse:    hb_3 = a W_3, dW_3 += a^T h_3, db_3 += a;   for l = 3..1:  zb_l = hb_l * s_l + sb_l * q_l,
+//                      dW_{l-1} += zb_l^T h_{l-1}, db_{l-1} += zb_l, hb_{l-1} = zb_l W_{l-1};   a += hb_0[:, :d];
+//                      the time column of W_0 gets t_n zb_1 (the tangents have no time component)
+// Products with W_l run through sm_gemm on the staged weights; products with W_l^T (the pull-backs) run through sm_gemm on
+// TRANSPOSED copies of the two 64 x 64 layers (same conflict-free fragment reads), and through cg_gemm_t, which reads the
+// staged matrix by columns, for the two thin layers (once per step each).  Weight gradients are MFMA accumulators with
+// K = the 16 rows of the tile (cg_outer), kept across all steps and tiles of the workgroup; every workgroup writes one
+// partial gradient and ode_small_grad_reduce adds the partials in workgroup order: the same bits run to run.
+// Rows are independent: no cross-workgroup wait of any kind.
+#pragma once
+
+static_assert(SM_MB == 1, "the gradient kernel is written for one 16-row block per tile");
+#define CG_MAXGRID 256                                 // workgroups (= partial gradients) at most
+#define CG_PMAX (4 * SM_W * SM_W + 4 * SM_W)           // floats of one partial gradient at most
+
+struct CgOut { float* dW[4]; float* db[4]; };
+
+extern "C" size_t cfm_cnf_grad_ws_bytes_internal(int B, int n_t) {
+    if (B <= 0 || n_t < 1) return 0;
+    const size_t tiles = ((size_t)B + SM_ROWS - 1) / SM_ROWS;
+    const size_t g = tiles < CG_MAXGRID ? tiles : CG_MAXGRID;
+    return cfm_align_up(sizeof(float) * (size_t)n_t, 256) + sizeof(float) * g * CG_PMAX;
+}
+
+__device__ __forceinline__ void cg_put(float* __restrict__ buf, const SmTile& v, int lane, int col) {
+#pragma unroll
+    for (int i = 0; i < SM_V; ++i) buf[sm_row(i, lane) * SM_LD + col] = v.v[i];
+}
+
+// out(C layout) = A[16 x 64] * M, M = the staged [64][SM_LD] matrix read by columns: out[r][n] = sum_k A[r][k] M[k][n]
+__device__ __forceinline__ void cg_gemm_t(const float* __restrict__ Abuf, const float* __restrict__ M, int wv, int lane,
+                                          f32x4& c) {
+    c = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int fr = lane & 15, fk = lane >> 4;
+    const float* ap = Abuf + fr * SM_LD + fk;
+    const float* bp = M + fk * SM_LD + wv * 16 + fr;
+    float a[SM_W / 4], b[SM_W / 4];
+#pragma unroll
+    for (int j = 0; j < SM_W / 4; ++j) { a[j] = ap[4 * j]; b[j] = bp[4 * j * SM_LD]; }
+#pragma unroll
+    for (int j = 0; j < SM_W / 4; ++j) c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j], b[j], c, 0, 0, 0);
+}
+
+// acc[mb](C layout of block mb) += Z^T H over the 16 rows of the tile: element i of lane -> dW[16 mb + 4 (lane >> 4) + i]
+// [16 wave + (lane & 15)], dW[n][k] = sum_r Z[r][n] H[r][k]
+__device__ __forceinline__ void cg_outer(const float* __restrict__ Zbuf, const float* __restrict__ Hbuf, int wv, int lane,
+                                         f32x4 (&acc)[4]) {
+    const int fr = lane & 15, fk = lane >> 4;
+    const float* zp = Zbuf + fk * SM_LD + fr;
+    const float* hp = Hbuf + fk * SM_LD + wv * 16 + fr;
+    float a[4][SM_ROWS / 4], b[SM_ROWS / 4];
+#pragma unroll
+    for (int j = 0; j < SM_ROWS / 4; ++j) {
+        b[j] = hp[4 * j * SM_LD];
+#pragma unroll
+        for (int mb = 0; mb < 4; ++mb) a[mb][j] = zp[4 * j * SM_LD + 16 * mb];
+    }
+#pragma unroll
+    for (int j = 0; j < SM_ROWS / 4; ++j) {
+#pragma unroll
+        for (int mb = 0; mb < 4; ++mb) acc[mb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[mb][j], b[j], acc[mb], 0, 0, 0);
+    }
+}
+
+__device__ __forceinline__ float cg_sum4(const SmTile& v) { return (v.v[0] + v.v[1]) + (v.v[2] + v.v[3]); }
+
+static size_t cg_lds_bytes() {
+    return sizeof(float) * (6 * SM_W * SM_LD + 4 * SM_W + SM_W + 5 * SM_ROWS * SM_LD);
+}
+
+// traj [n_t, B, 1 + d]: the forward solve (y_n is read); G [B, 1 + d]; g0 [B, 1 + d] or null; part [gridDim.x][P]:
+// the workgroup's partial gradient in the order W0, b0, W1, b1, W2, b2, W3, b3 (each as the caller's tensor is laid out)
+template <int MODE>
+__global__ __launch_bounds__(256) void ode_small_euler_grad(SmArgs A, int B, int d, const float* __restrict__ tspan, int n_t,
+                                                         const float* __restrict__ traj, const float* __restrict__ eps,
+                                                         const float* __restrict__ G, float* __restrict__ g0,
+                                                         float* __restrict__ part, int P) {
+    extern __shared__ __attribute__((aligned(16))) float small_lds[];
+    constexpr int TS = SM_ROWS * SM_LD, WS = SM_W * SM_LD;
+    float* Wl = small_lds;
+    float* WT = Wl + 4 * WS;                  // W1^T, W2^T
+    float* bl = WT + 2 * WS;
+    float* wt = bl + 4 * SM_W;
+    float* E = wt + SM_W;
+    float* X1 = E + TS;
+    float* X2 = X1 + TS;
+    float* X3 = X2 + TS;
+    float* Y3 = X3 + TS;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    sm_stage_weights(A, d, Wl, bl, wt, tid);
+#pragma unroll
+    for (int l = 1; l <= 2; ++l) {
+        const int in_l = A.dims[l], out_l = A.dims[l + 1];
+        for (int e = tid; e < SM_W * SM_LD; e += 256) {
+            const int k = e / SM_LD, r = e % SM_LD;          // WT[k][r] = W[r][k]
+            WT[(l - 1) * WS + e] = (r < out_l && k < in_l) ? A.W[l][(size_t)r * in_l + k] : 0.f;
+        }
+    }
+    const int D = d + 1;
+    const size_t n = (size_t)B * D;
+    const int col = wv * 16 + (lane & 15);
+    const bool lw = wv == 0 && (lane & 15) == 0;
+    const float* W1T = WT;
+    const float* W2T = WT + WS;
+    const float* W3 = Wl + 3 * WS;
+
+    f32x4 dWa[4][4];
+    float dba[4], dwt = 0.f;
+#pragma unroll
+    for (int l = 0; l < 4; ++l) {
+        dba[l] = 0.f;
+#pragma unroll
+        for (int mb = 0; mb < 4; ++mb) dWa[l][mb] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+
+    for (int row0 = blockIdx.x * SM_ROWS; row0 < B; row0 += gridDim.x * SM_ROWS) {
+        const int nrows = B - row0;
+        SmTile a, cv, ep, yn;
+#pragma unroll
+        for (int i = 0; i < SM_V; ++i) {
+            const int gr = row0 + sm_row(i, lane);
+            const bool ok = gr < B && col < d;
+            a.v[i] = ok ? G[(size_t)gr * D + 1 + col] : 0.f;
+            cv.v[i] = gr < B ? G[(size_t)gr * D] : 0.f;
+            ep.v[i] = (MODE == AUG_HUTCH && ok) ? eps[(size_t)gr * d + col] : 0.f;
+            yn.v[i] = (ok && n_t >= 2) ? traj[(size_t)(n_t - 2) * n + (size_t)gr * D + 1 + col] : 0.f;
+        }
+        __syncthreads();
+        for (int st = n_t - 2; st >= 0; --st) {
+            const float t = tspan[st], h = tspan[st + 1] - tspan[st];
+            const SmTile y = yn;
+            if (st > 0) {
+#pragma unroll
+                for (int i = 0; i < SM_V; ++i) {
+                    const int gr = row0 + sm_row(i, lane);
+                    yn.v[i] = (gr < B && col < d) ? traj[(size_t)(st - 1) * n + (size_t)gr * D + 1 + col] : 0.f;
+                }
+            }
+            SmTile ap, cp;
+#pragma unroll
+            for (int i = 0; i < SM_V; ++i) { ap.v[i] = h * a.v[i]; cp.v[i] = -(h * cv.v[i]); }    // cp = -h c
+
+            // ---- primal forward: s_l, q_l, h_l (the arithmetic of sm_field_aug) ----
+            SmTile s[3], q[3], hh[3];
+            f32x4 c[SM_MB];
+            cg_put(X1, y, lane, col);
+            sm_lds_barrier();
+            {
+                float* src = X1; float* dst = X2;
+#pragma unroll
+                for (int l = 0; l < 3; ++l) {
+                    const int N = A.dims[l + 1];
+                    sm_gemm(src, Wl + l * WS, 0, wv, lane, c);
+                    const float bv = (col < N) ? bl[l * SM_W + col] : 0.f;
+                    const float wtc = (l == 0 && col < N) ? wt[col] : 0.f;
+#pragma unroll
+                    for (int i = 0; i < SM_V; ++i) {
+                        float z = c[0][i] + bv;
+                        if (l == 0) z = fmaf(t, wtc, z);
+                        const float sl = (col < N && sm_row(i, lane) < nrows) ? selu_slope(z) : 0.f;
+                        s[l].v[i] = sl;
+                        q[l].v[i] = z > 0.f ? 0.f : sl;
+                        hh[l].v[i] = (col < N) ? selu_f(z) : 0.f;
+                    }
+                    if (l < 2) {
+                        cg_put(dst, hh[l], lane, col);
+                        sm_lds_barrier();
+                        float* tmp = src; src = dst; dst = tmp;
+                    }
+                }
+            }
+            sm_lds_barrier();       // layer 2 read X1: an exact direction writes T1 there with no barrier of its own before
+
+            // ---- the directions: tangents forward, their cotangents back ----
+            SmTile sb[3];
+#pragma unroll
+            for (int l = 0; l < 3; ++l) {
+#pragma unroll
+                for (int i = 0; i < SM_V; ++i) sb[l].v[i] = 0.f;
+            }
+            const int nk = (MODE == AUG_HUTCH) ? 1 : d;
+            for (int k = 0; k < nk; ++k) {
+                SmTile U1, U2, U3, tv;
+                if constexpr (MODE == AUG_HUTCH) {
+                    cg_put(E, ep, lane, col);
+                    sm_lds_barrier();
+                    sm_gemm(E, Wl, 0, wv, lane, c);
+#pragma unroll
+                    for (int i = 0; i < SM_V; ++i) U1.v[i] = c[0][i];
+                } else {
+                    const float w0 = Wl[col * SM_LD + k];                                   // W0[col][k]
+#pragma unroll
+                    for (int i = 0; i < SM_V; ++i) {
+                        tv.v[i] = (col == k && sm_row(i, lane) < nrows) ? 1.f : 0.f;
+                        U1.v[i] = w0;
+                    }
+                    cg_put(E, tv, lane, col);
+                }
+#pragma unroll
+                for (int i = 0; i < SM_V; ++i) tv.v[i] = s[0].v[i] * U1.v[i];
+                cg_put(X1, tv, lane, col);                                                  // T1
+                sm_lds_barrier();
+                sm_gemm(X1, Wl + 1 * WS, 0, wv, lane, c);
+#pragma unroll
+                for (int i = 0; i < SM_V; ++i) { U2.v[i] = c[0][i]; tv.v[i] = s[1].v[i] * U2.v[i]; }
+                cg_put(X2, tv, lane, col);                                                  // T2
+                sm_lds_barrier();
+                sm_gemm(X2, Wl + 2 * WS, 0, wv, lane, c);
+#pragma unroll
+                for (int i = 0; i < SM_V; ++i) { U3.v[i] = c[0][i]; tv.v[i] = cp.v[i] * (s[2].v[i] * U3.v[i]); }
+                cg_put(X3, tv, lane, col);                                                  // -h c T3
+                sm_lds_barrier();
+                cg_outer(E, X3, wv, lane, dWa[3]);
+                if constexpr (MODE == AUG_HUTCH) {
+                    cg_gemm_t(E, W3, wv, lane, c[0]);                                       // eps W3
+                } else {
+                    const float w3 = W3[k * SM_LD + col];                                   // W3[k][col]
+                    c[0] = f32x4{w3, w3, w3, w3};
+                }
+#pragma unroll
+                for (int i = 0; i < SM_V; ++i) {
+                    const float tb = cp.v[i] * c[0][i];
+                    sb[2].v[i] = fmaf(tb, U3.v[i], sb[2].v[i]);
+                    tv.v[i] = s[2].v[i] * tb;
+                }
+                cg_put(Y3, tv, lane, col);                                                  // Ub3
+                sm_lds_barrier();
+                cg_outer(Y3, X2, wv, lane, dWa[2]);
+                sm_gemm(Y3, W2T, 0, wv, lane, c);
+#pragma unroll
+                for (int i = 0; i < SM_V; ++i) {
+                    sb[1].v[i] = fmaf(c[0][i], U2.v[i], sb[1].v[i]);
+                    tv.v[i] = s[1].v[i] * c[0][i];
+                }
+                cg_put(X3, tv, lane, col);                                                  // Ub2
+                sm_lds_barrier();
+                cg_outer(X3, X1, wv, lane, dWa[1]);
+                sm_gemm(X3, W1T, 0, wv, lane, c);
+#pragma unroll
+                for (int i = 0; i < SM_V; ++i) {
+                    sb[0].v[i] = fmaf(c[0][i], U1.v[i], sb[0].v[i]);
+                    tv.v[i] = s[0].v[i] * c[0][i];
+                }
+                cg_put(Y3, tv, lane, col);                                                  // Ub1
+                sm_lds_barrier();
+                cg_outer(Y3, E, wv, lane, dWa[0]);
+                sm_lds_barrier();
+            }
+
+            // ---- primal reverse ----
+            SmTile zb;
+            cg_put(E, ap, lane, col);
+            cg_put(X1, hh[2], lane, col);
+            sm_lds_barrier();
+            dba[3] += cg_sum4(ap);
+            cg_outer(E, X1, wv, lane, dWa[3]);
+            cg_gemm_t(E, W3, wv, lane, c[0]);
+#pragma unroll
+            for (int i = 0; i < SM_V; ++i) zb.v[i] = c[0][i] * s[2].v[i] + sb[2].v[i] * q[2].v[i];
+            dba[2] += cg_sum4(zb);
+            cg_put(X2, zb, lane, col);
+            cg_put(X3, hh[1], lane, col);
+            sm_lds_barrier();
+            cg_outer(X2, X3, wv, lane, dWa[2]);
+            sm_gemm(X2, W2T, 0, wv, lane, c);
+#pragma unroll
+            for (int i = 0; i < SM_V; ++i) zb.v[i] = c[0][i] * s[1].v[i] + sb[1].v[i] * q[1].v[i];
+            dba[1] += cg_sum4(zb);
+            cg_put(E, zb, lane, col);
+            cg_put(X1, hh[0], lane, col);
+            sm_lds_barrier();
+            cg_outer(E, X1, wv, lane, dWa[1]);
+            sm_gemm(E, W1T, 0, wv, lane, c);
+#pragma unroll
+            for (int i = 0; i < SM_V; ++i) zb.v[i] = c[0][i] * s[0].v[i] + sb[0].v[i] * q[0].v[i];
+            {
+                const float zs = cg_sum4(zb);
+                dba[0] += zs;
+                dwt = fmaf(t, zs, dwt);
+            }
+            cg_put(X2, zb, lane, col);
+            cg_put(X3, y, lane, col);
+            sm_lds_barrier();
+            cg_outer(X2, X3, wv, lane, dWa[0]);
+            cg_gemm_t(X2, Wl, wv, lane, c[0]);                                              // zb1 W0[:, :d]
+#pragma unroll
+            for (int i = 0; i < SM_V; ++i) a.v[i] += c[0][i];
+            sm_lds_barrier();
+        }
+        if (g0) {
+#pragma unroll
+            for (int i = 0; i < SM_V; ++i) {
+                const int gr = row0 + sm_row(i, lane);
+                if (gr < B && col < d) g0[(size_t)gr * D + 1 + col] = a.v[i];
+                if (gr < B && lw) g0[(size_t)gr * D] = cv.v[i];
+            }
+        }
+    }
+
+    // ---- this workgroup's partial gradient ----
+    float* Pw = part + (size_t)blockIdx.x * P;
+    int off = 0;
+#pragma unroll
+    for (int l = 0; l < 4; ++l) {
+        const int in_l = A.dims[l], out_l = A.dims[l + 1];
+        const int K = (l == 0) ? d : in_l;
+#pragma unroll
+        for (int mb = 0; mb < 4; ++mb) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int r = 16 * mb + 4 * (lane >> 4) + i;
+                if (r < out_l && col < K) Pw[off + r * in_l + col] = dWa[l][mb][i];
+            }
+        }
+        float bsum = dba[l];
+        bsum += __shfl_xor(bsum, 16, 64);
+        bsum += __shfl_xor(bsum, 32, 64);
+        if (l == 0) {
+            float tsum = dwt;
+            tsum += __shfl_xor(tsum, 16, 64);
+            tsum += __shfl_xor(tsum, 32, 64);
+            if (lane < 16 && col < out_l) Pw[off + col * in_l + d] = tsum;
+        }
+        off += out_l * in_l;
+        if (lane < 16 && col < out_l) Pw[off + col] = bsum;
+        off += out_l;
+    }
+}
+
+// dW[], db[] = the partials added in workgroup order
+__global__ __launch_bounds__(256) void ode_small_grad_reduce(const float* __restrict__ part, int nparts, int P, SmArgs A,
+                                                          CgOut O) {
+    int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= P) return;
+    float sum = 0.f;
+    for (int g = 0; g < nparts; ++g) sum += part[(size_t)g * P + p];
+#pragma unroll
+    for (int l = 0; l < 4; ++l) {
+        const int nw = A.dims[l + 1] * A.dims[l], nb = A.dims[l + 1];
+        if (p >= 0 && p < nw) O.dW[l][p] = sum;
+        p -= nw;
+        if (p >= 0 && p < nb) O.db[l][p] = sum;
+        p -= nb;
+    }
+}
+
+template <int MODE>
+static int cnf_grad_launch(const SmArgs& A, int B, int d, const float* tspan_dev, int n_t, const float* traj,
+                           const float* eps, const float* G, float* g0, float* part, int P, const CgOut& O, hipStream_t s) {
+    const int raised = cfm_once_per_device([] {
+        hipError_t e = hipFuncSetAttribute((const void*)ode_small_euler_grad<MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+        return (e == hipSuccess) ? 1 : -1;
+    });
+    if (raised < 0) return CFM_EINVAL;
+    const int tiles = (B + SM_ROWS - 1) / SM_ROWS;
+    const int grid = tiles < CG_MAXGRID ? tiles : CG_MAXGRID;
+    hipLaunchKernelGGL(ode_small_euler_grad<MODE>, dim3(grid), dim3(256), cg_lds_bytes(), s, A, B, d, tspan_dev, n_t, traj, eps,
+                       G, g0, part, P);
+    int rc = cfm_status();
+    if (rc) return rc;
+    hipLaunchKernelGGL(ode_small_grad_reduce, dim3((P + 255) / 256), dim3(256), 0, s, (const float*)part, grid, P, A, O);
+    return cfm_status();
+}
+
+extern "C" int cfm_cnf_euler_grad_f32(const float* const* W, const float* const* b, const int* dims, int n_layers,
+                                      const float* traj, int B, const float* t_span, int n_t, int mode, const float* eps,
+                                      const float* g_final, float* const* dW, float* const* db, float* g_initial, void* ws,
+                                      void* stream) {
+    int d; SmArgs A;
+    if (!traj || !t_span || !g_final || !dW || !db || !ws || n_t < 1) return CFM_EINVAL;
+    int rc = cnf_check(W, b, dims, n_layers, B, mode, eps, &d, &A);
+    if (rc) return rc;
+    CgOut O;
+    int P = 0;
+    for (int l = 0; l < 4; ++l) {
+        if (!dW[l] || !db[l]) return CFM_EINVAL;
+        O.dW[l] = dW[l]; O.db[l] = db[l];
+        P += dims[l + 1] * (dims[l] + 1);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    float* tspan_dev = (float*)ws;
+    float* part = (float*)((char*)ws + cfm_align_up(sizeof(float) * (size_t)n_t, 256));
+    rc = cfm_hip(hipMemcpyAsync(tspan_dev, t_span, sizeof(float) * n_t, hipMemcpyHostToDevice, s));
+    if (rc) return rc;
+    return mode == 0 ? cnf_grad_launch<AUG_EXACT>(A, B, d, tspan_dev, n_t, traj, eps, g_final, g_initial, part, P, O, s)
+                     : cnf_grad_launch<AUG_HUTCH>(A, B, d, tspan_dev, n_t, traj, eps, g_final, g_initial, part, P, O, s);
+}

@@ -1613,3 +1613,6 @@ extern "C" int cfm_ode_dopri5_cnf_mlp_f32(const float* const* W, const float* co
     return cfm_ode_adaptive_cnf_mlp_f32(W, b, dims, n_layers, x0, B, t_span, n_t, mode, eps, CFM_ODE_DOPRI5, atol, rtol, traj,
                                         n_steps, nfe, ws, stream);
 }
+
+// ---- CNF training: the gradient of the Euler augmented solve (ode_small_euler_grad, cfm_cnf_euler_grad_f32) ----
+#include "cnf_grad.h"

@@ -57,6 +57,7 @@ extern "C" {
 #define CFM_OP_COST          7   /* cfm_sqeuclid_cost_ws_f32 (B0, B1, d)  */
 #define CFM_OP_MLP_TRAIN     8   /* cfm_mlp_backward_f32 (B, widest layer, largest weight's element count) */
 #define CFM_OP_TRANSPORT     9   /* cfm_transport_exact_f32 (B0, B1, 0) */
+#define CFM_OP_CNF_GRAD     10   /* cfm_cnf_euler_grad_f32 (B, n_t, 0): per-workgroup partial gradients + t_span */
 
 /* variants for cfm_sample_xt_ut_f32 (reference class in parentheses) */
 #define CFM_VARIANT_ICFM   0  /* ConditionalFlowMatcher / ExactOT...          */
@@ -501,6 +502,21 @@ int cfm_ode_adaptive_cnf_mlp_f32(const float* const* W, const float* const* b, c
 int cfm_ode_fixed_cnf_mlp_f32(const float* const* W, const float* const* b, const int* dims, int n_layers,
                               const float* x0, int B, const float* t_span, int n_t, int mode,
                               const float* eps, int scheme, float* traj, int* nfe, void* ws, void* stream);
+
+/* Gradient of the Euler augmented solve that cfm_ode_fixed_cnf_mlp_f32(..., CFM_ODE_EULER) wrote into traj: the
+ * backward half of the training loop of examples/2D_tutorials/Maximum_likelihood_CNF_tutorial.ipynb cell 5
+ * (NeuralODE(cnf_wrapper(model, "exact"), solver="euler", sensitivity="adjoint") ... loss.backward()).
+ * Discretise-then-optimise: the exact gradient of the recurrence y += h v, l -= h div that the forward ran (torchdyn's
+ * "adjoint" integrates the continuous adjoint with the same solver and differs from it by O(h)).
+ * traj: device [n_t,B,1+d] (the states y_n are read as checkpoints); t_span: host float[n_t], as given to the forward;
+ * mode / eps: as given to the forward; g_final: device [B,1+d] = dL/d[l_N, y_N].  Outputs (overwritten): dW[l], db[l]
+ * device, laid out as W[l], b[l]; g_initial device [B,1+d] = dL/d[l_0, y_0], or NULL.
+ * ws: cfm_workspace_bytes(CFM_OP_CNF_GRAD, B, n_t, 0).  Same envelope and CFM_EINVAL rule as cfm_mlp_divergence_f32.
+ * The result is the same bit pattern run to run (per-workgroup partials, added in a fixed order by a second launch). */
+int cfm_cnf_euler_grad_f32(const float* const* W, const float* const* b, const int* dims, int n_layers,
+                           const float* traj, int B, const float* t_span, int n_t, int mode,
+                           const float* eps, const float* g_final, float* const* dW, float* const* db,
+                           float* g_initial, void* ws, void* stream);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop
