@@ -43,7 +43,7 @@ static inline int cfm_device_cus() {
     });
 }
 
-// one net's operands of a layer launch that serves two nets (mlp.hip: cfm_mlp_launch_layer_two; mlp_train.hip)
+// one net's operands of a layer launch that serves one or two nets (mlp.hip: cfm_mlp_launch_layer; mlp_train.hip)
 struct MlpNetLayer {
     const float* X; const float* W; const float* bias; float* out; float* zout;
     const float* target; const float* lam; float scale; float* partial;      // last layer: loss target, row weights, seed scale, loss partials

@@ -13,6 +13,8 @@
 //     [out, in]) -> "NT" GEMM on the shared tile engine (gemm_core.h): K-major LDS
 //     tiles, two stages and one barrier per K step, ds_read_b64 fragments;
 //   * bias + time column + SELU fused into the accumulator epilogue.
+// Host side: plan_layer picks the kernel of a layer, launch_layer is the one dispatch over (activation, 16-byte loads,
+// engine) for one net or for two nets of equal sizes; cfm_mlp_launch_layer is the entry of the training steps (mlp_train.hip).
 #include "cfm_common.h"
 #include "gemm_core.h"
 #include "gemm_glds64.h"
@@ -206,20 +208,6 @@ static int mlp_glds_mode() {
 extern "C" void cfm_mlp_set_glds(int mode) { g_mlp_glds = mode < 0 ? 0 : (mode > 2 ? 2 : mode); }
 extern "C" int cfm_mlp_get_glds(void) { return mlp_glds_mode(); }
 
-template <bool ACT, bool VECA, bool VECB>
-static void launch_layer_t(int tile, const float* X, int lda, const float* W, int ldw, const float* bias,
-                           const float* t, float tval, int t_per_row, int tcol, int B, int K, int N, float* out,
-                           hipStream_t s, float* zout, const float* mse_u = nullptr, float mse_scale = 0.f, float mse_inv_n = 0.f,
-                           float* mse_partial = nullptr) {
-    if (tile == 0) {
-        const int tm = (B + 127) / 128, tn = (N + 127) / 128;
-        hipLaunchKernelGGL((mlp_layer<128, 128, 16, ACT, VECA, VECB>), dim3(tm * tn), dim3(256), 0, s, X, lda, W, ldw, bias, t, tval, t_per_row, tcol, B, K, N, out, tn, zout, mse_u, mse_scale, mse_inv_n, mse_partial);
-    } else {
-        const int tm = (B + 63) / 64, tn = (N + 63) / 64;
-        hipLaunchKernelGGL((mlp_layer<64, 64, 32, ACT, VECA, VECB>), dim3(tm * tn), dim3(256), 0, s, X, lda, W, ldw, bias, t, tval, t_per_row, tcol, B, K, N, out, tn, zout, mse_u, mse_scale, mse_inv_n, mse_partial);
-    }
-}
-
 // Which kernel a layer runs on: the tile so the grid covers the chip; 16-byte loads per operand when its rows allow it
 // (K % 4 == 0, row pitch % 4 == 0, aligned base): the 785-wide rows of a time-varying first layer do not; the
 // direct-to-LDS form of the 64 x 64 tile (round 6) where its preconditions hold.
@@ -238,86 +226,80 @@ static LayerPlan plan_layer(const float* X, int lda, const float* W, int ldw, in
     return P;
 }
 
-// one layer launch
-static int launch_layer(const float* X, int lda, const float* W, int ldw, const float* bias,
-                        const float* t, float tval, int t_per_row, int tcol, int B, int K, int N, float* out,
-                        bool act, hipStream_t s, float* zout = nullptr, const float* mse_u = nullptr, float mse_scale = 0.f,
-                        float mse_inv_n = 0.f, float* mse_partial = nullptr, int* mse_blocks = nullptr) {
-    const LayerPlan P = plan_layer(X, lda, W, ldw, B, K, N);
-    const int tile = P.tile;
-    if (mse_blocks) *mse_blocks = P.tm * P.tn;
-    if (P.glds) {
-        const LayerEpi E = {W, ldw, bias, t, tval, t_per_row, tcol, B, N, out, zout, mse_u, mse_scale, mse_inv_n, mse_partial, nullptr};
-        constexpr int lds_bytes = Glds64<MLP_GLDS_NST>::LDS_BYTES;
-        if (act) hipLaunchKernelGGL(mlp_layer_glds<true>, dim3(P.tm * P.tn), dim3(256), lds_bytes, s, X, lda, W, ldw, K, P.tn, E);
-        else hipLaunchKernelGGL(mlp_layer_glds<false>, dim3(P.tm * P.tn), dim3(256), lds_bytes, s, X, lda, W, ldw, K, P.tn, E);
-        return cfm_status();
-    }
-#define CFM_LL(ACT_, VA_, VB_) launch_layer_t<ACT_, VA_, VB_>(tile, X, lda, W, ldw, bias, t, tval, t_per_row, tcol, B, K, N, out, s, zout, mse_u, mse_scale, mse_inv_n, mse_partial)
-    if (act) { if (P.va) { if (P.vb) CFM_LL(true, true, true); else CFM_LL(true, true, false); }
-               else      { if (P.vb) CFM_LL(true, false, true); else CFM_LL(true, false, false); } }
-    else     { if (P.va) { if (P.vb) CFM_LL(false, true, true); else CFM_LL(false, true, false); }
-               else      { if (P.vb) CFM_LL(false, false, true); else CFM_LL(false, false, false); } }
-#undef CFM_LL
-    return cfm_status();
-}
-
+// One net alone runs mlp_layer, whose positional arguments are filled from its LayerArgs; two nets run mlp_layer_two on
+// twice the grid.  (Row weights travel in a LayerEpi only, which mlp_layer builds itself: a net that has them and runs
+// alone takes mlp_layer_two on one net's grid — no workgroup reaches the table's second half.)
 template <bool ACT, bool VECA, bool VECB>
-static void launch_layer_two_t(int tile, const LayerArgs2& T, unsigned per_net, unsigned nets, hipStream_t s) {
-    if (tile == 0) hipLaunchKernelGGL((mlp_layer_two<128, 128, 16, ACT, VECA, VECB>), dim3(nets * per_net), dim3(256), 0, s, T, per_net);
+static void launch_layer_t(const LayerPlan& P, const LayerArgs* A, int nets, hipStream_t s) {
+    const unsigned per_net = (unsigned)(P.tm * P.tn);
+    if (nets == 1 && A[0].E.lam == nullptr) {
+        const LayerArgs& a = A[0]; const LayerEpi& E = a.E;
+#define CFM_L1(BM_, BN_, BK_) hipLaunchKernelGGL((mlp_layer<BM_, BN_, BK_, ACT, VECA, VECB>), dim3(per_net), dim3(256), 0, s, a.X, a.lda, E.W, E.ldw, \
+        E.bias, E.tptr, E.tval, E.t_per_row, E.tcol, E.B, a.K, E.N, E.out, a.tiles_n, E.zout, E.mse_u, E.mse_scale, E.mse_inv_n, E.mse_partial)
+        if (P.tile == 0) CFM_L1(128, 128, 16); else CFM_L1(64, 64, 32);
+#undef CFM_L1
+        return;
+    }
+    LayerArgs2 T; T.net[0] = A[0]; T.net[1] = A[nets - 1];
+    if (P.tile == 0) hipLaunchKernelGGL((mlp_layer_two<128, 128, 16, ACT, VECA, VECB>), dim3(nets * per_net), dim3(256), 0, s, T, per_net);
     else hipLaunchKernelGGL((mlp_layer_two<64, 64, 32, ACT, VECA, VECB>), dim3(nets * per_net), dim3(256), 0, s, T, per_net);
 }
-// nets = 2: both nets of the table on one grid; nets = 1: net 0 alone (no workgroup reaches the second half)
-static int launch_layer_two(const LayerPlan& P, const LayerArgs2& T, unsigned nets, bool act, hipStream_t s) {
-    const unsigned per_net = (unsigned)(P.tm * P.tn);
-    if (P.glds) {
+
+// One layer of one net, or of two nets of equal sizes (P[q], A[q]: net q's plan and arguments).  The plan is made PER NET, as
+// if that net ran alone; equal plans (the sizes are equal, so only an operand's alignment can make them differ) share
+// one launch of 2 x the grid, unequal ones take this launcher once each, as one net.
+static int launch_layer(const LayerPlan* P, const LayerArgs* A, int nets, bool act, hipStream_t s) {
+    if (nets == 2 && (P[0].va != P[1].va || P[0].vb != P[1].vb || P[0].glds != P[1].glds)) {
+        for (int q = 0; q < 2; ++q) {
+            const int rc = launch_layer(P + q, A + q, 1, act, s);
+            if (rc) return rc;
+        }
+        return 0;
+    }
+    if (P->glds) {
         constexpr int lds_bytes = Glds64<MLP_GLDS_NST>::LDS_BYTES;
-        if (act) hipLaunchKernelGGL(mlp_layer_glds_two<true>, dim3(nets * per_net), dim3(256), lds_bytes, s, T, per_net);
-        else hipLaunchKernelGGL(mlp_layer_glds_two<false>, dim3(nets * per_net), dim3(256), lds_bytes, s, T, per_net);
+        const unsigned per_net = (unsigned)(P->tm * P->tn);
+        if (nets == 1) {
+            const LayerArgs& a = A[0];
+            if (act) hipLaunchKernelGGL(mlp_layer_glds<true>, dim3(per_net), dim3(256), lds_bytes, s, a.X, a.lda, a.E.W, a.E.ldw, a.K, a.tiles_n, a.E);
+            else hipLaunchKernelGGL(mlp_layer_glds<false>, dim3(per_net), dim3(256), lds_bytes, s, a.X, a.lda, a.E.W, a.E.ldw, a.K, a.tiles_n, a.E);
+        } else {
+            LayerArgs2 T; T.net[0] = A[0]; T.net[1] = A[1];
+            if (act) hipLaunchKernelGGL(mlp_layer_glds_two<true>, dim3(2 * per_net), dim3(256), lds_bytes, s, T, per_net);
+            else hipLaunchKernelGGL(mlp_layer_glds_two<false>, dim3(2 * per_net), dim3(256), lds_bytes, s, T, per_net);
+        }
         return cfm_status();
     }
-#define CFM_LL(ACT_, VA_, VB_) launch_layer_two_t<ACT_, VA_, VB_>(P.tile, T, per_net, nets, s)
-    if (act) { if (P.va) { if (P.vb) CFM_LL(true, true, true); else CFM_LL(true, true, false); }
-               else      { if (P.vb) CFM_LL(true, false, true); else CFM_LL(true, false, false); } }
-    else     { if (P.va) { if (P.vb) CFM_LL(false, true, true); else CFM_LL(false, true, false); }
-               else      { if (P.vb) CFM_LL(false, false, true); else CFM_LL(false, false, false); } }
+#define CFM_LL(ACT_, VA_, VB_) launch_layer_t<ACT_, VA_, VB_>(*P, A, nets, s)
+    if (act) { if (P->va) { if (P->vb) CFM_LL(true, true, true); else CFM_LL(true, true, false); }
+               else       { if (P->vb) CFM_LL(true, false, true); else CFM_LL(true, false, false); } }
+    else     { if (P->va) { if (P->vb) CFM_LL(false, true, true); else CFM_LL(false, true, false); }
+               else       { if (P->vb) CFM_LL(false, false, true); else CFM_LL(false, false, false); } }
 #undef CFM_LL
     return cfm_status();
 }
 
-// One layer of the two nets of cfm_mlp_sf2m_step_f32 (mlp_train.hip): equal sizes, one time vector, per-net operands.
-// The kernel is chosen PER NET by plan_layer, as if that net ran alone; equal choices (the sizes are equal, so only an
-// operand's alignment can make them differ) share one launch of 2 x the grid, unequal ones take one launch each.
-// Last layer (act = false, target != NULL): the loss epilogue, plain (lam == NULL) or weighted.
-int cfm_mlp_launch_layer_two(const MlpNetLayer* net, int lda, int ldw, const float* t, int tcol, int B, int K, int N,
-                             bool act, float inv_n, hipStream_t s, int* n_partials) {
-    LayerPlan P[2]; LayerArgs2 T;
-    for (int q = 0; q < 2; ++q) {
+// Plans and launches one layer out = act(X W^T + b [+ time * W[:, tcol]]) of `nets` nets (cfm_common.h: MlpNetLayer) with
+// shared sizes and one time: `t` (device: a scalar, or [B] with t_per_row) or, when t is NULL, the by-value tval.  A net
+// with a target (act = false) gets the loss epilogue, plain (lam == NULL) or weighted: out = the loss gradient seed, one
+// loss partial per workgroup, *n_partials of them.
+static int launch_net_layer(const MlpNetLayer* net, int nets, int lda, int ldw, const float* t, float tval, int t_per_row, int tcol,
+                            int B, int K, int N, bool act, float inv_n, hipStream_t s, int* n_partials) {
+    LayerPlan P[2]; LayerArgs A[2];
+    for (int q = 0; q < nets; ++q) {
         P[q] = plan_layer(net[q].X, lda, net[q].W, ldw, B, K, N);
-        const LayerEpi E = {net[q].W, ldw, net[q].bias, t, 0.f, tcol >= 0 ? 1 : 0, tcol, B, N, net[q].out, net[q].zout,
-                            net[q].target, net[q].scale, inv_n, net[q].partial, net[q].lam};
-        T.net[q] = LayerArgs{net[q].X, lda, K, P[q].tn, E};
+        const LayerEpi E = {net[q].W, ldw, net[q].bias, t, tval, t_per_row, tcol, B, N, net[q].out, net[q].zout,
+                            net[q].target, net[q].scale, net[q].partial ? inv_n : 0.f, net[q].partial, net[q].lam};
+        A[q] = LayerArgs{net[q].X, lda, K, P[q].tn, E};
     }
     if (n_partials) *n_partials = P[0].tm * P[0].tn;      // (the tile follows from the sizes alone: equal for both nets)
-    if (P[0].va == P[1].va && P[0].vb == P[1].vb && P[0].glds == P[1].glds) return launch_layer_two(P[0], T, 2, act, s);
-    for (int q = 0; q < 2; ++q) {
-        LayerArgs2 T1; T1.net[0] = T.net[q]; T1.net[1] = T.net[q];
-        const int rc = launch_layer_two(P[q], T1, 1, act, s);
-        if (rc) return rc;
-    }
-    return 0;
+    return launch_layer(P, A, nets, act, s);
 }
 
-// (mlp_train.hip: the fused regression step runs its forward through the same launcher)
-int cfm_mlp_launch_layer(const float* X, int lda, const float* W, int ldw, const float* bias, const float* t,
-                         int t_per_row, int tcol, int B, int K, int N, float* out, bool act, hipStream_t s, float* zout) {
-    return launch_layer(X, lda, W, ldw, bias, t, 0.f, t_per_row, tcol, B, K, N, out, act, s, zout);
-}
-// the last layer of the fused regression step: out = (2 / n) (v - u), one loss partial per workgroup (*n_partials of them)
-int cfm_mlp_launch_layer_mse(const float* X, int lda, const float* W, int ldw, const float* bias, const float* t,
-                             int t_per_row, int tcol, int B, int K, int N, float* out, hipStream_t s, const float* u,
-                             float scale, float inv_n, float* partial, int* n_partials) {
-    return launch_layer(X, lda, W, ldw, bias, t, 0.f, t_per_row, tcol, B, K, N, out, false, s, nullptr, u, scale, inv_n, partial, n_partials);
+// (mlp_train.hip: the fused training steps run their forward through the same launcher)
+int cfm_mlp_launch_layer(const MlpNetLayer* net, int nets, int lda, int ldw, const float* t, int t_per_row, int tcol, int B,
+                         int K, int N, bool act, float inv_n, hipStream_t s, int* n_partials) {
+    return launch_net_layer(net, nets, lda, ldw, t, 0.f, t_per_row, tcol, B, K, N, act, inv_n, s, n_partials);
 }
 
 // Forward through all layers.  dims[0] counts the time column when the net is
@@ -336,8 +318,8 @@ int cfm_mlp_forward_impl(const float* x, const float* t, float tval, int has_t, 
         const int K = (first && has_t) ? in - 1 : in;
         const int tcol = (first && has_t) ? K : -1;
         float* dst = (l == n_layers - 1) ? out : buf[l & 1];
-        int rc = launch_layer(cur, K, W[l], in, b[l], t, tval, t_per_row, tcol, B, K, on, dst,
-                              l != n_layers - 1, s);
+        const MlpNetLayer net = {cur, W[l], b[l], dst, nullptr, nullptr, nullptr, 0.f, nullptr};
+        int rc = launch_net_layer(&net, 1, K, in, t, tval, t_per_row, tcol, B, K, on, l != n_layers - 1, 0.f, s, nullptr);
         if (rc) return rc;
         cur = dst;
     }
@@ -370,8 +352,8 @@ extern "C" int cfm_mlp_forward_train_f32(const float* x, const float* const* W, 
     for (int l = 0; l < n_layers; ++l) {
         const bool last = (l == n_layers - 1);
         float* dst = last ? out : hidden[l];
-        int rc = launch_layer(cur, dims[l], W[l], dims[l], b[l], nullptr, 0.f, 0, -1, B, dims[l], dims[l + 1], dst,
-                              !last, (hipStream_t)stream, last ? nullptr : preact[l]);
+        const MlpNetLayer net = {cur, W[l], b[l], dst, last ? nullptr : preact[l], nullptr, nullptr, 0.f, nullptr};
+        int rc = launch_net_layer(&net, 1, dims[l], dims[l], nullptr, 0.f, 0, -1, B, dims[l], dims[l + 1], !last, 0.f, (hipStream_t)stream, nullptr);
         if (rc) return rc;
         cur = dst;
     }

@@ -23,6 +23,10 @@
 // All GEMMs are v_mfma_f32_32x32x2_f32 (exact fp32, 157 TFLOP/s peak) on the shared tile engine of gemm_core.h:
 // K-major LDS tiles whatever the operand's storage order (k-contiguous operands are transposed on the way in),
 // two stages, ds_read_b64 fragments.
+//
+// Host side: ONE driver for the regression step (one net) and the SF2M step (two nets of equal sizes per launch) —
+// mlp_train_forward, mlp_backward_impl, launch_gemm (one product) and launch_gemm_pair (dgrad + wgrad of a layer) all take
+// `nets`; carve_train_ws is the one statement of the CFM_OP_MLP_TRAIN workspace layout.
 #include "cfm_common.h"
 #include "gemm_core.h"
 
@@ -233,58 +237,109 @@ extern "C" size_t cfm_mlp_train_ws_bytes_internal(int B, int maxw, int max_param
     return sizeof(float) * ((size_t)2 * B * maxw + (size_t)MLP_MAX_SPLITS * ((size_t)max_params + maxw) * 4) + 4 * MLP_LOSS_PARTIALS;
 }
 
-int cfm_gemm_pick_tile(long M, long N, long splits);      // mlp.hip
-int cfm_mlp_launch_layer(const float* X, int lda, const float* W, int ldw, const float* bias, const float* t,
-                         int t_per_row, int tcol, int B, int K, int N, float* out, bool act, hipStream_t s, float* zout);
-int cfm_mlp_launch_layer_mse(const float* X, int lda, const float* W, int ldw, const float* bias, const float* t,
-                             int t_per_row, int tcol, int B, int K, int N, float* out, hipStream_t s, const float* u,
-                             float scale, float inv_n, float* partial, int* n_partials);
+// the widest layer and the largest weight matrix of a net: the sizes of its CFM_OP_MLP_TRAIN workspace
+static void mlp_widest(const int* dims, int n_layers, int* maxw, size_t* maxp) {
+    *maxw = 0; *maxp = 0;
+    for (int l = 0; l <= n_layers; ++l) *maxw = dims[l] > *maxw ? dims[l] : *maxw;
+    for (int l = 0; l < n_layers; ++l) { const size_t p = (size_t)dims[l] * dims[l + 1]; *maxp = p > *maxp ? p : *maxp; }
+}
 
-int cfm_mlp_launch_layer_two(const MlpNetLayer* net, int lda, int ldw, const float* t, int tcol, int B, int K, int N,
-                             bool act, float inv_n, hipStream_t s, int* n_partials);
+// a CFM_OP_MLP_TRAIN workspace (cfm_mlp_train_ws_bytes_internal), carved: two [B, maxw] gradient buffers, the pool of
+// split-K partials, the loss partials at its end
+struct TrainWs { float* gbuf[2]; float* pool; size_t pool_floats; float* lpart; };
+static TrainWs carve_train_ws(void* ws, int B, int maxw, size_t maxp) {
+    TrainWs w;
+    w.gbuf[0] = (float*)ws; w.gbuf[1] = w.gbuf[0] + (size_t)B * maxw;
+    w.pool = w.gbuf[1] + (size_t)B * maxw;
+    w.pool_floats = (size_t)MLP_MAX_SPLITS * (maxp + maxw) * 4;
+    w.lpart = w.pool + w.pool_floats;
+    return w;
+}
 
-static GemmArgs gemm_args(const float* A, int lda, const float* Bm, int ldb, float* C, int ldc, size_t split_stride,
-                          const float* H, int M, int N, int Kc, int k_chunk, int tiles_n, float* colsum, const float* tvec,
-                          float* tsum) {
+// mlp.hip
+int cfm_gemm_pick_tile(long M, long N, long splits);
+int cfm_mlp_launch_layer(const MlpNetLayer* net, int nets, int lda, int ldw, const float* t, int t_per_row, int tcol, int B,
+                         int K, int N, bool act, float inv_n, hipStream_t s, int* n_partials);
+
+// one product of each net of a launch: per-net operands (the sizes, pitches and tvec are shared)
+struct GemmOps { const float* A; const float* Bm; float* C; const float* H; float* colsum; float* tsum; };
+
+static GemmArgs gemm_args(const GemmOps& o, int lda, int ldb, int ldc, size_t split_stride, int M, int N, int Kc, int k_chunk,
+                          int tiles_n, const float* tvec) {
     GemmArgs G;
-    G.A = A; G.lda = lda; G.Bm = Bm; G.ldb = ldb; G.C = C; G.ldc = ldc; G.split_stride = split_stride; G.H = H;
-    G.M = M; G.N = N; G.Kc = Kc; G.k_chunk = k_chunk; G.tiles_n = tiles_n; G.colsum = colsum; G.tvec = tvec; G.tsum = tsum;
+    G.A = o.A; G.lda = lda; G.Bm = o.Bm; G.ldb = ldb; G.C = o.C; G.ldc = ldc; G.split_stride = split_stride; G.H = o.H;
+    G.M = M; G.N = N; G.Kc = Kc; G.k_chunk = k_chunk; G.tiles_n = tiles_n; G.colsum = o.colsum; G.tvec = tvec; G.tsum = o.tsum;
     return G;
 }
 
-template <bool AK, bool BK_, int EPI, bool VA, bool VB>
-static void launch_gemm_t(int tile, const float* A, int lda, const float* Bm, int ldb, float* C, int ldc, size_t split_stride,
-                          const float* H, int M, int N, int Kc, int k_chunk, int S, hipStream_t s, float* colsum,
-                          const float* tvec, float* tsum) {
-    if (tile == 0) {
-        const int tm = (M + 127) / 128, tn = (N + 127) / 128;
-        hipLaunchKernelGGL((gemm_f32_mfma<128, 128, 16, AK, BK_, EPI, VA, VB>), dim3(tm * tn, S), dim3(256), 0, s,
-                           gemm_args(A, lda, Bm, ldb, C, ldc, split_stride, H, M, N, Kc, k_chunk, tn, colsum, tvec, tsum));
-    } else {
-        const int tm = (M + 63) / 64, tn = (N + 63) / 64;
-        hipLaunchKernelGGL((gemm_f32_mfma<64, 64, 32, AK, BK_, EPI, VA, VB>), dim3(tm * tn, S), dim3(256), 0, s,
-                           gemm_args(A, lda, Bm, ldb, C, ldc, split_stride, H, M, N, Kc, k_chunk, tn, colsum, tvec, tsum));
+// nets == 1: gemm_f32_mfma; nets == 2: gemm_f32_mfma_two on twice the grid (MAXNETS == 1: a product no two-net caller has,
+// for which no two-net kernel is built)
+template <bool AK, bool BK_, int EPI, int MAXNETS, bool VA, bool VB>
+static void launch_gemm_t(int tile, const GemmOps* op, int nets, int lda, int ldb, int ldc, size_t split_stride, int M, int N,
+                          int Kc, int k_chunk, int S, hipStream_t s, const float* tvec) {
+    const int bm = tile == 0 ? 128 : 64;
+    const int tm = (M + bm - 1) / bm, tn = (N + bm - 1) / bm;
+    GemmArgs2 T;
+    for (int q = 0; q < nets; ++q) T.net[q] = gemm_args(op[q], lda, ldb, ldc, split_stride, M, N, Kc, k_chunk, tn, tvec);
+    const dim3 grid(nets * tm * tn, S);
+    if (MAXNETS == 1 || nets == 1) {
+        if (tile == 0) hipLaunchKernelGGL((gemm_f32_mfma<128, 128, 16, AK, BK_, EPI, VA, VB>), grid, dim3(256), 0, s, T.net[0]);
+        else hipLaunchKernelGGL((gemm_f32_mfma<64, 64, 32, AK, BK_, EPI, VA, VB>), grid, dim3(256), 0, s, T.net[0]);
+    } else if constexpr (MAXNETS == 2) {
+        if (tile == 0) hipLaunchKernelGGL((gemm_f32_mfma_two<128, 128, 16, AK, BK_, EPI, VA, VB>), grid, dim3(256), 0, s, T, (unsigned)(tm * tn));
+        else hipLaunchKernelGGL((gemm_f32_mfma_two<64, 64, 32, AK, BK_, EPI, VA, VB>), grid, dim3(256), 0, s, T, (unsigned)(tm * tn));
     }
 }
 
 static bool gemm_vec_ok(const float* p, int ld, int extent) { return (ld % 4 == 0) && ((uintptr_t)p & 15) == 0 && (extent % 4 == 0); }
 
-template <bool AK, bool BK_, int EPI>
-static int launch_gemm(const float* A, int lda, const float* Bm, int ldb, float* C, int ldc, size_t split_stride,
-                       const float* H, int M, int N, int Kc, int S, hipStream_t s, float* colsum = nullptr,
-                       const float* tvec = nullptr, float* tsum = nullptr) {
+// One product of one net or of two nets of equal sizes: tile and split from the sizes, 16-byte loads per net from its own
+// operands.  Two nets whose choices are equal share one launch; unequal ones (an operand of one net off the 16-byte grid)
+// take this launcher once each, as one net.
+template <bool AK, bool BK_, int EPI, int MAXNETS = 2>
+static int launch_gemm(const GemmOps* op, int nets, int lda, int ldb, int ldc, size_t split_stride, int M, int N, int Kc, int S,
+                       hipStream_t s, const float* tvec = nullptr) {
+    // 16-byte loads per operand: K-contiguous needs Kc % 4 == 0 (k_chunk is a multiple of 32), K-major needs the row
+    // extent % 4 == 0; both need the pitch % 4 == 0 and an aligned base
+    bool va[2], vb[2];
+    for (int q = 0; q < nets; ++q) { va[q] = gemm_vec_ok(op[q].A, lda, AK ? M : Kc); vb[q] = gemm_vec_ok(op[q].Bm, ldb, BK_ ? N : Kc); }
+    if (nets == 2 && (va[0] != va[1] || vb[0] != vb[1])) {
+        for (int q = 0; q < 2; ++q) {
+            const int rc = launch_gemm<AK, BK_, EPI, MAXNETS>(op + q, 1, lda, ldb, ldc, split_stride, M, N, Kc, S, s, tvec);
+            if (rc) return rc;
+        }
+        return 0;
+    }
     int k_chunk = (Kc + S - 1) / S;
     k_chunk = (k_chunk + 31) / 32 * 32;
     const int tile = cfm_gemm_pick_tile(M, N, S);
-    // 16-byte loads per operand: K-contiguous needs Kc % 4 == 0 (k_chunk is a multiple of 32), K-major needs the row
-    // extent % 4 == 0; both need the pitch % 4 == 0 and an aligned base
-    const bool va = gemm_vec_ok(A, lda, AK ? M : Kc);
-    const bool vb = gemm_vec_ok(Bm, ldb, BK_ ? N : Kc);
-#define CFM_LG(VA_, VB_) launch_gemm_t<AK, BK_, EPI, VA_, VB_>(tile, A, lda, Bm, ldb, C, ldc, split_stride, H, M, N, Kc, k_chunk, S, s, colsum, tvec, tsum)
-    if (va) { if (vb) CFM_LG(true, true); else CFM_LG(true, false); }
-    else    { if (vb) CFM_LG(false, true); else CFM_LG(false, false); }
+#define CFM_LG(VA_, VB_) launch_gemm_t<AK, BK_, EPI, MAXNETS, VA_, VB_>(tile, op, nets, lda, ldb, ldc, split_stride, M, N, Kc, k_chunk, S, s, tvec)
+    if (va[0]) { if (vb[0]) CFM_LG(true, true); else CFM_LG(true, false); }
+    else       { if (vb[0]) CFM_LG(false, true); else CFM_LG(false, false); }
 #undef CFM_LG
     return cfm_status();
+}
+
+// dgrad (dop: dz . W, SELU' of the pre-activations H) and wgrad (wop: dz^T . h, bias column sums riding along) of one
+// layer [N, K] in ONE launch, gemm_pair_f32_mfma (one net) or gemm_pair_f32_mfma_two (two nets): when both products run
+// on 64 x 64 tiles with 16-byte loads (every hidden layer at C3), in every net.  false: nothing launched, the caller takes
+// two launches.
+static bool launch_gemm_pair(const GemmOps* dop, const GemmOps* wop, int nets, int B, int K, int N, int S, hipStream_t s) {
+    if (cfm_gemm_pick_tile(N, K, S) != 2 || cfm_gemm_pick_tile(B, K, 1) != 2) return false;
+    for (int q = 0; q < nets; ++q)
+        if (!(gemm_vec_ok(dop[q].A, N, N) && gemm_vec_ok(wop[q].Bm, K, K) && gemm_vec_ok(dop[q].Bm, K, K))) return false;
+    int k_chunk_w = (B + S - 1) / S; k_chunk_w = (k_chunk_w + 31) / 32 * 32;
+    const int k_chunk_d = (N + 31) / 32 * 32;
+    const int tn = (K + 63) / 64, tiles_w = ((N + 63) / 64) * tn, tiles_d = ((B + 63) / 64) * tn;
+    GemmArgs2 Ga, Gw;
+    for (int q = 0; q < nets; ++q) {
+        Ga.net[q] = gemm_args(dop[q], N, K, K, 0, B, K, N, k_chunk_d, tn, nullptr);
+        Gw.net[q] = gemm_args(wop[q], N, K, K, (size_t)N * K, N, K, B, k_chunk_w, tn, nullptr);
+    }
+    const dim3 grid(nets * (tiles_d + tiles_w * S));
+    if (nets == 1) hipLaunchKernelGGL(gemm_pair_f32_mfma, grid, dim3(256), 0, s, Ga.net[0], tiles_d, Gw.net[0], tiles_w, S);
+    else hipLaunchKernelGGL(gemm_pair_f32_mfma_two, grid, dim3(256), 0, s, Ga, tiles_d, Gw, tiles_w, S);
+    return true;
 }
 
 // batch splits of a weight gradient dW[N, K]: enough workgroups to fill the chip, at least 64 rows per split
@@ -297,28 +352,32 @@ static int wgrad_splits(int N, int K, int B) {
     return S;
 }
 
-// Backward through all layers.  acts[l] = h_l (l = 0: the network input [B, dims[0]]; l = 1 .. n-1: the
-// saved hidden activations), preact[l] = z_l for l = 1 .. n-1 (preact[0] unused); dout [B, dims[n]].
-// Writes dW[l] ([dims[l+1], dims[l]]), db[l] and, if dx is not NULL, the input gradient [B, dims[0]].
+// What the backward needs of one net.  acts[l] = h_l (l = 0: the network input [B, dims[0]]; l = 1 .. n-1: the saved
+// hidden activations), zs[l] = z_l for l = 1 .. n-1 (zs[0] unused); dout [B, dims[n]]; dW[l] ([dims[l+1], dims[l]]) and
+// db[l] receive the gradients.  has_loss: `loss` is one more job for the final reduction (the loss partials of a fused step).
+struct NetBackward {
+    const float* acts[MLP_MAX_LAYERS]; const float* zs[MLP_MAX_LAYERS]; const float* const* W; float* const* dW; float* const* db;
+    const float* dout; TrainWs ws; ReduceJob loss; bool has_loss;
+};
+
+// Backward through all layers of one net, or of two nets of equal sizes (the flow and the score net of the SF2M step): layer
+// by layer the same launches, for two nets each on twice the grid, with tile, split and pairing decided per net.
 // Launches: per layer ONE launch for wgrad (bias column sums ride along) + dgrad (round 6; two where the shapes do not allow
-// the pair), then ONE reduction of every split-K partial (weights and biases of all layers).  The workspace's pool holds
-// four layers' partials at 32 splits: a deeper net that fills it gets one more reduction per refill (see the loop).
+// the pair), then ONE reduction of every split-K partial (weights and biases of all layers and nets, and their loss
+// partials).  A workspace's pool holds four layers' partials at 32 splits: deeper nets that fill it get one more reduction
+// per refill (see the loop).
 // tvec != NULL: the network input is [acts[0] (B x dims[0] - 1, pitch dims[0] - 1), tvec (B)] — the time column is
-// kept apart (the fused regression step never concatenates it); its weight gradient is the weighted column sum.
-// extra: one more job for the final reduction (the loss partials of the fused step), or NULL.
-static int mlp_backward_impl(const float* const* acts, const float* const* preact, const float* const* W,
-                             const int* dims, int n_layers, int B, const float* dout, float* const* dW,
-                             float* const* db, float* dx, void* ws, hipStream_t s, const float* tvec,
-                             const ReduceJob* extra, void* const* layer_done = nullptr) {
-    int maxw = 0; size_t maxp = 0;
-    for (int l = 0; l <= n_layers; ++l) maxw = dims[l] > maxw ? dims[l] : maxw;
-    for (int l = 0; l < n_layers; ++l) { const size_t p = (size_t)dims[l] * dims[l + 1]; maxp = p > maxp ? p : maxp; }
-    float* gbuf[2] = {(float*)ws, (float*)ws + (size_t)B * maxw};
-    float* pool = gbuf[1] + (size_t)B * maxw;
-    const size_t pool_floats = (size_t)MLP_MAX_SPLITS * (maxp + maxw) * 4;
+// kept apart (the fused steps never concatenate it); its weight gradient is the weighted column sum.
+// nets == 1 only (the SF2M step has neither): dx, if not NULL, receives the input gradient [B, dims[0]]; layer_done, if not
+// NULL, asks for the bucketed form (one reduction per layer, see the loop).
+// The caller bounds n_layers by what ONE ReduceTable holds: MLP_MAX_LAYERS - 1 for one net, SF2M_MAX_LAYERS for two.
+static int mlp_backward_impl(const NetBackward* nb, int nets, const int* dims, int n_layers, int B, hipStream_t s,
+                             const float* tvec, float* dx, void* const* layer_done) {
+    const size_t pool_floats = nb[0].ws.pool_floats;
     size_t used = 0;
     ReduceTable T; T.count = 0;
-    const float* dz = dout;
+    const float* dz[2];
+    for (int q = 0; q < nets; ++q) dz[q] = nb[q].dout;
     for (int l = n_layers - 1; l >= 0; --l) {
         const bool split_t = (l == 0 && tvec != nullptr);
         const int Kfull = dims[l], N = dims[l + 1];
@@ -333,61 +392,53 @@ static int mlp_backward_impl(const float* const* acts, const float* const* preac
         if (used + need > pool_floats) {
             // the pool is full (a fifth layer at S = 32): reduce what has been collected and start it again at offset zero.
             // Stream order puts the reduction in front of the next product, so no slot is rewritten before it is read;
-            // every job keeps its partials and its split order: bit-equal to an unbounded pool.
+            // every job keeps its partials and its split order: bit-equal to an unbounded pool.  (The loss jobs stay in
+            // the final launch.)
             if (T.count) { hipLaunchKernelGGL(reduce_splits_multi, dim3(256, T.count), dim3(256), 0, s, T); T.count = 0; }
             used = 0;
         }
-        float* part = pool + used; used += (size_t)S * np;
-        float* bpart = pool + used; used += (size_t)S * N;
-        float* tpart = nullptr;
-        if (split_t) { tpart = pool + used; used += (size_t)S * N; }
-        // dgrad of the same layer: dz_prev[B,K] = (dz[B,N] . W[N,K]) * selu'(z_prev) — reads dz_l like wgrad and nothing of it:
-        // ONE launch for both when both run on 64 x 64 tiles with 16-byte loads (every hidden layer at C3)
-        float* dprev = (l > 0) ? gbuf[l & 1] : nullptr;
-        int rc = 0;
-        bool paired = false;
-        if (l > 0 && cfm_gemm_pick_tile(N, K, S) == 2 && cfm_gemm_pick_tile(B, K, 1) == 2 &&
-            gemm_vec_ok(dz, N, N) && gemm_vec_ok(acts[l], K, K) && gemm_vec_ok(W[l], K, K) && gemm_vec_ok(dz, N, N)) {
-            int k_chunk_w = (B + S - 1) / S; k_chunk_w = (k_chunk_w + 31) / 32 * 32;
-            const int k_chunk_d = (N + 31) / 32 * 32;
-            const int tnw = (K + 63) / 64, tiles_w = ((N + 63) / 64) * tnw;
-            const int tnd = (K + 63) / 64, tiles_d = ((B + 63) / 64) * tnd;
-            const GemmArgs Ga = gemm_args(dz, N, W[l], K, dprev, K, 0, preact[l], B, K, N, k_chunk_d, tnd, nullptr, nullptr, nullptr);
-            const GemmArgs Gw = gemm_args(dz, N, acts[l], K, part, K, np, nullptr, N, K, B, k_chunk_w, tnw, bpart, nullptr, nullptr);
-            hipLaunchKernelGGL(gemm_pair_f32_mfma, dim3(tiles_d + tiles_w * S), dim3(256), 0, s, Ga, tiles_d, Gw, tiles_w, S);
-            rc = cfm_status();
-            paired = true;
-        } else {
-            rc = launch_gemm<true, true, EPI_PLAIN>(dz, N, acts[l], K, part, K, np, nullptr, N, K, B, S, s, bpart,
-                                                    split_t ? tvec : nullptr, tpart);
+        const size_t o_part = used; used += (size_t)S * np;
+        const size_t o_bpart = used; used += (size_t)S * N;
+        const size_t o_tpart = used; if (split_t) used += (size_t)S * N;
+        // dgrad of the same layer: dz_prev[B,K] = (dz[B,N] . W[N,K]) * selu'(z_prev) — reads dz_l like wgrad and nothing of it
+        GemmOps wop[2], dop[2];
+        for (int q = 0; q < nets; ++q) {
+            float* pool = nb[q].ws.pool;
+            wop[q] = GemmOps{dz[q], nb[q].acts[l], pool + o_part, nullptr, pool + o_bpart, split_t ? pool + o_tpart : nullptr};
+            dop[q] = GemmOps{dz[q], nb[q].W[l], l > 0 ? nb[q].ws.gbuf[l & 1] : nullptr, nb[q].zs[l], nullptr, nullptr};
         }
+        const bool paired = l > 0 && launch_gemm_pair(dop, wop, nets, B, K, N, S, s);
+        int rc = paired ? cfm_status()
+                        : launch_gemm<true, true, EPI_PLAIN>(wop, nets, N, K, K, np, N, K, B, S, s, split_t ? tvec : nullptr);
         if (rc) return rc;
-        T.job[T.count++] = ReduceJob{part, dW[l], np, np, S, split_t ? K : 0, Kfull, 0};
-        T.job[T.count++] = ReduceJob{bpart, db[l], (unsigned long long)N, (unsigned long long)N, S, 0, 0, 0};
-        if (split_t) T.job[T.count++] = ReduceJob{tpart, dW[l] + K, (unsigned long long)N, (unsigned long long)N, S, 1, Kfull, 0};
+        for (int q = 0; q < nets; ++q) {
+            T.job[T.count++] = ReduceJob{wop[q].C, nb[q].dW[l], np, np, S, split_t ? K : 0, Kfull, 0};
+            T.job[T.count++] = ReduceJob{wop[q].colsum, nb[q].db[l], (unsigned long long)N, (unsigned long long)N, S, 0, 0, 0};
+            if (split_t) T.job[T.count++] = ReduceJob{wop[q].tsum, nb[q].dW[l] + K, (unsigned long long)N, (unsigned long long)N, S, 1, Kfull, 0};
+        }
         if (layer_done) {
             // bucketed form (data parallel): this layer's gradients are final as soon as its own reduction has run —
             // the caller's communication stream waits for layer_done[l] and all-reduces them while the remaining
             // layers' products run.  Same jobs, same order of the partial sums: bit-equal to the one-reduction form.
-            if (l == 0 && extra) T.job[T.count++] = *extra;
+            if (l == 0 && nb[0].has_loss) T.job[T.count++] = nb[0].loss;
             hipLaunchKernelGGL(reduce_splits_multi, dim3(256, T.count), dim3(256), 0, s, T);
             T.count = 0; used = 0;      // (the next layer's partials go where these were: its product runs behind this reduction)
             if (layer_done[l]) { const hipError_t e = hipEventRecord((hipEvent_t)layer_done[l], s); if (e != hipSuccess) return (int)e; }
         }
-        // dgrad: dz_prev[B,K] = (dz[B,N] . W[N,K]) * selu'(z_prev)
         if (l > 0) {
             if (!paired) {
-                rc = launch_gemm<false, true, EPI_SELU_GRAD>(dz, N, W[l], K, dprev, K, 0, preact[l], B, K, N, 1, s);
+                rc = launch_gemm<false, true, EPI_SELU_GRAD>(dop, nets, N, K, K, 0, B, K, N, 1, s);
                 if (rc) return rc;
             }
-            dz = dprev;
+            for (int q = 0; q < nets; ++q) dz[q] = dop[q].C;
         } else if (dx) {
-            rc = launch_gemm<false, true, EPI_PLAIN>(dz, N, W[0], Kfull, dx, Kfull, 0, nullptr, B, Kfull, N, 1, s);
+            const GemmOps xop = {dz[0], nb[0].W[0], dx, nullptr, nullptr, nullptr};
+            rc = launch_gemm<false, true, EPI_PLAIN, 1>(&xop, 1, N, Kfull, Kfull, 0, B, Kfull, N, 1, s);
             if (rc) return rc;
         }
     }
     if (layer_done) return cfm_status();
-    if (extra) T.job[T.count++] = *extra;
+    for (int q = 0; q < nets; ++q) if (nb[q].has_loss) T.job[T.count++] = nb[q].loss;
     hipLaunchKernelGGL(reduce_splits_multi, dim3(256, T.count), dim3(256), 0, s, T);
     return cfm_status();
 }
@@ -398,7 +449,13 @@ extern "C" int cfm_mlp_backward_f32(const float* const* acts, const float* const
     if (!acts || !W || !dims || !dout || !dW || !db || n_layers < 1 || n_layers > MLP_MAX_LAYERS - 1 || B < 0 || !ws) return CFM_EINVAL;
     if (n_layers > 1 && !preact) return CFM_EINVAL;
     if (B == 0) return 0;
-    return mlp_backward_impl(acts, preact, W, dims, n_layers, B, dout, dW, db, dx, ws, (hipStream_t)stream, nullptr, nullptr);
+    int maxw; size_t maxp;
+    mlp_widest(dims, n_layers, &maxw, &maxp);
+    NetBackward nb;
+    nb.acts[0] = acts[0]; nb.zs[0] = nullptr;
+    for (int l = 1; l < n_layers; ++l) { nb.acts[l] = acts[l]; nb.zs[l] = preact[l]; }
+    nb.W = W; nb.dW = dW; nb.db = db; nb.dout = dout; nb.ws = carve_train_ws(ws, B, maxw, maxp); nb.has_loss = false;
+    return mlp_backward_impl(&nb, 1, dims, n_layers, B, (hipStream_t)stream, nullptr, dx, nullptr);
 }
 
 // ------------------------------------------------------- fused regression step ----
@@ -426,6 +483,50 @@ __global__ __launch_bounds__(256) void mse_grad(float* __restrict__ v, const flo
     if (threadIdx.x == 0) partial[blockIdx.x] = ((sh[0] + sh[1]) + (sh[2] + sh[3])) * inv_n;
 }
 
+// What the training forward needs of one net: parameters, the buffers that keep h_l and z_l (hidden[l], preact[l]: [B, dims[l + 1]],
+// l = 0 .. n - 2), the output g [B, dims[n]], and its loss: target, row weights (or NULL), seed scale, loss partials.
+struct NetForward {
+    const float* const* W; const float* const* b; float* const* hidden; float* const* preact; float* g;
+    const float* target; const float* lam; float scale; float* lpart;
+};
+
+// one loss partial per workgroup of the last layer (an upper bound: the 128 x 128 form has fewer)
+static bool loss_partials_fit(int B, int N) { return (long)((B + 63) / 64) * ((N + 63) / 64) <= MLP_LOSS_PARTIALS; }
+
+// Training forward of one net or of two nets of equal sizes on the same input [xt, t], keeping h_l and z_l.  fuse_loss: the
+// LAST layer's epilogue forms each net's loss gradient seed in place of its output and one loss partial per workgroup,
+// *n_lpart of them (round 6: the MSE was a launch of its own and a second pass over v); otherwise g receives the output.
+static int mlp_train_forward(const NetForward* nf, int nets, const float* xt, const float* t, const int* dims, int n_layers, int B,
+                             float inv_n, bool fuse_loss, hipStream_t s, int* n_lpart) {
+    const float* cur[2] = {xt, xt};
+    for (int l = 0; l < n_layers; ++l) {
+        const bool last = (l == n_layers - 1);
+        const bool first_t = (l == 0 && t != nullptr);
+        const int K = first_t ? dims[0] - 1 : dims[l];
+        MlpNetLayer net[2];
+        for (int q = 0; q < nets; ++q) {
+            float* dst = last ? nf[q].g : nf[q].hidden[l];
+            net[q] = MlpNetLayer{cur[q], nf[q].W[l], nf[q].b[l], dst, last ? nullptr : nf[q].preact[l], nullptr, nullptr, 0.f, nullptr};
+            if (last && fuse_loss) { net[q].target = nf[q].target; net[q].lam = nf[q].lam; net[q].scale = nf[q].scale; net[q].partial = nf[q].lpart; }
+            cur[q] = dst;
+        }
+        const int rc = cfm_mlp_launch_layer(net, nets, K, dims[l], first_t ? t : nullptr, first_t ? 1 : 0, first_t ? K : -1, B, K,
+                                            dims[l + 1], !last, inv_n, s, (last && fuse_loss) ? n_lpart : nullptr);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+// the backward's view of a net the training forward has run: input, saved activations, seed, and its loss job
+static void net_backward_of(NetBackward* nb, const NetForward& nf, const float* xt, int n_layers, float* const* dW, float* const* db,
+                            const TrainWs& ws, float* loss, int n_lpart) {
+    nb->acts[0] = xt; nb->zs[0] = nullptr;
+    for (int l = 1; l < n_layers; ++l) { nb->acts[l] = nf.hidden[l - 1]; nb->zs[l] = nf.preact[l - 1]; }
+    nb->W = nf.W; nb->dW = dW; nb->db = db; nb->dout = nf.g; nb->ws = ws;
+    nb->loss = ReduceJob{nf.lpart, loss, 1ull, 1ull, n_lpart, 0, 0, 1};      // (pad = 1: one number out of n_lpart partials)
+    nb->has_loss = true;
+}
+
 // One regression step of the vector field on a coupled batch, everything but the optimizer update:
 //     v = net([xt, t]);  loss = mean((v - ut)^2);  dW, db = d loss / d parameters
 // — what `vt = model(torch.cat([xt, t[:, None]], -1)); loss = torch.mean((vt - ut) ** 2); loss.backward()` does in the
@@ -444,177 +545,30 @@ extern "C" int cfm_mlp_regression_step_f32(const float* xt, const float* t, cons
         return CFM_EINVAL;
     if (n_layers > 1 && (!hidden || !preact)) return CFM_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    const int has_t = t != nullptr;
-    if (has_t && dims[0] < 2) return CFM_EINVAL;
-    int maxw = 0; size_t maxp = 0;
-    for (int l = 0; l <= n_layers; ++l) maxw = dims[l] > maxw ? dims[l] : maxw;
-    for (int l = 0; l < n_layers; ++l) { const size_t p = (size_t)dims[l] * dims[l + 1]; maxp = p > maxp ? p : maxp; }
-    float* lpart = (float*)((char*)ws + cfm_mlp_train_ws_bytes_internal(B, maxw, (int)maxp) - 4 * MLP_LOSS_PARTIALS);
+    if (t && dims[0] < 2) return CFM_EINVAL;
+    int maxw; size_t maxp;
+    mlp_widest(dims, n_layers, &maxw, &maxp);
+    const TrainWs tw = carve_train_ws(ws, B, maxw, maxp);
     const size_t nel = (size_t)B * dims[n_layers];
     const float inv_n = 1.0f / (float)nel;
-    // forward, keeping h_l and z_l; the LAST layer's epilogue forms the loss gradient seed g = (2 / n) (v - u) and one
-    // loss partial per workgroup (round 6: the MSE was a launch of its own and a second pass over v)
-    const float* cur = xt;
+    const NetForward nf = {W, b, hidden, preact, g, ut, nullptr, 2.0f * inv_n, tw.lpart};
+    // a last layer of more workgroups than loss partials: the loss is a launch of its own behind the forward
+    const bool fused = loss_partials_fit(B, dims[n_layers]);
     int n_lpart = MSE_BLOCKS;
-    bool mse_fused = false;
-    for (int l = 0; l < n_layers; ++l) {
-        const bool last = (l == n_layers - 1);
-        const bool first_t = (l == 0 && has_t);
-        const int K = first_t ? dims[0] - 1 : dims[l];
-        float* dst = last ? g : hidden[l];
-        int rc;
-        const long last_wgs = (long)((B + 63) / 64) * ((dims[l + 1] + 63) / 64);      // (an upper bound: the 128 x 128 form has fewer)
-        if (last && last_wgs <= MLP_LOSS_PARTIALS) {
-            rc = cfm_mlp_launch_layer_mse(cur, K, W[l], dims[l], b[l], first_t ? t : nullptr, first_t ? 1 : 0, first_t ? K : -1,
-                                          B, K, dims[l + 1], dst, s, ut, 2.0f * inv_n, inv_n, lpart, &n_lpart);
-            mse_fused = true;
-        } else {
-            rc = cfm_mlp_launch_layer(cur, K, W[l], dims[l], b[l], first_t ? t : nullptr, first_t ? 1 : 0, first_t ? K : -1,
-                                      B, K, dims[l + 1], dst, !last, s, last ? nullptr : preact[l]);
-        }
-        if (rc) return rc;
-        cur = dst;
-    }
-    if (!mse_fused) {
-        hipLaunchKernelGGL(mse_grad, dim3(MSE_BLOCKS), dim3(256), 0, s, g, ut, nel, 2.0f * inv_n, inv_n, lpart);
-        const int rc = cfm_status();
+    int rc = mlp_train_forward(&nf, 1, xt, t, dims, n_layers, B, inv_n, fused, s, &n_lpart);
+    if (rc) return rc;
+    if (!fused) {
+        hipLaunchKernelGGL(mse_grad, dim3(MSE_BLOCKS), dim3(256), 0, s, g, ut, nel, 2.0f * inv_n, inv_n, tw.lpart);
+        rc = cfm_status();
         if (rc) return rc;
     }
     // backward (+ the loss partials in its final reduction)
-    const float* acts[MLP_MAX_LAYERS]; const float* zs[MLP_MAX_LAYERS];
-    acts[0] = xt; zs[0] = nullptr;
-    for (int l = 1; l < n_layers; ++l) { acts[l] = hidden[l - 1]; zs[l] = preact[l - 1]; }
-    const ReduceJob lj = ReduceJob{lpart, loss, 1ull, 1ull, n_lpart, 0, 0, 1};      // (pad = 1: one number out of n_lpart partials)
-    return mlp_backward_impl(acts, zs, W, dims, n_layers, B, g, dW, db, nullptr, ws, s, has_t ? t : nullptr, &lj, layer_done);
+    NetBackward nb;
+    net_backward_of(&nb, nf, xt, n_layers, dW, db, tw, loss, n_lpart);
+    return mlp_backward_impl(&nb, 1, dims, n_layers, B, s, t, nullptr, layer_done);
 }
 
 // ------------------------------------------------------------ the SF2M step: two nets ----
-// one product of each of two nets: per-net operands, shared sizes
-struct GemmOps { const float* A; const float* Bm; float* C; const float* H; float* colsum; float* tsum; };
-
-template <bool AK, bool BK_, int EPI, bool VA, bool VB>
-static void launch_gemm_two_t(int tile, const GemmOps* op, unsigned nets, int lda, int ldb, int ldc, size_t split_stride, int M, int N,
-                              int Kc, int k_chunk, int S, hipStream_t s, const float* tvec) {
-    const int bm = tile == 0 ? 128 : 64;
-    const int tm = (M + bm - 1) / bm, tn = (N + bm - 1) / bm;
-    GemmArgs2 T;
-    for (unsigned q = 0; q < 2; ++q) {
-        const GemmOps& o = op[q < nets ? q : 0];
-        T.net[q] = gemm_args(o.A, lda, o.Bm, ldb, o.C, ldc, split_stride, o.H, M, N, Kc, k_chunk, tn, o.colsum, tvec, o.tsum);
-    }
-    if (tile == 0)
-        hipLaunchKernelGGL((gemm_f32_mfma_two<128, 128, 16, AK, BK_, EPI, VA, VB>), dim3(nets * tm * tn, S), dim3(256), 0, s, T, (unsigned)(tm * tn));
-    else
-        hipLaunchKernelGGL((gemm_f32_mfma_two<64, 64, 32, AK, BK_, EPI, VA, VB>), dim3(nets * tm * tn, S), dim3(256), 0, s, T, (unsigned)(tm * tn));
-}
-
-// launch_gemm for two nets: tile and split from the sizes (equal for both), 16-byte loads per net from its own operands;
-// equal choices share one launch, unequal ones (an operand of one net off the 16-byte grid) take one launch each
-template <bool AK, bool BK_, int EPI>
-static int launch_gemm_two(const GemmOps* op, int lda, int ldb, int ldc, size_t split_stride, int M, int N, int Kc, int S,
-                           hipStream_t s, const float* tvec = nullptr) {
-    int k_chunk = (Kc + S - 1) / S;
-    k_chunk = (k_chunk + 31) / 32 * 32;
-    const int tile = cfm_gemm_pick_tile(M, N, S);
-    bool va[2], vb[2];
-    for (int q = 0; q < 2; ++q) { va[q] = gemm_vec_ok(op[q].A, lda, AK ? M : Kc); vb[q] = gemm_vec_ok(op[q].Bm, ldb, BK_ ? N : Kc); }
-    const bool same = va[0] == va[1] && vb[0] == vb[1];
-    for (int q = 0; q < (same ? 1 : 2); ++q) {
-        const GemmOps* o = op + q; const unsigned nets = same ? 2u : 1u;
-#define CFM_LG(VA_, VB_) launch_gemm_two_t<AK, BK_, EPI, VA_, VB_>(tile, o, nets, lda, ldb, ldc, split_stride, M, N, Kc, k_chunk, S, s, tvec)
-        if (va[q]) { if (vb[q]) CFM_LG(true, true); else CFM_LG(true, false); }
-        else       { if (vb[q]) CFM_LG(false, true); else CFM_LG(false, false); }
-#undef CFM_LG
-        const int rc = cfm_status();
-        if (rc) return rc;
-    }
-    return 0;
-}
-
-// what mlp_backward_impl needs of one net
-struct NetBackward {
-    const float* acts[MLP_MAX_LAYERS]; const float* zs[MLP_MAX_LAYERS]; const float* const* W; float* const* dW; float* const* db;
-    const float* dout; void* ws; ReduceJob loss;
-};
-
-// mlp_backward_impl for two nets of equal sizes: layer by layer the same launches, each on twice the grid (tile, split
-// and pairing decided per net exactly as above), and ONE reduction of both nets' partials and loss partials (one more
-// per refill of the pool for nets deeper than four layers at 32 splits, as above).
-static int mlp_backward_two_impl(const NetBackward* nb, const int* dims, int n_layers, int B, hipStream_t s, const float* tvec) {
-    int maxw = 0; size_t maxp = 0;
-    for (int l = 0; l <= n_layers; ++l) maxw = dims[l] > maxw ? dims[l] : maxw;
-    for (int l = 0; l < n_layers; ++l) { const size_t p = (size_t)dims[l] * dims[l + 1]; maxp = p > maxp ? p : maxp; }
-    float* gbuf[2][2]; float* pool[2];
-    for (int q = 0; q < 2; ++q) {
-        gbuf[q][0] = (float*)nb[q].ws; gbuf[q][1] = gbuf[q][0] + (size_t)B * maxw;
-        pool[q] = gbuf[q][1] + (size_t)B * maxw;
-    }
-    const size_t pool_floats = (size_t)MLP_MAX_SPLITS * (maxp + maxw) * 4;
-    size_t used = 0;
-    ReduceTable T; T.count = 0;
-    const float* dz[2] = {nb[0].dout, nb[1].dout};
-    for (int l = n_layers - 1; l >= 0; --l) {
-        const bool split_t = (l == 0 && tvec != nullptr);
-        const int Kfull = dims[l], N = dims[l + 1];
-        const int K = split_t ? Kfull - 1 : Kfull;
-        const int S = wgrad_splits(N, K, B);
-        const size_t np = (size_t)N * K;
-        const size_t need = (size_t)S * (np + (size_t)N * (split_t ? 2 : 1));
-        if (need > pool_floats) return CFM_EINVAL;      // (cannot happen with the documented workspace: see mlp_backward_impl)
-        if (used + need > pool_floats) {
-            // both pools are full: reduce both nets' jobs so far and start again at offset zero (see mlp_backward_impl);
-            // the loss jobs stay in the final launch
-            if (T.count) { hipLaunchKernelGGL(reduce_splits_multi, dim3(256, T.count), dim3(256), 0, s, T); T.count = 0; }
-            used = 0;
-        }
-        const size_t o_part = used; used += (size_t)S * np;
-        const size_t o_bpart = used; used += (size_t)S * N;
-        const size_t o_tpart = used; if (split_t) used += (size_t)S * N;
-        bool pair_ok[2];
-        GemmOps wop[2], dop[2];
-        for (int q = 0; q < 2; ++q) {
-            float* dprev = (l > 0) ? gbuf[q][l & 1] : nullptr;
-            wop[q] = GemmOps{dz[q], nb[q].acts[l], pool[q] + o_part, nullptr, pool[q] + o_bpart, split_t ? pool[q] + o_tpart : nullptr};
-            dop[q] = GemmOps{dz[q], nb[q].W[l], dprev, nb[q].zs[l], nullptr, nullptr};
-            pair_ok[q] = l > 0 && cfm_gemm_pick_tile(N, K, S) == 2 && cfm_gemm_pick_tile(B, K, 1) == 2 &&
-                         gemm_vec_ok(dz[q], N, N) && gemm_vec_ok(nb[q].acts[l], K, K) && gemm_vec_ok(nb[q].W[l], K, K);
-        }
-        int rc = 0;
-        const bool paired = pair_ok[0] && pair_ok[1];
-        if (paired) {
-            int k_chunk_w = (B + S - 1) / S; k_chunk_w = (k_chunk_w + 31) / 32 * 32;
-            const int k_chunk_d = (N + 31) / 32 * 32;
-            const int tnw = (K + 63) / 64, tiles_w = ((N + 63) / 64) * tnw;
-            const int tnd = (K + 63) / 64, tiles_d = ((B + 63) / 64) * tnd;
-            GemmArgs2 Ga, Gw;
-            for (int q = 0; q < 2; ++q) {
-                Ga.net[q] = gemm_args(dz[q], N, nb[q].W[l], K, dop[q].C, K, 0, nb[q].zs[l], B, K, N, k_chunk_d, tnd, nullptr, nullptr, nullptr);
-                Gw.net[q] = gemm_args(dz[q], N, nb[q].acts[l], K, wop[q].C, K, np, nullptr, N, K, B, k_chunk_w, tnw, wop[q].colsum, nullptr, nullptr);
-            }
-            hipLaunchKernelGGL(gemm_pair_f32_mfma_two, dim3(2 * (tiles_d + tiles_w * S)), dim3(256), 0, s, Ga, tiles_d, Gw, tiles_w, S);
-            rc = cfm_status();
-        } else {
-            rc = launch_gemm_two<true, true, EPI_PLAIN>(wop, N, K, K, np, N, K, B, S, s, split_t ? tvec : nullptr);
-        }
-        if (rc) return rc;
-        for (int q = 0; q < 2; ++q) {
-            T.job[T.count++] = ReduceJob{wop[q].C, nb[q].dW[l], np, np, S, split_t ? K : 0, Kfull, 0};
-            T.job[T.count++] = ReduceJob{wop[q].colsum, nb[q].db[l], (unsigned long long)N, (unsigned long long)N, S, 0, 0, 0};
-            if (split_t) T.job[T.count++] = ReduceJob{wop[q].tsum, nb[q].dW[l] + K, (unsigned long long)N, (unsigned long long)N, S, 1, Kfull, 0};
-        }
-        if (l > 0) {
-            if (!paired) {
-                rc = launch_gemm_two<false, true, EPI_SELU_GRAD>(dop, N, K, K, 0, B, K, N, 1, s);
-                if (rc) return rc;
-            }
-            dz[0] = dop[0].C; dz[1] = dop[1].C;
-        }
-    }
-    T.job[T.count++] = nb[0].loss; T.job[T.count++] = nb[1].loss;
-    hipLaunchKernelGGL(reduce_splits_multi, dim3(256, T.count), dim3(256), 0, s, T);
-    return cfm_status();
-}
-
 // the deepest pair of nets whose reduction jobs fit ONE ReduceTable: 2 nets x (2 per layer + the time column + the loss)
 #define SF2M_MAX_LAYERS ((2 * MLP_MAX_LAYERS + 2 - 4) / 4)
 
@@ -635,50 +589,27 @@ extern "C" int cfm_mlp_sf2m_step_f32(const float* xt, const float* t, const floa
     if (n_layers > SF2M_MAX_LAYERS) return CFM_EINVAL;      // the one reduction's table is full at two nets of 7 layers
     if (n_layers > 1 && (!hidden || !preact)) return CFM_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    const int has_t = t != nullptr;
-    if (has_t && dims[0] < 2) return CFM_EINVAL;
-    int maxw = 0; size_t maxp = 0;
-    for (int l = 0; l <= n_layers; ++l) maxw = dims[l] > maxw ? dims[l] : maxw;
-    for (int l = 0; l < n_layers; ++l) { const size_t p = (size_t)dims[l] * dims[l + 1]; maxp = p > maxp ? p : maxp; }
+    if (t && dims[0] < 2) return CFM_EINVAL;
     // one loss partial per workgroup of the last layer (this step has no separate loss launch to fall back on)
-    if ((long)((B + 63) / 64) * ((dims[n_layers] + 63) / 64) > MLP_LOSS_PARTIALS) return CFM_EINVAL;
+    if (!loss_partials_fit(B, dims[n_layers])) return CFM_EINVAL;
+    int maxw; size_t maxp;
+    mlp_widest(dims, n_layers, &maxw, &maxp);
     // two CFM_OP_MLP_TRAIN workspaces back to back: the flow net's, then the score net's
-    const size_t ws_one = cfm_mlp_train_ws_bytes_internal(B, maxw, (int)maxp), ws_pitch = cfm_align_up(ws_one, 256);
-    NetBackward nb[2];
-    float* lpart[2];
-    for (int q = 0; q < 2; ++q) {
-        nb[q].ws = (char*)ws + q * ws_pitch;
-        lpart[q] = (float*)((char*)nb[q].ws + ws_one - 4 * MLP_LOSS_PARTIALS);
-        nb[q].W = W + q * n_layers; nb[q].dW = dW + q * n_layers; nb[q].db = db + q * n_layers;
-        nb[q].acts[0] = xt; nb[q].zs[0] = nullptr;
-        for (int l = 1; l < n_layers; ++l) { nb[q].acts[l] = hidden[q * (n_layers - 1) + l - 1]; nb[q].zs[l] = preact[q * (n_layers - 1) + l - 1]; }
-    }
-    nb[0].dout = g_flow; nb[1].dout = g_score;
+    const size_t ws_pitch = cfm_align_up(cfm_mlp_train_ws_bytes_internal(B, maxw, (int)maxp), 256);
     const size_t nel = (size_t)B * dims[n_layers];
     const float inv_n = 1.0f / (float)nel;
-    const float* cur[2] = {xt, xt};
-    int n_lpart = 0;
-    for (int l = 0; l < n_layers; ++l) {
-        const bool last = (l == n_layers - 1);
-        const bool first_t = (l == 0 && has_t);
-        const int K = first_t ? dims[0] - 1 : dims[l];
-        MlpNetLayer net[2];
-        for (int q = 0; q < 2; ++q) {
-            float* dst = last ? (q ? g_score : g_flow) : hidden[q * (n_layers - 1) + l];
-            net[q] = MlpNetLayer{cur[q], W[q * n_layers + l], b[q * n_layers + l], dst, last ? nullptr : preact[q * (n_layers - 1) + l],
-                                 nullptr, nullptr, 0.f, nullptr};
-            if (last) {
-                net[q].target = q ? eps : ut; net[q].lam = q ? lam : nullptr; net[q].partial = lpart[q];
-                net[q].scale = q ? (2.0f * inv_n) * score_weight : 2.0f * inv_n;
-            }
-            cur[q] = dst;
-        }
-        const int rc = cfm_mlp_launch_layer_two(net, K, dims[l], first_t ? t : nullptr, first_t ? K : -1, B, K, dims[l + 1], !last, inv_n, s,
-                                                last ? &n_lpart : nullptr);
-        if (rc) return rc;
+    TrainWs tw[2]; NetForward nf[2];
+    for (int q = 0; q < 2; ++q) {
+        tw[q] = carve_train_ws((char*)ws + q * ws_pitch, B, maxw, maxp);
+        nf[q] = NetForward{W + q * n_layers, b + q * n_layers, hidden + q * (n_layers - 1), preact + q * (n_layers - 1), q ? g_score : g_flow,
+                           q ? eps : ut, q ? lam : nullptr, q ? (2.0f * inv_n) * score_weight : 2.0f * inv_n, tw[q].lpart};
     }
-    for (int q = 0; q < 2; ++q) nb[q].loss = ReduceJob{lpart[q], losses + q, 1ull, 1ull, n_lpart, 0, 0, 1};
-    return mlp_backward_two_impl(nb, dims, n_layers, B, s, has_t ? t : nullptr);
+    int n_lpart = 0;
+    const int rc = mlp_train_forward(nf, 2, xt, t, dims, n_layers, B, inv_n, true, s, &n_lpart);
+    if (rc) return rc;
+    NetBackward nb[2];
+    for (int q = 0; q < 2; ++q) net_backward_of(&nb[q], nf[q], xt, n_layers, dW + q * n_layers, db + q * n_layers, tw[q], losses + q, n_lpart);
+    return mlp_backward_impl(nb, 2, dims, n_layers, B, s, t, nullptr, nullptr);
 }
 
 // ------------------------------------------------------------------- Adam ----

@@ -8,8 +8,10 @@ NaN before the call, so that a split-K partial which the reduction reads and no 
      workgroups must still write zero partials and zero column sums), also through the weighted column sum of a time column
   2. dgrad + wgrad in one launch (gemm_pair_f32_mfma) and the SELU' epilogue: two layers with caller-made pre-activations
      in {+1, -200}, where selu'(z) is exactly SELU_SCALE or exactly 0; selu_grad itself at its edges against float64
-  3. the two-net kernels of cfm_mlp_sf2m_step_f32, also when one net's operands are off the 16-byte grid (one launch per net)
+  3. the two-net kernels of cfm_mlp_sf2m_step_f32, also when one net's operands are off the 16-byte grid (one launch per
+     net, on the one-net kernels)
   4. nets deeper than the split-K pool of the workspace holds at once (it is reduced and reused)
+  5. the regression step's unfused loss (mse_grad behind a last layer of more workgroups than loss partials)
 
 Which kernel a case reaches follows from the launch rules restated in exact_util.py; each case asserts it."""
 import ctypes
@@ -332,11 +334,14 @@ def _lin(x, w, b, t):
 
 # (B, K, N, time) of test_mse_epilogue_is_exact; `off`: which operand sits off the 16-byte grid (None: all aligned).
 # W one float off: plan_layer's VECB differs between the nets (K % 4 == 0 and no time column: the pitch is K), the forward
-# takes one launch per net (mlp_layer_two / mlp_layer_glds_two with nets = 1).  g two floats off (8 bytes: the epilogue's
-# float2 stores stay aligned): gemm_vec_ok(dz) differs, launch_gemm_two runs the weight gradient with same == false.
+# takes one launch per net through the one-net form of launch_layer (mlp_layer_glds where K % 16 == 0, else mlp_layer; the
+# score net's weighted loss layer, for which mlp_layer has no argument, mlp_layer_two on one net's grid: the K = 20 case).
+# g two floats off (8 bytes: the epilogue's float2 stores stay aligned): gemm_vec_ok(dz) differs, launch_gemm runs the
+# weight gradient once per net (gemm_f32_mfma).
 SF2M_CASES = [(64, 48, 64, False, None), (256, 20, 16, True, None), (128, 64, 128, False, None), (1024, 512, 32, True, None),
               (64, 48, 64, False, "score_W"), (128, 64, 128, False, "flow_W"), (256, 20, 16, True, "score_g"),
-              (1024, 512, 32, True, "flow_g"), (128, 64, 128, False, "score_g")]
+              (1024, 512, 32, True, "flow_g"), (128, 64, 128, False, "score_g"), (256, 20, 16, False, "score_W"),
+              (256, 20, 16, False, "flow_W")]
 
 
 @pytest.mark.parametrize("score_weight", [1.0, 0.5])
@@ -347,7 +352,8 @@ def test_sf2m_one_layer_is_exact(dev, B, K, N, timed, off, score_weight):
     (-(2 / n) e and (2 w / n) r lam), both losses (counts over n), every loss partial (an integer over n, one per output
     tile, summing to the count), dW and db of both nets (integers times a power of two).  Forward: mlp_layer_two or
     mlp_layer_glds_two (K % 16 == 0), 64 x 64 tiles; backward: gemm_f32_mfma_two<64, 64, 32, true, true, EPI_PLAIN>, S from
-    wgrad_splits, the time column's weighted sum where timed."""
+    wgrad_splits, the time column's weighted sum where timed.  A net off the 16-byte grid: the one-net kernels, once per net
+    (see SF2M_CASES)."""
     n = B * N
     assert n & (n - 1) == 0
     x, wf, bf, t, vf = _layer_data(B, K, N, "row" if timed else None, seed=B + K + N)
@@ -378,7 +384,7 @@ def test_sf2m_one_layer_is_exact(dev, B, K, N, timed, off, score_weight):
         assert plan_vb[0] != plan_vb[1], "premise: plan_layer differs between the nets"
     if off and off.endswith("_g"):
         gd[which] = _off_grid(gd[which], 2)
-        assert vec_ok(gd[0], N, N) != vec_ok(gd[1], N, N), "premise: launch_gemm_two with same == false"
+        assert vec_ok(gd[0], N, N) != vec_ok(gd[1], N, N), "premise: launch_gemm with unequal flags (one launch per net)"
     dWd, dbd, losses = [_nan((N, Kf), dev) for _ in range(2)], [_nan((N,), dev) for _ in range(2)], _nan((2,), dev)
     one = _ws_bytes(lib, _lib, B, dims)
     assert one % 256 == 0
@@ -398,13 +404,13 @@ def test_sf2m_one_layer_is_exact(dev, B, K, N, timed, off, score_weight):
 
 # (B, K, H, N, time); `off`: None, or the net whose W[1] sits one float and whose hidden / pre-activation buffers sit two
 # floats off the 16-byte grid: plan_layer (VECA of the second layer), the pairing condition and gemm_vec_ok of both
-# backward products then differ between the nets — the split path of cfm_mlp_launch_layer_two and launch_gemm_two
+# backward products then differ between the nets — the one-launch-per-net path of cfm_mlp_launch_layer and launch_gemm
 @pytest.mark.parametrize("B,K,H,N,timed", [(64, 48, 64, 64, False), (256, 20, 64, 16, True), (1024, 512, 64, 32, True)])
 def test_sf2m_two_layers_are_bit_equal_to_two_regression_steps(dev, B, K, H, N, timed):
     """Two layers cannot be exact past the SELU, so the property is the one the header promises: with lam = 1 and
     score_weight = 1 the step's gradients and losses are, net for net, the bits of cfm_mlp_regression_step_f32 on the
     same pointers (the flow net on ut, the score net on -eps) — aligned (gemm_pair_f32_mfma_two, mlp_layer_two /
-    mlp_layer_glds_two), and with either net off the 16-byte grid (one launch per net, unpaired).  The flow net's bits
+    mlp_layer_glds_two), and with either net off the 16-byte grid (one launch per net on the one-net kernels, unpaired).  The flow net's bits
     do not move when the SCORE net goes off the grid."""
     g = torch.Generator().manual_seed(B + K)
     Kf = K + int(timed)
@@ -591,3 +597,53 @@ def test_sf2m_step_of_two_seven_layer_nets_at_a_training_batch(dev):
              for p, q in zip(params, list(f.parameters()) + list(s.parameters()))]
     print(f"two 7-layer nets at B = {B}: losses {devs[0]:.2e} {devs[1]:.2e}, gradients max {max(devs[2:]):.2e}")
     assert max(devs) <= 1e-5, devs
+
+
+# ------------------------------------------------------------------- 5. the regression step's unfused loss ----
+def test_regression_step_unfused_loss_behind_a_tall_last_layer(dev):
+    """A last layer of more 64 x 64 output tiles than the workspace has loss partials (B = 64 * 4097 rows, N = 1): the
+    regression step runs it as a plain layer and forms seed and loss in mse_grad (MSE_BLOCKS = 256 partials), the SF2M step,
+    which has no such launch, answers CFM_EINVAL.  One untimed layer on integer data, ut = v - e with e in {-3 .. 3}:
+      g      bit-equal to fl((v - ut) fl(2 fl(1 / n))): v - ut is an exact integer, the product one rounding — torch's CPU
+             float32 multiply is the reference
+      loss   against the float64 mean of squares within 16 * 2^-24 relative: every term is non-negative, each of the 256
+             partials an exact integer sum below 2^24 (asserted: the sum of ALL squares is) times inv_n, one rounding; the
+             reduction adds at most four per lane and six tree levels
+      dW, db genuine fp32 sums of the seeds: against float64 within B 2^-24 sum |terms|, the bound of db[0] above."""
+    B, K, N = 64 * 4097, 4, 1
+    assert ((B + 63) // 64) * ((N + 63) // 64) > LOSS_PARTIALS, "premise: more output tiles than loss partials"
+    x, w, b, _, v = _layer_data(B, K, N, None, seed=B + K + N)
+    e = _ints(torch.Generator().manual_seed(17), (B, N), -3, 3)
+    ut = v - e
+    n = B * N
+    assert int(ut.abs().max()) < LIMIT and int(v.abs().max()) < LIMIT
+    assert int((e * e).sum()) < LIMIT, "premise: every loss partial is an exact integer below 2^24"
+    scale = np.float32(2) * (np.float32(1) / np.float32(n))                # 2.0f * (1.0f / (float)n)
+    g_ref = (v - ut).float() * torch.tensor(scale, dtype=torch.float32)
+    loss_ref = float((e * e).sum()) / n
+    terms_W = g_ref.double() * x.double()                                  # [B, K]: dW[0, k] = sum_b g[b] x[b, k]
+    terms_b = g_ref.double()
+    _lib, lib = _lib_()
+    dims = [K, N]
+    xd, wd, bd, utd = (q.float().to(dev) for q in (x, w, b, ut))
+    gd, dWd, dbd, loss = _nan((B, N), dev), _nan((N, K), dev), _nan((N,), dev), _nan((1,), dev)
+    one = _ws_bytes(lib, _lib, B, dims)
+    _regression_step(xd, None, utd, [wd], [bd], dims, B, None, None, gd, [dWd], [dbd], loss, _nan_ws(one, dev))
+    assert torch.equal(gd.cpu(), g_ref), _first_diff(gd, g_ref)
+    got_loss = float(loss.cpu().double())
+    print(f"unfused loss: {got_loss!r} against {loss_ref!r}, relative error {abs(got_loss - loss_ref) / loss_ref:.3e}")
+    assert abs(got_loss - loss_ref) <= 16 * 2.0 ** -24 * loss_ref, (got_loss, loss_ref)
+    for name, got, terms in (("dW", dWd.reshape(K), terms_W), ("db", dbd, terms_b)):
+        err = (got.cpu().double() - terms.sum(0)).abs()
+        bound = B * 2.0 ** -24 * terms.abs().sum(0)
+        print(f"{name}: max error {float(err.max()):.3e}, smallest slack {float((bound - err).min()):.3e}")
+        assert bool((err <= bound).all()), (name, float(err.max()), float(bound.min()))
+    # the SF2M step at this shape: refused, nothing launched
+    cd = (ctypes.c_int * 2)(*dims)
+    gs, dW2, db2, losses = _nan((B, N), dev), [_nan((N, K), dev) for _ in range(2)], [_nan((N,), dev) for _ in range(2)], _nan((2,), dev)
+    lam = torch.ones(B, device=dev)
+    rc = lib.cfm_mlp_sf2m_step_f32(_lib.ptr(xd), None, _lib.ptr(utd), _lib.ptr(utd), _lib.ptr(lam), _arr([wd, wd]), _arr([bd, bd]), None, None,
+                                   _arr(dW2), _arr(db2), cd, 1, B, _lib.ptr(gd), _lib.ptr(gs), _lib.ptr(losses), 1.0, _lib.ptr(_nan_ws(2 * one, dev)),
+                                   _lib.stream_ptr())
+    torch.cuda.synchronize()
+    assert rc == -1, ("CFM_EINVAL", rc)
