@@ -25,7 +25,9 @@
 //              fallback of a failed list certificate, and the A/B reference (cfm_assign_set_async(0, ...)).
 //   asg_step   every chip-wide step   UMIN0, INITRED, AUCTION, ARR, CONVERT, UMIN, COLRED, ROOTMIN,
 //                                     SAP, MS_FINISH, CERT       (125 VGPRs, <= 48 KiB LDS at n = 4096)
-//   asg_build  candidate lists        BUILD            (n <= 4096; 8 waves, 128 KiB of row strips)
+//   asg_build  candidate lists        BUILD            (n <= 4096; 8 waves, 128 VGPRs, no scratch: four waves per SIMD.  n a multiple
+//                                                       of 1024: 8 n bytes of prices + 2 KiB of LDS, two workgroups per CU;
+//                                                       other n: up to 128 KiB of row strips, one)
 //   asg_solve  one-workgroup list solver   SOLVER      (n <= 4096; 152 KiB of solver state: the forest phases run here)
 //
 //   init     Jonker-Volgenant row + column reduction: u_i = min_j c_ij,
@@ -279,6 +281,7 @@ struct AsgWs {
     // candidate lists (n <= SP_NMAX): SP_K columns / costs per row, bound of the dropped ones
     uint2* cl;        // {column, fp32 cost bits}
     double* cT;
+    double* pb;       // the prices the lists were built from (the list solver moves p afterwards): cfm_assign_debug_lists
 };
 
 // S[c] without dynamic indexing of the by-value kernel argument (which would push the whole
@@ -303,6 +306,7 @@ __device__ __forceinline__ AsgWs asg_shift(const AsgWs& w0, size_t off) {
     ASG_SH(S[0].col); ASG_SH(S[0].row); ASG_SH(S[0].base); ASG_SH(S[0].rj); ASG_SH(S[0].root);
     ASG_SH(S[1].col); ASG_SH(S[1].row); ASG_SH(S[1].base); ASG_SH(S[1].rj); ASG_SH(S[1].root);
     w.cl = w0.cl ? reinterpret_cast<uint2*>(reinterpret_cast<char*>(w0.cl) + off) : nullptr;
+    w.pb = w0.pb ? reinterpret_cast<double*>(reinterpret_cast<char*>(w0.pb) + off) : nullptr;
 #undef ASG_SH
     return w;
 }
@@ -314,7 +318,7 @@ __device__ __forceinline__ AsgWs asg_shift(const AsgWs& w0, size_t off) {
 
 static inline size_t asg_ws_bytes(int n) {
     size_t N = ((size_t)n + 3) & ~(size_t)3;     // every array starts 16-byte aligned
-    size_t lists = (n <= 4096) ? N * 64 * 8 + 8 * N : 0;
+    size_t lists = (n <= 4096) ? N * 64 * 8 + 8 * N + 8 * N : 0;
     return 512 + 2048 + 512 + 8 * N * (4 + 4) + 4 * N * (10 + 6) + 64 + 16 + 16 * N * MS_YMAX + lists + 256;
 }
 
@@ -345,8 +349,8 @@ static inline AsgWs asg_carve(void* ws, int n) {
     w.part_d = (double*)q; q += 8 * N * MS_YMAX;
     w.part_i = (int*)q; q += 4 * N * MS_YMAX;
     w.part_r = (int*)q; q += 4 * N * MS_YMAX;
-    w.cT = (double*)q; w.cl = nullptr;
-    if (n <= 4096) { q += 8 * N; w.cl = (uint2*)q; q += 8 * N * 64; }
+    w.cT = (double*)q; w.cl = nullptr; w.pb = nullptr;
+    if (n <= 4096) { q += 8 * N; w.cl = (uint2*)q; q += 8 * N * 64; w.pb = (double*)q; q += 8 * N; }
     return w;
 }
 
@@ -1821,7 +1825,7 @@ __global__ __launch_bounds__(WT) void asg_auction(AsgWs w0, int n_host, size_t s
 }
 
 // ---------------------------------------------------------------- build ------
-__global__ __launch_bounds__(SP_BUILD_WAVES * 64) void asg_build(AsgWs w0, int n_host, size_t stride) {
+__global__ __launch_bounds__(SP_BUILD_WAVES * 64, 4) void asg_build(AsgWs w0, int n_host, size_t stride) {
     extern __shared__ __attribute__((aligned(16))) char build_lds[];
     const AsgWs w = asg_shift(w0, stride * blockIdx.y);
     __shared__ int sh_flag[4];

@@ -126,6 +126,17 @@ static std::atomic<int> g_fallback_count{0}, g_fallback_error{0};
 static void asg_fallback_error(int err) { g_fallback_error.store(err, std::memory_order_relaxed); }
 extern "C" void cfm_assign_debug_fallback(int* out2) { out2[0] = g_fallback_count.load(); out2[1] = g_fallback_error.load(); }
 extern "C" void cfm_assign_debug_small(int* out16) { for (int q = 0; q < 16; ++q) out16[q] = g_thr.small_last[q]; }
+// Test hook: the candidate lists of the last solve on `ws` that built any (n <= SP_NMAX; problem b of a batch workspace,
+// b = 0 for a single solve) — cl_out: n x SP_K {column, fp32 cost bits}, cT_out: n bounds, p_out: the n prices the build
+// read.  Host buffers; blocking.  The caller tells a solve that never reached the build by clearing the workspace first.
+extern "C" int cfm_assign_debug_lists(const void* ws, int n, int b, void* cl_out, double* cT_out, double* p_out) {
+    if (!ws || n < 2 || n > SP_NMAX || b < 0 || b >= ASG_BATCH_MAX || !cl_out || !cT_out || !p_out) return CFM_EINVAL;
+    const AsgWs w = asg_carve((char*)const_cast<void*>(ws) + (size_t)b * asg_batch_stride(n), n);
+    int rc = cfm_hip(hipMemcpy(cl_out, w.cl, (size_t)n * SP_K * sizeof(uint2), hipMemcpyDeviceToHost));
+    if (!rc) rc = cfm_hip(hipMemcpy(cT_out, w.cT, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    if (!rc) rc = cfm_hip(hipMemcpy(p_out, w.pb, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    return rc;
+}
 // dynamic LDS above the 64 KiB default needs the attribute.  Bit 0: asg_step / asg_auction, bit 1: the list build + solver.
 static int asg_raise_lds() {
     return cfm_once_per_device([] {
@@ -229,6 +240,13 @@ static int asg_size(AsgLaunch& L, int n, int nb, void* ws, size_t stride, hipStr
     if (wide_blocks > 512) wide_blocks = 512;
     if (P.wide_blocks_cap > 0 && wide_blocks > P.wide_blocks_cap) wide_blocks = P.wide_blocks_cap;
     L.blocks_build = wide_blocks < (n + 63) / 64 ? (n + 63) / 64 : wide_blocks;     // the list build streams the matrix once: its own grid
+    if (sp_build_fast(n)) {
+        // its fast path runs four waves per SIMD = TWO workgroups per CU, each staging the prices once: two per CU over
+        // the whole batch, between 8 rows (the grid the slow path takes) and 1 row per wave
+        L.blocks_build = 2 * cfm_device_cus() / nb;
+        if (L.blocks_build < n / (8 * SP_BUILD_WAVES)) L.blocks_build = n / (8 * SP_BUILD_WAVES);
+        if (L.blocks_build > n / SP_BUILD_WAVES) L.blocks_build = n / SP_BUILD_WAVES;
+    }
     // a batch shares the chip: ASG_BATCH_WGS workgroups in all (every workgroup of a bid round stages the prices whether
     // its rows bid or not; measured at n = 4096: 8 problems 9.1 ms with 256 workgroups each, 6.5 ms with 64); the rounds
     // then take the queue form (wide_bid_queue)

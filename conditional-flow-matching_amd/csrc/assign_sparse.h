@@ -40,10 +40,11 @@
 #define SP_CAP 64          // list entries per batch (16 waves x 4 entries kept in registers)
 #define SP_SEED_HOPS 96    // longest walk to the root when the surviving trees of a phase are seeded into the next one
 
-// dynamic LDS of the two candidate-list kernels: the list builder's strips (one fp32 row per building
-// wave) and the solver's state (34 B per column)
+// dynamic LDS of the two candidate-list kernels: the list builder's (fast path: the prices + 64 column slots per
+// building wave; slow path: one fp32 row strip per building wave) and the solver's state (37 B per column)
+__host__ __device__ static inline bool sp_build_fast(int n) { return (n & 1023) == 0 && n > SP_K; }      // n <= SP_NMAX: at most 16 float4 per lane
 static inline size_t sp_build_lds_bytes(int n) {
-    if ((n & 1023) == 0 && n > 64) return 64;              // (the fast path of wide_build keeps the strip in registers)
+    if (sp_build_fast(n)) return (size_t)n * sizeof(double) + (size_t)SP_BUILD_WAVES * SP_K * sizeof(int);
     return (size_t)SP_BUILD_WAVES * (size_t)((n + 63) / 64) * 64 * sizeof(float) + 64;
 }
 static inline size_t sp_solver_lds_bytes(int n) { return (size_t)((n + 15) & ~15) * 37 + 4096; }
@@ -123,137 +124,161 @@ __device__ __forceinline__ int sp_count(const float* __restrict__ r, int nt, flo
     return wave_sum_i(c);
 }
 
-// One wave per row.  Lane l owns columns l, 64 + l, ...; r[t] = fl32((c + p) - rowmin) >= 0
-// lives in the wave's LDS strip (lane-major: conflict free).  A threshold tau with
-// count(r < tau) in [32, 64] is found by bisection; members are r < tau, and every
-// non-member satisfies (c + p) >= rowmin + tau * (1 - 2^-22) =: T.
+// The rule, for one row (one wave): r_k = fl32((c_k + p_k) - rowmin) >= 0; a threshold tau with count(r < tau) in
+// [32, 64] is found by bisection between 0 and the successor of hi = max over the lanes of the lane's smallest r
+// (count(r <= hi) >= 64); members are r < tau, and every non-member satisfies (c + p) >= rowmin + tau * (1 - 2^-22) =: T.
+// `count(t)` = the columns of the row with r < t, uniform over the wave.
+template <class Count>
+__device__ __forceinline__ float sp_tau(float lmin, Count count) {
+    const float hi = wave_max_f(lmin);
+    const float t1 = __uint_as_float(__float_as_uint(hi) + 1u);
+    if (count(t1) <= SP_K) return t1;
+    float lo = 0.f, hh = t1; int clo = 0;
+    for (int it = 0; it < 48 && clo < SP_K / 2; ++it) {
+        const float mid = 0.5f * (lo + hh);
+        if (!(mid > lo && mid < hh)) break;
+        const int cm = count(mid);
+        if (cm <= SP_K) { lo = mid; clo = cm; } else hh = mid;
+    }
+    return lo;
+}
+
+// Fast path (n a multiple of 1024, <= 4096).  A lane owns the columns 256 j + 4 lane + e of the row, as slot t = 4 j + e
+// of a strip of n / 64 REGISTERS (one instance of the code per size: 1024, 2048, 3072, 4096).
+//   * The workgroup stages the fp64 prices in LDS ONCE (32 KiB at n = 4096) in the order the lanes read them: columns
+//     256 j + 4 l + {0, 1} as one 16-byte word at A[64 j + l], + {2, 3} at B[64 j + l] — both passes over a row take
+//     them with conflict-free ds_read_b128.  (They came from the L2 twice per row before: 64 KiB per 16 KiB row.)
+//   * The 16 float4 of the row land in the strip's own registers and are replaced in place by r: 64 + ~40 live
+//     registers, four waves per SIMD (two workgroups per CU) where the form that held row, prices and strip together
+//     needed 202 and ran two.
+//   * A count is 64 compares into scalar masks + scalar pop counts (no per-lane counter, no wave reduction).
+//   * The compaction leaves only the member COLUMNS in 64 LDS slots of the wave (slot-major, then lane — the order of
+//     the list); then lane <-> list entry: one gather of the costs from the row (cache resident: just read) and ONE
+//     512-byte store of the list, padding included.  (A global load + store per non-empty slot, one after the other,
+//     before: up to 64 dependent round trips per row.)
+template <int NJ>      // NJ = n / 256: float4 per lane and row
+__device__ __forceinline__ void wide_build_fast(gfp M, const AsgWs& w, char* lds) {
+    constexpr int n = 256 * NJ, nq = 64 * NJ, NS = 4 * NJ;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    double2* pl = reinterpret_cast<double2*>(lds);
+    for (int q = tid; q < n / 2; q += SP_BUILD_WAVES * 64) {
+        const double2 v = *reinterpret_cast<const double2*>(w.p + 2 * q);
+        pl[(q & 1) * nq + (q >> 1)] = v;
+        if (blockIdx.x == 0) *reinterpret_cast<double2*>(w.pb + 2 * q) = v;      // (cfm_assign_debug_lists: the solver moves w.p)
+    }
+    __syncthreads();
+    const double2* pA = pl + lane;
+    const double2* pB = pA + nq;
+    int* kb = reinterpret_cast<int*>(lds + (size_t)n * sizeof(double)) + wv * SP_K;
+    const int wave_gid = wv * gridDim.x + blockIdx.x, n_waves = gridDim.x * SP_BUILD_WAVES;
+    for (int i = wave_gid; i < n; i += n_waves) {
+        gfp row = M + (size_t)i * n;
+        float rr[NS];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {        // the whole row in one burst of float4 requests
+            const float4 c = asg_ld4(row + 256 * j + 4 * lane);
+            rr[4 * j + 0] = c.x; rr[4 * j + 1] = c.y; rr[4 * j + 2] = c.z; rr[4 * j + 3] = c.w;
+        }
+        double m = INFINITY;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const double2 pa = pA[64 * j], pb = pB[64 * j];
+            m = fmin(m, fmin(fmin((double)rr[4 * j + 0] + pa.x, (double)rr[4 * j + 1] + pa.y),
+                             fmin((double)rr[4 * j + 2] + pb.x, (double)rr[4 * j + 3] + pb.y)));
+        }
+        m = wave_min_d(m);
+        // (prices and fp64 costs are formed AGAIN below, not kept from the first pass: 2 x 128 registers otherwise)
+        asm volatile("" ::: "memory");
+#pragma unroll
+        for (int t = 0; t < NS; ++t) asm volatile("" : "+v"(rr[t]));
+        float lmin = INFINITY;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const double2 pa = pA[64 * j], pb = pB[64 * j];
+            const float x0 = (float)(((double)rr[4 * j + 0] + pa.x) - m), x1 = (float)(((double)rr[4 * j + 1] + pa.y) - m);
+            const float x2 = (float)(((double)rr[4 * j + 2] + pb.x) - m), x3 = (float)(((double)rr[4 * j + 3] + pb.y) - m);
+            rr[4 * j + 0] = x0; rr[4 * j + 1] = x1; rr[4 * j + 2] = x2; rr[4 * j + 3] = x3;
+            lmin = fminf(lmin, fminf(fminf(x0, x1), fminf(x2, x3)));
+        }
+        const float tau = sp_tau(lmin, [&](float tq) -> int {
+            int c = 0;
+#pragma unroll
+            for (int t = 0; t < NS; ++t) c += __popcll(__ballot(rr[t] < tq));
+            return c;
+        });
+        int off = 0;                                                   // (count(r < tau) <= SP_K: the wave's 64 slots hold them)
+#pragma unroll
+        for (int t = 0; t < NS; ++t) {
+            const bool mem = rr[t] < tau;
+            const unsigned long long mask = __ballot(mem);
+            if (mask) {                                                // (an empty slot costs its compare and a scalar branch)
+                const int pos = off + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
+                if (mem) kb[pos] = (t >> 2) * 256 + 4 * lane + (t & 3);
+                off += __popcll(mask);
+            }
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");           // the wave's own LDS writes (LDS is in order within a wave)
+        uint2 e = make_uint2(SP_NOCOL, 0x7f800000u);
+        if (lane < off) { const int k = kb[lane]; e = make_uint2((unsigned)k, __float_as_uint(row[k])); }
+        w.cl[(size_t)i * SP_K + lane] = e;
+        if (lane == 0) w.cT[i] = (tau == INFINITY) ? INFINITY : (m + (double)tau * (1.0 - 2.4e-7) - 1e-290);
+    }
+}
+
+// One wave per row.  Slow path (any other n): lane l owns columns l, 64 + l, ...; r[t] lives in the wave's LDS strip
+// (lane-major: conflict free).  n <= SP_K: every column is listed (tau = +inf).
 __device__ __forceinline__ void wide_build(gfp M, const AsgWs& w, const AsgState* st,
                            char* lds) {
     const int n = st->n;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (wv >= SP_BUILD_WAVES) return;
+    if (sp_build_fast(n)) {
+        if (n == 1024) wide_build_fast<4>(M, w, lds);
+        else if (n == 2048) wide_build_fast<8>(M, w, lds);
+        else if (n == 3072) wide_build_fast<12>(M, w, lds);
+        else wide_build_fast<16>(M, w, lds);
+        return;
+    }
+    if (blockIdx.x == 0)                                  // (what cfm_assign_debug_lists hands out: the solver moves w.p)
+        for (int k = threadIdx.x; k < n; k += SP_BUILD_WAVES * 64) w.pb[k] = w.p[k];
     const int nt = (n + 63) / 64;
     float* r = reinterpret_cast<float*>(lds) + (size_t)wv * nt * 64 + lane;   // r[t * 64]
     const int wave_gid = wv * gridDim.x + blockIdx.x, n_waves = gridDim.x * SP_BUILD_WAVES;
-    const bool fastb = ((n & 1023) == 0) && n > SP_K;     // n <= SP_NMAX = 4096: at most 16 float4 per lane
     for (int i = wave_gid; i < n; i += n_waves) {
         gfp row = M + (size_t)i * n;
         float lmin = INFINITY;
         double m = INFINITY;
-        // fast path (round 6): the strip stays in REGISTERS (64 floats per lane at n = 4096) — the bisection's counts and the
-        // compaction were 64 ds_read_b32 per lane and pass.  asg_build 61.5 -> 47.0 us per C3 solve, 229 -> 178 us per batch of
-        // four (gpurun_out/r6_build_ab.txt).  202 VGPRs: still 8 waves per CU; forced to 128 (amdgpu_waves_per_eu) it spills
-        // 94 registers — measured no further
-        float rr[64];
-        if (fastb) {
-            // whole row in one burst of float4 requests (lane owns columns 256 j + 4 lane + e <-> strip
-            // slot t = 4 j + e); the prices are read twice (32 KiB, cache resident), the row once
-            const int nj = n >> 8;
-            float4 c4[16];
+        for (int t0 = 0; t0 < nt; t0 += 8) {
+            float c[8]; double pk[8];
 #pragma unroll
-            for (int j = 0; j < 16; ++j)
-                c4[j] = asg_ld4(row + 256 * (j < nj ? j : 0) + 4 * lane);
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                if (j < nj) {
-                    const double2 pa = *reinterpret_cast<const double2*>(w.p + 256 * j + 4 * lane);
-                    const double2 pb = *reinterpret_cast<const double2*>(w.p + 256 * j + 4 * lane + 2);
-                    m = fmin(m, fmin(fmin((double)c4[j].x + pa.x, (double)c4[j].y + pa.y),
-                                     fmin((double)c4[j].z + pb.x, (double)c4[j].w + pb.y)));
-                }
+            for (int q = 0; q < 8; ++q) {
+                const int k = (t0 + q) * 64 + lane;
+                c[q] = (k < n) ? row[k] : INFINITY; pk[q] = (k < n) ? w.p[k] : 0.0;
             }
-            m = wave_min_d(m);
-            asm volatile("" ::: "memory");       // (the prices are READ AGAIN below, not kept: 128 registers otherwise, and the strip spills)
 #pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                if (j < nj) {
-                    const double2 pa = *reinterpret_cast<const double2*>(w.p + 256 * j + 4 * lane);
-                    const double2 pb = *reinterpret_cast<const double2*>(w.p + 256 * j + 4 * lane + 2);
-                    const float x0 = (float)(((double)c4[j].x + pa.x) - m), x1 = (float)(((double)c4[j].y + pa.y) - m);
-                    const float x2 = (float)(((double)c4[j].z + pb.x) - m), x3 = (float)(((double)c4[j].w + pb.y) - m);
-                    rr[4 * j + 0] = x0; rr[4 * j + 1] = x1; rr[4 * j + 2] = x2; rr[4 * j + 3] = x3;
-                    lmin = fminf(lmin, fminf(fminf(x0, x1), fminf(x2, x3)));
-                } else {
-                    rr[4 * j + 0] = INFINITY; rr[4 * j + 1] = INFINITY; rr[4 * j + 2] = INFINITY; rr[4 * j + 3] = INFINITY;
-                }
+            for (int q = 0; q < 8; ++q) m = fmin(m, (double)c[q] + pk[q]);
+        }
+        m = wave_min_d(m);
+        for (int t0 = 0; t0 < nt; t0 += 8) {
+            float c[8]; double pk[8];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const int k = (t0 + q) * 64 + lane;
+                c[q] = (k < n) ? row[k] : INFINITY; pk[q] = (k < n) ? w.p[k] : 0.0;
             }
-        } else {
-            for (int t0 = 0; t0 < nt; t0 += 8) {
-                float c[8]; double pk[8];
 #pragma unroll
-                for (int q = 0; q < 8; ++q) {
-                    const int k = (t0 + q) * 64 + lane;
-                    c[q] = (k < n) ? row[k] : INFINITY; pk[q] = (k < n) ? w.p[k] : 0.0;
-                }
-#pragma unroll
-                for (int q = 0; q < 8; ++q) m = fmin(m, (double)c[q] + pk[q]);
-            }
-            m = wave_min_d(m);
-            for (int t0 = 0; t0 < nt; t0 += 8) {
-                float c[8]; double pk[8];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) {
-                    const int k = (t0 + q) * 64 + lane;
-                    c[q] = (k < n) ? row[k] : INFINITY; pk[q] = (k < n) ? w.p[k] : 0.0;
-                }
-#pragma unroll
-                for (int q = 0; q < 8; ++q) {
-                    const int k = (t0 + q) * 64 + lane;
-                    if (t0 + q < nt) {
-                        const float x = (k < n) ? (float)(((double)c[q] + pk[q]) - m) : INFINITY;
-                        r[(t0 + q) * 64] = x; lmin = fminf(lmin, x);
-                    }
+            for (int q = 0; q < 8; ++q) {
+                const int k = (t0 + q) * 64 + lane;
+                if (t0 + q < nt) {
+                    const float x = (k < n) ? (float)(((double)c[q] + pk[q]) - m) : INFINITY;
+                    r[(t0 + q) * 64] = x; lmin = fminf(lmin, x);
                 }
             }
         }
-        float tau;
-        auto count = [&](float tq) -> int {
-            if (!fastb) return sp_count(r, nt, tq);
-            int c = 0;
-#pragma unroll
-            for (int t = 0; t < 64; ++t) c += (rr[t] < tq) ? 1 : 0;          // (slots beyond the row hold +inf)
-            return wave_sum_i(c);
-        };
-        if (n <= SP_K) {
-            tau = INFINITY;
-        } else {
-            const float hi = wave_max_f(lmin);                 // count(r <= hi) >= 64
-            const float t1 = __uint_as_float(__float_as_uint(hi) + 1u);
-            if (count(t1) <= SP_K) {
-                tau = t1;
-            } else {
-                float lo = 0.f, hh = t1; int clo = 0;
-                for (int it = 0; it < 48 && clo < SP_K / 2; ++it) {
-                    const float mid = 0.5f * (lo + hh);
-                    if (!(mid > lo && mid < hh)) break;
-                    const int cm = count(mid);
-                    if (cm <= SP_K) { lo = mid; clo = cm; } else hh = mid;
-                }
-                tau = lo;
-            }
-        }
+        const float tau = (n <= SP_K) ? INFINITY : sp_tau(lmin, [&](float tq) -> int { return sp_count(r, nt, tq); });
         const bool all = (tau == INFINITY);
         int off = 0;
-        if (fastb) {
-            int ln = lane; asm volatile("" : "+v"(ln));     // (opaque: the 64 column indices are formed per row — hoisted out of the row loop they spill)
-            const unsigned long long below = (1ull << ln) - 1ull;
-            gfp rowl = row + 4 * ln;
-#pragma unroll
-            for (int t = 0; t < 64; ++t) {
-                const int k = (t >> 2) * 256 + 4 * ln + (t & 3);
-                const bool mem = rr[t] < tau;                                    // (fastb: n > SP_K, tau finite; slots beyond the row: +inf)
-                const unsigned long long mask = __ballot(mem);
-                if (mask) {
-                    if (mem) {
-                        const int pos = off + __popcll(mask & below);
-                        w.cl[(size_t)i * SP_K + pos] = make_uint2((unsigned)k, __float_as_uint(rowl[(t >> 2) * 256 + (t & 3)]));
-                    }
-                    off += __popcll(mask);
-                }
-            }
-        } else
         for (int t = 0; t < nt; ++t) {
-            const int k = fastb ? ((t >> 2) * 256 + 4 * lane + (t & 3)) : (t * 64 + lane);
+            const int k = t * 64 + lane;
             const bool mem = (k < n) && (all || r[t * 64] < tau);
             const unsigned long long mask = __ballot(mem);
             if (mask) {

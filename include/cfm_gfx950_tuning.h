@@ -44,6 +44,7 @@ int cfm_mlp_get_glds(void);                    /* the mode in force (tests resto
 /* read-backs (blocking) */
 int cfm_assign_debug_times(const void* ws, double* us32);          /* microseconds per mode of the last solve on ws */
 int cfm_assign_debug_solver(const void* ws, int n, long long* out16);   /* -DSP_PROFILE builds: list-solver cycle counters */
+int cfm_assign_debug_lists(const void* ws, int n, int b, void* cl_out, double* cT_out, double* p_out);   /* candidate lists of the last solve on ws (problem b of a batch): n x 64 {column, cost bits}, n bounds, the n prices they were built from — host buffers */
 void cfm_assign_debug_small(int* out16);                           /* status block of this thread's last one-workgroup solve */
 void cfm_assign_debug_fallback(int* out2);                         /* {solves of this PROCESS (all threads) redone by the dense machine, last device error} */
 int cfm_plan_zero_entries_f64(double* pi, const int64_t* flat, int n, void* stream);   /* pi.flat[flat[q]] = 0 (sample_map(replace=False) bookkeeping of the mirror) */
