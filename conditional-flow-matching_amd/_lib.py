@@ -114,6 +114,8 @@ EXTRA_SIGNATURES = {
     "cfm_assign_set_async": (None, [_i, _i, _i]),
     "cfm_assign_get_async": (None, [_vp]),
     "cfm_assign_set_async_min_n": (None, [_i]),
+    "cfm_assign_set_sweep": (None, [_i]),
+    "cfm_assign_debug_sweep": (_i, [_i, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cfm_assign_debug_small": (None, [_vp]),
     "cfm_assign_debug_lists": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
     "cfm_assign_debug_solver": (_i, [_vp, _i, _vp]),

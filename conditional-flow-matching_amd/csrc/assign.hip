@@ -77,6 +77,7 @@
 #include <string.h>
 #include <mutex>
 #include <atomic>
+#include <vector>
 #include <time.h>
 
 enum { MODE_UMIN0 = 0,     // u_i = min_j c_ij, cost range, key / bid state reset          (f1)
@@ -116,18 +117,23 @@ struct AsgParams {
     double async_theta;    // ... its epsilon reduction factor (a phase costs it microseconds, not ~15 launches: gentler scaling pays)
     int async_min_n;       // ... smallest n it is used for (round 6: 512 — n = 512, d = 2: 2.86 ms against 3.60 on the synchronous rounds; at
                            //     n <= 256 the one-workgroup solver stays ahead: C1 0.92 against 1.68 ms; gpurun_out -> profiles/r6_experiments.txt)
+    int sweep;             // the plain matrix sweeps of the unpolled head: 1 = the lean asg_sweep kernel, 0 = asg_step, < 0 = the defaults below (cfm_assign_set_sweep)
 };
 
 // Process-wide tuning defaults.  A solve works on a snapshot taken under the lock, so setters
 // called from another thread never tear a running solve.
 static std::mutex g_params_mu;
+// The form of the sweeps while cfm_assign_set_sweep has not chosen one, for batches (the throughput entry, beside dense
+// work) and for lone solves: profiles/asg_sweep_lean.txt holds the measurements behind both
+#define ASG_SWEEP_BATCH_DEFAULT 1
+#define ASG_SWEEP_LONE_DEFAULT 1
 // async_blocks / async_last_div: measured in the C3 pipelined loop, three interleaved passes of nine regions each on one box
 // (profiles/r5_async_sweep.txt): synchronous rounds 1.18 - 1.21 ms per step; asynchronous on 16 workgroups per problem
 // 1.10 - 1.12, with the last phase cut at a quarter of the usual 2 % 1.07 - 1.11; 24 / 32 workgroups 1.09 - 1.13; cut / 8: 1.10 - 1.11.
 // async_theta: 40 C3 instances (profiles/r5_async_sweep.txt): theta 5 / 4 / 3 / 2.5 / 2: lone solve 2.33 / 2.28 / 2.08 / 1.92 / 1.93 ms — gentler
 // scaling leaves the list solver 15 free rows instead of 27 and shorter searches (1.04 vs 1.56 ms) for 0.1 ms more auction; the
 // sequential step 2.96 -> 2.56 ms (2.47 at theta 2), the pipelined step 1.07 -> 1.01-1.04 on the same box (1.04-1.05 at theta 2).
-static AsgParams g_params = {5.0, 8e-3, 1e-6, 0.02, 4000, 10, 10, 800000, 1, 64, 0.0, 0, 96, 512, 1, 2, 16, 4, 2.5, 512};   // (10 epsilon = 0 rounds: measured 2.35 ms per C3 solve against 2.56 with 15 and 2.46 with 8 once the forest phases ran in the list solver)
+static AsgParams g_params = {5.0, 8e-3, 1e-6, 0.02, 4000, 10, 10, 800000, 1, 64, 0.0, 0, 96, 512, 1, 2, 16, 4, 2.5, 512, -1};   // (10 epsilon = 0 rounds: measured 2.35 ms per C3 solve against 2.56 with 15 and 2.46 with 8 once the forest phases ran in the list solver)
 static AsgParams asg_params_snapshot() { std::lock_guard<std::mutex> lk(g_params_mu); return g_params; }
 
 extern "C" void cfm_assign_set_params(double theta, double eps0_frac, double eps_last_frac,
@@ -155,6 +161,12 @@ extern "C" void cfm_assign_set_async(int on, int blocks, int last_div) {
     g_params.async_auction = on < 0 ? 0 : (on > 2 ? 2 : on);        // 1: the epsilon > 0 phases; 2: the epsilon = 0 rounds too
     if (blocks >= 0) g_params.async_blocks = blocks;
     if (last_div > 0) g_params.async_last_div = last_div;      // (bits 8+: see asg_pack_pad0)
+}
+// A/B switch like cfm_assign_set_async: 0 = every chip-wide step is an asg_step launch, 1 = the sweeps of the unpolled head
+// are asg_sweep launches (AsgLaunch::program), in every solve; < 0 = back to the defaults (per form of the solve)
+extern "C" void cfm_assign_set_sweep(int mode) { std::lock_guard<std::mutex> lk(g_params_mu); g_params.sweep = mode < 0 ? -1 : (mode > 0 ? 1 : 0); }
+static inline int asg_sweep_form(const AsgParams& P, int nb) {
+    return P.sweep >= 0 ? P.sweep : (nb > 1 ? ASG_SWEEP_BATCH_DEFAULT : ASG_SWEEP_LONE_DEFAULT);
 }
 extern "C" void cfm_assign_set_async_min_n(int n) { std::lock_guard<std::mutex> lk(g_params_mu); if (n >= 64) g_params.async_min_n = n; }
 extern "C" void cfm_assign_get_async(int* out3) {
@@ -403,6 +415,28 @@ __device__ __forceinline__ void asg_st(unsigned long long* p, unsigned long long
 // workgroups, measured): the arrival is two-level, 16 first-level words in separate cache lines
 // (blockIdx % 16), whose last arrivers forward the group's payload sum to the top word.
 #define ASG_ARRIVE_GROUPS 16
+// Two-level RESULTS (asg_sweep: four times the workgroups of asg_step; 1024 of them posting a minimum and a sum to ONE
+// word each serialise for ~20 us — measured, profiles/asg_sweep_lean.txt): a workgroup posts its share of the cost range
+// (UMIN0) or of the certificate (CERT) into the spare words of its arrival group's line, and the group's last arriver
+// forwards the group's values to the state block before it draws the top-level ticket.  Words of a group's line (zero
+// between launches: asg_init, and the forwarder clears what it read):
+enum { ASG_SUB_TICKET = 0, ASG_SUB_COST = 1,      // certificate: partial sum of the matched costs (fp64 atomic add)
+       ASG_SUB_SLACK = 2,                         // certificate: ~ordered minimum slack (atomic max; 0 = nothing posted)
+       ASG_SUB_LO = 3, ASG_SUB_HI = 4 };          // cost range: ~ordered minimum, ordered maximum (32 bits, atomic max)
+__device__ __forceinline__ unsigned long long* asg_sub_line(unsigned long long* sub) {
+    const unsigned G = gridDim.x < ASG_ARRIVE_GROUPS ? gridDim.x : ASG_ARRIVE_GROUPS;
+    return sub + 16 * (blockIdx.x % G);
+}
+__device__ __forceinline__ void asg_forward_group(AsgState* st, unsigned long long* c) {
+    const unsigned long long cs = asg_ld(c + ASG_SUB_COST), ms = asg_ld(c + ASG_SUB_SLACK);
+    const unsigned lo = asg_ld(reinterpret_cast<unsigned*>(c + ASG_SUB_LO)), hi = asg_ld(reinterpret_cast<unsigned*>(c + ASG_SUB_HI));
+    if (cs) { atomicAdd(&st->total_cost, __longlong_as_double((long long)cs)); asg_st(c + ASG_SUB_COST, 0ull); }
+    if (ms) { atomicMin(&st->minslack_ord, ~ms); asg_st(c + ASG_SUB_SLACK, 0ull); }
+    if (lo) { atomicMin(&st->cmin_bits, ~lo); asg_st(c + ASG_SUB_LO, 0ull); }
+    if (hi) { atomicMax(&st->cmax_bits, hi); asg_st(c + ASG_SUB_HI, 0ull); }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // performed before the top-level ticket is drawn
+}
+template <bool FWD = false>
 __device__ __forceinline__ bool asg_arrive_last(AsgState* st, unsigned long long* sub, int* sh_flag,
                                                 unsigned payload, bool wait) {
     if (wait) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -417,6 +451,7 @@ __device__ __forceinline__ bool asg_arrive_last(AsgState* st, unsigned long long
         int last = 0; unsigned total = 0;
         if ((unsigned)(t >> 32) == gsize - 1u) {
             asg_st(c, 0ull);
+            if (FWD) asg_forward_group(st, c);      // (every poster of the group waited for its atomics before its ticket)
             const unsigned gp = (unsigned)t + payload;
             const unsigned long long t2 = __hip_atomic_fetch_add(&st->arrive, (1ull << 32) | (unsigned long long)gp,
                                                                  __ATOMIC_RELAXED, ASG_AGENT);
@@ -730,10 +765,13 @@ __device__ __forceinline__ int wide_bid_queue(gfp M, const AsgWs& w, const doubl
 
 // MODE_UMIN0: row minima (bidval), the cost range (one pair of atomics per workgroup) and the reset
 // of the key / bid state.  sh: >= 64 floats of LDS.
+// T: threads of the workgroup (asg_step: WT; asg_sweep: ASG_SWEEP_T) — every minimum / maximum below is order-free, so
+// the workgroup size changes no bit of what a sweep leaves.
+template <int T>
 __device__ __forceinline__ void wide_umin0(gfp M, const AsgWs& w, AsgState* st,
                                            int wave_gid, int n_waves, int n, float* sh) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    for (int j = blockIdx.x * WT + threadIdx.x; j < n; j += gridDim.x * WT) { w.key[j] = 0ull; w.bidcol[j] = -1; w.grp_ticket[j] = 0; }
+    for (int j = blockIdx.x * T + threadIdx.x; j < n; j += gridDim.x * T) { w.key[j] = 0ull; w.bidcol[j] = -1; w.grp_ticket[j] = 0; }
     float lo = INFINITY, hi = -INFINITY;
     const bool vec = ((n & 3) == 0);
     for (int i = wave_gid; i < n; i += n_waves) {
@@ -769,8 +807,13 @@ __device__ __forceinline__ void wide_umin0(gfp M, const AsgWs& w, AsgState* st,
     if (lane == 0) { sh[wv] = lo; sh[16 + wv] = hi; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        for (int q = 1; q < WT / 64; ++q) { lo = fminf(lo, sh[q]); hi = fmaxf(hi, sh[16 + q]); }
-        if (lo <= hi) { atomicMin(&st->cmin_bits, f2ord(lo)); atomicMax(&st->cmax_bits, f2ord(hi)); }
+        for (int q = 1; q < T / 64; ++q) { lo = fminf(lo, sh[q]); hi = fmaxf(hi, sh[16 + q]); }
+        if (lo <= hi) {
+            if (T < WT) {        // two-level: see asg_forward_group
+                unsigned long long* c = asg_sub_line(w.arrive_sub);
+                atomicMax(reinterpret_cast<unsigned*>(c + ASG_SUB_LO), ~f2ord(lo)); atomicMax(reinterpret_cast<unsigned*>(c + ASG_SUB_HI), f2ord(hi));
+            } else { atomicMin(&st->cmin_bits, f2ord(lo)); atomicMax(&st->cmax_bits, f2ord(hi)); }
+        }
     }
 }
 
@@ -780,14 +823,16 @@ __device__ __forceinline__ void wide_umin0(gfp M, const AsgWs& w, AsgState* st,
 // The auction then starts two epsilon phases later (eps0 = 8e-3 instead of 0.2 of the cost range).
 // Lane <-> column, the grid splits the rows; the partial maxima go straight into the keys (the
 // encoding is monotone, so the max of the encoded values is the encoded max; row bits = none).
+// Q rows in flight per lane: 8 in the 16-wave workgroup, 4 in the lean one (its budget is 64 VGPRs).
+template <int T>
 __device__ __forceinline__ void wide_initred(gfp M, const AsgWs& w, double* sh_d, int n, int rb) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    constexpr int NW = WT / 64, Q = 8;
+    constexpr int NW = T / 64, Q = (T >= 1024) ? 8 : 4;
     const unsigned none = (1u << rb) - 1u;
     if ((n & 255) == 0 && n >= 3072 && n <= WIDE_PLDS_MAX) {
         // 16-byte form (round 6): a lane owns FOUR adjacent columns, a wave reads 1 KiB of a row per request instead of 256 B
         // (C3: 31.8 -> 19.8 us, batch of four 131 -> 52 us; profiles/r6_experiments.txt 16).  The step's LDS holds the prices + owners of n >= 3072 columns
-        // (>= 36 KiB): room for the 16 x 256 partial maxima.
+        // (>= 36 KiB): room for the 16 x 256 partial maxima; the lean workgroup's 4 x 256 are its whole 8 KiB.
         const int n_groups = n >> 8;
         int Y = gridDim.x / n_groups; Y = Y < 1 ? 1 : Y;
         for (int unit = blockIdx.x; unit < n_groups * Y; unit += gridDim.x) {
@@ -813,7 +858,7 @@ __device__ __forceinline__ void wide_initred(gfp M, const AsgWs& w, double* sh_d
             double* mine = sh_d + (size_t)(wv * 64 + lane) * 4;
             mine[0] = m0; mine[1] = m1; mine[2] = m2; mine[3] = m3;
             __syncthreads();
-            if (wv < 4) {                                   // wave e reduces column 4 lane + e of the group over the 16 waves
+            if (wv < 4) {                                   // wave e reduces column 4 lane + e of the group over the NW waves
                 double m = -INFINITY;
 #pragma unroll
                 for (int q = 0; q < NW; ++q) m = fmax(m, sh_d[(size_t)(q * 64 + lane) * 4 + wv]);
@@ -859,6 +904,8 @@ __device__ __forceinline__ void wide_initred(gfp M, const AsgWs& w, double* sh_d
 // reduction) or for the free rows of the next multi-source phase.  Result in bidval[row]; for the
 // roots the wave also files the root's entry of the first scan list (the start of the phase).
 #define MS_NONE 0x7fffffff
+// K: 16-byte pieces of the row (+ their prices) in flight per lane and trip: 4, or 2 on the lean kernel's 64 VGPRs.
+template <int K>
 __device__ __forceinline__ void wide_umin(gfp M, const AsgWs& w, const AsgState* st,
                           int wave_gid, int n_waves, bool roots_only, const int n) {
     const int cnt = roots_only ? st->nF : n;
@@ -870,10 +917,10 @@ __device__ __forceinline__ void wide_umin(gfp M, const AsgWs& w, const AsgState*
         gfp row = M + (size_t)i * n;
         double m = INFINITY;
         if (vec) {
-            for (int j0 = lane * 4; j0 < n; j0 += 1024) {
-                float4 c[4]; double2 pa[4], pb[4];
+            for (int j0 = lane * 4; j0 < n; j0 += 256 * K) {
+                float4 c[K]; double2 pa[K], pb[K];
 #pragma unroll
-                for (int k = 0; k < 4; ++k) {
+                for (int k = 0; k < K; ++k) {
                     const int j = j0 + 256 * k;
                     if (j < n) {
                         c[k] = asg_ld4(row + j);
@@ -882,7 +929,7 @@ __device__ __forceinline__ void wide_umin(gfp M, const AsgWs& w, const AsgState*
                     }
                 }
 #pragma unroll
-                for (int k = 0; k < 4; ++k) {
+                for (int k = 0; k < K; ++k) {
                     const int j = j0 + 256 * k;
                     if (j < n) {
                         m = fmin(fmin(m, (double)c[k].x + pa[k].x), (double)c[k].y + pa[k].y);
@@ -906,14 +953,16 @@ __device__ __forceinline__ void wide_umin(gfp M, const AsgWs& w, const AsgState*
 }
 
 // the rest of a multi-source phase start: labels unset (all threads of the grid)
+template <int T>
 __device__ __forceinline__ void wide_ms_reset(const AsgWs& w, int n) {
-    for (int k = blockIdx.x * WT + threadIdx.x; k < n; k += gridDim.x * WT) { w.dist[k] = INFINITY; w.pred[k] = -1; }
+    for (int k = blockIdx.x * T + threadIdx.x; k < n; k += gridDim.x * T) { w.dist[k] = INFINITY; w.pred[k] = -1; }
 }
 
 // Column reduction of the free columns: p_k <- max_i (u_i - c_ik), the largest price at which
 // column k is still not cheaper than any row's current minimum.  No u_i changes, every matched
 // edge stays tight, the dual objective rises by the price drop.  One workgroup per column
 // (strided reads: 64 B sector per row, only nFC columns).
+template <int T>
 __device__ __forceinline__ void wide_colred(gfp M, const AsgWs& w, const AsgState* st,
                             double* sh_d, const int n) {
     const int nFC = st->nFC;
@@ -921,11 +970,11 @@ __device__ __forceinline__ void wide_colred(gfp M, const AsgWs& w, const AsgStat
     for (int t = blockIdx.x; t < nFC; t += gridDim.x) {
         const int k = w.listFC[t];
         double m = -INFINITY;
-        for (int i0 = threadIdx.x; i0 < n; i0 += WT * 4) {
+        for (int i0 = threadIdx.x; i0 < n; i0 += T * 4) {
             float c[4]; double u[4];
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const int i = i0 + q * WT;
+                const int i = i0 + q * T;
                 c[q] = (i < n) ? M[(size_t)i * n + k] : 0.f;
                 u[q] = (i < n) ? w.bidval[i] : -INFINITY;
             }
@@ -937,7 +986,7 @@ __device__ __forceinline__ void wide_colred(gfp M, const AsgWs& w, const AsgStat
         __syncthreads();
         if (threadIdx.x == 0) {
             double r = sh_d[0];
-            for (int q = 1; q < WT / 64; ++q) r = fmax(r, sh_d[q]);
+            for (int q = 1; q < T / 64; ++q) r = fmax(r, sh_d[q]);
             if (r < w.p[k]) w.p[k] = r;      // prices of free columns only ever go down here
         }
         __syncthreads();
@@ -1050,6 +1099,7 @@ __device__ __forceinline__ void wide_relax(gfp M, const AsgWs& w, AsgState* st,
 
 // ------------------------------------------------------------ wide: cert -----
 // pre_a: the match of row wave_gid, loaded with the state block in the kernel prologue.
+template <int T, int K>
 __device__ __forceinline__ void wide_cert(gfp M, const AsgWs& w, AsgState* st, int wave_gid,
                           int n_waves, int pre_a, double* sh_d, const int n) {
     const int lane = threadIdx.x & 63;
@@ -1061,11 +1111,11 @@ __device__ __forceinline__ void wide_cert(gfp M, const AsgWs& w, AsgState* st, i
         const double ui = (double)row[ai] + w.p[ai];
         double m = INFINITY;
         if ((n & 3) == 0) {
-            // 4 float4 of the row and their prices in flight per lane and trip
-            for (int j0 = lane * 4; j0 < n; j0 += 1024) {
-                float4 c4[4]; double2 pa[4], pb[4];
+            // K float4 of the row and their prices in flight per lane and trip
+            for (int j0 = lane * 4; j0 < n; j0 += 256 * K) {
+                float4 c4[K]; double2 pa[K], pb[K];
 #pragma unroll
-                for (int k = 0; k < 4; ++k) {
+                for (int k = 0; k < K; ++k) {
                     const int j = j0 + 256 * k;
                     if (j < n) {
                         c4[k] = asg_ld4(row + j);
@@ -1074,7 +1124,7 @@ __device__ __forceinline__ void wide_cert(gfp M, const AsgWs& w, AsgState* st, i
                     }
                 }
 #pragma unroll
-                for (int k = 0; k < 4; ++k) {
+                for (int k = 0; k < K; ++k) {
                     if (j0 + 256 * k < n) {
                         m = fmin(m, fmin(fmin(((double)c4[k].x + pa[k].x) - ui, ((double)c4[k].y + pa[k].y) - ui),
                                          fmin(((double)c4[k].z + pb[k].x) - ui, ((double)c4[k].w + pb[k].y) - ui)));
@@ -1094,9 +1144,15 @@ __device__ __forceinline__ void wide_cert(gfp M, const AsgWs& w, AsgState* st, i
     __syncthreads();
     if (threadIdx.x == 0) {
         double m = sh_d[0], c = sh_d[16], b = sh_d[32];
-        for (int q = 1; q < WT / 64; ++q) { m = fmin(m, sh_d[q]); c += sh_d[16 + q]; b += sh_d[32 + q]; }
-        atomicMin(&st->minslack_ord, d2ord(m));
-        if (c != 0.0) atomicAdd(&st->total_cost, c);
+        for (int q = 1; q < T / 64; ++q) { m = fmin(m, sh_d[q]); c += sh_d[16 + q]; b += sh_d[32 + q]; }
+        if (T < WT) {            // two-level: see asg_forward_group
+            unsigned long long* g = asg_sub_line(w.arrive_sub);
+            atomicMax(g + ASG_SUB_SLACK, ~d2ord(m));
+            if (c != 0.0) atomicAdd(reinterpret_cast<double*>(g + ASG_SUB_COST), c);
+        } else {
+            atomicMin(&st->minslack_ord, d2ord(m));
+            if (c != 0.0) atomicAdd(&st->total_cost, c);
+        }
         if (b != 0.0) atomicOr(&st->cert_bad, 1);
     }
     __syncthreads();
@@ -1338,11 +1394,12 @@ __device__ __forceinline__ void auc_decide(AucCtl& C, const AucParams* st, int c
 }
 
 // control step of a launch: thread 0 of the last-arriving workgroup (MODE_CERT: the whole workgroup)
+template <int T>
 __device__ __forceinline__ void step_ctrl(const AsgWs& w, AsgState* st, int mode, int n, int payload, int par) {
     if (mode == MODE_CERT) {
         // the pass has filled minslack / total_cost: export the result to the caller's buffers
         int* perm = st->out_perm;
-        for (int i = threadIdx.x; i < n; i += WT) perm[i] = w.a[i];
+        for (int i = threadIdx.x; i < n; i += T) perm[i] = w.a[i];
         if (threadIdx.x == 0) {
             asg_book(st, mode);
             const double minslack = ord2d(asg_ld(&st->minslack_ord));
@@ -1552,17 +1609,17 @@ __global__ __launch_bounds__(WT) void asg_step(AsgWs w0, int n_host, int par, si
         int* sh_i = reinterpret_cast<int*>(step_lds + sizeof(double) * WT);
         wide_relax(M, w, st, sh_d, sh_i, sh_i + WT, n);
     } else if (mode == MODE_UMIN0) {
-        wide_umin0(M, w, st, wave_gid, n_waves, n, reinterpret_cast<float*>(step_lds));
+        wide_umin0<WT>(M, w, st, wave_gid, n_waves, n, reinterpret_cast<float*>(step_lds));
     } else if (mode == MODE_INITRED) {
-        wide_initred(M, w, reinterpret_cast<double*>(step_lds), n, st->rb);
+        wide_initred<WT>(M, w, reinterpret_cast<double*>(step_lds), n, st->rb);
     } else if (mode == MODE_UMIN) {
-        wide_umin(M, w, st, wave_gid, n_waves, false, n);
+        wide_umin<4>(M, w, st, wave_gid, n_waves, false, n);
     } else if (mode == MODE_COLRED) {
-        wide_colred(M, w, st, reinterpret_cast<double*>(step_lds), n);
+        wide_colred<WT>(M, w, st, reinterpret_cast<double*>(step_lds), n);
     } else if (mode == MODE_ROOTMIN) {
-        wide_umin(M, w, st, wave_gid, n_waves, true, n); wide_ms_reset(w, n);
+        wide_umin<4>(M, w, st, wave_gid, n_waves, true, n); wide_ms_reset<WT>(w, n);
     } else if (mode == MODE_CERT) {
-        wide_cert(M, w, st, wave_gid, n_waves, (wave_gid < n) ? w.a[wave_gid] : 0, reinterpret_cast<double*>(step_lds), n);
+        wide_cert<WT, 4>(M, w, st, wave_gid, n_waves, (wave_gid < n) ? w.a[wave_gid] : 0, reinterpret_cast<double*>(step_lds), n);
     } else if (blockIdx.x == 0) {
         if (mode == MODE_CONVERT) {
             const int nF = ctrl_convert(w, st, sh);
@@ -1584,7 +1641,44 @@ __global__ __launch_bounds__(WT) void asg_step(AsgWs w0, int n_host, int par, si
         }
     }
     const bool wait = (mode == MODE_SAP || mode == MODE_UMIN0 || mode == MODE_CERT || mode == MODE_CONVERT || mode == MODE_MS_FINISH);
-    if (asg_arrive_last(st, w.arrive_sub, &sh[30], payload, wait)) step_ctrl(w, st, mode, n, sh[31], par & 1);
+    if (asg_arrive_last(st, w.arrive_sub, &sh[30], payload, wait)) step_ctrl<WT>(w, st, mode, n, sh[31], par & 1);
+}
+
+// The LEAN kernel of the plain matrix sweeps (UMIN0, INITRED, UMIN, COLRED, ROOTMIN, CERT): the bodies asg_step runs, in
+// 4-wave workgroups of at most 64 VGPRs and 8 KiB of LDS.  A 16-wave asg_step workgroup at 125 VGPRs is the whole register
+// file of a CU: it starts only on an EMPTY CU and nothing else runs there meanwhile; eight of these fit a CU, or two of
+// them beside a dense workgroup.  The host launches four times the workgroups of the asg_step grid: the same number of
+// waves.  Same state machine: the arrival (the first-level words are indexed blockIdx % 16 whatever the grid), the
+// control step and the time books are asg_step's; the cost range and the certificate's minimum / sum travel through the
+// arrival groups (asg_forward_group) instead of four times the atomics on one word.  No waiting of any kind: a workgroup works, adds its ticket and leaves.
+// In any other mode the launch is a no-op (the mode belongs to asg_step / the list pair).
+// par: the parity of the asg_step launch BEHIND which this launch stands in its program (the INITRED control step leaves
+// the first control record of the bid rounds for the next asg_step launch: see AsgLaunch::program).
+#define ASG_SWEEP_T 256
+#define ASG_SWEEP_LDS 8192
+__global__ __launch_bounds__(ASG_SWEEP_T, 8) void asg_sweep(AsgWs w0, int n_host, int par, size_t stride) {
+    // ONE array: the partial maxima of the 16-byte INITRED form fill it; the arrival's two flag words alias its head (every
+    // sweep ends on a barrier behind its last LDS read, and asg_arrive_last starts on one)
+    __shared__ __attribute__((aligned(16))) char lds[ASG_SWEEP_LDS];
+    const AsgWs w = asg_shift(w0, stride * blockIdx.y);
+    AsgState* st = w.st;
+    const int mode = st->mode, err = st->error, rb = st->rb;
+    gfp M = ASG_GLOBAL(st->Mptr);
+    const int n = n_host;
+    const int wv = threadIdx.x >> 6;
+    const int wave_gid = wv * gridDim.x + blockIdx.x, n_waves = gridDim.x * (ASG_SWEEP_T / 64);
+    const int pre_a = (wave_gid < n) ? w.a[wave_gid] : 0;
+    if (err) return;
+    if (mode == MODE_UMIN0) wide_umin0<ASG_SWEEP_T>(M, w, st, wave_gid, n_waves, n, reinterpret_cast<float*>(lds));
+    else if (mode == MODE_INITRED) wide_initred<ASG_SWEEP_T>(M, w, reinterpret_cast<double*>(lds), n, rb);
+    else if (mode == MODE_UMIN) wide_umin<2>(M, w, st, wave_gid, n_waves, false, n);
+    else if (mode == MODE_COLRED) wide_colred<ASG_SWEEP_T>(M, w, st, reinterpret_cast<double*>(lds), n);
+    else if (mode == MODE_ROOTMIN) { wide_umin<2>(M, w, st, wave_gid, n_waves, true, n); wide_ms_reset<ASG_SWEEP_T>(w, n); }
+    else if (mode == MODE_CERT) wide_cert<ASG_SWEEP_T, 2>(M, w, st, wave_gid, n_waves, pre_a, reinterpret_cast<double*>(lds), n);
+    else return;
+    const bool wait = (mode == MODE_UMIN0 || mode == MODE_CERT);
+    int* flag = reinterpret_cast<int*>(lds);
+    if (asg_arrive_last<true>(st, w.arrive_sub, flag, 0u, wait)) step_ctrl<ASG_SWEEP_T>(w, st, mode, n, flag[1], par & 1);
 }
 
 // ------------------------------------------------------- asynchronous phase A ------

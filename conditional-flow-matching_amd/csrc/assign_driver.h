@@ -4,7 +4,7 @@
 // host thread / workspace into hipGraphs and replayed (a solve is ~200 launches; with several
 // couplings in flight on different streams the host launch rate would be the limit).  Falls back
 // to plain launches when the stream cannot be captured (the legacy default stream) or CFM_ASG_GRAPH=0.
-//   PRG_BULK   `bulk` x asg_step                                  (unpolled head of a solve)
+//   PRG_BULK   `bulk` x asg_step, or the whole solve in 9 / 11 launches (unpolled head of a solve)
 //   PRG_CHUNK  `chunk` x asg_step, asg_build, asg_solve, 2 x asg_step   (polled; progresses from any state)
 // Both are written once, in AsgLaunch::program.  asg_run is the solve: check, size, upload, programs, drive.
 #pragma once
@@ -46,10 +46,10 @@ extern "C" size_t cfm_assign_batch_ws_bytes_internal(int n, int nb) {
 // What identifies a captured pair of programs: where it runs and every quantity its launches were captured with.
 struct AsgProgramId {
     void* ws = nullptr; int n = 0, nb = 0; hipStream_t stream = nullptr;
-    int chunk = 0, bulk = 0, blocks = 0, blocks_auction = 0, sparse = 0, async_auction = 0;
+    int chunk = 0, bulk = 0, blocks = 0, blocks_auction = 0, sparse = 0, async_auction = 0, sweep = 0;
     bool same_place(const AsgProgramId& o) const { return ws == o.ws && n == o.n && nb == o.nb && stream == o.stream; }
     bool operator==(const AsgProgramId& o) const {
-        return same_place(o) && chunk == o.chunk && bulk == o.bulk && blocks == o.blocks && blocks_auction == o.blocks_auction && sparse == o.sparse && async_auction == o.async_auction;
+        return same_place(o) && chunk == o.chunk && bulk == o.bulk && blocks == o.blocks && blocks_auction == o.blocks_auction && sparse == o.sparse && async_auction == o.async_auction && sweep == o.sweep;
     }
 };
 struct AsgGraph {
@@ -82,6 +82,7 @@ static thread_local struct AsgThread {
     int small_last[16] = {0};      // status block of this thread's last one-workgroup solve (phase times)
     struct { hipStream_t s; int dev, n; } cu_cache[4] = {};      // asg_stream_cus: the last few streams
     unsigned cu_clock = 0;
+    int last_run[8] = {0};         // launch record of this thread's last chip-wide solve (cfm_assign_debug_sweep, mode -1)
 } g_thr;
 extern "C" void cfm_set_blocking_sync(int on) { g_thr.blocking_sync = on ? 1 : 0; }
 static hipError_t asg_wait(hipEvent_t ev) {
@@ -169,19 +170,43 @@ static int asg_stream_cus(hipStream_t s) {
 struct AsgLaunch {
     AsgWs w; int n, blocks, blocks_build, nb; size_t stride; size_t lds_step, lds_build, lds_solve; int sparse; hipStream_t s;
     int async_auction = 0, blocks_auction = 0;
-    int chunk = 0, bulk = 0;       // asg_step launches of a polled chunk / of the unpolled head (both even)
+    int chunk = 0, bulk = 0;       // asg_step launches of a polled chunk / of the unpolled head in the asg_step form (both even)
+    int sweep = 0;                 // 1: the lean form of the head (asg_sweep)
     // the head holds the whole solve (see program)
     bool head_is_whole() const { return async_auction >= 2 && sparse && bulk > 0; }
-    AsgProgramId id(void* ws) const { return {ws, n, nb, s, chunk, bulk, blocks, blocks_auction, sparse, async_auction}; }
-    // Issues program `prg` on stream `s` (dry: issues nothing) and returns the number of its launches.
-    // every program holds an EVEN number of asg_step launches and starts on an even launch count, so the parity
-    // argument (which control record a bid round reads, see AucCtl) is the position inside the program.
+    AsgProgramId id(void* ws) const { return {ws, n, nb, s, chunk, bulk, blocks, blocks_auction, sparse, async_auction, sweep}; }
+    // asg_step launches of the head: the polled chunks go on from their parity
+    int head_steps() const {
+        if (bulk <= 0) return 0;
+        if (!sweep) return head_is_whole() ? 8 : bulk;
+        return head_is_whole() ? 1 : bulk - 2;
+    }
+    // Issues program `prg` on stream `s` (dry: issues nothing) and returns the number of its launches (kinds: of them
+    // asg_step [0] and asg_sweep [1] launches).
+    // The parity argument (which control record a bid round reads, see AucCtl) counts the asg_step launches of a solve:
+    // launch k of them gets k & 1.  In the asg_step form every program holds an even number of them, so k is the position
+    // inside the program; the lean head holds ONE (its CONVERT step), so the chunks behind it start on parity 1 — a chunk
+    // holds an even number, every later chunk starts there too.  An asg_sweep launch takes no part in the count and gets
+    // the parity of the asg_step launch in FRONT of it: the control step of INITRED leaves the first record of the bid
+    // rounds in ctl[par ^ 1], where the next asg_step launch looks.
     // grid.y = the problems of a batch (one carving each, `stride` bytes apart)
-    int program(int prg, bool dry = false) const {
-        int k = 0, issued = 0;
+    int program(int prg, bool dry = false, int* kinds = nullptr) const {
+        int k = (prg == PRG_CHUNK) ? (head_steps() & 1) : 0, issued = 0, n_step = 0, n_sweep = 0;
         auto steps = [&](int cnt) {
-            for (int c = 0; c < cnt; ++c, ++k, ++issued)
+            for (int c = 0; c < cnt; ++c, ++k, ++issued, ++n_step)
                 if (!dry) hipLaunchKernelGGL(asg_step, dim3(blocks, nb), dim3(WT), lds_step, s, w, n, k & 1, stride);
+        };
+        // the plain matrix sweeps, when the program knows that the state is at one: the lean kernel on four times the
+        // workgroups (the same number of waves); a no-op in any other mode
+        auto sweeps = [&](int cnt) {
+            for (int c = 0; c < cnt; ++c, ++issued, ++n_sweep)
+                if (!dry) hipLaunchKernelGGL(asg_sweep, dim3(4 * blocks, nb), dim3(ASG_SWEEP_T), 0, s, w, n, (k & 1) ^ 1, stride);
+        };
+        // CONVERT (and whatever the state holds instead: any mode is served) is the work of ONE workgroup: nothing reads
+        // the grid of that launch but the strides of the mode it runs and the arrival's group count, both from gridDim
+        auto narrow_step = [&]() {
+            if (!dry) hipLaunchKernelGGL(asg_step, dim3(1, nb), dim3(WT), lds_step, s, w, n, k & 1, stride);
+            ++k; ++issued; ++n_step;
         };
         // asynchronous phase A: ONE launch behind the two init steps (a no-op in any other state, like every kernel here)
         auto auction = [&]() {
@@ -201,17 +226,23 @@ struct AsgLaunch {
             // that takes this road — every C3 instance seen so far — is finished when the head is; the others are
             // picked up by the polled chunks.  (Round 4's head was 96 steps, then chunks of 10 steps + the pair + 2: a
             // lone solve paid ~35 no-op launches, 0.15 ms, around its list build and behind its last step.)
-            steps(2); auction(); steps(4); list_pair(); steps(2);
+            // The lean form: UMIN0, INITRED as sweeps, the auction, CONVERT on one workgroup, UMIN, COLRED as sweeps, the
+            // list pair, the certificate as a sweep — 9 launches, no spare ones (the parity contract: above).  A problem
+            // that leaves this road (epsilon = 0 rounds left over, more free rows than the list solver takes) finds
+            // no-ops or a one-workgroup step here and is picked up by the polled chunks, which are asg_step launches.
+            if (sweep) { sweeps(2); auction(); narrow_step(); sweeps(2); list_pair(); sweeps(1); }
+            else { steps(2); auction(); steps(4); list_pair(); steps(2); }
         } else if (prg == PRG_BULK) {
-            steps(2);      // (bulk is even and > 0)
+            if (sweep) sweeps(2); else steps(2);      // (bulk is even and > 0; a solve starts at UMIN0, INITRED)
             if (bulk > 2) { auction(); steps(bulk - 2); }
         } else {
             auction(); steps(chunk);
             if (sparse) { list_pair(); steps(2); }      // certificate + whatever the guess missed
         }
+        if (kinds) { kinds[0] = n_step; kinds[1] = n_sweep; }
         return issued;
     }
-    int count(int prg) const { return program(prg, true); }
+    int count(int prg, int* kinds = nullptr) const { return program(prg, true, kinds); }
 };
 
 // Step 1: argument checks and the trivial sizes (B <= 1: nothing is left to do behind this).
@@ -289,6 +320,7 @@ static int asg_size(AsgLaunch& L, int n, int nb, void* ws, size_t stride, hipStr
     // reduction (the synchronous rounds needed ~96 launches here)
     L.bulk = ((n >= P.bulk_min_n) ? P.bulk : 0) & ~1;
     if (L.async_auction && L.bulk > 16) L.bulk = 16;
+    L.sweep = asg_sweep_form(P, nb);
     return 0;
 }
 // AsgState::pad0 as asg_auction decodes it.  Bits 0-7: the last phase is cut at stop_frac / this (the low byte of
@@ -362,9 +394,14 @@ static AsgGraph& asg_programs(const AsgLaunch& L, void* ws, bool* use_graph) {
 static int asg_drive(const AsgLaunch& L, AsgGraph& G, bool use_graph, void* ws, long max_launches, int* cert_out, int* err_out) {
     const int nb = L.nb; hipStream_t s = L.s;
     long launched = 0;
+    int* rec = g_thr.last_run;      // {launches, of them asg_step, asg_sweep, chunks run, launches of the head, of a chunk, form, 0}
+    for (int q = 0; q < 8; ++q) rec[q] = 0;
+    rec[4] = L.count(PRG_BULK); rec[5] = L.count(PRG_CHUNK); rec[6] = L.sweep;
     auto run = [&](int prg) -> int {
-        const int cnt = L.count(prg);
+        int kinds[2] = {0, 0};
+        const int cnt = L.count(prg, kinds);
         launched += cnt;
+        rec[0] += cnt; rec[1] += kinds[0]; rec[2] += kinds[1]; rec[3] += (prg == PRG_CHUNK);
         if (cnt == 0) return 0;
         if (use_graph) return cfm_hip(hipGraphLaunch(G.exec[prg], s));
         L.program(prg); return cfm_status();
@@ -510,4 +547,73 @@ extern "C" int cfm_assign_exact_batch_f32(const float* const* M, int nb, int B, 
         }
     }
     return rc;
+}
+
+// Test hook (tuning export): ONE sweep step of the chip-wide machine on a caller-made state, with the kernel
+// cfm_assign_set_sweep selects (0: asg_step on `blocks` workgroups, 1: asg_sweep on 4 x blocks, unset: as a batch would;
+// blocks <= 0: the grid of a lone solve of this size).  mode: MODE_UMIN0 / INITRED / UMIN / COLRED / ROOTMIN / CERT.  M and ws (cfm_workspace_bytes of
+// the exact solver) are device pointers, everything else host memory; blocking.
+//   in:  p_in [n] prices / duals (UMIN, COLRED, ROOTMIN, CERT), bidval_in [n] row minima (INITRED, COLRED), list [n_list]
+//        the free columns (COLRED) or free rows (ROOTMIN), perm_in [n] row -> column (CERT)
+//   out: bidval_out / key_out / p_out [n] as the step left them — every array the step may write is filled with a
+//        sentinel first (all-ones bytes: NaN / ~0; the keys of INITRED start at 0 as UMIN0 leaves them), so an element a
+//        grid skips shows; state_out [8]: {cmin bits, cmax bits, mode after the step, certified, minslack bits (2 words),
+//        control steps booked, 0}; cost_out: the certificate's total cost
+// mode = -1: no launch — state_out receives the launch record of this thread's last chip-wide solve: {launches, of them
+// asg_step, asg_sweep, polled chunks run, launches of the head program, of a chunk program, form (0 / 1), 0}.
+extern "C" int cfm_assign_debug_sweep(int mode, const float* M, int n, int blocks, const double* p_in, const double* bidval_in,
+                                      const int* list, int n_list, const int* perm_in, double* bidval_out,
+                                      unsigned long long* key_out, double* p_out, int* state_out, double* cost_out,
+                                      void* ws, void* stream) {
+    if (mode == -1) { if (!state_out) return CFM_EINVAL; for (int q = 0; q < 8; ++q) state_out[q] = g_thr.last_run[q]; return 0; }
+    const bool known = mode == MODE_UMIN0 || mode == MODE_INITRED || mode == MODE_UMIN || mode == MODE_COLRED || mode == MODE_ROOTMIN || mode == MODE_CERT;
+    if (!known || !M || !ws || n < 2 || n > (1 << 20) || !state_out || n_list < 0 || n_list > n) return CFM_EINVAL;
+    if (((uintptr_t)ws & 15) != 0 || ((uintptr_t)M & 15) != 0) return CFM_EALIGN;
+    const bool need_p = mode != MODE_UMIN0 && mode != MODE_INITRED, need_u = mode == MODE_INITRED || mode == MODE_COLRED;
+    const bool need_list = mode == MODE_COLRED || mode == MODE_ROOTMIN;
+    if ((need_p && !p_in) || (need_u && !bidval_in) || (need_list && !list) || (mode == MODE_CERT && !perm_in)) return CFM_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const AsgParams P = asg_params_snapshot();
+    AsgLaunch L;
+    int rc = asg_size(L, n, 1, ws, 0, s, P, P.sparse); if (rc) return rc;
+    if (blocks > 0) L.blocks = blocks > 512 ? 512 : blocks;
+    const AsgWs& w = L.w;
+    const size_t N = (size_t)n;
+    // sentinels, then the caller's state
+    rc = cfm_hip(hipMemsetAsync(ws, 0xff, asg_ws_bytes(n), s)); if (rc) return rc;
+    const AsgProblem pr = {M, w.listA, nullptr, nullptr, nullptr};      // (the certificate's step exports the permutation: into scratch)
+    rc = asg_upload(L, &pr, ws, P); if (rc) return rc;                    // (also clears the arrival words)
+    rc = cfm_hip(hipMemsetAsync(w.auc, 0, 512, s)); if (rc) return rc;
+    auto put = [&](void* dst, const void* src, size_t bytes) { return cfm_hip(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s)); };
+    if (mode == MODE_INITRED) { rc = cfm_hip(hipMemsetAsync(w.key, 0, 8 * N, s)); if (rc) return rc; }
+    if (need_p) { rc = put(w.p, p_in, 8 * N); if (rc) return rc; }
+    if (need_u) { rc = put(w.bidval, bidval_in, 8 * N); if (rc) return rc; }
+    if (need_list) { rc = put(mode == MODE_COLRED ? w.listFC : w.listF, list, 4 * (size_t)n_list); if (rc) return rc; }
+    std::vector<int> owner;
+    if (mode == MODE_CERT) {
+        owner.assign(N, -1);
+        for (size_t i = 0; i < N; ++i) if (perm_in[i] >= 0 && perm_in[i] < n) owner[perm_in[i]] = (int)i;
+        rc = put(w.a, perm_in, 4 * N); if (rc) return rc;
+        rc = put(w.owner, owner.data(), 4 * N); if (rc) return rc;
+    }
+    // the words of the state block the step reads beside what asg_upload set
+    AsgState h;
+    rc = cfm_hip(hipMemcpyAsync(&h, w.st, sizeof(h), hipMemcpyDeviceToHost, s)); if (rc) return rc;
+    rc = cfm_hip(hipStreamSynchronize(s)); if (rc) return rc;
+    h.mode = mode; h.nF = mode == MODE_ROOTMIN ? n_list : 0; h.nFC = mode == MODE_COLRED ? n_list : 0; h.cur = 0;
+    h.cert_bad = 0; h.total_cost = 0.0; h.minslack_ord = ~0ull;
+    rc = put(w.st, &h, sizeof(h)); if (rc) return rc;
+    if (asg_sweep_form(P, 2)) hipLaunchKernelGGL(asg_sweep, dim3(4 * L.blocks, 1), dim3(ASG_SWEEP_T), 0, s, w, n, 1, (size_t)0);
+    else hipLaunchKernelGGL(asg_step, dim3(L.blocks, 1), dim3(WT), L.lds_step, s, w, n, 1, (size_t)0);
+    rc = cfm_status(); if (rc) return rc;
+    rc = cfm_hip(hipStreamSynchronize(s)); if (rc) return rc;
+    rc = cfm_hip(hipMemcpy(&h, w.st, sizeof(h), hipMemcpyDeviceToHost)); if (rc) return rc;
+    if (bidval_out) { rc = cfm_hip(hipMemcpy(bidval_out, w.bidval, 8 * N, hipMemcpyDeviceToHost)); if (rc) return rc; }
+    if (key_out) { rc = cfm_hip(hipMemcpy(key_out, w.key, 8 * N, hipMemcpyDeviceToHost)); if (rc) return rc; }
+    if (p_out) { rc = cfm_hip(hipMemcpy(p_out, w.p, 8 * N, hipMemcpyDeviceToHost)); if (rc) return rc; }
+    state_out[0] = (int)h.cmin_bits; state_out[1] = (int)h.cmax_bits; state_out[2] = h.mode; state_out[3] = h.certified;
+    state_out[4] = (int)(h.minslack_ord & 0xffffffffull); state_out[5] = (int)(h.minslack_ord >> 32);
+    state_out[6] = h.st_steps; state_out[7] = 0;
+    if (cost_out) *cost_out = h.total_cost;
+    return 0;
 }

@@ -27,12 +27,17 @@ void cfm_assign_set_stop_early(double f);        /* phase cut of every epsilon p
 void cfm_assign_set_wide_blocks(int cap);        /* upper bound on the grid of the chip-wide step kernel (0: none) */
 void cfm_assign_set_bulk(int bulk, int min_n);   /* launches enqueued before the first poll, for n >= min_n */
 /* on = 2 (the DEFAULT): every bid of a solve — the epsilon > 0 phases AND the epsilon = 0 rounds — in the one-launch
- * asynchronous auction (asg_auction), the whole solve as one unpolled program of 12 launches; on = 1: only the epsilon > 0
+ * asynchronous auction (asg_auction), the whole solve as one unpolled program of 9 launches (11 with cfm_assign_set_sweep(0)); on = 1: only the epsilon > 0
  * phases there, the epsilon = 0 rounds as synchronous launches; on = 0: every round a launch (the A/B reference; always
  * the path of n < 512 and n > 8192).  blocks >= 0: workgroups per problem of the auction in the batch entry (0: as the
  * other kernels); last_div > 0: its last phase is cut at stop_frac / last_div.  The grid is capped at the CUs the
  * stream may use (CU-masked streams); a grid that cannot hold 1/256 of the rows per workgroup falls back to on = 0. */
 void cfm_assign_set_async(int on, int blocks, int last_div);
+/* The plain matrix sweeps of a solve's unpolled head (row minima, initial prices, column reduction, certificate):
+ * 1 = in the lean 4-wave kernel asg_sweep, which shares a CU with dense work; 0 = every chip-wide step is an asg_step
+ * launch (16-wave workgroups that each need an empty CU) — the A/B reference; < 0 = the library's defaults again (chosen
+ * per form of the solve, batch or lone: csrc/assign.hip).  Same results bit for bit. */
+void cfm_assign_set_sweep(int mode);
 void cfm_assign_set_async_min_n(int n);          /* smallest n that takes the one-launch auction (default 512; >= 64) */
 void cfm_assign_get_async(int* out3);            /* {on, blocks, last_div} as set (tests restore what they changed) */
 void cfm_assign_set_small(int on);               /* 0: problems of n <= 256 take the chip-wide machine too */
@@ -45,6 +50,12 @@ int cfm_mlp_get_glds(void);                    /* the mode in force (tests resto
 int cfm_assign_debug_times(const void* ws, double* us32);          /* microseconds per mode of the last solve on ws */
 int cfm_assign_debug_solver(const void* ws, int n, long long* out16);   /* -DSP_PROFILE builds: list-solver cycle counters */
 int cfm_assign_debug_lists(const void* ws, int n, int b, void* cl_out, double* cT_out, double* p_out);   /* candidate lists of the last solve on ws (problem b of a batch): n x 64 {column, cost bits}, n bounds, the n prices they were built from — host buffers */
+/* ONE sweep step (mode 0 UMIN0, 1 INITRED, 5 UMIN, 6 COLRED, 7 ROOTMIN, 10 CERT) on a caller-made state with the kernel
+ * cfm_assign_set_sweep selects; mode -1: the launch record of this thread's last chip-wide solve.  M, ws: device; the rest
+ * host.  Arguments and outputs: csrc/assign_driver.h. */
+int cfm_assign_debug_sweep(int mode, const float* M, int n, int blocks, const double* p_in, const double* bidval_in,
+                           const int* list, int n_list, const int* perm_in, double* bidval_out,
+                           unsigned long long* key_out, double* p_out, int* state_out, double* cost_out, void* ws, void* stream);
 void cfm_assign_debug_small(int* out16);                           /* status block of this thread's last one-workgroup solve */
 void cfm_assign_debug_fallback(int* out2);                         /* {solves of this PROCESS (all threads) redone by the dense machine, last device error} */
 int cfm_plan_zero_entries_f64(double* pi, const int64_t* flat, int n, void* stream);   /* pi.flat[flat[q]] = 0 (sample_map(replace=False) bookkeeping of the mirror) */
