@@ -1,5 +1,5 @@
-// cnf_grad.h — gradient of the Euler solve of the augmented CNF state (included by ode.hip after the small-field tile
-// code: SmTile, sm_gemm, sm_stage_weights, selu_f, selu_slope, cnf_check).
+// cnf_grad.h — gradient of the Euler solve of the augmented CNF state (included by ode.hip; the tile engine it runs on
+// comes from small_field.h: SmTile, sm_gemm, sm_stage_weights, selu_f, selu_slope, small_grid; cnf_check from ode.hip).
 //
 // Forward (ode_small_fixed<CFM_ODE_EULER, MODE>):  y_{n+1} = y_n + h_n v(y_n, t_n),  l_{n+1} = l_n - h_n div(y_n, t_n).
 // Given G = dL/d[l_N, y_N]:  c = G[:, 0] never changes (l enters linearly), a_N = G[:, 1:], and for n = N-1 .. 0
@@ -77,9 +77,9 @@ __device__ __forceinline__ void cg_outer(const float* __restrict__ Zbuf, const f
 
 __device__ __forceinline__ float cg_sum4(const SmTile& v) { return (v.v[0] + v.v[1]) + (v.v[2] + v.v[3]); }
 
-static size_t cg_lds_bytes() {
-    return sizeof(float) * (6 * SM_W * SM_LD + 4 * SM_W + SM_W + 5 * SM_ROWS * SM_LD);
-}
+// one staged net, the transposed copies of its two 64 x 64 layers, five tile buffers
+constexpr size_t cg_lds_bytes = small_lds_bytes(1, 5, false) + sizeof(float) * 2 * SM_W * SM_LD;
+static_assert(cg_lds_bytes == 127488, "the gradient kernel");
 
 // traj [n_t, B, 1 + d]: the forward solve (y_n is read); G [B, 1 + d]; g0 [B, 1 + d] or null; part [gridDim.x][P]:
 // the workgroup's partial gradient in the order W0, b0, W1, b1, W2, b2, W3, b3 (each as the caller's tensor is laid out)
@@ -163,7 +163,7 @@ __global__ __launch_bounds__(256) void ode_small_euler_grad(SmArgs A, int B, int
 #pragma unroll
                 for (int l = 0; l < 3; ++l) {
                     const int N = A.dims[l + 1];
-                    sm_gemm(src, Wl + l * WS, 0, wv, lane, c);
+                    sm_gemm(src, Wl + l * WS, wv, lane, c);
                     const float bv = (col < N) ? bl[l * SM_W + col] : 0.f;
                     const float wtc = (l == 0 && col < N) ? wt[col] : 0.f;
 #pragma unroll
@@ -197,7 +197,7 @@ __global__ __launch_bounds__(256) void ode_small_euler_grad(SmArgs A, int B, int
                 if constexpr (MODE == AUG_HUTCH) {
                     cg_put(E, ep, lane, col);
                     sm_lds_barrier();
-                    sm_gemm(E, Wl, 0, wv, lane, c);
+                    sm_gemm(E, Wl, wv, lane, c);
 #pragma unroll
                     for (int i = 0; i < SM_V; ++i) U1.v[i] = c[0][i];
                 } else {
@@ -213,12 +213,12 @@ __global__ __launch_bounds__(256) void ode_small_euler_grad(SmArgs A, int B, int
                 for (int i = 0; i < SM_V; ++i) tv.v[i] = s[0].v[i] * U1.v[i];
                 cg_put(X1, tv, lane, col);                                                  // T1
                 sm_lds_barrier();
-                sm_gemm(X1, Wl + 1 * WS, 0, wv, lane, c);
+                sm_gemm(X1, Wl + 1 * WS, wv, lane, c);
 #pragma unroll
                 for (int i = 0; i < SM_V; ++i) { U2.v[i] = c[0][i]; tv.v[i] = s[1].v[i] * U2.v[i]; }
                 cg_put(X2, tv, lane, col);                                                  // T2
                 sm_lds_barrier();
-                sm_gemm(X2, Wl + 2 * WS, 0, wv, lane, c);
+                sm_gemm(X2, Wl + 2 * WS, wv, lane, c);
 #pragma unroll
                 for (int i = 0; i < SM_V; ++i) { U3.v[i] = c[0][i]; tv.v[i] = cp.v[i] * (s[2].v[i] * U3.v[i]); }
                 cg_put(X3, tv, lane, col);                                                  // -h c T3
@@ -239,7 +239,7 @@ __global__ __launch_bounds__(256) void ode_small_euler_grad(SmArgs A, int B, int
                 cg_put(Y3, tv, lane, col);                                                  // Ub3
                 sm_lds_barrier();
                 cg_outer(Y3, X2, wv, lane, dWa[2]);
-                sm_gemm(Y3, W2T, 0, wv, lane, c);
+                sm_gemm(Y3, W2T, wv, lane, c);
 #pragma unroll
                 for (int i = 0; i < SM_V; ++i) {
                     sb[1].v[i] = fmaf(c[0][i], U2.v[i], sb[1].v[i]);
@@ -248,7 +248,7 @@ __global__ __launch_bounds__(256) void ode_small_euler_grad(SmArgs A, int B, int
                 cg_put(X3, tv, lane, col);                                                  // Ub2
                 sm_lds_barrier();
                 cg_outer(X3, X1, wv, lane, dWa[1]);
-                sm_gemm(X3, W1T, 0, wv, lane, c);
+                sm_gemm(X3, W1T, wv, lane, c);
 #pragma unroll
                 for (int i = 0; i < SM_V; ++i) {
                     sb[0].v[i] = fmaf(c[0][i], U1.v[i], sb[0].v[i]);
@@ -275,7 +275,7 @@ __global__ __launch_bounds__(256) void ode_small_euler_grad(SmArgs A, int B, int
             cg_put(X3, hh[1], lane, col);
             sm_lds_barrier();
             cg_outer(X2, X3, wv, lane, dWa[2]);
-            sm_gemm(X2, W2T, 0, wv, lane, c);
+            sm_gemm(X2, W2T, wv, lane, c);
 #pragma unroll
             for (int i = 0; i < SM_V; ++i) zb.v[i] = c[0][i] * s[1].v[i] + sb[1].v[i] * q[1].v[i];
             dba[1] += cg_sum4(zb);
@@ -283,7 +283,7 @@ __global__ __launch_bounds__(256) void ode_small_euler_grad(SmArgs A, int B, int
             cg_put(X1, hh[0], lane, col);
             sm_lds_barrier();
             cg_outer(E, X1, wv, lane, dWa[1]);
-            sm_gemm(E, W1T, 0, wv, lane, c);
+            sm_gemm(E, W1T, wv, lane, c);
 #pragma unroll
             for (int i = 0; i < SM_V; ++i) zb.v[i] = c[0][i] * s[0].v[i] + sb[0].v[i] * q[0].v[i];
             {
@@ -360,14 +360,9 @@ __global__ __launch_bounds__(256) void ode_small_grad_reduce(const float* __rest
 template <int MODE>
 static int cnf_grad_launch(const SmArgs& A, int B, int d, const float* tspan_dev, int n_t, const float* traj,
                            const float* eps, const float* G, float* g0, float* part, int P, const CgOut& O, hipStream_t s) {
-    const int raised = cfm_once_per_device([] {
-        hipError_t e = hipFuncSetAttribute((const void*)ode_small_euler_grad<MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-        return (e == hipSuccess) ? 1 : -1;
-    });
-    if (raised < 0) return CFM_EINVAL;
-    const int tiles = (B + SM_ROWS - 1) / SM_ROWS;
-    const int grid = tiles < CG_MAXGRID ? tiles : CG_MAXGRID;
-    hipLaunchKernelGGL(ode_small_euler_grad<MODE>, dim3(grid), dim3(256), cg_lds_bytes(), s, A, B, d, tspan_dev, n_t, traj, eps,
+    const int grid = small_grid<ode_small_euler_grad<MODE>, 128 * 1024>(B, CG_MAXGRID);
+    if (grid < 0) return CFM_EINVAL;
+    hipLaunchKernelGGL(ode_small_euler_grad<MODE>, dim3(grid), dim3(256), cg_lds_bytes, s, A, B, d, tspan_dev, n_t, traj, eps,
                        G, g0, part, P);
     int rc = cfm_status();
     if (rc) return rc;

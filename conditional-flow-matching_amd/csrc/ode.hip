@@ -15,7 +15,7 @@
 //           elementwise kernels; the scalar step controller runs on the host in
 //           fp32 (one 8-byte read-back per step attempt).
 #include "cfm_common.h"
-#include "sde_srk.h"
+#include "small_field.h"
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -150,7 +150,6 @@ static int check_mlp(const int* dims, int n_layers, int* d_out) {
     return 0;
 }
 
-#define SM_WMAX 64   // largest layer width of the fused small-field paths (= SM_W below)
 static int g_ode_fused = -1;     // -1: from the environment (CFM_ODE_FUSED=0 disables), else 0 / 1
 extern "C" void cfm_ode_set_fused(int on) { g_ode_fused = on ? 1 : 0; }
 static int ode_small_enabled() {
@@ -276,8 +275,7 @@ extern "C" int cfm_ode_fixed_mlp_f32(const float* const* W, const float* const* 
     if (rc) return rc;
     // small vector fields: rows are independent and the steps are fixed, so ONE launch integrates the
     // whole t_span (a workgroup walks its 64-row tile through every step, weights resident in LDS)
-    if (ode_small_enabled() && n_layers == 4 && dims[1] <= SM_WMAX && dims[2] <= SM_WMAX && dims[3] <= SM_WMAX &&
-        d + 1 <= SM_WMAX && n >= (size_t)n_t && n_t >= 2) {
+    if (ode_small_enabled() && small_envelope(dims, n_layers, nullptr) == 0 && d + 1 <= SM_W && n >= (size_t)n_t && n_t >= 2) {
         rc = ode_fixed_small(scheme, W, b, dims, B, d, t_span, n_t, traj, w.xt, s);
         if (nfe) *nfe = ns * (n_t - 1);
         return rc;
@@ -452,8 +450,7 @@ static int ode_dopri5_layers(int tab, const float* const* W, const float* const*
     if (rc) return rc;
 
     // small vector fields: the whole step attempt in one kernel, controller on the device
-    if (ode_small_enabled() && n_layers == 4 && dims[1] <= SM_WMAX && dims[2] <= SM_WMAX && dims[3] <= SM_WMAX &&
-        d + 1 <= SM_WMAX && n >= (size_t)n_t)
+    if (ode_small_enabled() && small_envelope(dims, n_layers, nullptr) == 0 && d + 1 <= SM_W && n >= (size_t)n_t)
         return ode_adaptive_small<0>(tab, W, b, dims, B, d, t_span, n_t, tsign, nullptr, atol, rtol, traj, n_steps, nfe, w.x,
                                    w.k[0], w.xt, (void*)(w.red + 16), w.sync, t, dt, evals, s);
 
@@ -511,43 +508,9 @@ static int ode_dopri5_layers(int tab, const float* const* W, const float* const*
     return (t < T) ? CFM_ENOCONV : 0;
 }
 
-// =====================================================================================
-// Fused Dormand-Prince step for SMALL vector fields (4 linear layers, every width <= 64:
-// the reference's 2-D tutorials and single-cell models, MLP(dim, w=64)).
-//
-// The layer-per-kernel driver above spends ~31 launches and one host read-back per step
-// attempt: 266 us per step at B = 8192, d = 50, w = 64 where the arithmetic is ~20 us.
-// Rows are independent inside a step (only the error norm couples them), so here ONE persistent
-// kernel does the whole adaptive solve: a workgroup keeps the four weight matrices in LDS (68 KB)
-// and owns a 16-row tile (SM_MB = 1: B = 8192 -> 512 workgroups, two per CU, so one workgroup's
-// MFMA phase overlaps the other's SELU epilogue; measured 3.46 ms against 3.87 ms for 32-row tiles
-// with two accumulator chains per wave and one workgroup per CU), holds x and k1..k7 of its tile
-// in MFMA accumulator layout in registers, and runs the six stage evaluations back to back.  Wave w
-// owns output columns 16w..16w+15: a v_mfma_f32_16x16x4_f32 accumulator chain with the same
-// ascending-k fp32 fma chain and epilogue as mlp_layer: bitwise the same field values.  The
-// accept / reject decision and the next step size are taken ON THE DEVICE by every workgroup from
-// the same all-reduced error norm (same fp32 controller as the host loop above); the host launches
-// once and reads the step counters back.
-// =====================================================================================
-#define SM_W 64
-#define SM_LD 68     // row stride = 4 (mod 64): fragment reads (row = lane & 15, k = lane >> 4) hit 64 distinct banks
-#define SM_MB 1      // 16-row blocks per tile = independent MFMA accumulator chains per wave
-#define SM_ROWS (16 * SM_MB)
-#define SM_V (4 * SM_MB)   // tile floats per lane: element i -> row sm_row(i, lane), column 16 * wave + (lane & 15)
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-struct SmTile { float v[SM_V]; };
-__device__ __forceinline__ int sm_row(int i, int lane) { return 16 * (i >> 2) + 4 * (lane >> 4) + (i & 3); }
-
-
-// same SELU as mlp.hip (bitwise)
-__device__ __forceinline__ float selu_f(float x) {
-    return x > 0.f ? 1.0507009873554805f * x : (1.0507009873554805f * 1.6732632423543772f) * expm1f(x);
-}
 struct SmState { float t, dt; int ckpt, steps, evals, par, done, pad; };
 // One persistent solve at a time per process, whatever its augmentation mode (see ode_dopri5_small)
 static std::mutex g_persistent_mu;
-struct SmArgs { const float* W[4]; const float* b[4]; int dims[5]; };
 
 // the step-size clipping the host loop does before every attempt
 __device__ __forceinline__ void sm_prestep(const SmState& st, const float* __restrict__ tspan, int n_t,
@@ -558,216 +521,6 @@ __device__ __forceinline__ void sm_prestep(const SmState& st, const float* __res
     dt_old = dt; flag = false;
     if (st.ckpt < n_t && st.t + dt > tspan[st.ckpt]) { dt_old = dt; flag = true; dt = tspan[st.ckpt] - st.t; }
     lands = (st.ckpt < n_t) && (flag || st.t + dt == tspan[st.ckpt]);
-}
-
-// Workgroup barrier that orders LDS traffic only: global stores of the tile (trajectory rows) stay in
-// flight across it instead of being drained (s_waitcnt vmcnt(0)) the way __syncthreads() would
-__device__ __forceinline__ void sm_lds_barrier() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-
-// one layer on the tile: out(C layout) = A[SM_ROWS x K] * W_l[64 x K]^T, this wave's 16 columns
-__device__ __forceinline__ void sm_gemm(const float* __restrict__ Abuf, const float* __restrict__ Wl, int K,
-                                        int wv, int lane, f32x4 (&c)[SM_MB]) {
-#pragma unroll
-    for (int m = 0; m < SM_MB; ++m) c[m] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int fr = lane & 15, fk = lane >> 4;
-    const float* ap = Abuf + fr * SM_LD + fk;
-    const float* bp = Wl + (wv * 16 + fr) * SM_LD + fk;
-    // every layer runs the full 16 k-steps (rows / columns beyond K are zero in both operands, and
-    // fma(0, 0, acc) leaves acc alone), fully unrolled: all operand reads are in flight before the
-    // first MFMA issues, then the accumulator chain(s) run back to back in ascending k
-    (void)K;
-    float a[SM_MB][SM_W / 4], b[SM_W / 4];
-#pragma unroll
-    for (int j = 0; j < SM_W / 4; ++j) {
-#pragma unroll
-        for (int m = 0; m < SM_MB; ++m) a[m][j] = ap[16 * m * SM_LD + 4 * j];
-        b[j] = bp[4 * j];
-    }
-#pragma unroll
-    for (int j = 0; j < SM_W / 4; ++j) {
-#pragma unroll
-        for (int m = 0; m < SM_MB; ++m) c[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[m][j], b[j], c[m], 0, 0, 0);
-    }
-}
-
-// f(t, y) for the tile; y arrives in C layout, the result leaves in C layout (columns >= d are 0)
-__device__ __forceinline__ SmTile sm_field(const SmTile& y, float t, const SmArgs& A, int d, float* Abuf0,
-                                           float* Abuf1, const float* Wl, const float* bl, const float* wt,
-                                           int wv, int lane) {
-    const int col = wv * 16 + (lane & 15);
-#pragma unroll
-    for (int i = 0; i < SM_V; ++i) Abuf0[sm_row(i, lane) * SM_LD + col] = (col < d) ? y.v[i] : 0.f;
-    sm_lds_barrier();
-    SmTile acc;
-    float* src = Abuf0; float* dst = Abuf1;
-#pragma unroll
-    for (int l = 0; l < 4; ++l) {
-        const int K = (l == 0) ? d : A.dims[l];
-        const int N = A.dims[l + 1];
-        f32x4 c[SM_MB];
-        sm_gemm(src, Wl + l * SM_W * SM_LD, K, wv, lane, c);
-        const float bv = (col < N) ? bl[l * SM_W + col] : 0.f;
-        const float wtc = (l == 0 && col < N) ? wt[col] : 0.f;
-#pragma unroll
-        for (int i = 0; i < SM_V; ++i) {
-            float v = c[i >> 2][i & 3] + bv;
-            if (l == 0) v = fmaf(t, wtc, v);
-            if (l < 3) v = selu_f(v);
-            acc.v[i] = (col < N) ? v : 0.f;
-        }
-        if (l < 3) {
-#pragma unroll
-            for (int i = 0; i < SM_V; ++i) dst[sm_row(i, lane) * SM_LD + col] = acc.v[i];
-            sm_lds_barrier();
-            float* tmp = src; src = dst; dst = tmp;
-        }
-    }
-    return acc;
-}
-
-// ---- CNF augmentation: v = f(t, x) and its divergence on the tile ----------------------------------------------
-// J = W3 diag(s3) W2 diag(s2) W1 diag(s1) W0[:, :d],  s_l = selu'(z_l) at the layer's pre-activation.
-//   AUG_EXACT: tr J = sum_k (J e_k)_k.  T1 = s1 * W0[:, k] needs no product; T2 = s2 * (W1 T1), T3 = s3 * (W2 T2);
-//              only row k of W3 is needed, so the last product is a dot product: 2 GEMMs per direction.
-//   AUG_HUTCH: eps^T J eps (eps fixed per solve): T1 = s1 * (W0 eps), T2, T3, Ju = W3 T3: 4 GEMMs.
-// The lane that owns (row, col) of z_l owns (row, col) of every tangent tile, so s_l stays in its registers; the
-// tangent tiles take the primal's LDS staging buffers in the same strict alternation (a barrier after every write).
-enum { AUG_NONE = 0, AUG_EXACT = 1, AUG_HUTCH = 2 };
-
-// selu'(z) as PyTorch's elu_backward takes it: scale for z > 0, scale * alpha * exp(z) otherwise (z = 0 included)
-__device__ __forceinline__ float selu_slope(float z) {
-    return z > 0.f ? 1.0507009873554805f : (1.0507009873554805f * 1.6732632423543772f) * expf(z);
-}
-
-// per-row sum of a C-layout tile over its 64 columns: 16 lanes of a wave (butterfly: every lane gets the same bits),
-// then the 4 waves in a fixed order through red[4][SM_ROWS]; every lane gets the sums of its SM_V rows
-__device__ __forceinline__ SmTile sm_rowsum(SmTile p, float* red, int wv, int lane) {
-#pragma unroll
-    for (int i = 0; i < SM_V; ++i) {
-#pragma unroll
-        for (int o = 1; o < 16; o <<= 1) p.v[i] += __shfl_xor(p.v[i], o, 64);
-    }
-    if ((lane & 15) == 0) {
-#pragma unroll
-        for (int i = 0; i < SM_V; ++i) red[wv * SM_ROWS + sm_row(i, lane)] = p.v[i];
-    }
-    sm_lds_barrier();
-    SmTile r;
-#pragma unroll
-    for (int i = 0; i < SM_V; ++i) {
-        const int row = sm_row(i, lane);
-        r.v[i] = ((red[row] + red[SM_ROWS + row]) + red[2 * SM_ROWS + row]) + red[3 * SM_ROWS + row];
-    }
-    return r;
-}
-
-// f(t, y) exactly as sm_field (bitwise the same v), plus div (per row, in every lane holding the row).
-// eps: the probe tile (C layout, zero outside [rows, d]); nrows: rows of the tile below B (the rest stay zero in
-// every tangent tile).
-template <int MODE>
-__device__ __forceinline__ SmTile sm_field_aug(const SmTile& y, float t, const SmArgs& A, int d, float* Abuf0,
-                                               float* Abuf1, const float* Wl, const float* bl, const float* wt,
-                                               const SmTile& eps, int nrows, float* red, int wv, int lane,
-                                               SmTile& div) {
-    const int col = wv * 16 + (lane & 15);
-#pragma unroll
-    for (int i = 0; i < SM_V; ++i) Abuf0[sm_row(i, lane) * SM_LD + col] = (col < d) ? y.v[i] : 0.f;
-    sm_lds_barrier();
-    SmTile acc, sl[3];
-    float* src = Abuf0; float* dst = Abuf1;
-#pragma unroll
-    for (int l = 0; l < 4; ++l) {
-        const int K = (l == 0) ? d : A.dims[l];
-        const int N = A.dims[l + 1];
-        f32x4 c[SM_MB];
-        sm_gemm(src, Wl + l * SM_W * SM_LD, K, wv, lane, c);
-        const float bv = (col < N) ? bl[l * SM_W + col] : 0.f;
-        const float wtc = (l == 0 && col < N) ? wt[col] : 0.f;
-#pragma unroll
-        for (int i = 0; i < SM_V; ++i) {
-            float v = c[i >> 2][i & 3] + bv;
-            if (l == 0) v = fmaf(t, wtc, v);
-            if (l < 3) {
-                sl[l].v[i] = (col < N && sm_row(i, lane) < nrows) ? selu_slope(v) : 0.f;
-                v = selu_f(v);
-            }
-            acc.v[i] = (col < N) ? v : 0.f;
-        }
-        if (l < 3) {
-#pragma unroll
-            for (int i = 0; i < SM_V; ++i) dst[sm_row(i, lane) * SM_LD + col] = acc.v[i];
-            sm_lds_barrier();
-            float* tmp = src; src = dst; dst = tmp;
-        }
-    }
-    SmTile q;
-    if constexpr (MODE == AUG_HUTCH) {
-#pragma unroll
-        for (int i = 0; i < SM_V; ++i) Abuf0[sm_row(i, lane) * SM_LD + col] = (col < d) ? eps.v[i] : 0.f;
-        sm_lds_barrier();
-        src = Abuf0; dst = Abuf1;
-        SmTile tg;
-#pragma unroll
-        for (int l = 0; l < 4; ++l) {
-            const int N = A.dims[l + 1];
-            f32x4 c[SM_MB];
-            sm_gemm(src, Wl + l * SM_W * SM_LD, N, wv, lane, c);
-#pragma unroll
-            for (int i = 0; i < SM_V; ++i) {
-                float u = c[i >> 2][i & 3];
-                if (l < 3) u = sl[l].v[i] * u;
-                tg.v[i] = (col < N) ? u : 0.f;
-            }
-            if (l < 3) {
-#pragma unroll
-                for (int i = 0; i < SM_V; ++i) dst[sm_row(i, lane) * SM_LD + col] = tg.v[i];
-                sm_lds_barrier();
-                float* tmp = src; src = dst; dst = tmp;
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < SM_V; ++i) q.v[i] = (col < d) ? eps.v[i] * tg.v[i] : 0.f;
-    } else {
-        (void)eps;
-        const int N1 = A.dims[1], N2 = A.dims[2], N3 = A.dims[3];
-#pragma unroll
-        for (int i = 0; i < SM_V; ++i) q.v[i] = 0.f;
-        for (int k = 0; k < d; ++k) {
-            const float w0 = (col < N1) ? Wl[col * SM_LD + k] : 0.f;                      // W0[col][k]
-#pragma unroll
-            for (int i = 0; i < SM_V; ++i) Abuf0[sm_row(i, lane) * SM_LD + col] = sl[0].v[i] * w0;
-            sm_lds_barrier();
-            f32x4 c[SM_MB];
-            sm_gemm(Abuf0, Wl + 1 * SM_W * SM_LD, N1, wv, lane, c);
-#pragma unroll
-            for (int i = 0; i < SM_V; ++i) Abuf1[sm_row(i, lane) * SM_LD + col] = (col < N2) ? sl[1].v[i] * c[i >> 2][i & 3] : 0.f;
-            sm_lds_barrier();
-            sm_gemm(Abuf1, Wl + 2 * SM_W * SM_LD, N2, wv, lane, c);
-            const float w3 = (col < N3) ? Wl[3 * SM_W * SM_LD + k * SM_LD + col] : 0.f;  // W3[k][col]
-#pragma unroll
-            for (int i = 0; i < SM_V; ++i) q.v[i] = fmaf(w3, (col < N3) ? sl[2].v[i] * c[i >> 2][i & 3] : 0.f, q.v[i]);
-        }
-    }
-    div = sm_rowsum(q, red, wv, lane);
-    return acc;
-}
-
-// weights -> LDS, zero padded to [4][64][SM_LD]; biases; the time column of layer 0
-__device__ __forceinline__ void sm_stage_weights(const SmArgs& A, int d, float* Wl, float* bl, float* wt, int tid) {
-    for (int l = 0; l < 4; ++l) {
-        const int in_l = A.dims[l], out_l = A.dims[l + 1];
-        const int K = (l == 0) ? d : in_l;
-        for (int e = tid; e < SM_W * SM_LD; e += 256) {
-            const int r = e / SM_LD, k = e % SM_LD;
-            Wl[l * SM_W * SM_LD + e] = (r < out_l && k < K) ? A.W[l][(size_t)r * in_l + k] : 0.f;
-        }
-        if (tid < SM_W) bl[l * SM_W + tid] = (tid < out_l) ? A.b[l][tid] : 0.f;
-    }
-    if (tid < SM_W) wt[tid] = (tid < A.dims[1]) ? A.W[0][(size_t)tid * A.dims[0] + d] : 0.f;
 }
 
 // Grid-wide rendezvous + all-reduce of a persistent launch (grid <= workgroups that are resident at
@@ -781,8 +534,8 @@ __device__ __forceinline__ void sm_stage_weights(const SmArgs& A, int d, float* 
 // the re-arm before anything a reader of attempt a + 1 can see.  Measured on MI355X, 256 workgroups:
 // an arrival counter + polling cost 7-9 us per rendezvous, a two-level counter tree 15 us.
 // The wait is bounded (wall clock, ~4 s): a mis-sized launch turns into an error code, never a hung GPU.
-__device__ __forceinline__ bool sm_grid_allsum(double* __restrict__ row, double mine, int tid, int lane, int wv,
-                                               double* sh_total, int* sh_ok) {
+__device__ __forceinline__ bool sm_grid_allsum(double* __restrict__ row, double mine, int lane, int wv, double* sh_total,
+                                               int* sh_ok) {
     if (wv == 0) {
         if (lane == 0) __hip_atomic_store(&row[blockIdx.x], mine, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
         int ok = 1;
@@ -808,7 +561,6 @@ __device__ __forceinline__ bool sm_grid_allsum(double* __restrict__ row, double 
         tsum = wave_sum_d(tsum);
         if (lane == 0) { *sh_total = tsum; *sh_ok = ok; }
     }
-    (void)tid;
     sm_lds_barrier();
     return *sh_ok != 0;
 }
@@ -972,8 +724,8 @@ __global__ __launch_bounds__(256) void ode_small_dopri(SmArgs A, int B, int d, S
         esum = wave_sum_d(esum);
         if (lane == 0) redw[wv] = esum;
         if (RESIDENT) sm_lds_barrier(); else __syncthreads();   // (the streamed path re-reads its rows below)
-        if (!sm_grid_allsum(partial + (size_t)(attempt % 3) * SM_MAXGRID, redw[0] + redw[1] + redw[2] + redw[3], tid, lane,
-                            wv, &sh_total, &sh_ok)) { err = 2; break; }
+        if (!sm_grid_allsum(partial + (size_t)(attempt % 3) * SM_MAXGRID, redw[0] + redw[1] + redw[2] + redw[3], lane, wv,
+                            &sh_total, &sh_ok)) { err = 2; break; }
         // accept / reject, next step size (identical in every workgroup and lane)
         const float ratio = (float)sqrt(sh_total / (double)n);
         const bool accept = ratio <= 1.f;
@@ -1020,21 +772,15 @@ __global__ __launch_bounds__(256) void ode_small_dopri(SmArgs A, int B, int d, S
     if (blockIdx.x == 0 && tid == 0) { st.pad = err; st_io[1] = st; }
 }
 
-static size_t sm_lds_bytes(int mode) {
-    return sizeof(float) * (4 * SM_W * SM_LD + 4 * SM_W + SM_W + 2 * SM_ROWS * SM_LD + (mode ? 4 * SM_ROWS : 0));
-}
-
 template <int TAB, int MODE>
 static int ode_dopri5_small(const float* const* W, const float* const* b, const int* dims, int B, int d,
                             const float* t_span, int n_t, float tsign, const float* eps, float atol, float rtol,
                             float* traj, int* n_steps, int* nfe, float* xbuf, float* kbuf, float* tspan_dev,
                             void* state_dev, char* sync_dev, float t0, float dt0, int evals0, hipStream_t s) {
-    SmArgs A;
-    for (int l = 0; l < 4; ++l) { A.W[l] = W[l]; A.b[l] = b[l]; }
-    for (int l = 0; l < 5; ++l) A.dims[l] = dims[l];
-    const size_t lds = sm_lds_bytes(MODE);
+    const SmArgs A = small_args(W, b, dims);
+    constexpr size_t lds = small_lds_bytes(1, 2, MODE != AUG_NONE);
     // (one result per TAB and MODE: the grid is sized from the occupancy of the instantiation that is launched)
-    const int resident = cfm_once_per_device([lds] {
+    const int resident = cfm_once_per_device([] {
         hipError_t e = hipFuncSetAttribute((const void*)ode_small_dopri<TAB, true, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
         hipError_t e2 = hipFuncSetAttribute((const void*)ode_small_dopri<TAB, false, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
         // workgroups that can be resident at once: the grid rendezvous needs grid <= this
@@ -1085,245 +831,7 @@ static int ode_dopri5_small(const float* const* W, const float* const* b, const 
     return cur.done && cur.pad == 0 ? 0 : CFM_ENOCONV;
 }
 
-// ------------------------------------------------------------ SF2M: Euler-Maruyama ----
-// y <- y + h (v(te, y) + s(te, y)) + g sqrt|h| xi  for every step of the grid, the whole trajectory of a tile in ONE
-// launch: both small fields (flow v and score s: 4 layers, widths <= 64) live in LDS (2 x 69 KB), the state in
-// registers.  Same arithmetic, in the same order, as the launch-per-step scheme (sde.py: two forward passes on
-// mlp_layer + cfm_sde_em_step_f32: f = fma(1, s, +-v); r = fma(h, f, y); r = fma(g sqrt|h|, xi, r)) — with the
-// caller's noise (xi != NULL) the trajectory is bit-equal to it.  xi == NULL: N(0, 1) from Philox4x32-10 in the
-// kernel (counter = step, element index; key = seed), Box-Muller.
-// Replaces torchsde.sdeint(SDE(model, score_model), x0, ts, method="euler", dt=...), i.e.
-// runner/src/models/components/solver.py:157-182 at sde_solver: euler, for the small fields the examples train.  (The
-// notebooks themselves do not select it: SF2M_tutorial.ipynb cell 5 passes solver="euler", a keyword torchsde ignores,
-// and runs torchsde's default "srk" — ode_small_srk below.)
-__device__ __forceinline__ void philox_round(unsigned (&c)[4], unsigned k0, unsigned k1) {
-    const unsigned long long p0 = (unsigned long long)0xD2511F53u * c[0], p1 = (unsigned long long)0xCD9E8D57u * c[2];
-    const unsigned n0 = (unsigned)(p1 >> 32) ^ c[1] ^ k0, n1 = (unsigned)p1;
-    const unsigned n2 = (unsigned)(p0 >> 32) ^ c[3] ^ k1, n3 = (unsigned)p0;
-    c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-}
-// w3: counter word 3 names the stream (0x5f2d: the Euler-Maruyama increments and xi1 of srk; 0x5f2e: xi2 of srk)
-__device__ __forceinline__ void philox_normal4_w3(unsigned long long seed, unsigned step, unsigned long long elem, unsigned w3,
-                                                  float (&z)[4]) {
-    unsigned c[4] = {(unsigned)elem, (unsigned)(elem >> 32), step, w3};
-    unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) { philox_round(c, k0, k1); k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
-    // Box-Muller on (0, 1] uniforms
-    const float u0 = ((float)(c[0] >> 8) + 1.0f) * (1.0f / 16777216.0f), u1 = (float)(c[1] >> 8) * (1.0f / 16777216.0f);
-    const float u2 = ((float)(c[2] >> 8) + 1.0f) * (1.0f / 16777216.0f), u3 = (float)(c[3] >> 8) * (1.0f / 16777216.0f);
-    const float r0 = sqrtf(-2.0f * logf(u0)), r1 = sqrtf(-2.0f * logf(u2));
-    float s0, c0, s1, c1;
-    sincosf(6.283185307179586f * u1, &s0, &c0); sincosf(6.283185307179586f * u3, &s1, &c1);
-    z[0] = r0 * c0; z[1] = r0 * s0; z[2] = r1 * c1; z[3] = r1 * s1;
-}
-__device__ __forceinline__ void philox_normal4(unsigned long long seed, unsigned step, unsigned long long elem, float (&z)[4]) {
-    philox_normal4_w3(seed, step, elem, 0x5f2du, z);
-}
-
-struct EmStep { float te, h, gs; int is_out; };      // per step: field time, step, g sqrt|h|, trajectory point after it
-
-__global__ __launch_bounds__(256) void ode_small_em(SmArgs F, SmArgs S, int has_s, int B, int d,
-                                                    const EmStep* __restrict__ steps, int n_steps, int reverse,
-                                                    const float* __restrict__ xi, unsigned long long seed,
-                                                    const float* __restrict__ y0, float* __restrict__ out) {
-    extern __shared__ __attribute__((aligned(16))) float small_lds[];
-    float* WlF = small_lds;
-    float* blF = WlF + 4 * SM_W * SM_LD;
-    float* wtF = blF + 4 * SM_W;
-    float* WlS = wtF + SM_W;
-    float* blS = WlS + 4 * SM_W * SM_LD;
-    float* wtS = blS + 4 * SM_W;
-    float* Ab0 = wtS + SM_W;
-    float* Ab1 = Ab0 + SM_ROWS * SM_LD;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    sm_stage_weights(F, d, WlF, blF, wtF, tid);
-    if (has_s) sm_stage_weights(S, d, WlS, blS, wtS, tid);
-    const size_t n = (size_t)B * d;
-    const int col = wv * 16 + (lane & 15);
-    for (int row0 = blockIdx.x * SM_ROWS; row0 < B; row0 += gridDim.x * SM_ROWS) {
-        SmTile x;
-#pragma unroll
-        for (int i = 0; i < SM_V; ++i) {
-            const int gr = row0 + sm_row(i, lane);
-            x.v[i] = (gr < B && col < d) ? y0[(size_t)gr * d + col] : 0.f;
-        }
-        __syncthreads();
-        int oidx = 0;
-        for (int k = 0; k < n_steps; ++k) {
-            const EmStep st = steps[k];
-            const SmTile v = sm_field(x, st.te, F, d, Ab0, Ab1, WlF, blF, wtF, wv, lane);
-            SmTile sc;
-            if (has_s) sc = sm_field(x, st.te, S, d, Ab0, Ab1, WlS, blS, wtS, wv, lane);
-            static_assert(SM_V == 4, "ode_small_em draws ONE Philox block of 4 normals per lane and step: with SM_MB > 1 "
-                                     "elements i and i + 4 would share a normal (draw SM_V / 4 blocks, counter word + (i >> 2))");
-            float z[4] = {0.f, 0.f, 0.f, 0.f};
-            if (!xi && st.gs != 0.f) philox_normal4(seed, (unsigned)k, (unsigned long long)(row0 / SM_ROWS) * 256 + tid, z);
-#pragma unroll
-            for (int i = 0; i < SM_V; ++i) {
-                const int gr = row0 + sm_row(i, lane);
-                const bool ok = gr < B && col < d;
-                float f = reverse ? -v.v[i] : v.v[i];
-                if (has_s) f = fmaf(1.0f, sc.v[i], f);
-                float r = fmaf(st.h, f, x.v[i]);
-                const float noise = xi ? (ok ? xi[(size_t)k * n + (size_t)gr * d + col] : 0.f) : z[i & 3];
-                r = fmaf(st.gs, noise, r);
-                x.v[i] = ok ? r : 0.f;
-                if (st.is_out && ok) out[(size_t)oidx * n + (size_t)gr * d + col] = r;
-            }
-            oidx += st.is_out ? 1 : 0;
-        }
-        __syncthreads();
-    }
-}
-
-// steps_host: n_steps records {te, h, g sqrt|h|, is_out} (host); ws: >= 16 n_steps bytes of device scratch.
-// Ws == NULL: no score field.  Returns CFM_EINVAL for anything but two 4-layer fields of widths <= 64 with a time
-// column (the caller then steps launch by launch).
-extern "C" int cfm_sde_em_mlp_f32(const float* const* Wf, const float* const* bf, const float* const* Ws,
-                                  const float* const* bs, const int* dims, int n_layers, const float* y0, int B,
-                                  const void* steps_host, int n_steps, int reverse, const float* xi,
-                                  unsigned long long seed, float* out, void* ws, void* stream) {
-    if (!Wf || !bf || !dims || !y0 || !out || !steps_host || !ws || B < 0 || n_steps < 0) return CFM_EINVAL;
-    if (n_layers != 4) return CFM_EINVAL;
-    const int d = dims[4];
-    if (dims[0] != d + 1 || d > SM_W) return CFM_EINVAL;
-    for (int l = 1; l <= 3; ++l) if (dims[l] > SM_W || dims[l] < 1) return CFM_EINVAL;
-    if (B == 0 || n_steps == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    SmArgs F, S;
-    for (int l = 0; l < 4; ++l) { F.W[l] = Wf[l]; F.b[l] = bf[l]; S.W[l] = Ws ? Ws[l] : Wf[l]; S.b[l] = bs ? bs[l] : bf[l]; }
-    for (int l = 0; l < 5; ++l) { F.dims[l] = dims[l]; S.dims[l] = dims[l]; }
-    const size_t lds = sizeof(float) * (2 * (4 * SM_W * SM_LD + 4 * SM_W + SM_W) + 2 * SM_ROWS * SM_LD);
-    const int raised = cfm_once_per_device([] {
-        hipError_t e = hipFuncSetAttribute((const void*)ode_small_em, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        return (e == hipSuccess) ? 1 : -1;
-    });
-    if (raised < 0) return CFM_EINVAL;
-    int rc = cfm_hip(hipMemcpyAsync(ws, steps_host, sizeof(EmStep) * (size_t)n_steps, hipMemcpyHostToDevice, s));
-    if (rc) return rc;
-    const int tiles = (B + SM_ROWS - 1) / SM_ROWS;
-    hipLaunchKernelGGL(ode_small_em, dim3(tiles < 4096 ? tiles : 4096), dim3(256), lds, s, F, S, (Ws && bs) ? 1 : 0, B, d,
-                       (const EmStep*)ws, n_steps, reverse, xi, seed, y0, out);
-    return cfm_status();
-}
-
-// ------------------------------------------------------------ SF2M: srk (SRI2W1, constant g) ----
-// The scheme torchsde.sdeint runs when no method is given (diagonal Ito noise -> "srk"), which is how the reference's
-// notebooks call it (single-cell_example.ipynb, mnist_example.ipynb, conditional_mnist.ipynb; SF2M_tutorial.ipynb's
-// solver="euler" is an ignored keyword) and what runner/src/models/components/solver.py:169-179 runs for
-// sde_solver: srk.  Per step three evaluations of the field pair, at t, t + h and t + h/2 (sde_srk.h has the
-// scheme); x, k1, k2 stay in registers for the whole trajectory of the tile.  Layout, LDS use and the xi == NULL
-// Philox mode are ode_small_em's; xi != NULL is [n_steps, 2, B, d] (plane 0: xi1, plane 1: xi2) and the trajectory
-// is then bit-equal to the launch-per-step scheme (three forward passes per field + cfm_sde_srk_step_f32).
-__global__ __launch_bounds__(256) void ode_small_srk(SmArgs F, SmArgs S, int has_s, int B, int d,
-                                                     const SrkStep* __restrict__ steps, int n_steps, int reverse,
-                                                     const float* __restrict__ xi, unsigned long long seed,
-                                                     const float* __restrict__ y0, float* __restrict__ out) {
-    extern __shared__ __attribute__((aligned(16))) float small_lds[];
-    float* WlF = small_lds;
-    float* blF = WlF + 4 * SM_W * SM_LD;
-    float* wtF = blF + 4 * SM_W;
-    float* WlS = wtF + SM_W;
-    float* blS = WlS + 4 * SM_W * SM_LD;
-    float* wtS = blS + 4 * SM_W;
-    float* Ab0 = wtS + SM_W;
-    float* Ab1 = Ab0 + SM_ROWS * SM_LD;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    sm_stage_weights(F, d, WlF, blF, wtF, tid);
-    if (has_s) sm_stage_weights(S, d, WlS, blS, wtS, tid);
-    const size_t n = (size_t)B * d;
-    const int col = wv * 16 + (lane & 15);
-    // drift of the pair at (te, y): +-v [+ 1 * s], the sum the launch-per-step kernel forms
-    auto drift = [&](const SmTile& y, float te) {
-        SmTile f = sm_field(y, te, F, d, Ab0, Ab1, WlF, blF, wtF, wv, lane);
-        SmTile sc;
-        if (has_s) sc = sm_field(y, te, S, d, Ab0, Ab1, WlS, blS, wtS, wv, lane);
-#pragma unroll
-        for (int i = 0; i < SM_V; ++i) f.v[i] = srk_drift(reverse ? -f.v[i] : f.v[i], has_s ? sc.v[i] : 0.f, has_s, 1.0f);
-        return f;
-    };
-    for (int row0 = blockIdx.x * SM_ROWS; row0 < B; row0 += gridDim.x * SM_ROWS) {
-        SmTile x;
-#pragma unroll
-        for (int i = 0; i < SM_V; ++i) {
-            const int gr = row0 + sm_row(i, lane);
-            x.v[i] = (gr < B && col < d) ? y0[(size_t)gr * d + col] : 0.f;
-        }
-        __syncthreads();
-        int oidx = 0;
-        for (int k = 0; k < n_steps; ++k) {
-            const SrkStep st = steps[k];
-            static_assert(SM_V == 4, "ode_small_srk draws TWO Philox blocks of 4 normals per lane and step (xi1, xi2): with "
-                                     "SM_MB > 1 elements i and i + 4 would share them (draw 2 SM_V / 4 blocks)");
-            float z1[4] = {0.f, 0.f, 0.f, 0.f}, z2[4] = {0.f, 0.f, 0.f, 0.f};
-            if (xi) {
-#pragma unroll
-                for (int i = 0; i < SM_V; ++i) {
-                    const int gr = row0 + sm_row(i, lane);
-                    if (gr < B && col < d) {
-                        const size_t e = (size_t)gr * d + col;
-                        z1[i] = xi[(size_t)(2 * k) * n + e];
-                        z2[i] = xi[(size_t)(2 * k + 1) * n + e];
-                    }
-                }
-            } else if (st.gs != 0.f) {
-                const unsigned long long elem = (unsigned long long)(row0 / SM_ROWS) * 256 + tid;
-                philox_normal4_w3(seed, (unsigned)k, elem, 0x5f2du, z1);
-                philox_normal4_w3(seed, (unsigned)k, elem, 0x5f2eu, z2);
-            }
-            const SmTile k1 = drift(x, st.te1);
-            SmTile ys;
-#pragma unroll
-            for (int i = 0; i < SM_V; ++i) ys.v[i] = srk_stage2(x.v[i], k1.v[i], st.h);
-            const SmTile k2 = drift(ys, st.te2);
-#pragma unroll
-            for (int i = 0; i < SM_V; ++i) ys.v[i] = srk_stage3(x.v[i], k1.v[i], k2.v[i], st.h, st.c3, z1[i], z2[i]);
-            const SmTile k3 = drift(ys, st.te3);
-#pragma unroll
-            for (int i = 0; i < SM_V; ++i) {
-                const int gr = row0 + sm_row(i, lane);
-                const bool ok = gr < B && col < d;
-                const float r = srk_final(x.v[i], k1.v[i], k2.v[i], k3.v[i], st.h, st.gs, z1[i]);
-                x.v[i] = ok ? r : 0.f;
-                if (st.is_out && ok) out[(size_t)oidx * n + (size_t)gr * d + col] = r;
-            }
-            oidx += st.is_out ? 1 : 0;
-        }
-        __syncthreads();
-    }
-}
-
-// steps_host: n_steps SrkStep records (host); ws: >= 32 n_steps bytes of device scratch.  Everything else as
-// cfm_sde_em_mlp_f32.
-extern "C" int cfm_sde_srk_mlp_f32(const float* const* Wf, const float* const* bf, const float* const* Ws,
-                                   const float* const* bs, const int* dims, int n_layers, const float* y0, int B,
-                                   const void* steps_host, int n_steps, int reverse, const float* xi,
-                                   unsigned long long seed, float* out, void* ws, void* stream) {
-    if (!Wf || !bf || !dims || !y0 || !out || !steps_host || !ws || B < 0 || n_steps < 0) return CFM_EINVAL;
-    if (n_layers != 4) return CFM_EINVAL;
-    const int d = dims[4];
-    if (dims[0] != d + 1 || d > SM_W || d < 1) return CFM_EINVAL;
-    for (int l = 1; l <= 3; ++l) if (dims[l] > SM_W || dims[l] < 1) return CFM_EINVAL;
-    if (B == 0 || n_steps == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    SmArgs F, S;
-    for (int l = 0; l < 4; ++l) { F.W[l] = Wf[l]; F.b[l] = bf[l]; S.W[l] = Ws ? Ws[l] : Wf[l]; S.b[l] = bs ? bs[l] : bf[l]; }
-    for (int l = 0; l < 5; ++l) { F.dims[l] = dims[l]; S.dims[l] = dims[l]; }
-    const size_t lds = sizeof(float) * (2 * (4 * SM_W * SM_LD + 4 * SM_W + SM_W) + 2 * SM_ROWS * SM_LD);
-    const int raised = cfm_once_per_device([] {
-        hipError_t e = hipFuncSetAttribute((const void*)ode_small_srk, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        return (e == hipSuccess) ? 1 : -1;
-    });
-    if (raised < 0) return CFM_EINVAL;
-    static_assert(sizeof(SrkStep) == 32, "the host packs 32-byte records");
-    int rc = cfm_hip(hipMemcpyAsync(ws, steps_host, sizeof(SrkStep) * (size_t)n_steps, hipMemcpyHostToDevice, s));
-    if (rc) return rc;
-    const int tiles = (B + SM_ROWS - 1) / SM_ROWS;
-    hipLaunchKernelGGL(ode_small_srk, dim3(tiles < 4096 ? tiles : 4096), dim3(256), lds, s, F, S, (Ws && bs) ? 1 : 0, B, d,
-                       (const SrkStep*)ws, n_steps, reverse, xi, seed, y0, out);
-    return cfm_status();
-}
+#include "sde_small.h"
 
 // Fixed-step explicit Runge-Kutta (euler / midpoint / rk4: fx_stages<SCHEME>() = 1, 2 or 4 stages) for the same small
 // fields: every step of the tile inside one launch, the stage tiles in registers.  Same arithmetic as the layer driver's
@@ -1414,20 +922,12 @@ template <int SCHEME, int MODE>
 static int ode_fixed_small_t(const float* const* W, const float* const* b, const int* dims, int B, int d,
                              const float* t_span, int n_t, float* traj, float* tspan_dev, const float* eps,
                              hipStream_t s) {
-    SmArgs A;
-    for (int l = 0; l < 4; ++l) { A.W[l] = W[l]; A.b[l] = b[l]; }
-    for (int l = 0; l < 5; ++l) A.dims[l] = dims[l];
-    const size_t lds = sm_lds_bytes(MODE);
-    const int raised = cfm_once_per_device([] {
-        hipError_t e = hipFuncSetAttribute((const void*)ode_small_fixed<SCHEME, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-        return (e == hipSuccess) ? 1 : -1;
-    });
-    if (raised < 0) return CFM_EINVAL;
+    const int grid = small_grid<ode_small_fixed<SCHEME, MODE>, 128 * 1024>(B);
+    if (grid < 0) return CFM_EINVAL;
     int rc = cfm_hip(hipMemcpyAsync(tspan_dev, t_span, sizeof(float) * n_t, hipMemcpyHostToDevice, s));
     if (rc) return rc;
-    const int tiles = (B + SM_ROWS - 1) / SM_ROWS;
-    hipLaunchKernelGGL((ode_small_fixed<SCHEME, MODE>), dim3(tiles < 4096 ? tiles : 4096), dim3(256), lds, s, A, B, d, tspan_dev,
-                       n_t, traj, eps);
+    hipLaunchKernelGGL((ode_small_fixed<SCHEME, MODE>), dim3(grid), dim3(256), small_lds_bytes(1, 2, MODE != AUG_NONE), s,
+                       small_args(W, b, dims), B, d, tspan_dev, n_t, traj, eps);
     return cfm_status();
 }
 
@@ -1485,28 +985,23 @@ __global__ __launch_bounds__(256) void ode_small_div(SmArgs A, int B, int d, con
 template <int MODE>
 static int cnf_eval(const SmArgs& A, int B, int d, const float* x, int ldx, float t, const float* eps, float* v, int ldv,
                     float* div, int lddiv, float dsign, hipStream_t s) {
-    const int raised = cfm_once_per_device([] {
-        hipError_t e = hipFuncSetAttribute((const void*)ode_small_div<MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-        return (e == hipSuccess) ? 1 : -1;
-    });
-    if (raised < 0) return CFM_EINVAL;
-    const int tiles = (B + SM_ROWS - 1) / SM_ROWS;
-    hipLaunchKernelGGL(ode_small_div<MODE>, dim3(tiles < 4096 ? tiles : 4096), dim3(256), sm_lds_bytes(MODE), s, A, B, d, x,
-                       ldx, t, eps, v, ldv, div, lddiv, dsign);
+    const int grid = small_grid<ode_small_div<MODE>, 128 * 1024>(B);
+    if (grid < 0) return CFM_EINVAL;
+    hipLaunchKernelGGL(ode_small_div<MODE>, dim3(grid), dim3(256), small_lds_bytes(1, 2, true), s, A, B, d, x, ldx, t, eps, v, ldv,
+                       div, lddiv, dsign);
     return cfm_status();
 }
 
-// the envelope of the CNF entries: the small-field kernels (4 layers, widths <= 64, [x, t] -> dx), fused path on,
-// mode 0 (exact trace) or 1 (Hutchinson, eps given)
+// the envelope of the CNF entries: the small-field kernels (small_envelope, every width >= 1, d + 1 <= SM_W), fused path
+// on, mode 0 (exact trace) or 1 (Hutchinson, eps given)
 static int cnf_check(const float* const* W, const float* const* b, const int* dims, int n_layers, int B, int mode,
                      const float* eps, int* d_out, SmArgs* A) {
     int d;
     if (!W || !b || B <= 0 || (mode != 0 && mode != 1) || (mode == 1 && !eps)) return CFM_EINVAL;
-    if (n_layers != 4 || check_mlp(dims, n_layers, &d)) return CFM_EINVAL;
-    for (int l = 1; l <= 3; ++l) if (dims[l] < 1 || dims[l] > SM_WMAX) return CFM_EINVAL;
-    if (d < 1 || d + 1 > SM_WMAX || !ode_small_enabled()) return CFM_EINVAL;
-    for (int l = 0; l < 4; ++l) { A->W[l] = W[l]; A->b[l] = b[l]; }
-    for (int l = 0; l < 5; ++l) A->dims[l] = dims[l];
+    if (small_envelope(dims, n_layers, &d)) return CFM_EINVAL;
+    for (int l = 1; l <= 3; ++l) if (dims[l] < 1) return CFM_EINVAL;
+    if (d < 1 || d + 1 > SM_W || !ode_small_enabled()) return CFM_EINVAL;
+    *A = small_args(W, b, dims);
     *d_out = d;
     return 0;
 }

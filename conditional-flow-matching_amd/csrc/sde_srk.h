@@ -1,4 +1,4 @@
-// sde_srk.h — per-element arithmetic of one `srk` step, shared by the one-launch sampler (ode.hip: ode_small_srk)
+// sde_srk.h — per-element arithmetic of one `srk` step, shared by the one-launch sampler (sde_small.h: ode_small_srk)
 // and the launch-per-step kernel (elem.hip: sde_srk_step_kernel).  Both call these helpers and nothing else for the
 // state updates, which is what makes the two paths bit-equal on the same noise.
 //
