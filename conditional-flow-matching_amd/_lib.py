@@ -120,6 +120,8 @@ EXTRA_SIGNATURES = {
     "cfm_assign_debug_lists": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
     "cfm_assign_debug_solver": (_i, [_vp, _i, _vp]),
     "cfm_plan_zero_entries_f64": (_i, [_vp, _vp, _i, _vp]),
+    "cfm_sinkhorn_dispatch_info": (_i, [_i, _i, _i, _vp]),
+    "cfm_sinkhorn_points_dispatch_info": (_i, [_i, _i, _i, _vp]),
     "cfm_ode_set_fused": (None, [_i]),
     "cfm_mlp_set_glds": (None, [_i]),
     "cfm_mlp_get_glds": (_i, []),

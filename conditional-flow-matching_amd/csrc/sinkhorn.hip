@@ -361,8 +361,9 @@ __device__ __forceinline__ void sk_row_fast(const float* __restrict__ row, int B
     for (int seg = 0; seg < B1; seg += 4096) {
         if (seg > 0) {
 #pragma unroll
-            for (int k = 0; k < SK_ROW_PRE; ++k)
-                pre[k] = *reinterpret_cast<const float4*>(row + seg + lane * 4 + 256 * k);
+            for (int k = 0; k < SK_ROW_PRE; ++k)     // (a last segment shorter than 4096 columns: nothing behind the row is read)
+                pre[k] = (seg + 256 * k < B1) ? *reinterpret_cast<const float4*>(row + seg + lane * 4 + 256 * k)
+                                              : make_float4(0.f, 0.f, 0.f, 0.f);
         }
         const int ntrip = min(4096, B1 - seg) / (256 * UT);     // B1 % 1024 == 0
 #pragma unroll
@@ -623,6 +624,53 @@ __global__ void sk_finish(SkState* st, const double* u, const double* v0, const 
     }
 }
 
+// The shape arithmetic of cfm_sinkhorn_log_f32, in one place: which kernels a B0 x B1 problem takes and on what
+// grids.  Pure host arithmetic (no GPU call); the entry point only adds what the runtime decides (noted per field).
+struct SkShape {
+    int vec;             // float4 loads: B1 % 4 == 0 and a 16-byte aligned matrix
+    int row_fast;        // whole 1024-column trips, aligned rows, v fits in LDS: streaming (or one-shot fast) row pass
+    int v_in_lds;        // by size: v (fp64) fits 128 KiB of LDS (0 too when raising the LDS attribute fails)
+    int nchunk, rows_per_chunk;      // row strips of the column pass
+    int rows_per_wg, row_wgs;        // the one-shot / generic row pass
+    int stream_nf4;      // float4 per lane and unit of the streaming row pass (0: not eligible)
+    int stream_want;     // its grid before the cap at CUs x CFM_SK_STREAM workgroups (0 workgroups per CU: one-shot)
+    size_t lds_bytes;    // dynamic LDS of the row pass
+};
+static inline SkShape sk_shape(int B0, int B1, bool m_aligned16) {
+    SkShape sh;
+    sh.nchunk = sk_nchunk(B0, B1);
+    sh.rows_per_chunk = (B0 + sh.nchunk - 1) / sh.nchunk;
+    sh.vec = (((B1 & 3) == 0) && m_aligned16) ? 1 : 0;
+    sh.v_in_lds = ((size_t)B1 * 8 <= 128 * 1024) ? 1 : 0;
+    // fast row pass: whole 1024-column trips, 16-byte aligned rows, v fits in LDS
+    sh.row_fast = (sh.vec && (B1 % 1024 == 0) && sh.v_in_lds) ? 1 : 0;
+    sh.rows_per_wg = sh.row_fast ? SK_RPW : 8;
+    sh.row_wgs = (B0 + sh.rows_per_wg - 1) / sh.rows_per_wg;
+    sh.lds_bytes = sh.v_in_lds ? (size_t)B1 * 8 : 0;
+    sh.stream_nf4 = 0; sh.stream_want = 0;
+    if (sh.row_fast) {
+        // units of 256 * nf4 columns: the largest of 4, 8, 12, 16 float4 per lane that divides the row
+        for (int q = 4; q <= SK_STREAM_UNIT; q += 4)
+            if ((B1 / 256) % q == 0) sh.stream_nf4 = q;
+        sh.stream_want = (B0 + SK_STREAM_WAVES - 1) / SK_STREAM_WAVES;
+    }
+    return sh;
+}
+
+extern "C" int cfm_sinkhorn_dispatch_info(int B0, int B1, int m_aligned16, long long* out16) {
+    if (B0 <= 0 || B1 <= 0 || !out16) return CFM_EINVAL;
+    const SkShape sh = sk_shape(B0, B1, m_aligned16 != 0);
+    const SkWs w = sk_carve((void*)nullptr, B0, B1);
+    const long long o[16] = {sh.vec, sh.row_fast, sh.v_in_lds, sh.nchunk, sh.rows_per_chunk, sh.rows_per_wg, sh.row_wgs,
+                             sh.stream_nf4, sh.stream_want, (long long)sh.lds_bytes,
+                             (long long)(uintptr_t)w.u, (long long)(uintptr_t)w.v[0],
+                             (long long)(uintptr_t)w.v[1], (long long)(uintptr_t)w.pm,
+                             (long long)(uintptr_t)w.ps,
+                             (long long)(uintptr_t)(w.ps + (size_t)sh.nchunk * (size_t)B1)};
+    for (int k = 0; k < 16; ++k) out16[k] = o[k];
+    return 0;
+}
+
 extern "C" int cfm_sinkhorn_log_f32(const float* M, int B0, int B1, double reg, int max_iter,
                                     double stop_thr, int check_every, float* f, float* g,
                                     int* iters_done, float* last_err, void* ws, void* stream) {
@@ -631,20 +679,17 @@ extern "C" int cfm_sinkhorn_log_f32(const float* M, int B0, int B1, double reg, 
     if (((uintptr_t)ws & 15) != 0) return CFM_EALIGN;
     hipStream_t s = (hipStream_t)stream;
     SkWs w = sk_carve(ws, B0, B1);
-    const int nchunk = sk_nchunk(B0, B1);
-    const int rows_per_chunk = (B0 + nchunk - 1) / nchunk;
+    const SkShape sh = sk_shape(B0, B1, ((uintptr_t)M & 15) == 0);
+    const int nchunk = sh.nchunk, rows_per_chunk = sh.rows_per_chunk, vec = sh.vec;
     const int col_tiles = (B1 + 255) / 256;
-    const int vec = ((B1 & 3) == 0) && (((uintptr_t)M & 15) == 0);
     const double inv_reg = 1.0 / reg;
     const double a = 1.0 / B0, b = 1.0 / B1;
     const double precise_below = 1e-4 / sqrt((double)B1);
     const double loga = log(a), logb = log(b);
-    // fast row pass: whole 1024-column trips, 16-byte aligned rows, v fits in LDS
-    const bool row_fast = vec && (B1 % 1024 == 0) && ((size_t)B1 * 8 <= 128 * 1024);
-    const int rows_per_wg = row_fast ? SK_RPW : 8;
-    const int row_wgs = (B0 + rows_per_wg - 1) / rows_per_wg;
-    int v_in_lds = ((size_t)B1 * 8 <= 128 * 1024) ? 1 : 0;
-    if (v_in_lds && (size_t)B1 * 8 > 48 * 1024) {
+    const bool row_fast = sh.row_fast != 0;
+    const int rows_per_wg = sh.rows_per_wg, row_wgs = sh.row_wgs;
+    int v_in_lds = sh.v_in_lds;
+    if (v_in_lds && sh.lds_bytes > 48 * 1024) {
         const int raised = cfm_once_per_device([] {   // dynamic LDS above the 64 KiB default needs the attribute (per device)
             hipError_t e = hipFuncSetAttribute((const void*)sk_row_pass<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
             hipError_t e2 = hipFuncSetAttribute((const void*)sk_row_pass<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
@@ -666,10 +711,8 @@ extern "C" int cfm_sinkhorn_log_f32(const float* M, int B0, int B1, double reg, 
                 if (hipFuncSetAttribute(fns[q], hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess) pc = 0;
             return pc < 0 ? 0 : pc;
         });
-        // units of 256 * nf4 columns: the largest of 4, 8, 12, 16 float4 per lane that divides the row
-        for (int q = 4; q <= SK_STREAM_UNIT; q += 4)
-            if ((B1 / 256) % q == 0) stream_nf4 = q;
-        const int want = (B0 + SK_STREAM_WAVES - 1) / SK_STREAM_WAVES;
+        stream_nf4 = sh.stream_nf4;
+        const int want = sh.stream_want;
         stream_grid = (per_cu > 0 && stream_nf4 > 0) ? (want < cus * per_cu ? want : cus * per_cu) : 0;
     }
 

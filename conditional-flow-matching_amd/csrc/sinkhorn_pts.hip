@@ -253,6 +253,40 @@ static void pts_launch(int grid, size_t lds, hipStream_t s, const float* own, co
                   case 5: pts_launch<5>(__VA_ARGS__); break; case 6: pts_launch<6>(__VA_ARGS__); break; \
                   case 7: pts_launch<7>(__VA_ARGS__); break; default: pts_launch<8>(__VA_ARGS__); break; }
 
+// The shape arithmetic of cfm_sinkhorn_log_points_f32, in one place (pure host arithmetic, no GPU call).
+struct PtsShape {
+    int stage_cap;           // points of the other cloud staged per chunk (whole trips of PTS_STRIDE * PTS_U)
+    int col_grid, row_grid;  // workgroups of the column / row update (PTS_OWN own points each)
+    int trip_u, pre;         // other points per trip and lane, points per thread requested in the prologue
+    size_t lds_bytes;
+};
+static inline PtsShape pts_shape(int B0, int B1, int d) {
+    PtsShape sh;
+    // stage as much of the other cloud as fits 128 KiB of LDS (8 B potential + 4 d B coordinates per point)
+    const int n_max = B0 > B1 ? B0 : B1;
+    int stage_cap = (128 * 1024) / (8 + 4 * d);
+    stage_cap = stage_cap / (PTS_STRIDE * PTS_U) * (PTS_STRIDE * PTS_U);          // whole trips
+    if (stage_cap > n_max) stage_cap = (n_max + PTS_STRIDE * PTS_U - 1) / (PTS_STRIDE * PTS_U) * (PTS_STRIDE * PTS_U);
+    sh.stage_cap = stage_cap;
+    sh.lds_bytes = (size_t)stage_cap * (8 + 4 * d);
+    sh.col_grid = (B1 + PTS_OWN - 1) / PTS_OWN;
+    sh.row_grid = (B0 + PTS_OWN - 1) / PTS_OWN;
+    static_assert(PtsTrip<5>::U == PTS_U && PtsTrip<6>::U == PTS_U / 2, "trip_u below restates PtsTrip<D>::U");
+    sh.trip_u = (d <= 5) ? PTS_U : PTS_U / 2;
+    sh.pre = (d <= 5) ? PTS_PRE : PTS_PRE / 2;      // PRE of sk_pts_pass<D>
+    return sh;
+}
+
+extern "C" int cfm_sinkhorn_points_dispatch_info(int B0, int B1, int d, long long* out8) {
+    if (B0 <= 0 || B1 <= 0 || d < 1 || d > 8 || !out8) return CFM_EINVAL;
+    const PtsShape sh = pts_shape(B0, B1, d);
+    const long long o[8] = {sh.stage_cap, sh.col_grid, sh.row_grid, sh.trip_u, sh.pre, (long long)sh.lds_bytes,
+                            (sh.stage_cap > 0) ? (B0 + sh.stage_cap - 1) / sh.stage_cap : 0,
+                            (sh.stage_cap > 0) ? (B1 + sh.stage_cap - 1) / sh.stage_cap : 0};
+    for (int k = 0; k < 8; ++k) out8[k] = o[k];
+    return 0;
+}
+
 extern "C" int cfm_sinkhorn_log_points_f32(const float* x0, const float* x1, int B0, int B1, int d, double reg,
                                            int max_iter, double stop_thr, int check_every, float* f, float* g,
                                            int* iters_done, float* last_err, void* ws, void* stream) {
@@ -269,12 +303,10 @@ extern "C" int cfm_sinkhorn_log_points_f32(const float* x0, const float* x1, int
     const double a = 1.0 / B0, b = 1.0 / B1;
     const double precise_below = 1e-4 / sqrt((double)B1);
     const double loga = log(a), logb = log(b);
-    // stage as much of the other cloud as fits 128 KiB of LDS (8 B potential + 4 d B coordinates per point)
     const int n_max = B0 > B1 ? B0 : B1;
-    int stage_cap = (128 * 1024) / (8 + 4 * d);
-    stage_cap = stage_cap / (PTS_STRIDE * PTS_U) * (PTS_STRIDE * PTS_U);          // whole trips
-    if (stage_cap > n_max) stage_cap = (n_max + PTS_STRIDE * PTS_U - 1) / (PTS_STRIDE * PTS_U) * (PTS_STRIDE * PTS_U);
-    const size_t lds = (size_t)stage_cap * (8 + 4 * d);
+    const PtsShape sh = pts_shape(B0, B1, d);
+    const int stage_cap = sh.stage_cap;
+    const size_t lds = sh.lds_bytes;
     (void)cfm_once_per_device([] {          // the attribute is per device
         const void* fns[8] = {(const void*)sk_pts_pass<1>, (const void*)sk_pts_pass<2>, (const void*)sk_pts_pass<3>,
                               (const void*)sk_pts_pass<4>, (const void*)sk_pts_pass<5>, (const void*)sk_pts_pass<6>,
@@ -284,7 +316,7 @@ extern "C" int cfm_sinkhorn_log_points_f32(const float* x0, const float* x1, int
     });
     const int n = n_max;
     hipLaunchKernelGGL(sk_pts_init, dim3((n + 255) / 256), dim3(256), 0, s, st, u, v[0], v[1], B0, B1, max_iter);
-    const int col_grid = (B1 + PTS_OWN - 1) / PTS_OWN, row_grid = (B0 + PTS_OWN - 1) / PTS_OWN;
+    const int col_grid = sh.col_grid, row_grid = sh.row_grid;
     const bool poll = max_iter > 4096;
     int host_done = 0;
     for (int ii = 0; ii <= max_iter; ++ii) {

@@ -58,6 +58,15 @@ int cfm_assign_debug_sweep(int mode, const float* M, int n, int blocks, const do
                            unsigned long long* key_out, double* p_out, int* state_out, double* cost_out, void* ws, void* stream);
 void cfm_assign_debug_small(int* out16);                           /* status block of this thread's last one-workgroup solve */
 void cfm_assign_debug_fallback(int* out2);                         /* {solves of this PROCESS (all threads) redone by the dense machine, last device error} */
+/* Kernel selection of the two Sinkhorn entry points for a shape: the host arithmetic the entry points themselves use, no
+ * GPU call.  cfm_sinkhorn_dispatch_info (m_aligned16: the matrix starts on a 16-byte boundary) fills out16 =
+ * {vec, row_fast, v_in_lds (by size), nchunk, rows_per_chunk, rows_per_wg, row_wgs, stream_nf4, stream grid before the
+ * cap at the CU count, LDS bytes of the row pass, then the byte offsets of u, v[0], v[1], pm, ps in the workspace and
+ * the end of ps}.  row_fast = 1 is the streaming row pass (the one-shot fast pass under CFM_SK_STREAM=0), else the
+ * generic one.  cfm_sinkhorn_points_dispatch_info fills out8 = {stage_cap, col_grid, row_grid, other points per trip and
+ * lane, prologue points per thread, LDS bytes, staged chunks of x0, staged chunks of x1}. */
+int cfm_sinkhorn_dispatch_info(int B0, int B1, int m_aligned16, long long* out16);
+int cfm_sinkhorn_points_dispatch_info(int B0, int B1, int d, long long* out8);
 int cfm_plan_zero_entries_f64(double* pi, const int64_t* flat, int n, void* stream);   /* pi.flat[flat[q]] = 0 (sample_map(replace=False) bookkeeping of the mirror) */
 
 #if defined(__GNUC__)
