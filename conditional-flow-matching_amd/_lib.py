@@ -96,6 +96,10 @@ SIGNATURES = {
                                          _vp, _vp]),
     "cfm_ode_fixed_cnf_mlp_f32": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "cfm_cnf_euler_grad_f32": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cfm_mlp_grad_field_f32": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _f, _vp, _vp, _vp, _vp]),
+    "cfm_ode_fixed_gradmlp_f32": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "cfm_ode_adaptive_gradmlp_f32": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp]),
+    "cfm_ode_fixed_cnf_gradmlp_f32": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
 }
 # solver selectors of the cfm_ode_adaptive_* / cfm_ode_fixed_* entries (include/cfm_gfx950.h)
 ODE_TABLEAU = {"dopri5": 0, "tsit5": 1}

@@ -11,7 +11,10 @@ Counterpart of the reference's density evaluation:
 For ``MLP(time_varying=True)`` fields of the small-kernel envelope (4 layers, widths <= 64) on fp32
 inputs the divergence runs in the HIP kernel ``cfm_mlp_divergence_f32``, and ``NeuralODE(CNF(mlp))``
 integrates the augmented state in one persistent launch (``cfm_ode_euler_cnf_mlp_f32`` /
-``cfm_ode_dopri5_cnf_mlp_f32``).  Anything else is evaluated with ``torch.func`` in the input's dtype.
+``cfm_ode_dopri5_cnf_mlp_f32``).  For the action-matching field ``GradModel(MLP(dim, out_dim=1, time_varying=True))`` of
+that envelope with the exact trace, ``-div`` is minus the Laplacian of the action: one evaluation runs in
+``cfm_mlp_grad_field_f32`` and a fixed-step ``NeuralODE(CNF(GradModel(mlp)))`` in ``cfm_ode_fixed_cnf_gradmlp_f32``
+(DESIGN.md 4.10).  Anything else is evaluated with ``torch.func`` in the input's dtype.
 
 Training by maximum likelihood (the tutorial's cell 5: ``NeuralODE(cnf_wrapper(model, "exact"), solver="euler",
 sensitivity="adjoint")``, ``loss.backward()``) is ``DifferentiableCNF``: the Euler solve of the augmented state with a
@@ -32,7 +35,7 @@ import torch
 
 from . import _lib
 from ._lib import ptr, stream_ptr
-from .models import MLP
+from .models import MLP, GradModel
 from .utils import torch_wrapper
 
 ESTIMATORS = ("exact", "hutch_gaussian", "hutch_rademacher")
@@ -94,11 +97,23 @@ class CNF(torch.nn.Module):
         """The MLP when the HIP kernels take this field at state width d, else None."""
         return self.model if _small_envelope(self.model, d) else None
 
+    def hip_grad(self, d):
+        """The action MLP when the field is a GradModel that the gradient-field kernels take at state width d with
+        the exact trace, else None."""
+        if isinstance(self.model, GradModel) and self.estimator == "exact":
+            return self.model.hip_action(d)
+        return None
+
     # ---- evaluation ----
     def forward(self, t, x):
         y = x[:, 1:]
         eps = self._probe(y)
         d = y.shape[1]
+        a = self.hip_grad(d)
+        if a is not None and x.dim() == 2 and x.dtype == torch.float32 and torch.cuda.is_available():
+            got = self.model.field_hip(a, y, float(torch.as_tensor(t).reshape(-1)[0]), laplacian=True)
+            if got is not None:
+                return torch.cat([-got[1][:, None], got[0]], 1).to(x.device)
         m = self.hip_mlp(d)
         if (m is not None and x.dtype == torch.float32 and torch.cuda.is_available()
                 and all(p.dtype == torch.float32 for p in m.parameters())):

@@ -1,5 +1,5 @@
 // cnf_grad.h — gradient of the Euler solve of the augmented CNF state (included by ode.hip; the tile engine it runs on
-// comes from small_field.h: SmTile, sm_gemm, sm_stage_weights, selu_f, selu_slope, small_grid; cnf_check from ode.hip).
+// comes from small_field.h: SmTile, sm_gemm, cg_gemm_t, sm_stage_weights, selu_f, selu_slope, small_grid; cnf_check from ode.hip).
 //
 // Forward (ode_small_fixed<CFM_ODE_EULER, MODE>):  y_{n+1} = y_n + h_n v(y_n, t_n),  l_{n+1} = l_n - h_n div(y_n, t_n).
 // Given G = dL/d[l_N, y_N]:  c = G[:, 0] never changes (l enters linearly), a_N = G[:, 1:], and for n = N-1 .. 0
@@ -38,20 +38,6 @@ extern "C" size_t cfm_cnf_grad_ws_bytes_internal(int B, int n_t) {
 __device__ __forceinline__ void cg_put(float* __restrict__ buf, const SmTile& v, int lane, int col) {
 #pragma unroll
     for (int i = 0; i < SM_V; ++i) buf[sm_row(i, lane) * SM_LD + col] = v.v[i];
-}
-
-// out(C layout) = A[16 x 64] * M, M = the staged [64][SM_LD] matrix read by columns: out[r][n] = sum_k A[r][k] M[k][n]
-__device__ __forceinline__ void cg_gemm_t(const float* __restrict__ Abuf, const float* __restrict__ M, int wv, int lane,
-                                          f32x4& c) {
-    c = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int fr = lane & 15, fk = lane >> 4;
-    const float* ap = Abuf + fr * SM_LD + fk;
-    const float* bp = M + fk * SM_LD + wv * 16 + fr;
-    float a[SM_W / 4], b[SM_W / 4];
-#pragma unroll
-    for (int j = 0; j < SM_W / 4; ++j) { a[j] = ap[4 * j]; b[j] = bp[4 * j * SM_LD]; }
-#pragma unroll
-    for (int j = 0; j < SM_W / 4; ++j) c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j], b[j], c, 0, 0, 0);
 }
 
 // acc[mb](C layout of block mb) += Z^T H over the 16 rows of the tile: element i of lane -> dW[16 mb + 4 (lane >> 4) + i]

@@ -16,6 +16,7 @@
 //           fp32 (one 8-byte read-back per step attempt).
 #include "cfm_common.h"
 #include "small_field.h"
+#include "grad_field.h"
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -328,16 +329,17 @@ static int read_red(hipStream_t s, const double* dev, int count, double* host) {
     return 0;
 }
 
-template <int TAB, int MODE>
+template <int TAB, int MODE, int FIELD>
 static int ode_dopri5_small(const float* const* W, const float* const* b, const int* dims, int B, int d,
                             const float* t_span, int n_t, float tsign, const float* eps, float atol, float rtol,
                             float* traj, int* n_steps, int* nfe, float* xbuf, float* kbuf, float* tspan_dev,
                             void* state_dev, char* sync_dev, float t0, float dt0, int evals0, hipStream_t s);
 
 // the tableau selector (validated by the entry points) picks the instantiation
-template <int MODE, class... Args>
+template <int MODE, int FIELD = FIELD_MLP, class... Args>
 static int ode_adaptive_small(int tab, Args... args) {
-    return tab == CFM_ODE_TSIT5 ? ode_dopri5_small<CFM_ODE_TSIT5, MODE>(args...) : ode_dopri5_small<CFM_ODE_DOPRI5, MODE>(args...);
+    return tab == CFM_ODE_TSIT5 ? ode_dopri5_small<CFM_ODE_TSIT5, MODE, FIELD>(args...)
+                                : ode_dopri5_small<CFM_ODE_DOPRI5, MODE, FIELD>(args...);
 }
 
 // Time direction of a t_span (torchdyn's rule): a strictly decreasing grid is integrated as
@@ -574,8 +576,9 @@ __device__ __forceinline__ bool sm_grid_allsum(double* __restrict__ row, double 
 // workgroup stores its fp64 partial, one grid rendezvous, and then every workgroup adds the partials up in
 // the same fixed order (so the solve is reproducible bit for bit), derives the same accept / reject
 // decision and next step size from that sum (the fp32 controller of the host loop above).  `lines` is only
-// touched by SM_PROF builds (phase stamps).
-template <int TAB, bool RESIDENT, int MODE>
+// touched by SM_PROF builds (phase stamps).  FIELD: what the stage evaluations call (FIELD_GRAD: grad_field.h, plain
+// solves only); everything around the call is the same code.
+template <int TAB, bool RESIDENT, int MODE, int FIELD = FIELD_MLP>
 __global__ __launch_bounds__(256) void ode_small_dopri(SmArgs A, int B, int d, SmState* __restrict__ st_io,
                                                     float* __restrict__ xbuf, float* __restrict__ kbuf,
                                                     const float* __restrict__ tspan, int n_t, float atol, float rtol,
@@ -585,6 +588,7 @@ __global__ __launch_bounds__(256) void ode_small_dopri(SmArgs A, int B, int d, S
     // MODE != AUG_NONE: the state is [B, 1 + d] (column 0 = l, the log-density accumulator, d l / dt = -div); each
     // row's l and its stage values sit in the registers of every lane that holds the row
     constexpr bool AUG = MODE != AUG_NONE;
+    static_assert(FIELD == FIELD_MLP || !AUG, "the gradient field has fixed-step augmented solves only");
     extern __shared__ __attribute__((aligned(16))) float small_lds[];
     float* Wl = small_lds;                           // [4][64][SM_LD]
     float* bl = Wl + 4 * SM_W * SM_LD;               // [4][64]
@@ -671,6 +675,9 @@ __global__ __launch_bounds__(256) void ode_small_dopri(SmArgs A, int B, int d, S
                     SmTile dv;                                                                       \
                     KOUT = sm_field_aug<MODE>(y, tf, A, d, Ab0, Ab1, Wl, bl, wt, ep, B - row0, red, wv, lane, dv); \
                     _Pragma("unroll") for (int i = 0; i < SM_V; ++i) LOUT.v[i] = -dv.v[i];         \
+                } else if constexpr (FIELD == FIELD_GRAD) {                                          \
+                    SmTile dv;                                                                       \
+                    KOUT = gf_field<false>(y, tf, A, d, Ab0, Ab1, Wl, bl, wt, B - row0, red, wv, lane, dv); \
                 } else {                                                                             \
                     KOUT = sm_field(y, tf, A, d, Ab0, Ab1, Wl, bl, wt, wv, lane);                    \
                 }                                                                                    \
@@ -772,22 +779,22 @@ __global__ __launch_bounds__(256) void ode_small_dopri(SmArgs A, int B, int d, S
     if (blockIdx.x == 0 && tid == 0) { st.pad = err; st_io[1] = st; }
 }
 
-template <int TAB, int MODE>
+template <int TAB, int MODE, int FIELD>
 static int ode_dopri5_small(const float* const* W, const float* const* b, const int* dims, int B, int d,
                             const float* t_span, int n_t, float tsign, const float* eps, float atol, float rtol,
                             float* traj, int* n_steps, int* nfe, float* xbuf, float* kbuf, float* tspan_dev,
                             void* state_dev, char* sync_dev, float t0, float dt0, int evals0, hipStream_t s) {
     const SmArgs A = small_args(W, b, dims);
     constexpr size_t lds = small_lds_bytes(1, 2, MODE != AUG_NONE);
-    // (one result per TAB and MODE: the grid is sized from the occupancy of the instantiation that is launched)
+    // (one result per TAB, MODE and FIELD: the grid is sized from the occupancy of the instantiation that is launched)
     const int resident = cfm_once_per_device([] {
-        hipError_t e = hipFuncSetAttribute((const void*)ode_small_dopri<TAB, true, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-        hipError_t e2 = hipFuncSetAttribute((const void*)ode_small_dopri<TAB, false, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+        hipError_t e = hipFuncSetAttribute((const void*)ode_small_dopri<TAB, true, MODE, FIELD>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+        hipError_t e2 = hipFuncSetAttribute((const void*)ode_small_dopri<TAB, false, MODE, FIELD>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
         // workgroups that can be resident at once: the grid rendezvous needs grid <= this
         int pa = 0, pb = 0;
         if (e == hipSuccess && e2 == hipSuccess &&
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&pa, (const void*)ode_small_dopri<TAB, true, MODE>, 256, lds) == hipSuccess &&
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&pb, (const void*)ode_small_dopri<TAB, false, MODE>, 256, lds) == hipSuccess &&
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&pa, (const void*)ode_small_dopri<TAB, true, MODE, FIELD>, 256, lds) == hipSuccess &&
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&pb, (const void*)ode_small_dopri<TAB, false, MODE, FIELD>, 256, lds) == hipSuccess &&
             pa > 0 && pb > 0)
             return cfm_device_cus() * (pa < pb ? pa : pb);
         return -1;
@@ -813,10 +820,10 @@ static int ode_dopri5_small(const float* const* W, const float* const* b, const 
     // CFM_ETIMEOUT after 4 s).  The call is synchronous anyway: the lock is held until the solve has finished.
     std::lock_guard<std::mutex> persistent_lock(g_persistent_mu);
     if (tiles <= grid)
-        hipLaunchKernelGGL((ode_small_dopri<TAB, true, MODE>), dim3(grid), dim3(256), lds, s, A, B, d, st, xbuf, kbuf, tspan_dev, n_t,
+        hipLaunchKernelGGL((ode_small_dopri<TAB, true, MODE, FIELD>), dim3(grid), dim3(256), lds, s, A, B, d, st, xbuf, kbuf, tspan_dev, n_t,
                            atol, rtol, traj, partial, lines, 1000000, tsign, eps);
     else
-        hipLaunchKernelGGL((ode_small_dopri<TAB, false, MODE>), dim3(grid), dim3(256), lds, s, A, B, d, st, xbuf, kbuf, tspan_dev, n_t,
+        hipLaunchKernelGGL((ode_small_dopri<TAB, false, MODE, FIELD>), dim3(grid), dim3(256), lds, s, A, B, d, st, xbuf, kbuf, tspan_dev, n_t,
                            atol, rtol, traj, partial, lines, 1000000, tsign, eps);
     rc = cfm_status();
     if (rc) return rc;
@@ -839,8 +846,8 @@ static int ode_dopri5_small(const float* const* W, const float* const* b, const 
 // euler that is fmaf(dt, 1.f * k, x).  A decreasing t_span needs nothing else: dt < 0 steps it, bit for bit the forward
 // solve of -f(-s, x) on s = -t_span.  MODE != AUG_NONE: the trajectory is [n_t, B, 1 + d] with column 0 = l, whose
 // stage derivatives are -div f at the stage points (the field does not read l, so l has no stage states); the x columns
-// are bitwise those of the plain solve.
-template <int SCHEME, int MODE>
+// are bitwise those of the plain solve.  FIELD_GRAD: the field is grad_field.h's; AUG_EXACT carries its Laplacian.
+template <int SCHEME, int MODE, int FIELD = FIELD_MLP>
 __global__ __launch_bounds__(256) void ode_small_fixed(SmArgs A, int B, int d, const float* __restrict__ tspan, int n_t,
                                                     float* __restrict__ traj, const float* __restrict__ eps) {
     constexpr bool AUG = MODE != AUG_NONE;
@@ -889,7 +896,15 @@ __global__ __launch_bounds__(256) void ode_small_fixed(SmArgs A, int B, int d, c
                     }
                     tsg = t + (float)fx_c<SCHEME>(sg - 1) * dt;
                 }
-                if constexpr (AUG) {
+                if constexpr (FIELD == FIELD_GRAD) {
+                    static_assert(FIELD == FIELD_MLP || MODE != AUG_HUTCH, "exact trace only");
+                    SmTile dv;
+                    f[sg] = gf_field<AUG>(y, tsg, A, d, Ab0, Ab1, Wl, bl, wt, B - row0, red, wv, lane, dv);
+                    if constexpr (AUG) {
+#pragma unroll
+                        for (int i = 0; i < SM_V; ++i) lf[sg].v[i] = -dv.v[i];
+                    }
+                } else if constexpr (AUG) {
                     SmTile dv;
                     f[sg] = sm_field_aug<MODE>(y, tsg, A, d, Ab0, Ab1, Wl, bl, wt, ep, B - row0, red, wv, lane, dv);
 #pragma unroll
@@ -918,26 +933,26 @@ __global__ __launch_bounds__(256) void ode_small_fixed(SmArgs A, int B, int d, c
     }
 }
 
-template <int SCHEME, int MODE>
+template <int SCHEME, int MODE, int FIELD>
 static int ode_fixed_small_t(const float* const* W, const float* const* b, const int* dims, int B, int d,
                              const float* t_span, int n_t, float* traj, float* tspan_dev, const float* eps,
                              hipStream_t s) {
-    const int grid = small_grid<ode_small_fixed<SCHEME, MODE>, 128 * 1024>(B);
+    const int grid = small_grid<ode_small_fixed<SCHEME, MODE, FIELD>, 128 * 1024>(B);
     if (grid < 0) return CFM_EINVAL;
     int rc = cfm_hip(hipMemcpyAsync(tspan_dev, t_span, sizeof(float) * n_t, hipMemcpyHostToDevice, s));
     if (rc) return rc;
-    hipLaunchKernelGGL((ode_small_fixed<SCHEME, MODE>), dim3(grid), dim3(256), small_lds_bytes(1, 2, MODE != AUG_NONE), s,
+    hipLaunchKernelGGL((ode_small_fixed<SCHEME, MODE, FIELD>), dim3(grid), dim3(256), small_lds_bytes(1, 2, MODE != AUG_NONE), s,
                        small_args(W, b, dims), B, d, tspan_dev, n_t, traj, eps);
     return cfm_status();
 }
 
 // the scheme selector (validated by the entry points) picks the instantiation
-template <int MODE>
+template <int MODE, int FIELD = FIELD_MLP>
 static int ode_fixed_small_m(int scheme, const float* const* W, const float* const* b, const int* dims, int B, int d,
                              const float* t_span, int n_t, float* traj, float* tspan_dev, const float* eps, hipStream_t s) {
-    if (scheme == CFM_ODE_RK4) return ode_fixed_small_t<CFM_ODE_RK4, MODE>(W, b, dims, B, d, t_span, n_t, traj, tspan_dev, eps, s);
-    if (scheme == CFM_ODE_MIDPOINT) return ode_fixed_small_t<CFM_ODE_MIDPOINT, MODE>(W, b, dims, B, d, t_span, n_t, traj, tspan_dev, eps, s);
-    return ode_fixed_small_t<CFM_ODE_EULER, MODE>(W, b, dims, B, d, t_span, n_t, traj, tspan_dev, eps, s);
+    if (scheme == CFM_ODE_RK4) return ode_fixed_small_t<CFM_ODE_RK4, MODE, FIELD>(W, b, dims, B, d, t_span, n_t, traj, tspan_dev, eps, s);
+    if (scheme == CFM_ODE_MIDPOINT) return ode_fixed_small_t<CFM_ODE_MIDPOINT, MODE, FIELD>(W, b, dims, B, d, t_span, n_t, traj, tspan_dev, eps, s);
+    return ode_fixed_small_t<CFM_ODE_EULER, MODE, FIELD>(W, b, dims, B, d, t_span, n_t, traj, tspan_dev, eps, s);
 }
 
 static int ode_fixed_small(int scheme, const float* const* W, const float* const* b, const int* dims, int B, int d,
@@ -947,7 +962,8 @@ static int ode_fixed_small(int scheme, const float* const* W, const float* const
 
 // ---- CNF: one evaluation of [v, div] (the tile kernel of the augmented solves, once) --------------------------
 // x: rows of stride ldx (d values each); v: rows of stride ldv; div[row * lddiv] = dsign * div.
-template <int MODE>
+// FIELD_GRAD: v = grad_x s and div = its Laplacian (AUG_EXACT), or v alone (AUG_NONE: div is not touched).
+template <int MODE, int FIELD = FIELD_MLP>
 __global__ __launch_bounds__(256) void ode_small_div(SmArgs A, int B, int d, const float* __restrict__ x, int ldx,
                                                   float t, const float* __restrict__ eps, float* __restrict__ v,
                                                   int ldv, float* __restrict__ div, int lddiv, float dsign) {
@@ -971,23 +987,26 @@ __global__ __launch_bounds__(256) void ode_small_div(SmArgs A, int B, int d, con
             ep.v[i] = (MODE == AUG_HUTCH && ok) ? eps[(size_t)gr * d + col] : 0.f;
         }
         __syncthreads();
-        SmTile dv;
-        const SmTile f = sm_field_aug<MODE>(y, t, A, d, Ab0, Ab1, Wl, bl, wt, ep, B - row0, red, wv, lane, dv);
+        SmTile dv, f;
+        if constexpr (FIELD == FIELD_GRAD) f = gf_field<MODE == AUG_EXACT>(y, t, A, d, Ab0, Ab1, Wl, bl, wt, B - row0, red, wv, lane, dv);
+        else f = sm_field_aug<MODE>(y, t, A, d, Ab0, Ab1, Wl, bl, wt, ep, B - row0, red, wv, lane, dv);
 #pragma unroll
         for (int i = 0; i < SM_V; ++i) {
             const int gr = row0 + sm_row(i, lane);
             if (gr < B && col < d) v[(size_t)gr * ldv + col] = f.v[i];
-            if (gr < B && wv == 0 && (lane & 15) == 0) div[(size_t)gr * lddiv] = dsign * dv.v[i];
+            if constexpr (MODE != AUG_NONE) {
+                if (gr < B && wv == 0 && (lane & 15) == 0) div[(size_t)gr * lddiv] = dsign * dv.v[i];
+            }
         }
     }
 }
 
-template <int MODE>
+template <int MODE, int FIELD = FIELD_MLP>
 static int cnf_eval(const SmArgs& A, int B, int d, const float* x, int ldx, float t, const float* eps, float* v, int ldv,
                     float* div, int lddiv, float dsign, hipStream_t s) {
-    const int grid = small_grid<ode_small_div<MODE>, 128 * 1024>(B);
+    const int grid = small_grid<ode_small_div<MODE, FIELD>, 128 * 1024>(B);
     if (grid < 0) return CFM_EINVAL;
-    hipLaunchKernelGGL(ode_small_div<MODE>, dim3(grid), dim3(256), small_lds_bytes(1, 2, true), s, A, B, d, x, ldx, t, eps, v, ldv,
+    hipLaunchKernelGGL((ode_small_div<MODE, FIELD>), dim3(grid), dim3(256), small_lds_bytes(1, 2, true), s, A, B, d, x, ldx, t, eps, v, ldv,
                        div, lddiv, dsign);
     return cfm_status();
 }
@@ -1004,6 +1023,17 @@ static int cnf_check(const float* const* W, const float* const* b, const int* di
     *A = small_args(W, b, dims);
     *d_out = d;
     return 0;
+}
+
+// a fixed-step grid: strictly monotone, either way
+static int fx_monotone(const float* t_span, int n_t) {
+    for (int k = 0; k + 1 < n_t; ++k)
+        if (!(t_span[k + 1] > t_span[k]) && !(t_span[k + 1] < t_span[k])) return 0;
+    if (n_t > 2) {
+        const int up = t_span[1] > t_span[0];
+        for (int k = 1; k + 1 < n_t; ++k) if ((t_span[k + 1] > t_span[k]) != up) return 0;
+    }
+    return 1;
 }
 
 extern "C" int cfm_mlp_divergence_f32(const float* const* W, const float* const* b, const int* dims, int n_layers,
@@ -1026,12 +1056,7 @@ extern "C" int cfm_ode_fixed_cnf_mlp_f32(const float* const* W, const float* con
     if (!x0 || !t_span || !traj || !ws || n_t < 1 || !fx_known(scheme)) return CFM_EINVAL;
     int rc = cnf_check(W, b, dims, n_layers, B, mode, eps, &d, &A);
     if (rc) return rc;
-    for (int k = 0; k + 1 < n_t; ++k)                  // strictly monotone, either way
-        if (!(t_span[k + 1] > t_span[k]) && !(t_span[k + 1] < t_span[k])) return CFM_EINVAL;
-    if (n_t > 2) {
-        const int up = t_span[1] > t_span[0];
-        for (int k = 1; k + 1 < n_t; ++k) if ((t_span[k + 1] > t_span[k]) != up) return CFM_EINVAL;
-    }
+    if (!fx_monotone(t_span, n_t)) return CFM_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     const int width = maxwidth(dims, n_layers);
     OdeWs w = ode_carve(ws, B, width, d + 1);          // workspace of CFM_OP_ODE at d + 1
@@ -1051,19 +1076,22 @@ extern "C" int cfm_ode_euler_cnf_mlp_f32(const float* const* W, const float* con
     return cfm_ode_fixed_cnf_mlp_f32(W, b, dims, n_layers, x0, B, t_span, n_t, mode, eps, CFM_ODE_EULER, traj, nfe, ws, stream);
 }
 
-template <int MODE>
+// Adaptive solve of a small field whose first evaluations and initial step come from the one-evaluation kernel:
+// the augmented MLP field (state [B, 1 + d]) and the plain gradient field (state [B, d]).
+template <int MODE, int FIELD = FIELD_MLP>
 static int cnf_dopri5(int tab, const SmArgs& A, const float* const* W, const float* const* b, const int* dims, int d,
                       const float* x0, int B, const float* ts, int n_t, float tsign, const float* eps, float atol,
                       float rtol, float* traj, int* n_steps, int* nfe, void* ws, hipStream_t s) {
-    const int D = d + 1;
-    OdeWs w = ode_carve(ws, B, maxwidth(dims, 4), D);  // workspace of CFM_OP_ODE at d + 1: every buffer is [B, 1 + d]
+    const int D = MODE != AUG_NONE ? d + 1 : d;
+    OdeWs w = ode_carve(ws, B, maxwidth(dims, 4), D);  // workspace of CFM_OP_ODE at D: every buffer is [B, D]
     const size_t n = (size_t)B * D;
     if (n < (size_t)n_t) return CFM_EINVAL;            // t_span copy: w.xt
     int evals = 0;
-    // augmented field in solver time: k = [-div, v] at tsign * t (the sign of g = -f(-s, .) rides on the coefficients)
+    // the field in solver time, at tsign * t (the sign of g = -f(-s, .) rides on the coefficients); augmented: k = [-div, v]
     auto f = [&](float t, const float* xin, float* kout) -> int {
         ++evals;
-        return cnf_eval<MODE>(A, B, d, xin + 1, D, tsign * t, eps, kout + 1, D, kout, D, -1.f, s);
+        if constexpr (MODE == AUG_NONE) return cnf_eval<MODE, FIELD>(A, B, d, xin, D, tsign * t, eps, kout, D, nullptr, 0, 0.f, s);
+        else return cnf_eval<MODE, FIELD>(A, B, d, xin + 1, D, tsign * t, eps, kout + 1, D, kout, D, -1.f, s);
     };
     int rc = cfm_hip(hipMemcpyAsync(w.x, x0, n * sizeof(float), hipMemcpyDeviceToDevice, s));
     if (rc) return rc;
@@ -1075,8 +1103,8 @@ static int cnf_dopri5(int tab, const SmArgs& A, const float* const* W, const flo
     float dt;
     rc = ode_init_step(f, n, t, tsign, atol, rtol, w, s, &dt);   // d0, d1, d2 over all B (1 + d) elements
     if (rc) return rc;
-    return ode_adaptive_small<MODE>(tab, W, b, dims, B, d, ts, n_t, tsign, eps, atol, rtol, traj, n_steps, nfe, w.x, w.k[0], w.xt,
-                                  (void*)(w.red + 16), w.sync, t, dt, evals, s);
+    return ode_adaptive_small<MODE, FIELD>(tab, W, b, dims, B, d, ts, n_t, tsign, eps, atol, rtol, traj, n_steps, nfe, w.x, w.k[0],
+                                         w.xt, (void*)(w.red + 16), w.sync, t, dt, evals, s);
 }
 
 extern "C" int cfm_ode_adaptive_cnf_mlp_f32(const float* const* W, const float* const* b, const int* dims, int n_layers,
@@ -1107,6 +1135,87 @@ extern "C" int cfm_ode_dopri5_cnf_mlp_f32(const float* const* W, const float* co
                                           int* nfe, void* ws, void* stream) {
     return cfm_ode_adaptive_cnf_mlp_f32(W, b, dims, n_layers, x0, B, t_span, n_t, mode, eps, CFM_ODE_DOPRI5, atol, rtol, traj,
                                         n_steps, nfe, ws, stream);
+}
+
+// ---- action matching: v = grad_x s(x, t) of a scalar action net (grad_field.h) -------------------------------------
+// The envelope of the gradient-field entries: 4 layers [d + 1, n1, n2, n3, 1], 1 <= every width <= SM_W, d + 1 <= SM_W,
+// fused path on.  There is no layer-per-kernel form of this field.
+static int grad_check(const float* const* W, const float* const* b, const int* dims, int n_layers, int B, int* d_out,
+                      SmArgs* A) {
+    if (!W || !b || !dims || B <= 0 || n_layers != 4) return CFM_EINVAL;
+    const int d = dims[0] - 1;
+    if (dims[4] != 1 || d < 1 || d + 1 > SM_W) return CFM_EINVAL;
+    for (int l = 1; l <= 3; ++l) if (dims[l] < 1 || dims[l] > SM_W) return CFM_EINVAL;
+    if (!ode_small_enabled()) return CFM_EINVAL;
+    *A = small_args(W, b, dims);
+    *d_out = d;
+    return 0;
+}
+
+extern "C" int cfm_mlp_grad_field_f32(const float* const* W, const float* const* b, const int* dims, int n_layers,
+                                      const float* x, int ldx, int B, float t, float* v, float* lap, void* ws,
+                                      void* stream) {
+    int d; SmArgs A;
+    (void)ws;
+    if (!x || !v) return CFM_EINVAL;
+    int rc = grad_check(W, b, dims, n_layers, B, &d, &A);
+    if (rc) return rc;
+    if (ldx < d) return CFM_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    return lap ? cnf_eval<AUG_EXACT, FIELD_GRAD>(A, B, d, x, ldx, t, nullptr, v, d, lap, 1, 1.f, s)
+               : cnf_eval<AUG_NONE, FIELD_GRAD>(A, B, d, x, ldx, t, nullptr, v, d, nullptr, 0, 0.f, s);
+}
+
+// D = d (plain) or d + 1 (augmented, MODE = AUG_EXACT): the state width of x0 / traj and of the CFM_OP_ODE workspace
+template <int MODE>
+static int grad_fixed(const float* const* W, const float* const* b, const int* dims, int n_layers, const float* x0, int B,
+                      const float* t_span, int n_t, int scheme, float* traj, int* nfe, void* ws, void* stream) {
+    int d; SmArgs A;
+    if (!x0 || !t_span || !traj || !ws || n_t < 1 || !fx_known(scheme)) return CFM_EINVAL;
+    int rc = grad_check(W, b, dims, n_layers, B, &d, &A);
+    if (rc) return rc;
+    if (!fx_monotone(t_span, n_t)) return CFM_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const int D = MODE != AUG_NONE ? d + 1 : d;
+    OdeWs w = ode_carve(ws, B, maxwidth(dims, n_layers), D);
+    const size_t n = (size_t)B * D;
+    if ((size_t)n_t > 3 * n) return CFM_EINVAL;        // t_span copy: w.x .. w.xt
+    rc = cfm_hip(hipMemcpyAsync(traj, x0, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (rc) return rc;
+    if (nfe) *nfe = fx_stages_host(scheme) * (n_t - 1);
+    if (n_t < 2) return 0;
+    return ode_fixed_small_m<MODE, FIELD_GRAD>(scheme, W, b, dims, B, d, t_span, n_t, traj, w.x, nullptr, s);
+}
+
+extern "C" int cfm_ode_fixed_gradmlp_f32(const float* const* W, const float* const* b, const int* dims, int n_layers,
+                                         const float* x0, int B, const float* t_span, int n_t, int scheme, float* traj,
+                                         int* nfe, void* ws, void* stream) {
+    return grad_fixed<AUG_NONE>(W, b, dims, n_layers, x0, B, t_span, n_t, scheme, traj, nfe, ws, stream);
+}
+
+extern "C" int cfm_ode_fixed_cnf_gradmlp_f32(const float* const* W, const float* const* b, const int* dims, int n_layers,
+                                             const float* x0, int B, const float* t_span, int n_t, int mode,
+                                             const float* eps, int scheme, float* traj, int* nfe, void* ws, void* stream) {
+    (void)eps;
+    if (mode != 0) return CFM_EINVAL;                  // the exact trace only
+    return grad_fixed<AUG_EXACT>(W, b, dims, n_layers, x0, B, t_span, n_t, scheme, traj, nfe, ws, stream);
+}
+
+extern "C" int cfm_ode_adaptive_gradmlp_f32(const float* const* W, const float* const* b, const int* dims, int n_layers,
+                                            const float* x0, int B, const float* t_span, int n_t, int tableau, float atol,
+                                            float rtol, float* traj, int* n_steps, int* nfe, void* ws, void* stream) {
+    int d; SmArgs A;
+    if (!x0 || !t_span || !traj || !ws || n_t < 2 || !rk_adaptive_known(tableau)) return CFM_EINVAL;
+    int rc = grad_check(W, b, dims, n_layers, B, &d, &A);
+    if (rc) return rc;
+    float* ts = (float*)malloc(sizeof(float) * (size_t)n_t);
+    if (!ts) return CFM_EINVAL;
+    const float tsign = ode_direction(t_span, n_t, ts);
+    rc = tsign == 0.f ? CFM_EINVAL
+                      : cnf_dopri5<AUG_NONE, FIELD_GRAD>(tableau, A, W, b, dims, d, x0, B, ts, n_t, tsign, nullptr, atol, rtol,
+                                                         traj, n_steps, nfe, ws, (hipStream_t)stream);
+    free(ts);
+    return rc;
 }
 
 // ---- CNF training: the gradient of the Euler augmented solve (ode_small_euler_grad, cfm_cnf_euler_grad_f32) ----

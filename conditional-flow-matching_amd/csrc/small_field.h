@@ -1,5 +1,5 @@
 // small_field.h — the 16-row tile engine of the fused small-field kernels of ode.hip, sde_small.h and cnf_grad.h
-// (SmTile, sm_gemm, sm_field, sm_field_aug, weights staged in LDS), its LDS byte count, envelope check, launch helper.
+// (SmTile, sm_gemm, cg_gemm_t, sm_field, sm_field_aug, weights staged in LDS), its LDS byte count, envelope check, launch helper.
 #pragma once
 #include "cfm_common.h"
 
@@ -68,6 +68,20 @@ __device__ __forceinline__ void sm_gemm(const float* __restrict__ Abuf, const fl
 #pragma unroll
         for (int m = 0; m < SM_MB; ++m) c[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[m][j], b[j], c[m], 0, 0, 0);
     }
+}
+
+// out(C layout) = A[16 x 64] * M, M = the staged [64][SM_LD] matrix read by columns: out[r][n] = sum_k A[r][k] M[k][n]
+__device__ __forceinline__ void cg_gemm_t(const float* __restrict__ Abuf, const float* __restrict__ M, int wv, int lane,
+                                          f32x4& c) {
+    c = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int fr = lane & 15, fk = lane >> 4;
+    const float* ap = Abuf + fr * SM_LD + fk;
+    const float* bp = M + fk * SM_LD + wv * 16 + fr;
+    float a[SM_W / 4], b[SM_W / 4];
+#pragma unroll
+    for (int j = 0; j < SM_W / 4; ++j) { a[j] = ap[4 * j]; b[j] = bp[4 * j * SM_LD]; }
+#pragma unroll
+    for (int j = 0; j < SM_W / 4; ++j) c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j], b[j], c, 0, 0, 0);
 }
 
 // f(t, y) for the tile; y arrives in C layout, the result leaves in C layout (columns >= d are 0)

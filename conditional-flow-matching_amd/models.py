@@ -197,16 +197,75 @@ class MLP(torch.nn.Module):
 
 class GradModel(torch.nn.Module):
     """Vector field as the gradient of a scalar potential: ``forward(x)`` differentiates
-    ``sum(action(x))`` w.r.t. ``x`` (graph kept, so the result can be trained through) and drops
-    the last (time) column.  Counterpart of the action-matching helper at
-    torchcfm/models/models.py:24-32; pure autograd, nothing to accelerate."""
+    ``sum(action(x))`` w.r.t. ``x`` and drops the last (time) column.  Counterpart of the action-matching
+    helper at torchcfm/models/models.py:24-32.
+
+    * With grad enabled this is the reference's code: ``create_graph=True``, so the result can be trained through.
+    * With grad disabled (``NeuralODE.trajectory`` runs under ``no_grad``) the gradient is still taken, under
+      ``torch.enable_grad()`` on a detached copy of ``x`` — torchdyn never disables grad, so the reference's class
+      never meets this case — and returned without a graph.
+    * A no-grad call on an fp32 CUDA ``[B, d + 1]`` tensor whose time column is constant over the batch, with an
+      action ``MLP(dim=d, out_dim=1, time_varying=True)`` of the small-kernel envelope (``hip_action``), is one launch
+      of ``cfm_mlp_grad_field_f32`` (a forward and a reverse sweep on the 16-row tile engine).
+      ``NeuralODE(torch_wrapper(GradModel(mlp)))`` and ``CNF(GradModel(mlp))`` run whole solves on it (ode.py, cnf.py).
+    """
 
     def __init__(self, action):
         super().__init__()
         self.action = action
 
+    def hip_action(self, d):
+        """The action MLP when the gradient-field kernels take it at state width d (4 linear layers
+        [d + 1, n1, n2, n3, 1], every width <= 64, d + 1 <= 64, fp32, time varying), else None."""
+        a = self.action
+        if not (isinstance(a, MLP) and a.time_varying):
+            return None
+        lins = a._linears()
+        if len(lins) != 4 or d < 1 or d + 1 > 64 or lins[0].in_features != d + 1 or lins[3].out_features != 1:
+            return None
+        if not all(1 <= l.out_features <= 64 for l in lins[:3]) or any(l.bias is None for l in lins):
+            return None
+        if not all(p.dtype == torch.float32 for p in a.parameters()):
+            return None
+        return a
+
+    def field_hip(self, a, y, t, laplacian=False):
+        """v [B, d] (and the Laplacian [B]) of the action ``a`` at the rows ``y`` [B, d] and scalar time ``t``, from
+        ``cfm_mlp_grad_field_f32``; None when the library declines (CFM_EINVAL: the fused small-field path is off)."""
+        lib = _lib.load()
+        dev = _lib.require_gpu()
+        Wp, bp, dims, keep = a.hip_params(dev)
+        yd = y.detach()
+        if not (yd.is_cuda and yd.dtype == torch.float32 and yd.device == dev and yd.stride(1) == 1
+                and yd.stride(0) >= yd.shape[1]):
+            yd = _lib.to_dev_f32(yd, dev)
+        B, d = yd.shape
+        v = torch.empty((B, d), dtype=torch.float32, device=dev)
+        lap = torch.empty((B,), dtype=torch.float32, device=dev) if laplacian else None
+        rc = lib.cfm_mlp_grad_field_f32(Wp, bp, dims, 4, ptr(yd), yd.stride(0), B, float(t), ptr(v), ptr(lap), None,
+                                        stream_ptr())
+        if rc == -1:
+            return None
+        check(rc, "cfm_mlp_grad_field_f32")
+        return (v, lap) if laplacian else v
+
     def forward(self, x):
-        inp = x.requires_grad_(True)
-        potential = self.action(inp).sum()
-        (dpot,) = torch.autograd.grad(potential, inp, create_graph=True)
+        if torch.is_grad_enabled():
+            inp = x.requires_grad_(True)
+            potential = self.action(inp).sum()
+            (dpot,) = torch.autograd.grad(potential, inp, create_graph=True)
+            return dpot[..., :-1] if dpot.dim() != 2 else dpot[:, :-1]
+        wrapped = getattr(torch._C._functorch, "is_functorch_wrapped_tensor", lambda _: False)(x)   # inside vmap / jacrev
+        if x.dim() == 2 and x.is_cuda and x.dtype == torch.float32 and x.shape[0] > 0 and x.shape[1] >= 2 and not wrapped:
+            a = self.hip_action(x.shape[1] - 1)
+            # the kernel takes one time for the batch: only a constant time column may go there
+            if a is not None and bool((x[:, -1] == x[0, -1]).all()):
+                v = self.field_hip(a, x[:, :-1], float(x[0, -1]))
+                if v is not None:
+                    return v.to(x.device)
+        with torch.enable_grad():
+            inp = x.detach().requires_grad_(True)
+            potential = self.action(inp).sum()
+            (dpot,) = torch.autograd.grad(potential, inp)
+        dpot = dpot.detach()
         return dpot[..., :-1] if dpot.dim() != 2 else dpot[:, :-1]

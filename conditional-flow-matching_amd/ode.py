@@ -5,7 +5,10 @@ examples/images/cifar10/utils_cifar.py:63-68).
 
 When the vector field is ``torch_wrapper(MLP(time_varying=True))`` the whole solve runs in
 the HIP drivers (``cfm_ode_fixed_mlp_f32`` / ``cfm_ode_adaptive_mlp_f32``); ``CNF(MLP)`` (cnf.py) of
-the small-kernel envelope on fp32 ``[B, 1 + d]`` states runs in ``cfm_ode_*_cnf_mlp_f32``.  Any
+the small-kernel envelope on fp32 ``[B, 1 + d]`` states runs in ``cfm_ode_*_cnf_mlp_f32``.  The action-matching
+field ``torch_wrapper(GradModel(MLP(dim, out_dim=1, time_varying=True)))`` of that envelope (``GradModel.hip_action``)
+on fp32 states runs in ``cfm_ode_fixed_gradmlp_f32`` / ``cfm_ode_adaptive_gradmlp_f32``, and ``CNF(GradModel(mlp))``
+with the exact trace and a fixed-step solver in ``cfm_ode_fixed_cnf_gradmlp_f32``.  Any
 other vector field (e.g. a UNet) is stepped by the same algorithm at the tensor level — host
 control flow only, the field itself runs wherever the user's module runs.  ``last_path`` says
 which of the two ran ("hip" / "generic").
@@ -27,7 +30,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr, stream_ptr
-from .models import MLP
+from .models import MLP, GradModel
 from .utils import torch_wrapper
 
 # Adaptive pairs: c, a (rows 2..7; row 7 = b, so stage 7's state is the solution), e (x_err = dt * sum e_i k_i).
@@ -105,6 +108,14 @@ class NeuralODE(torch.nn.Module):
                 return m
         return None
 
+    def _hip_grad(self, x):
+        """The action MLP of torch_wrapper(GradModel(mlp)) when the gradient-field drivers take the solve, else None."""
+        vf = self.vf
+        if (isinstance(vf, torch_wrapper) and isinstance(vf.model, GradModel) and x.dim() == 2
+                and x.dtype == torch.float32 and torch.cuda.is_available()):
+            return vf.model.hip_action(x.shape[1])
+        return None
+
     @torch.no_grad()
     def trajectory(self, x, t_span):
         _check_t_span(torch.as_tensor(t_span, dtype=torch.float32).cpu())
@@ -115,6 +126,12 @@ class NeuralODE(torch.nn.Module):
         if m is not None and x.dim() == 2:
             self.last_path = "hip"
             return self._trajectory_hip(m, x, t_span)
+        a = self._hip_grad(x)
+        if a is not None:
+            traj = self._trajectory_hip(a, x, t_span, grad=True)
+            if traj is not None:
+                self.last_path = "hip"
+                return traj
         self.last_path = "generic"
         return self._trajectory_generic(x, t_span)
 
@@ -132,14 +149,21 @@ class NeuralODE(torch.nn.Module):
                     if traj is not None:
                         self.last_path = "hip"
                         return traj
+                a = cnf.hip_grad(x.shape[1] - 1)     # exact trace of a gradient field: the fixed-step schemes only
+                if a is not None and self.solver in _lib.ODE_SCHEME:
+                    traj = self._trajectory_cnf_hip(a, x, t_span, None, grad=True)
+                    if traj is not None:
+                        self.last_path = "hip"
+                        return traj
             self.last_path = "generic"
             return self._trajectory_generic(x, t_span)
         finally:
             cnf._solve_noise = None
 
-    def _trajectory_cnf_hip(self, m, x, t_span, eps):
-        """Augmented solve in cfm_ode_{fixed,adaptive}_cnf_mlp_f32; None when the library declines it (CFM_EINVAL:
-        the fused small-field path is switched off) so the caller steps it generically."""
+    def _trajectory_cnf_hip(self, m, x, t_span, eps, grad=False):
+        """Augmented solve in cfm_ode_{fixed,adaptive}_cnf_mlp_f32 (grad: m is the action net of a GradModel, fixed
+        steps, cfm_ode_fixed_cnf_gradmlp_f32); None when the library declines it (CFM_EINVAL: the fused small-field
+        path is switched off) so the caller steps it generically."""
         lib = _lib.load()
         dev = _lib.require_gpu()
         Wp, bp, dims, keep = m.hip_params(dev)
@@ -157,11 +181,10 @@ class NeuralODE(torch.nn.Module):
         steps = ctypes.c_int(0)
         tsp = ts.ctypes.data_as(ctypes.c_void_p)
         if self.solver in _lib.ODE_SCHEME:
-            rc = lib.cfm_ode_fixed_cnf_mlp_f32(Wp, bp, dims, 4, ptr(xd), B, tsp, n_t, mode, ptr(ed),
-                                               _lib.ODE_SCHEME[self.solver], ptr(traj), ctypes.byref(nfe), ptr(ws),
-                                               stream_ptr())
+            what = "cfm_ode_fixed_cnf_gradmlp_f32" if grad else "cfm_ode_fixed_cnf_mlp_f32"
+            rc = getattr(lib, what)(Wp, bp, dims, 4, ptr(xd), B, tsp, n_t, mode, ptr(ed), _lib.ODE_SCHEME[self.solver],
+                                    ptr(traj), ctypes.byref(nfe), ptr(ws), stream_ptr())
             steps.value = n_t - 1
-            what = "cfm_ode_fixed_cnf_mlp_f32"
         else:
             rc = lib.cfm_ode_adaptive_cnf_mlp_f32(Wp, bp, dims, 4, ptr(xd), B, tsp, n_t, mode, ptr(ed),
                                                   _lib.ODE_TABLEAU[self.solver], self.atol, self.rtol, ptr(traj),
@@ -178,7 +201,10 @@ class NeuralODE(torch.nn.Module):
         return (t_span, sol) if self.return_t_eval else sol
 
     # ---- HIP drivers ----
-    def _trajectory_hip(self, m, x, t_span):
+    def _trajectory_hip(self, m, x, t_span, grad=False):
+        """grad: m is the action net of a GradModel and the solve runs in the cfm_ode_*_gradmlp_f32 drivers; these have
+        no layer-per-kernel form, so None comes back when the library declines (CFM_EINVAL: the fused small-field path
+        is switched off, or t_span has more points than the workspace holds) and the caller steps it generically."""
         lib = _lib.load()
         dev = _lib.require_gpu()
         Wp, bp, dims, keep = m.hip_params(dev)
@@ -193,16 +219,19 @@ class NeuralODE(torch.nn.Module):
         nfe = ctypes.c_int(0)
         steps = ctypes.c_int(0)
         tsp = ts.ctypes.data_as(ctypes.c_void_p)
+        kind = "gradmlp" if grad else "mlp"
         if self.solver in _lib.ODE_SCHEME:
-            check(lib.cfm_ode_fixed_mlp_f32(Wp, bp, dims, n, ptr(xd), B, tsp, n_t, _lib.ODE_SCHEME[self.solver],
-                                            ptr(traj), ctypes.byref(nfe), ptr(ws), stream_ptr()),
-                  "cfm_ode_fixed_mlp_f32")
+            what = f"cfm_ode_fixed_{kind}_f32"
+            rc = getattr(lib, what)(Wp, bp, dims, n, ptr(xd), B, tsp, n_t, _lib.ODE_SCHEME[self.solver], ptr(traj),
+                                    ctypes.byref(nfe), ptr(ws), stream_ptr())
             steps.value = n_t - 1
         else:
-            check(lib.cfm_ode_adaptive_mlp_f32(Wp, bp, dims, n, ptr(xd), B, tsp, n_t, _lib.ODE_TABLEAU[self.solver],
-                                               self.atol, self.rtol, ptr(traj), ctypes.byref(steps),
-                                               ctypes.byref(nfe), ptr(ws), stream_ptr()),
-                  "cfm_ode_adaptive_mlp_f32")
+            what = f"cfm_ode_adaptive_{kind}_f32"
+            rc = getattr(lib, what)(Wp, bp, dims, n, ptr(xd), B, tsp, n_t, _lib.ODE_TABLEAU[self.solver], self.atol,
+                                    self.rtol, ptr(traj), ctypes.byref(steps), ctypes.byref(nfe), ptr(ws), stream_ptr())
+        if grad and rc == -1:
+            return None
+        check(rc, what)
         self.nfe, self.n_steps = nfe.value, steps.value
         return traj.to(x.device)
 

@@ -518,6 +518,34 @@ int cfm_cnf_euler_grad_f32(const float* const* W, const float* const* b, const i
                            const float* eps, const float* g_final, float* const* dW, float* const* db,
                            float* g_initial, void* ws, void* stream);
 
+/* K13 — action matching: the field v = grad_x s(x, t) of a scalar action net s = MLP([x, t]) with one output
+ * (4 linear layers, dims = [d + 1, n1, n2, n3, 1], 1 <= every width <= 64, d + 1 <= 64), and the solves over it.
+ * Replaces GradModel(MLP(dim, out_dim=1, time_varying=True)) (torchcfm/models/models.py:24-32) as
+ * examples/2D_tutorials/model-comparison-plotting.ipynb samples it (cell 4: NeuralODE(torch_wrapper(model), "euler")
+ * over 101 points) and evaluates its density (cells 4 and 7: CNF + the exact trace on 201 points backward in time).
+ * W, b, dims describe the ACTION net; its last bias is never read for a value.  Every entry returns CFM_EINVAL outside
+ * that envelope or with the fused small-field path disabled (cfm_ode_set_fused(0)): this field has no layer-per-kernel
+ * form.
+ * One evaluation: x device, B rows of d values at a row stride of ldx floats (ldx >= d); v device [B,d];
+ * lap device [B] = tr(dv/dx), the Laplacian of s, or NULL (v is the same bit pattern either way); ws may be NULL. */
+int cfm_mlp_grad_field_f32(const float* const* W, const float* const* b, const int* dims, int n_layers,
+                           const float* x, int ldx, int B, float t, float* v, float* lap, void* ws, void* stream);
+/* Solves of dx/dt = grad_x s(x, t): arguments, trajectory layout, nfe / n_steps and the reverse-time rule as
+ * cfm_ode_fixed_mlp_f32 / cfm_ode_adaptive_mlp_f32 (models.py:24-32 under the notebook's cell 4).  ws:
+ * cfm_workspace_bytes(CFM_OP_ODE, B, max width, d); CFM_EINVAL when t_span does not fit it (fixed: n_t > 3 B d,
+ * adaptive: n_t > B d). */
+int cfm_ode_fixed_gradmlp_f32(const float* const* W, const float* const* b, const int* dims, int n_layers,
+                              const float* x0, int B, const float* t_span, int n_t, int scheme, float* traj,
+                              int* nfe, void* ws, void* stream);
+int cfm_ode_adaptive_gradmlp_f32(const float* const* W, const float* const* b, const int* dims, int n_layers,
+                                 const float* x0, int B, const float* t_span, int n_t, int tableau, float atol,
+                                 float rtol, float* traj, int* n_steps, int* nfe, void* ws, void* stream);
+/* The augmented solve d[l, x]/dt = [-lap s, grad_x s] (models.py:24-32 under the notebook's cells 4 and 7): arguments as
+ * cfm_ode_fixed_cnf_mlp_f32, ws at d + 1.  mode 0 (exact trace) only: any other mode returns CFM_EINVAL; eps is ignored. */
+int cfm_ode_fixed_cnf_gradmlp_f32(const float* const* W, const float* const* b, const int* dims, int n_layers,
+                                  const float* x0, int B, const float* t_span, int n_t, int mode,
+                                  const float* eps, int scheme, float* traj, int* nfe, void* ws, void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
