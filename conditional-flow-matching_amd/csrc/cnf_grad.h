@@ -326,13 +326,15 @@ __global__ __launch_bounds__(256) void ode_small_euler_grad(SmArgs A, int B, int
     }
 }
 
-// dW[], db[] = the partials added in workgroup order
+// dW[], db[] = scale * the partials added in workgroup order (scale = 1 changes no bit); tail: null, or where the one
+// element that a partial carries behind db[3] goes (action_grad.h: the loss)
 __global__ __launch_bounds__(256) void ode_small_grad_reduce(const float* __restrict__ part, int nparts, int P, SmArgs A,
-                                                          CgOut O) {
+                                                          CgOut O, float scale, float* __restrict__ tail) {
     int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= P) return;
     float sum = 0.f;
     for (int g = 0; g < nparts; ++g) sum += part[(size_t)g * P + p];
+    sum *= scale;
 #pragma unroll
     for (int l = 0; l < 4; ++l) {
         const int nw = A.dims[l + 1] * A.dims[l], nb = A.dims[l + 1];
@@ -341,6 +343,7 @@ __global__ __launch_bounds__(256) void ode_small_grad_reduce(const float* __rest
         if (p >= 0 && p < nb) O.db[l][p] = sum;
         p -= nb;
     }
+    if (tail && p == 0) *tail = sum;
 }
 
 template <int MODE>
@@ -352,7 +355,7 @@ static int cnf_grad_launch(const SmArgs& A, int B, int d, const float* tspan_dev
                        G, g0, part, P);
     int rc = cfm_status();
     if (rc) return rc;
-    hipLaunchKernelGGL(ode_small_grad_reduce, dim3((P + 255) / 256), dim3(256), 0, s, (const float*)part, grid, P, A, O);
+    hipLaunchKernelGGL(ode_small_grad_reduce, dim3((P + 255) / 256), dim3(256), 0, s, (const float*)part, grid, P, A, O, 1.f, nullptr);
     return cfm_status();
 }
 

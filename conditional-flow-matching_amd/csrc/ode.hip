@@ -1220,3 +1220,6 @@ extern "C" int cfm_ode_adaptive_gradmlp_f32(const float* const* W, const float* 
 
 // ---- CNF training: the gradient of the Euler augmented solve (ode_small_euler_grad, cfm_cnf_euler_grad_f32) ----
 #include "cnf_grad.h"
+
+// ---- action-matching training: loss and parameter gradient in one launch (cfm_action_matching_grad_f32) ----
+#include "action_grad.h"

@@ -1,4 +1,4 @@
-// small_field.h — the 16-row tile engine of the fused small-field kernels of ode.hip, sde_small.h and cnf_grad.h
+// small_field.h — the 16-row tile engine of the fused small-field kernels of ode.hip, sde_small.h, cnf_grad.h and action_grad.h
 // (SmTile, sm_gemm, cg_gemm_t, sm_field, sm_field_aug, weights staged in LDS), its LDS byte count, envelope check, launch helper.
 #pragma once
 #include "cfm_common.h"

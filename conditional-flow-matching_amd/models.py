@@ -195,6 +195,21 @@ class MLP(torch.nn.Module):
         return self.forward_hip(x).to(x.dtype)
 
 
+def hip_action(a, d):
+    """The action net ``a`` when the gradient-field kernels take it at state width d (an MLP of 4 linear layers
+    [d + 1, n1, n2, n3, 1], every width <= 64, d + 1 <= 64, fp32, time varying), else None."""
+    if not (isinstance(a, MLP) and a.time_varying):
+        return None
+    lins = a._linears()
+    if len(lins) != 4 or d < 1 or d + 1 > 64 or lins[0].in_features != d + 1 or lins[3].out_features != 1:
+        return None
+    if not all(1 <= l.out_features <= 64 for l in lins[:3]) or any(l.bias is None for l in lins):
+        return None
+    if not all(l.weight.dtype == torch.float32 and l.bias.dtype == torch.float32 for l in lins):
+        return None
+    return a
+
+
 class GradModel(torch.nn.Module):
     """Vector field as the gradient of a scalar potential: ``forward(x)`` differentiates
     ``sum(action(x))`` w.r.t. ``x`` and drops the last (time) column.  Counterpart of the action-matching
@@ -215,19 +230,8 @@ class GradModel(torch.nn.Module):
         self.action = action
 
     def hip_action(self, d):
-        """The action MLP when the gradient-field kernels take it at state width d (4 linear layers
-        [d + 1, n1, n2, n3, 1], every width <= 64, d + 1 <= 64, fp32, time varying), else None."""
-        a = self.action
-        if not (isinstance(a, MLP) and a.time_varying):
-            return None
-        lins = a._linears()
-        if len(lins) != 4 or d < 1 or d + 1 > 64 or lins[0].in_features != d + 1 or lins[3].out_features != 1:
-            return None
-        if not all(1 <= l.out_features <= 64 for l in lins[:3]) or any(l.bias is None for l in lins):
-            return None
-        if not all(p.dtype == torch.float32 for p in a.parameters()):
-            return None
-        return a
+        """The action MLP when the gradient-field kernels take it at state width d (``hip_action`` above), else None."""
+        return hip_action(self.action, d)
 
     def field_hip(self, a, y, t, laplacian=False):
         """v [B, d] (and the Laplacian [B]) of the action ``a`` at the rows ``y`` [B, d] and scalar time ``t``, from

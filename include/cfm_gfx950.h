@@ -58,6 +58,7 @@ extern "C" {
 #define CFM_OP_MLP_TRAIN     8   /* cfm_mlp_backward_f32 (B, widest layer, largest weight's element count) */
 #define CFM_OP_TRANSPORT     9   /* cfm_transport_exact_f32 (B0, B1, 0) */
 #define CFM_OP_CNF_GRAD     10   /* cfm_cnf_euler_grad_f32 (B, n_t, 0): per-workgroup partial gradients + t_span */
+#define CFM_OP_ACTION_GRAD  11   /* cfm_action_matching_grad_f32 (B, 0, 0): per-workgroup partial gradients + loss terms */
 
 /* variants for cfm_sample_xt_ut_f32 (reference class in parentheses) */
 #define CFM_VARIANT_ICFM   0  /* ConditionalFlowMatcher / ExactOT...          */
@@ -545,6 +546,20 @@ int cfm_ode_adaptive_gradmlp_f32(const float* const* W, const float* const* b, c
 int cfm_ode_fixed_cnf_gradmlp_f32(const float* const* W, const float* const* b, const int* dims, int n_layers,
                                   const float* x0, int B, const float* t_span, int n_t, int mode,
                                   const float* eps, int scheme, float* traj, int* nfe, void* ws, void* stream);
+
+/* The action-matching objective and its parameter gradient: ActionMatchingLitModule.step
+ * (runner/src/models/cfm_module.py:670-694: a0 - a1 + 1/2 |ds/dx|^2 + ds/dt at (xt, t), mean over the batch) together with
+ * the loss.backward() that follows it, which in autograd is a double backward through autograd.grad(..., create_graph=True).
+ * W, b, dims: the ACTION net, in the envelope of cfm_mlp_grad_field_f32 (CFM_EINVAL outside it or with the fused
+ * small-field path off), any B >= 1.  x0, x1, xt: device [B,d]; t: device [B], the time column the net sees at xt (the
+ * endpoints are evaluated at t = 0 and t = 1).  xt NULL: the reference's interpolant t * x1 + (1 - t) * x0 (line 682), in
+ * its fp32 operation order.  Outputs (overwritten): loss device [1]; dW[l], db[l] device, laid out as
+ * W[l], b[l] = d loss / d W[l], d loss / d b[l]; db[3] is an exact 0 (the loss does not depend on b[3]).  No gradient
+ * with respect to x0, x1, xt, t (they carry no graph in the reference).  ws: cfm_workspace_bytes(CFM_OP_ACTION_GRAD, B, 0, 0).
+ * The result is the same bit pattern run to run (per-workgroup partials, added in a fixed order by a second launch). */
+int cfm_action_matching_grad_f32(const float* const* W, const float* const* b, const int* dims, int n_layers,
+                                 const float* x0, const float* x1, const float* xt, const float* t, int B,
+                                 float* loss, float* const* dW, float* const* db, void* ws, void* stream);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop
