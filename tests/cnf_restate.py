@@ -9,11 +9,17 @@ import cfm_oracle as oracle
 
 
 def mlp_params(d, w, seed, out_scale=1.0):
-    """Weights / biases (float32 numpy) of a seeded MLP(dim=d, time_varying=True, w=w); last layer scaled."""
-    import cfm_amd
+    """Weights / biases (float32 numpy) of a seeded, default-initialised field net; last layer scaled.  w an int: the
+    layers of MLP(dim=d, time_varying=True, w=w); w a triple of hidden widths: the Linear layers [d + 1, *w, d] created
+    in order under the seed (as grad_field_restate.action_params does for an action net)."""
     torch.manual_seed(seed)
-    m = cfm_amd.MLP(dim=d, time_varying=True, w=w)
-    lins = m._linears()
+    if isinstance(w, (int, np.integer)):
+        import cfm_amd
+        lins = cfm_amd.MLP(dim=d, time_varying=True, w=w)._linears()
+    else:
+        dims = [d + 1] + [int(n) for n in w] + [d]
+        assert len(dims) == 5, w
+        lins = [torch.nn.Linear(a, b) for a, b in zip(dims[:-1], dims[1:])]
     Ws = [l.weight.detach().numpy().astype(np.float32).copy() for l in lins]
     bs = [l.bias.detach().numpy().astype(np.float32).copy() for l in lins]
     Ws[3] *= np.float32(out_scale); bs[3] *= np.float32(out_scale)
@@ -39,12 +45,17 @@ def smooth_mlp_params(d, w, seed, box=3.0, margin=0.2, out_scale=1.0):
 
 
 def make_mlp(Ws, bs, device=None, dtype=torch.float32):
+    """cfm_amd.MLP(dim=d, time_varying=True) carrying these layers (any hidden widths): every Linear of MLP.net is given
+    the shaped parameters and its in / out extents."""
     import cfm_amd
     d = Ws[3].shape[0]
     m = cfm_amd.MLP(dim=d, time_varying=True, w=Ws[0].shape[0])
-    for k, l in enumerate(m._linears()):
-        l.weight.data = torch.from_numpy(np.ascontiguousarray(Ws[k])).to(dtype)
-        l.bias.data = torch.from_numpy(np.ascontiguousarray(bs[k])).to(dtype)
+    lins = m._linears()
+    assert len(lins) == 4
+    for k, l in enumerate(lins):
+        l.out_features, l.in_features = Ws[k].shape
+        l.weight = torch.nn.Parameter(torch.from_numpy(np.ascontiguousarray(Ws[k])).to(dtype))
+        l.bias = torch.nn.Parameter(torch.from_numpy(np.ascontiguousarray(bs[k])).to(dtype))
     return m.to(device) if device is not None else m
 
 

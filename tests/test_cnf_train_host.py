@@ -203,6 +203,59 @@ def test_generic_path_equals_restatement_and_notebook(estimator, ts):
         assert _rel(a, b.numpy()) <= 1e-10
 
 
+@pytest.mark.parametrize("estimator", ["exact", "hutch_gaussian"])
+def test_generic_path_equals_restatement_at_mixed_widths(estimator):
+    """Hidden widths (33, 64, 48): no two layers share a shape, so an exchanged pair of extents in the helpers
+    (cnf_restate.mlp_params / make_mlp) or in the restatement would not pass.  The written-out sweep is the third
+    statement of the same gradient."""
+    d, w, B = 3, (33, 64, 48), 6
+    Ws, bs = cr.mlp_params(d, w, seed=2)
+    assert [W.shape for W in Ws] == [(33, d + 1), (64, 33), (48, 64), (d, 48)]
+    assert [b.shape for b in bs] == [(33,), (64,), (48,), (d,)]
+    g = np.random.default_rng(11)
+    xa = np.concatenate([g.normal(size=(B, 1)), g.normal(size=(B, d))], 1)
+    G = g.normal(size=(B, d + 1))
+    eps = _probe(estimator, B, d, 13)
+    out64, gp64, gx64 = tr.grads_for_upstream(Ws, bs, xa, UP, G, eps)
+    assert [q.shape for q in gp64[0::2]] == [W.shape for W in Ws]
+
+    m = cr.make_mlp(Ws, bs, dtype=torch.float64)
+    assert [tuple(l.weight.shape) for l in m._linears()] == [W.shape for W in Ws]
+    cnf = cfm_amd.DifferentiableCNF(m, estimator=estimator, noise=None if eps is None else torch.tensor(eps))
+    x = torch.tensor(xa, requires_grad=True)
+    out = cnf.solve(x, torch.tensor(UP))
+    assert cnf.last_path == "generic" and out.dtype == torch.float64
+    got = _model_grads(m, (out * torch.tensor(G)).sum(), [x])
+    assert _rel(out.detach().numpy(), out64) <= 1e-12
+    for a, b in zip(got, gp64 + [gx64]):
+        assert _rel(a, b) <= 1e-10
+    gp, gx = _hand_sweep(Ws, bs, xa, UP, G, eps)
+    for a, b in zip(gp + [gx], gp64 + [gx64]):
+        assert _rel(a, b) <= 1e-12
+
+
+def test_int_width_helper_keeps_its_bits():
+    """mlp_params(d, w) with an int is the seeded MLP(dim=d, time_varying=True, w=w), as before it took triples; the
+    triple (w, w, w) creates the same layers in the same order, so it is the same net."""
+    torch.manual_seed(7)
+    want = [p.detach().numpy().copy() for p in cfm_amd.MLP(dim=3, time_varying=True, w=16).parameters()]
+    after = torch.rand(1)
+    Ws, bs = cr.mlp_params(3, 16, seed=7)
+    assert torch.equal(torch.rand(1), after)
+    Wt, bt = cr.mlp_params(3, (16, 16, 16), seed=7)
+    for k in range(4):
+        assert np.array_equal(Ws[k], want[2 * k]) and np.array_equal(bs[k], want[2 * k + 1])
+        assert np.array_equal(Wt[k], Ws[k]) and np.array_equal(bt[k], bs[k])
+    # make_mlp consumes the generator as it did: one MLP(w = the first hidden width) worth of initialisation
+    Wm, bm = cr.mlp_params(3, (16, 5, 9), seed=7)
+    draws = []
+    for make in (lambda: cfm_amd.MLP(dim=3, time_varying=True, w=16), lambda: cr.make_mlp(Wt, bt), lambda: cr.make_mlp(Wm, bm)):
+        torch.manual_seed(3)
+        make()
+        draws.append(torch.rand(1))
+    assert torch.equal(draws[0], draws[1]) and torch.equal(draws[0], draws[2])
+
+
 def test_nll_is_the_tutorial_loss():
     d, w, B = 2, 16, 6
     Ws, bs = cr.mlp_params(d, w, seed=4)

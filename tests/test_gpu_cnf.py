@@ -52,18 +52,37 @@ def _rows(B):
     return np.unique(np.concatenate([np.arange(64), np.arange(B - 64, B), np.arange(0, B, 97)]))
 
 
+WMIX, WMIX2 = (64, 17, 40), (33, 64, 48)       # non-square hidden layers: no two layers of a net share a shape
+
+
+def _wkey(w):
+    """The int that enters a case's seeds: w itself, or the sum of a triple of hidden widths."""
+    return w if isinstance(w, int) else sum(w)
+
+
 # ---------------------------------------------------------------------------------------- divergence
 @pytest.mark.parametrize("d", [2, 5, 50, 63])
 @pytest.mark.parametrize("w", [64, 32, 17])
 def test_divergence_one_evaluation_vs_float64_jacrev(dev, d, w):
+    _divergence_vs_float64_jacrev(dev, d, w)
+
+
+@pytest.mark.parametrize("d", [2, 63])
+@pytest.mark.parametrize("w", [WMIX, WMIX2], ids=lambda w: "-".join(map(str, w)))
+def test_divergence_one_evaluation_at_non_square_widths(dev, d, w):
+    """Both estimators (mode 0 and 1 below) on layers staged from four different shapes."""
+    _divergence_vs_float64_jacrev(dev, d, w)
+
+
+def _divergence_vs_float64_jacrev(dev, d, w):
     from cfm_amd import _lib
     from cfm_amd.ode import NeuralODE
     from cfm_amd.utils import torch_wrapper
     lib = _lib.load()
-    Ws, bs = R.mlp_params(d, w, seed=100 + d + w)
+    Ws, bs = R.mlp_params(d, w, seed=100 + d + _wkey(w))
     m = R.make_mlp(Ws, bs, dev)
     Wp, bp, dims, keep = m.hip_params(dev)
-    g = torch.Generator().manual_seed(d * 1000 + w)
+    g = torch.Generator().manual_seed(d * 1000 + _wkey(w))
     for B in (1, 15, 16, 17, 1000, 8193):
         x = torch.randn(B, d, generator=g)
         eps = torch.randint(0, 2, (B, d), generator=g).float() * 2 - 1
@@ -152,7 +171,7 @@ def _aug0(x):
 
 
 @pytest.mark.parametrize("estimator", ["exact", "hutch_rademacher"])
-@pytest.mark.parametrize("d,w,B", [(2, 64, 500), (5, 17, 77)])
+@pytest.mark.parametrize("d,w,B", [(2, 64, 500), (5, 17, 77), (3, WMIX, 50)])
 def test_augmented_euler_vs_oracle(dev, estimator, d, w, B):
     Ws, bs = R.mlp_params(d, w, seed=20 + d)
     torch.manual_seed(5)
@@ -184,9 +203,10 @@ def test_augmented_euler_hutchinson_basis_probes_sum_to_exact(dev):
 
 
 @pytest.mark.parametrize("estimator", ["exact", "hutch_rademacher"])
-@pytest.mark.parametrize("d,w,B,ts", [(2, 64, 700, [1.0, 0.0]), (5, 32, 130, [0.0, 0.5, 1.0]), (2, 17, 9000, [1.0, 0.4, 0.0])])
+@pytest.mark.parametrize("d,w,B,ts", [(2, 64, 700, [1.0, 0.0]), (5, 32, 130, [0.0, 0.5, 1.0]), (2, 17, 9000, [1.0, 0.4, 0.0]),
+                                      (5, WMIX2, 130, [1.0, 0.4, 0.0])])    # the oracle's ratios keep clear of 1 (asserted below)
 def test_augmented_dopri5_vs_oracle(dev, estimator, d, w, B, ts):
-    Ws, bs = R.mlp_params(d, w, seed=40 + d + w)
+    Ws, bs = R.mlp_params(d, w, seed=40 + d + _wkey(w))
     torch.manual_seed(6)
     x = torch.randn(B, d)
     eps = torch.randint(0, 2, (B, d)).float() * 2 - 1 if estimator != "exact" else None
@@ -198,6 +218,8 @@ def test_augmented_dopri5_vs_oracle(dev, estimator, d, w, B, ts):
     rev = float(ts[1]) < float(ts[0])
     ref, log = oracle.dopri5_trajectory(R.reverse(F) if rev else F, _aug0(x).numpy(), (-ts if rev else ts).numpy(),
                                         1e-5, 1e-5, return_log=True)
+    if not isinstance(w, int):      # the mixed-width case was chosen so that no fp32 rounding can flip an accept
+        assert all(abs(l[2] - 1.0) > 0.05 for l in log["log"]), [l[2] for l in log["log"]]
     assert node.n_steps == log["steps"] and node.nfe == log["nfe"], (node.n_steps, node.nfe, log["steps"], log["nfe"])
     assert np.abs(tr[..., 1:] - ref[..., 1:]).max() <= 1e-5 * np.abs(ref[..., 1:]).max()
     # l: every row to 1e-5 x max|l| when that holds; otherwise every row to 1e-5 x max|l| plus the oracle's own

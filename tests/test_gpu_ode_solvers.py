@@ -151,6 +151,75 @@ def test_fused_small_field_equals_layer_path(dev, B, d, w, n_t):
         assert bool(torch.isfinite(a[0]).all())
 
 
+# ---------------------------------------------------------------------------------------- non-square hidden layers
+WMIX, WMIX2 = (64, 17, 40), (33, 64, 48)       # no two layers of a net share a shape: extents and strides cannot be exchanged
+_WID = lambda w: "-".join(map(str, w))         # noqa: E731
+
+
+@pytest.mark.parametrize("w", [WMIX, WMIX2], ids=_WID)
+@pytest.mark.parametrize("B,d,n_t", [(300, 2, 25), (64, 63, 4)])
+def test_fused_small_field_equals_layer_path_at_non_square_widths(dev, B, d, w, n_t):
+    """test_fused_small_field_equals_layer_path with hidden layers [d + 1, *w, d] (sm_stage_weights pads each layer from
+    its own in / out extents), for all five solvers: same bits as the layer-per-kernel path on the register-staged
+    layer core, which takes every layer's K from that layer's own shape."""
+    from cfm_amd import _lib
+    from cfm_amd.ode import NeuralODE
+    from cfm_amd.utils import torch_wrapper
+    lib = _lib.load()
+    model = R.make_mlp(*R.mlp_params(d, w, 3), dev)
+    assert [l.out_features for l in model._linears()] == list(w) + [d]
+    x = torch.randn(B, d, generator=torch.Generator().manual_seed(9)).to(dev)
+    ts = torch.linspace(0, 1, n_t, device=dev)
+    solvers = ("dopri5", "tsit5", "midpoint", "rk4", "euler")
+    out = {}
+    glds0 = lib.cfm_mlp_get_glds()
+    try:
+        lib.cfm_mlp_set_glds(0)
+        for fused in (1, 0):
+            lib.cfm_ode_set_fused(fused)
+            for solver in solvers:
+                node = NeuralODE(torch_wrapper(model), solver=solver, atol=1e-4, rtol=1e-4)
+                out[(fused, solver)] = (node.trajectory(x, ts).cpu(), node.nfe, node.n_steps)
+                assert node.last_path == "hip"
+    finally:
+        lib.cfm_ode_set_fused(1); lib.cfm_mlp_set_glds(glds0)
+    for solver in solvers:
+        a, b = out[(1, solver)], out[(0, solver)]
+        assert a[1] == b[1] and a[2] == b[2], (solver, a[1:], b[1:])
+        assert torch.equal(a[0], b[0]), (solver, float((a[0] - b[0]).abs().max()))
+        assert bool(torch.isfinite(a[0]).all())
+
+
+@pytest.mark.parametrize("fused", [True, False])
+@pytest.mark.parametrize("d,w,B", [(5, WMIX, 77), (63, WMIX2, 33)], ids=lambda v: _WID(v) if isinstance(v, tuple) else str(v))
+def test_non_square_widths_vs_restatement(dev, d, w, B, fused):
+    """Two paths can agree on a wrong staging: rk4 on a non-uniform grid and an adaptive tsit5 solve against the float64
+    restatement, on both paths, each to 1e-5 of max|x|.  tsit5: the same attempts as the restatement, whose ratios keep
+    clear of 1 (asserted: every attempt of these two solves is accepted with a ratio below 0.06)."""
+    from cfm_amd import _lib
+    lib = _lib.load()
+    Ws, bs = R.mlp_params(d, w, seed=13)
+    f = R.mlp_field_np(Ws, bs)
+    x = torch.randn(B, d, generator=torch.Generator().manual_seed(5))
+    ts = torch.tensor([0.0, 0.13, 0.5, 0.62, 1.0])
+    lib.cfm_ode_set_fused(1 if fused else 0)
+    try:
+        fx = _node(Ws, bs, "rk4", 1e-4, dev)
+        tf = fx.trajectory(x, ts).cpu().numpy()
+        ad = _node(Ws, bs, "tsit5", 1e-4, dev)
+        ta = ad.trajectory(x, ts).cpu().numpy()
+    finally:
+        lib.cfm_ode_set_fused(1)
+    assert fx.last_path == "hip" and ad.last_path == "hip"
+    assert (fx.n_steps, fx.nfe) == (4, 16) and tf.shape == (5, B, d)
+    _close(tf, rk.fixed_trajectory(f, x.numpy(), ts.numpy(), "rk4"), f"rk4 {_WID(w)} fused={fused}")
+    ref, info = rk.adaptive_trajectory(f, x.numpy(), ts.numpy(), 1e-4, 1e-4, "tsit5", return_log=True)
+    assert rk.ratios_clear_of_one(info["log"])
+    assert all(accept and ratio < 0.06 for _, _, ratio, accept in info["log"]), info["log"]
+    assert (ad.n_steps, ad.nfe) == (info["steps"], info["nfe"]), (ad.n_steps, ad.nfe, info["steps"], info["nfe"])
+    _close(ta, ref, f"tsit5 {_WID(w)} fused={fused}")
+
+
 # ---------------------------------------------------------------------------------------- reverse time
 @pytest.mark.parametrize("fused", [True, False])
 @pytest.mark.parametrize("d,w", [(2, 64), (5, 32)])

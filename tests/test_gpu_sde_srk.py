@@ -119,6 +119,97 @@ def test_fused_sampler_against_the_float64_restatement(dev, B, d):
         assert err <= 2e-5, (name, err)
 
 
+# ---- non-square hidden layers: both fields are staged layer by layer from four different shapes ----
+WMIX, WMIX2 = (64, 17, 40), (33, 64, 48)
+
+
+def _two_mixed_fields(dev, d, w, seed):
+    """Drift and score nets [d + 1, *w, d] (the same layer sizes, as the one-launch kernels need; different weights)."""
+    import cnf_restate as R
+    return R.make_mlp(*R.mlp_params(d, w, seed), dev), R.make_mlp(*R.mlp_params(d, w, seed + 1), dev)
+
+
+def _em_restatement(v, s, y0, ts, dt, sigma, xi, reverse=False):
+    """Euler-Maruyama in float64 on the same noise: y += h (drift + score) + sigma sqrt(h) xi; [len(ts), B, d]"""
+    from cfm_amd.sde import _grid
+    Wv, bv = _np_params(v)
+    Ws, bs = _np_params(s)
+    y = np.asarray(y0, dtype=np.float64)
+    xi = np.asarray(xi, dtype=np.float64)
+    out = [y]
+    for k, (t, h, is_out) in enumerate(_grid(ts, dt)):
+        te = 1.0 - t if reverse else t
+        fl = oracle.mlp_forward_f64(Wv, bv, y, te)
+        y = y + h * ((-fl if reverse else fl) + oracle.mlp_forward_f64(Ws, bs, y, te)) + sigma * math.sqrt(h) * xi[k]
+        if is_out:
+            out.append(y)
+    return np.stack(out)
+
+
+def _fused_and_stepped(dev, sde, x0, ts, method, dt, xi):
+    """The one-launch sampler, and the launch-per-step scheme on the register-staged layer core (whose k order the
+    fused kernels share), on the same noise tensor."""
+    from cfm_amd.sde import sdeint
+    from cfm_amd import _lib
+    lib = _lib.load()
+    a = sdeint(sde, x0.to(dev), torch.tensor(ts), method=method, dt=dt, noise=xi.to(dev), fused=True).cpu()
+    glds0 = lib.cfm_mlp_get_glds()
+    try:
+        lib.cfm_mlp_set_glds(0)
+        b = sdeint(sde, x0.to(dev), torch.tensor(ts), method=method, dt=dt, noise=xi.to(dev), fused=False).cpu()
+    finally:
+        lib.cfm_mlp_set_glds(glds0)
+    return a, b
+
+
+@pytest.mark.parametrize("w", [WMIX, WMIX2], ids=lambda w: "-".join(map(str, w)))
+@pytest.mark.parametrize("d", [2, 64])
+def test_fused_sampler_against_the_float64_restatement_at_non_square_widths(dev, d, w):
+    """test_fused_sampler_against_the_float64_restatement (same grids, same bound) with both nets at non-square widths
+    and a partial second tile; and the same bits as the launch-per-step scheme."""
+    from cfm_amd.sde import FlowScoreSDE
+    B = 17
+    v, s = _two_mixed_fields(dev, d, w, seed=20 + d)
+    assert [l.out_features for l in v._linears()] == [l.out_features for l in s._linears()] == list(w) + [d]
+    g = torch.Generator().manual_seed(100 * d + B)
+    x0 = torch.randn((B, d), generator=g)
+    for name, ts, dt, rev in (("one step", [0.0, 1.0], 1.0, False), ("20 steps", list(np.linspace(0.0, 1.0, 5)), 0.05, False),
+                              ("non-uniform", NONUNIFORM, 0.1, False), ("non-uniform reverse", NONUNIFORM, 0.1, True)):
+        n = _n_steps(ts, dt)
+        xi = torch.randn((n, 2, B, d), generator=g)
+        a, b = _fused_and_stepped(dev, FlowScoreSDE(v, s, sigma=0.7, reverse=rev), x0, ts, "srk", dt, xi)
+        ref = _restatement(v, s, x0.numpy(), ts, dt, 0.7, xi.numpy(), reverse=rev)
+        assert a.shape == ref.shape == (len(ts), B, d)
+        err = np.abs(a.numpy() - ref).max() / np.abs(ref).max()
+        print(f"srk B={B} d={d} w={w} {name} ({n} steps): {err:.3e} of max|ref|")
+        assert err <= 2e-5, (name, err)
+        assert torch.equal(a, b), (name, float((a - b).abs().max()))
+
+
+@pytest.mark.parametrize("w", [WMIX, WMIX2], ids=lambda w: "-".join(map(str, w)))
+@pytest.mark.parametrize("d", [2, 64])
+def test_fused_euler_maruyama_against_the_float64_restatement_at_non_square_widths(dev, d, w):
+    """cfm_sde_em_mlp_f32 (method="euler") on the grids and under the bound of the srk test above (2e-5 max|ref|, this
+    file's bound for a sampler that carries an fp32 state through 20 steps of two fp32 fields), B = 17; and the same
+    bits as two forward passes + cfm_sde_em_step_f32 per step."""
+    from cfm_amd.sde import FlowScoreSDE
+    B = 17
+    v, s = _two_mixed_fields(dev, d, w, seed=40 + d)
+    g = torch.Generator().manual_seed(300 * d + B)
+    x0 = torch.randn((B, d), generator=g)
+    for name, ts, dt, rev in (("one step", [0.0, 1.0], 1.0, False), ("20 steps", list(np.linspace(0.0, 1.0, 5)), 0.05, False),
+                              ("non-uniform", NONUNIFORM, 0.1, False), ("non-uniform reverse", NONUNIFORM, 0.1, True)):
+        n = _n_steps(ts, dt)
+        xi = torch.randn((n, B, d), generator=g)
+        a, b = _fused_and_stepped(dev, FlowScoreSDE(v, s, sigma=0.7, reverse=rev), x0, ts, "euler", dt, xi)
+        ref = _em_restatement(v, s, x0.numpy(), ts, dt, 0.7, xi.numpy(), reverse=rev)
+        assert a.shape == ref.shape == (len(ts), B, d)
+        err = np.abs(a.numpy() - ref).max() / np.abs(ref).max()
+        print(f"euler B={B} d={d} w={w} {name} ({n} steps): {err:.3e} of max|ref|")
+        assert err <= 2e-5, (name, err)
+        assert torch.equal(a, b), (name, float((a - b).abs().max()))
+
+
 def test_wide_fields_take_the_launch_per_step_path(dev):
     from cfm_amd.sde import FlowScoreSDE, sdeint
     v, s = _two_fields(dev, d=3, w=128, seed=31)
