@@ -17,6 +17,7 @@ from .conditional_flow_matching import (  # noqa: F401
 )
 from .models import MLP  # noqa: F401
 from .cnf import CNF, DifferentiableCNF, log_likelihood  # noqa: F401
+from .ode import DifferentiableNeuralODE  # noqa: F401
 from .action_matching import action_matching_loss  # noqa: F401
 from .optim import FusedAdam  # noqa: F401
 from .train import RegressionStep, SF2MStep  # noqa: F401

@@ -25,6 +25,7 @@ ABI_VERSION = 3      # CFM_ABI_VERSION of include/cfm_gfx950.h
 OP_SINKHORN, OP_ASSIGN, OP_SAMPLE_DENSE, OP_MLP, OP_ODE, OP_UNBALANCED, OP_COST, OP_MLP_TRAIN, OP_TRANSPORT = 1, 2, 3, 4, 5, 6, 7, 8, 9
 OP_CNF_GRAD = 10
 OP_ACTION_GRAD = 11
+OP_ODE_GRAD = 12
 VARIANT_ICFM, VARIANT_SB, VARIANT_TARGET, VARIANT_VP = 0, 1, 2, 3
 
 ERRORS = {
@@ -102,6 +103,8 @@ SIGNATURES = {
     "cfm_ode_adaptive_gradmlp_f32": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp]),
     "cfm_ode_fixed_cnf_gradmlp_f32": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "cfm_action_matching_grad_f32": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "cfm_ode_fixed_grad_f32": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cfm_ode_fixed_grad_available": (_i, [_vp, _i]),
 }
 # solver selectors of the cfm_ode_adaptive_* / cfm_ode_fixed_* entries (include/cfm_gfx950.h)
 ODE_TABLEAU = {"dopri5": 0, "tsit5": 1}

@@ -63,6 +63,50 @@ __device__ __forceinline__ void cg_outer(const float* __restrict__ Zbuf, const f
 
 __device__ __forceinline__ float cg_sum4(const SmTile& v) { return (v.v[0] + v.v[1]) + (v.v[2] + v.v[3]); }
 
+// W1^T, W2^T -> LDS, zero padded to [2][64][SM_LD]: WT[l - 1][k][r] = W_l[r][k]
+__device__ __forceinline__ void cg_stage_transposed(const SmArgs& A, float* WT, int tid) {
+#pragma unroll
+    for (int l = 1; l <= 2; ++l) {
+        const int in_l = A.dims[l], out_l = A.dims[l + 1];
+        for (int e = tid; e < SM_W * SM_LD; e += 256) {
+            const int k = e / SM_LD, r = e % SM_LD;
+            WT[(l - 1) * SM_W * SM_LD + e] = (r < out_l && k < in_l) ? A.W[l][(size_t)r * in_l + k] : 0.f;
+        }
+    }
+}
+
+// A workgroup's partial gradient Pw in the order W0, b0, W1, b1, W2, b2, W3, b3 (each as the caller's tensor is laid
+// out) from its accumulators: dWa in cg_outer's layout, dba / dwt per lane (bias and time-column sums of the lane's rows)
+__device__ __forceinline__ void cg_store_partial(const SmArgs& A, int d, float* __restrict__ Pw, const f32x4 (&dWa)[4][4],
+                                                 const float (&dba)[4], float dwt, int lane, int col) {
+    int off = 0;
+#pragma unroll
+    for (int l = 0; l < 4; ++l) {
+        const int in_l = A.dims[l], out_l = A.dims[l + 1];
+        const int K = (l == 0) ? d : in_l;
+#pragma unroll
+        for (int mb = 0; mb < 4; ++mb) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int r = 16 * mb + 4 * (lane >> 4) + i;
+                if (r < out_l && col < K) Pw[off + r * in_l + col] = dWa[l][mb][i];
+            }
+        }
+        float bsum = dba[l];
+        bsum += __shfl_xor(bsum, 16, 64);
+        bsum += __shfl_xor(bsum, 32, 64);
+        if (l == 0) {
+            float tsum = dwt;
+            tsum += __shfl_xor(tsum, 16, 64);
+            tsum += __shfl_xor(tsum, 32, 64);
+            if (lane < 16 && col < out_l) Pw[off + col * in_l + d] = tsum;
+        }
+        off += out_l * in_l;
+        if (lane < 16 && col < out_l) Pw[off + col] = bsum;
+        off += out_l;
+    }
+}
+
 // one staged net, the transposed copies of its two 64 x 64 layers, five tile buffers
 constexpr size_t cg_lds_bytes = small_lds_bytes(1, 5, false) + sizeof(float) * 2 * SM_W * SM_LD;
 static_assert(cg_lds_bytes == 127488, "the gradient kernel");
@@ -87,14 +131,7 @@ __global__ __launch_bounds__(256) void ode_small_euler_grad(SmArgs A, int B, int
     float* Y3 = X3 + TS;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     sm_stage_weights(A, d, Wl, bl, wt, tid);
-#pragma unroll
-    for (int l = 1; l <= 2; ++l) {
-        const int in_l = A.dims[l], out_l = A.dims[l + 1];
-        for (int e = tid; e < SM_W * SM_LD; e += 256) {
-            const int k = e / SM_LD, r = e % SM_LD;          // WT[k][r] = W[r][k]
-            WT[(l - 1) * WS + e] = (r < out_l && k < in_l) ? A.W[l][(size_t)r * in_l + k] : 0.f;
-        }
-    }
+    cg_stage_transposed(A, WT, tid);
     const int D = d + 1;
     const size_t n = (size_t)B * D;
     const int col = wv * 16 + (lane & 15);
@@ -296,34 +333,7 @@ __global__ __launch_bounds__(256) void ode_small_euler_grad(SmArgs A, int B, int
         }
     }
 
-    // ---- this workgroup's partial gradient ----
-    float* Pw = part + (size_t)blockIdx.x * P;
-    int off = 0;
-#pragma unroll
-    for (int l = 0; l < 4; ++l) {
-        const int in_l = A.dims[l], out_l = A.dims[l + 1];
-        const int K = (l == 0) ? d : in_l;
-#pragma unroll
-        for (int mb = 0; mb < 4; ++mb) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int r = 16 * mb + 4 * (lane >> 4) + i;
-                if (r < out_l && col < K) Pw[off + r * in_l + col] = dWa[l][mb][i];
-            }
-        }
-        float bsum = dba[l];
-        bsum += __shfl_xor(bsum, 16, 64);
-        bsum += __shfl_xor(bsum, 32, 64);
-        if (l == 0) {
-            float tsum = dwt;
-            tsum += __shfl_xor(tsum, 16, 64);
-            tsum += __shfl_xor(tsum, 32, 64);
-            if (lane < 16 && col < out_l) Pw[off + col * in_l + d] = tsum;
-        }
-        off += out_l * in_l;
-        if (lane < 16 && col < out_l) Pw[off + col] = bsum;
-        off += out_l;
-    }
+    cg_store_partial(A, d, part + (size_t)blockIdx.x * P, dWa, dba, dwt, lane, col);
 }
 
 // dW[], db[] = scale * the partials added in workgroup order (scale = 1 changes no bit); tail: null, or where the one

@@ -1221,5 +1221,8 @@ extern "C" int cfm_ode_adaptive_gradmlp_f32(const float* const* W, const float* 
 // ---- CNF training: the gradient of the Euler augmented solve (ode_small_euler_grad, cfm_cnf_euler_grad_f32) ----
 #include "cnf_grad.h"
 
+// ---- training through the sampler: the gradient of the plain fixed-step solves (ode_small_fixed_grad, cfm_ode_fixed_grad_f32) ----
+#include "ode_grad.h"
+
 // ---- action-matching training: loss and parameter gradient in one launch (cfm_action_matching_grad_f32) ----
 #include "action_grad.h"

@@ -20,6 +20,9 @@ the default here stays ``dopri5``.  ``rk4`` is the 3/8 rule ("torchdyn-style rk4
 tree, so like ``dopri5`` its parity is unpinned).  ``nfe``: stages * (n_t - 1) for the fixed-step solvers, 2 + 6 * step
 attempts for the adaptive ones.
 
+``NeuralODE.trajectory`` carries no graph.  ``DifferentiableNeuralODE`` (fixed-step solvers) returns the same values with
+one: forward ``cfm_ode_fixed_mlp_f32``, backward ``cfm_ode_fixed_grad_f32``, the gradient of the recurrence.
+
 ``t_span`` is strictly monotone.  A decreasing one integrates backward in time as torchdyn does
 (SURVEY.md A.4): ``g(s, x) = -f(-s, x)`` on ``s = -t_span``.
 """
@@ -324,3 +327,109 @@ class NeuralODE(torch.nn.Module):
                 dt = f32(1e-12)
         self.n_steps = steps
         return torch.stack(sol)
+
+
+class _FixedStepODEFunction(torch.autograd.Function):
+    """The trajectory [n_t, B, d] of a fixed-step solve (cfm_ode_fixed_mlp_f32); backward: cfm_ode_fixed_grad_f32."""
+
+    @staticmethod
+    def forward(ctx, x, ts, scheme, dims, *params):
+        lib = _lib.load()
+        dev = x.device
+        Ws = [_lib.to_dev_f32(p, dev) for p in params[0::2]]
+        bs = [_lib.to_dev_f32(p, dev) for p in params[1::2]]
+        Wp = (ctypes.c_void_p * 4)(*[w.data_ptr() for w in Ws])
+        bp = (ctypes.c_void_p * 4)(*[b.data_ptr() for b in bs])
+        cdims = (ctypes.c_int * 5)(*dims)
+        xd = _lib.to_dev_f32(x, dev)
+        B, d = xd.shape
+        n_t = ts.shape[0]
+        traj = torch.empty((n_t, B, d), dtype=torch.float32, device=dev)
+        ws = _lib.workspace(_lib.OP_ODE, B, max(dims[1:4]), d, dev)
+        nfe = ctypes.c_int(0)
+        check(lib.cfm_ode_fixed_mlp_f32(Wp, bp, cdims, 4, ptr(xd), B, ts.ctypes.data_as(ctypes.c_void_p), n_t, scheme,
+                                        ptr(traj), ctypes.byref(nfe), ptr(ws), stream_ptr()), "cfm_ode_fixed_mlp_f32")
+        ctx.ts, ctx.scheme, ctx.dims = ts, scheme, dims
+        ctx.save_for_backward(traj, *params)
+        return traj
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        lib = _lib.load()
+        traj, *params = ctx.saved_tensors
+        dev = traj.device
+        Ws = [_lib.to_dev_f32(p, dev) for p in params[0::2]]
+        bs = [_lib.to_dev_f32(p, dev) for p in params[1::2]]
+        dWs = [torch.empty_like(w) for w in Ws]
+        dbs = [torch.empty_like(b) for b in bs]
+        Wp = (ctypes.c_void_p * 4)(*[w.data_ptr() for w in Ws])
+        bp = (ctypes.c_void_p * 4)(*[b.data_ptr() for b in bs])
+        dWp = (ctypes.c_void_p * 4)(*[w.data_ptr() for w in dWs])
+        dbp = (ctypes.c_void_p * 4)(*[b.data_ptr() for b in dbs])
+        cdims = (ctypes.c_int * 5)(*ctx.dims)
+        n_t, B, d = traj.shape
+        gd = _lib.to_dev_f32(g, dev)
+        g0 = torch.empty((B, d), dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
+        ws = _lib.workspace(_lib.OP_ODE_GRAD, B, n_t, 0, dev)
+        check(lib.cfm_ode_fixed_grad_f32(Wp, bp, cdims, 4, ptr(traj), B, ctx.ts.ctypes.data_as(ctypes.c_void_p), n_t,
+                                         ctx.scheme, ptr(gd), dWp, dbp, ptr(g0), ptr(ws), stream_ptr()),
+              "cfm_ode_fixed_grad_f32")
+        grads = [None] * len(params)
+        grads[0::2] = dWs
+        grads[1::2] = dbs
+        return (g0, None, None, None, *grads)
+
+
+class DifferentiableNeuralODE(NeuralODE):
+    """``NeuralODE`` whose trajectory carries a gradient: a loss can be put on ``node(x, t_span)`` (what the reference's
+    ``sensitivity="adjoint"`` is for: examples/images/cifar10/utils_cifar.py:63).
+
+    ``solver``: ``euler``, ``midpoint`` or ``rk4``.  ``trajectory(x, t_span)`` returns ``[n_t, B, d]``, differentiable
+    with respect to ``x`` and the field's parameters (not ``t_span``); the grid may be decreasing.  The gradient is that
+    of the Runge-Kutta recurrence the forward ran (discretise-then-optimise); torchdyn's ``"adjoint"``
+    integrates the continuous adjoint with the same solver, which differs from it by the scheme's truncation error and is
+    unpinned, as the forward solvers are.
+
+    ``last_path == "hip"``: the field is ``torch_wrapper(MLP(time_varying=True))`` of the small-kernel envelope (4 layers,
+    widths <= 64), the state is 2-D fp32 CUDA, every parameter is fp32 on its device and the library takes the solve
+    (``cfm_ode_fixed_grad_available``).  The forward is ``cfm_ode_fixed_mlp_f32``, bit-equal to
+    ``NeuralODE(vf, solver=s).trajectory(x, t_span)``; the backward is one call of ``cfm_ode_fixed_grad_f32`` over the saved
+    trajectory, once differentiable.  ``"generic"``: everything else (CPU, float64, wider nets, other fields, the fused
+    path switched off) runs the parent's recurrence in differentiable torch ops.  Nothing is printed."""
+
+    def __init__(self, vector_field, solver="euler", **kwargs):
+        super().__init__(vector_field, solver=solver, **kwargs)
+        if solver not in _lib.ODE_SCHEME:
+            raise NotImplementedError(f"solver {solver!r}: the gradient is that of a fixed-step recurrence; "
+                                      f"one of {tuple(_lib.ODE_SCHEME)}")
+
+    def _hip_grad_mlp(self, x):
+        """The MLP when cfm_ode_fixed_grad_f32 takes the solve of this state, else None."""
+        from .cnf import _small_envelope
+        m = self._hip_mlp()
+        if m is None or x.dim() != 2 or not x.is_cuda or x.dtype != torch.float32 or not _small_envelope(m, x.shape[1]):
+            return None
+        lins = m._linears()
+        if lins[3].bias is None or not all(p.dtype == torch.float32 and p.device == x.device for p in m.parameters()):
+            return None
+        dims = [lins[0].in_features] + [l.out_features for l in lins]
+        if _lib.load().cfm_ode_fixed_grad_available((ctypes.c_int * 5)(*dims), 4) != 0:
+            return None
+        return m
+
+    def trajectory(self, x, t_span):
+        ts = torch.as_tensor(t_span).detach().to(dtype=torch.float32).cpu()
+        _check_t_span(ts)
+        m = self._hip_grad_mlp(x)
+        if m is None:
+            self.last_path = "generic"
+            return self._trajectory_generic(x, ts)
+        lins = m._linears()
+        params = [p for l in lins for p in (l.weight, l.bias)]
+        dims = [lins[0].in_features] + [l.out_features for l in lins]
+        scheme = _lib.ODE_SCHEME[self.solver]
+        self.last_path = "hip"
+        self.n_steps = ts.numel() - 1
+        self.nfe = len(FIXED_TABLEAUS[self.solver]["b"]) * self.n_steps
+        return _FixedStepODEFunction.apply(x, np.ascontiguousarray(ts.numpy()), scheme, dims, *params)

@@ -59,6 +59,7 @@ extern "C" {
 #define CFM_OP_TRANSPORT     9   /* cfm_transport_exact_f32 (B0, B1, 0) */
 #define CFM_OP_CNF_GRAD     10   /* cfm_cnf_euler_grad_f32 (B, n_t, 0): per-workgroup partial gradients + t_span */
 #define CFM_OP_ACTION_GRAD  11   /* cfm_action_matching_grad_f32 (B, 0, 0): per-workgroup partial gradients + loss terms */
+#define CFM_OP_ODE_GRAD     12   /* cfm_ode_fixed_grad_f32 (B, n_t, 0): per-workgroup partial gradients + t_span */
 
 /* variants for cfm_sample_xt_ut_f32 (reference class in parentheses) */
 #define CFM_VARIANT_ICFM   0  /* ConditionalFlowMatcher / ExactOT...          */
@@ -518,6 +519,27 @@ int cfm_cnf_euler_grad_f32(const float* const* W, const float* const* b, const i
                            const float* traj, int B, const float* t_span, int n_t, int mode,
                            const float* eps, const float* g_final, float* const* dW, float* const* db,
                            float* g_initial, void* ws, void* stream);
+
+/* Gradient of the plain fixed-step solve that cfm_ode_fixed_mlp_f32(..., scheme) wrote into traj: what
+ * sensitivity="adjoint" asks of NeuralODE(model, solver="euler", sensitivity="adjoint")
+ * (examples/images/cifar10/utils_cifar.py:63; runner/src/models/cfm_module.py:290) when a loss is put on node(x, t_span).
+ * Discretise-then-optimise, as cfm_cnf_euler_grad_f32: the exact gradient of the Runge-Kutta recurrence the forward ran,
+ * for CFM_ODE_EULER, CFM_ODE_MIDPOINT and CFM_ODE_RK4.
+ * traj: device [n_t,B,d], the forward's (the states y_n are read as checkpoints, the stages are recomputed from them);
+ * t_span: host float[n_t], as given to the forward; g_traj: device [n_t,B,d] = dL/d traj, every slice (a loss on traj[-1]
+ * alone has zeros elsewhere).  Outputs (overwritten): dW[l], db[l] device, laid out as W[l], b[l]; g_initial device
+ * [B,d] = dL/d x0, or NULL.  n_t == 1: zero parameter gradients, g_initial = g_traj[0].
+ * ws: cfm_workspace_bytes(CFM_OP_ODE_GRAD, B, n_t, 0).  Envelope: 4 layers, 1 <= every width <= 64, 1 <= d, d + 1 <= 64,
+ * the fused small-field path on (cfm_ode_set_fused); CFM_EINVAL otherwise, there is no layer-per-kernel form.
+ * The result is the same bit pattern run to run (per-workgroup partials, added in a fixed order by a second launch). */
+int cfm_ode_fixed_grad_f32(const float* const* W, const float* const* b, const int* dims, int n_layers,
+                           const float* traj, int B, const float* t_span, int n_t, int scheme,
+                           const float* g_traj, float* const* dW, float* const* db, float* g_initial, void* ws,
+                           void* stream);
+/* Whether cfm_ode_fixed_grad_f32 takes a field of these dims (host int[n_layers + 1]): 0, or CFM_EINVAL.  No GPU work: a
+ * caller that differentiates through the solve (utils_cifar.py:63) asks before the forward, since a backward pass cannot
+ * fall back. */
+int cfm_ode_fixed_grad_available(const int* dims, int n_layers);
 
 /* K13 — action matching: the field v = grad_x s(x, t) of a scalar action net s = MLP([x, t]) with one output
  * (4 linear layers, dims = [d + 1, n1, n2, n3, 1], 1 <= every width <= 64, d + 1 <= 64), and the solves over it.
