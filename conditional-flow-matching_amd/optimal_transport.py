@@ -167,7 +167,15 @@ def transport_exact(M, warm_start=None, return_info=False):
     cfm_transport_exact_f32): device fp64 [B0,B1] plan and its cost.  Raises unless the fp64 certificate holds.
     warm_start: None — decide from the sizes; True / False — force.  The warm start is an optimal assignment of the
     smaller side's rows to distinct indices of the larger side (``assign_exact`` on the matrix padded with zero rows);
-    the solver validates it and never depends on it."""
+    the solver validates it and never depends on it.
+
+    The matrix must be finite: a row of NaN or +inf has no cheapest column (the greedy start would index with the
+    sentinel), and NaN reduced costs compare false in every relaxation AND in the certificate — the loops would run to
+    their guards (64 (B0 + B1) + 1024 phases of up to 4 (B0 + B1) + 16 sweeps on one workgroup) or certify a NaN cost.
+    Checked here, before anything is launched."""
+    if not bool(torch.isfinite(M).all()):
+        raise ValueError("transport_exact: the cost matrix has NaN or infinite entries; the transportation solver "
+                         "takes finite costs only")
     lib = _lib.load()
     B0, B1 = M.shape
     dev = M.device

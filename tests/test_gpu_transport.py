@@ -1,7 +1,9 @@
 """GPU: cfm_transport_exact_f32 — exact OT between uniform marginals of different sizes without the lcm expansion
 (round 6: primal-dual phases with a tree push, optional assignment warm start).  Checked against an independent LP
 solver (scipy.optimize.linprog / HiGHS) on the same fp32 matrix: equal optimal cost, exact marginals; cold start and
-warm start must agree; sizes up to B0 + B1 = 2048."""
+warm start must agree; sizes up to B0 + B1 = 2048.  The second half runs the solver at its edges: B0 + B1 = 2048 exactly
+(8 x 2040 and its transpose: p = 255, q = 1; one supplier; 1024 x 1024), large common divisors, both sides of the
+LDS-staging decision (130 x 138 / 130 x 139), the C entry's refusals, and constant / tied / badly scaled costs."""
 import numpy as np
 import pytest
 import torch
@@ -157,3 +159,153 @@ def test_transport_with_ties_and_sizes_it_refuses():
     big = torch.rand(1500, 1501, device=dev)
     with pytest.raises(NotImplementedError):
         ot.exact_plan_rect(big)
+
+
+# ---------------------------------------------------------------- the solver at its edges
+# Every case below goes through _check_transport: exact marginals (1e-15), plan >= 0, cost == sum P M (1e-12), cost ==
+# the reference (1e-9: HiGHS on the same fp32 matrix, or the value known in closed form), cold start == forced warm
+# start wherever a warm start exists (B0 != B1).  SUPPORT collects support / (R + C) per case: the arc list holds
+# TP_ARC_PER_NODE = 6 arcs per node and is rebuilt once fewer than R + C slots are free, so a ratio above 5 means the
+# rebuild ran; the largest ratio seen is printed (and recorded in DESIGN.md 4.7).
+SUPPORT = {}
+
+
+def _check_one(M, Mh, ref, warm, what):
+    import cfm_amd.optimal_transport as ot
+    B0, B1 = M.shape
+    plan, cost, info = ot.transport_exact(M, warm_start=warm, return_info=True)
+    P = plan.cpu().numpy()
+    np.testing.assert_allclose(P.sum(1), 1.0 / B0, rtol=0, atol=1e-15)
+    np.testing.assert_allclose(P.sum(0), 1.0 / B1, rtol=0, atol=1e-15)
+    assert (P >= 0).all()
+    assert cost == pytest.approx(float((P * Mh).sum()), rel=1e-12, abs=0.0)
+    gap = abs(cost - ref) / abs(ref) if ref != 0.0 else abs(cost)
+    ratio = info["support"] / (B0 + B1)
+    SUPPORT[what + (" warm" if warm else " cold")] = ratio
+    print(f"{what} {'warm' if warm else 'cold'}: phases {info['phases']} sweeps {info['sweeps']} support {info['support']} "
+          f"(x{ratio:.3f} of R + C; largest so far x{max(SUPPORT.values()):.3f}) staged {info['staged']} "
+          f"cost gap {gap:.2e}")
+    assert gap <= 1e-9, (what, cost, ref)
+    assert info["warm_start_used"] == bool(warm)
+    return cost, info
+
+
+def _check_transport(M, ref, what):
+    Mh = M.cpu().numpy().astype(np.float64)
+    cold, info = _check_one(M, Mh, ref, False, what)
+    if M.shape[0] != M.shape[1]:
+        warm, _ = _check_one(M, Mh, ref, True, what)
+        assert warm == pytest.approx(cold, rel=1e-12, abs=0.0)
+    return cold, info
+
+
+@pytest.mark.parametrize("B0,B1", [(8, 2040), (2040, 8), (1, 2047), (2047, 1)])
+def test_transport_at_the_size_bound_with_an_extreme_ratio(B0, B1):
+    """B0 + B1 = 2048 = TP_NMAX exactly.  8 vs 2040: gcd 8, every row supplies p = 255 units and every column takes
+    q = 1 (ratio 255), in both orientations (2040 x 8 goes through the transposed copy); 1 vs 2047: a single supplier
+    (the plan is the uniform row: cost = mean of M), staged in LDS by the size formula."""
+    from cfm_amd import _lib
+    dev = _lib.require_gpu()
+    M = _cloud_cost(B0, B1, 2, 100 * B0 + B1, dev)
+    ref = _lp_cost(M.cpu().numpy())
+    if min(B0, B1) == 1:
+        assert ref == pytest.approx(float(M.cpu().numpy().astype(np.float64).mean()), rel=1e-9)
+    _, info = _check_transport(M, ref, f"{B0}x{B1}")
+    assert info["staged"] == (min(B0, B1) == 1)
+
+
+def test_transport_square_at_the_size_bound():
+    """1024 x 1024 (p = q = 1: an assignment problem, no warm start exists) against SciPy's LSAP on the same fp32
+    matrix: cost = the assignment's total / 1024."""
+    from scipy.optimize import linear_sum_assignment
+    from cfm_amd import _lib
+    dev = _lib.require_gpu()
+    B = 1024
+    M = _cloud_cost(B, B, 2, 100 * B + B, dev)
+    Mh = M.cpu().numpy().astype(np.float64)
+    r, c = linear_sum_assignment(Mh)
+    _check_transport(M, float(Mh[r, c].sum()) / B, f"{B}x{B}")
+
+
+@pytest.mark.parametrize("B0,B1", [(48, 180), (90, 150)])
+def test_transport_with_a_large_common_divisor(B0, B1):
+    """gcd 12 (p / q = 15 / 4) and gcd 30 (5 / 3): exact_plan_rect would take the lcm route for these (lcm 720, 450),
+    so transport_exact is called directly."""
+    from cfm_amd import _lib
+    dev = _lib.require_gpu()
+    M = _cloud_cost(B0, B1, 3, 100 * B0 + B1, dev)
+    _check_transport(M, _lp_cost(M.cpu().numpy()), f"{B0}x{B1}")
+
+
+def test_transport_on_both_sides_of_the_staging_decision():
+    """Node state + staged matrix and flows <= 158 KiB = 161 792 B: 130 x 138 needs 161 384 and is staged in LDS,
+    130 x 139 needs 162 492 and works in global memory."""
+    from cfm_amd import _lib
+    dev = _lib.require_gpu()
+    staged = {}
+    for B0, B1 in ((130, 138), (130, 139)):
+        M = _cloud_cost(B0, B1, 2, 100 * B0 + B1, dev)
+        _, info = _check_transport(M, _lp_cost(M.cpu().numpy()), f"{B0}x{B1}")
+        staged[B1] = info["staged"]
+    assert staged == {138: True, 139: False}
+
+
+def test_transport_c_entry_refusals():
+    """CFM_EINVAL (-1): B0 + B1 = 2049, B0 = 0, a null plan; CFM_EALIGN (-2): a workspace pointer off by 8.  All four
+    return before anything is launched; exact_plan_rect turns 1025 vs 1024 into NotImplementedError."""
+    import cfm_amd.optimal_transport as ot
+    from cfm_amd import _lib
+    from cfm_amd._lib import ptr, stream_ptr
+    dev = _lib.require_gpu()
+    lib = _lib.load()
+    B0, B1 = 1025, 1024
+    M = torch.rand(B0, B1, device=dev)
+    plan = torch.empty((B0, B1), dtype=torch.float64, device=dev)
+    tot = torch.empty(1, dtype=torch.float64, device=dev); info = torch.empty(8, dtype=torch.int32, device=dev)
+    ws = torch.empty(8 * B0 * B1 + (1 << 20), dtype=torch.uint8, device=dev)      # larger than any layout of this shape
+    assert ws.data_ptr() % 16 == 0
+
+    def call(b0, b1, plan_, ws_):
+        return lib.cfm_transport_exact_f32(ptr(M), b0, b1, ptr(None), ptr(plan_), ptr(tot), ptr(info), ptr(ws_), stream_ptr())
+    assert call(B0, B1, plan, ws) == -1
+    assert call(0, B1, plan, ws) == -1
+    assert call(63, 64, None, ws) == -1
+    assert call(63, 64, plan, ws[8:]) == -2
+    torch.cuda.synchronize()
+    with pytest.raises(NotImplementedError):
+        ot.exact_plan_rect(M)
+
+
+def _tied_cloud_cost(B0, B1, seed, dev):
+    """every x1 row four times: columns in identical groups of four, the regime of the lcm expansion"""
+    import cfm_amd.optimal_transport as ot
+    g = torch.Generator().manual_seed(seed)
+    x0 = torch.randn(B0, 2, generator=g)
+    x1 = (torch.randn(B1 // 4, 2, generator=g) * 0.7 + 0.5).repeat_interleave(4, dim=0)
+    assert x1.shape[0] == B1
+    return ot.cost_matrix(x0.to(dev), x1.to(dev))
+
+
+@pytest.mark.parametrize("B0,B1", [(45, 64), (8, 200)])
+def test_transport_cost_structure(B0, B1):
+    """Constant, tied and badly scaled costs.  The certificate's tolerance is 1e-10 * max |M|, so it must follow the scale.
+
+    Scaled matrices: s M is rounded to fp32 again (each entry moves by at most 2^-24 relative, all entries >= 0), so the
+    two optima satisfy |opt(s M) / s - opt(M)| <= 2^-24 (1 + 2^-24) opt(M) and no closer; that is asserted as the
+    sanity check of the scale, and the 1e-9 bound is asserted against HiGHS on the SAME scaled fp32 matrix."""
+    from cfm_amd import _lib
+    dev = _lib.require_gpu()
+    cost, _ = _check_transport(torch.zeros(B0, B1, device=dev), 0.0, f"{B0}x{B1} zeros")
+    assert cost == 0.0
+    cost, _ = _check_transport(torch.full((B0, B1), 3.0, device=dev), 3.0, f"{B0}x{B1} constant 3")
+    assert cost == pytest.approx(3.0, rel=1e-12, abs=0.0)
+    Mt = _tied_cloud_cost(B0, B1, 100 * B0 + B1, dev)
+    _check_transport(Mt, _lp_cost(Mt.cpu().numpy()), f"{B0}x{B1} x1 rows four times")
+    M = _cloud_cost(B0, B1, 2, 100 * B0 + B1, dev)
+    base, _ = _check_transport(M, _lp_cost(M.cpu().numpy()), f"{B0}x{B1} cloud")
+    for s in (1e6, 1e-6):
+        Ms = (M * s).contiguous()
+        # (HiGHS works to absolute tolerances: it gets the matrix at O(1), rescaled in float64 — the same LP)
+        ref = _lp_cost(Ms.cpu().numpy().astype(np.float64) / s) * s
+        cs, _ = _check_transport(Ms, ref, f"{B0}x{B1} cloud * {s:g}")
+        assert abs(cs / s - base) <= 2.0 ** -24 * (1 + 2.0 ** -24) * base + 1e-15 * base

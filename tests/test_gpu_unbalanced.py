@@ -1,6 +1,9 @@
 """GPU: OTPlanSampler(method="unbalanced" | "partial") — the kernel-space fp64 solvers behind
 cfm_unbalanced_sinkhorn_f64 / cfm_partial_entropic_f64 against the committed golden plans
 (recorded from the reference wrapper over the restated POT loops) and against the oracle.
+Shapes here: 96 x 96, 96 x 64, 2 x 2, 32 x 32, 128 x 128 and 4096 x 4096 (every B1 even: the double2 row path); the
+shapes at which the device code takes another branch (odd B1, B1 > 512 with a partial group, ragged / empty strips,
+more than 1024 / 2048 rows, mid-loop revert, max_iter = 0) are in tests/test_gpu_unbalanced_shapes.py.
 
 Tolerance: plans are float64 sums of ~B terms in a different summation order than NumPy's
 dot -> 1e-9 relative to the largest entry (the north-star bound for potentials is 1e-5)."""

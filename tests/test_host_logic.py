@@ -158,3 +158,23 @@ def test_float64_inputs_to_the_sampler_warn_once_and_never_silently():
         call(OTPlanSampler("sinkhorn").__class__("exact"))     # a fresh sampler warns again
     msgs = [str(x.message) for x in w if "float64" in str(x.message)]
     assert len(msgs) == 1
+
+
+@pytest.mark.parametrize("bad", [float("nan"), float("inf"), float("-inf")])
+def test_transport_exact_refuses_non_finite_costs_before_anything_is_launched(bad, monkeypatch):
+    """The rectangular solver's relaxations and its certificate compare with < and >: NaN passes both, a row of
+    NaN / +inf has no cheapest column.  The host wrapper refuses such a matrix before the library is even loaded (so
+    this runs without a GPU), through transport_exact and through exact_plan_rect's route to it (127 x 128)."""
+    import cfm_amd.optimal_transport as ot
+
+    def no_load():
+        raise AssertionError("the library was loaded for a non-finite matrix")
+    monkeypatch.setattr(ot._lib, "load", no_load)
+    M = torch.rand(5, 7, generator=torch.Generator().manual_seed(0))
+    M[2, 3] = bad
+    with pytest.raises(ValueError, match="NaN or infinite"):
+        ot.transport_exact(M)
+    M2 = torch.rand(127, 128, generator=torch.Generator().manual_seed(1))
+    M2[126, :] = bad
+    with pytest.raises(ValueError, match="NaN or infinite"):
+        ot.exact_plan_rect(M2)
