@@ -16,7 +16,7 @@ from .conditional_flow_matching import (  # noqa: F401
     pad_t_like_x,
 )
 from .models import MLP  # noqa: F401
-from .cnf import CNF, DifferentiableCNF, log_likelihood  # noqa: F401
+from .cnf import CNF, DifferentiableCNF, RegularizedCNF, log_likelihood  # noqa: F401
 from .ode import DifferentiableNeuralODE  # noqa: F401
 from .action_matching import action_matching_loss  # noqa: F401
 from .optim import FusedAdam  # noqa: F401

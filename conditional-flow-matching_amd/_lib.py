@@ -98,6 +98,8 @@ SIGNATURES = {
                                          _vp, _vp]),
     "cfm_ode_fixed_cnf_mlp_f32": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "cfm_cnf_euler_grad_f32": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cfm_ode_euler_cnf_reg_mlp_f32": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "cfm_cnf_reg_euler_grad_f32": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cfm_mlp_grad_field_f32": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _f, _vp, _vp, _vp, _vp]),
     "cfm_ode_fixed_gradmlp_f32": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "cfm_ode_adaptive_gradmlp_f32": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp]),

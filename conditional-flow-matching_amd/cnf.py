@@ -24,6 +24,10 @@ gradient.  On the HIP path the forward is ``cfm_ode_fixed_cnf_mlp_f32`` at Euler
 solver instead, which differs from this by O(h); torchdyn is absent from the reference tree, so that variant is
 unpinned, as the forward solvers are.
 
+``RegularizedCNF`` adds the reference's kinetic and Jacobian penalties (``AugmentationModule`` with ``squared_l2_reg`` /
+``jacobian_frobenius_reg``, ``CNFLitModule.step``) as further state columns ``[l, (e), (f), y]``: forward
+``cfm_ode_euler_cnf_reg_mlp_f32``, backward one launch of ``cfm_cnf_reg_euler_grad_f32``.
+
 Hutchinson probes are fixed for a whole solve (FFJORD's convention, model-comparison's ``CNF.noise``
 slot): ``cnf.noise`` if set, else one draw per ``NeuralODE.trajectory`` call, kept as
 ``cnf.last_noise``.  The ML-CNF tutorial redraws the probe at every evaluation; that is not replicated.
@@ -335,3 +339,187 @@ class DifferentiableCNF(CNF):
         z, ell = out[:, 1:], out[:, 0]
         logp0 = prior_log_prob(z) if prior_log_prob is not None else standard_normal_log_prob(z)
         return -(logp0 - ell).mean()
+
+
+# ---- regularised CNF training: the kinetic and Jacobian penalties as path integrals ----------------
+REG_NAMES = ("squared_L2", "jacobian_frobenius")        # bit 0, bit 1 of reg_mask; the reference's order
+
+
+class _CNFRegEulerFunction(torch.autograd.Function):
+    """The final state [l, (e), (f), y] of the regularised Euler solve (cfm_ode_euler_cnf_reg_mlp_f32); backward:
+    cfm_cnf_reg_euler_grad_f32 over the saved trajectory and the saved ||J||_F^2 per (step, row)."""
+
+    @staticmethod
+    def forward(ctx, x_aug, ts, eps, dims, mask, *params):
+        lib = _lib.load()
+        dev = x_aug.device
+        Ws = [_lib.to_dev_f32(p, dev) for p in params[0::2]]
+        bs = [_lib.to_dev_f32(p, dev) for p in params[1::2]]
+        Wp = (ctypes.c_void_p * 4)(*[w.data_ptr() for w in Ws])
+        bp = (ctypes.c_void_p * 4)(*[b.data_ptr() for b in bs])
+        cdims = (ctypes.c_int * 5)(*dims)
+        xd = _lib.to_dev_f32(x_aug, dev)
+        B, D = xd.shape
+        n_t = ts.shape[0]
+        traj = torch.empty((n_t, B, D), dtype=torch.float32, device=dev)
+        jsq = torch.empty((max(n_t - 1, 1), B), dtype=torch.float32, device=dev) if mask & 2 else None
+        ws = _lib.workspace(_lib.OP_ODE, B, max(dims[1:4]), D, dev)
+        ed = _lib.to_dev_f32(eps, dev) if eps is not None else None
+        nfe = ctypes.c_int(0)
+        rc = lib.cfm_ode_euler_cnf_reg_mlp_f32(Wp, bp, cdims, 4, ptr(xd), B, ts.ctypes.data_as(ctypes.c_void_p), n_t,
+                                               0 if eps is None else 1, ptr(ed), mask, ptr(traj), ptr(jsq),
+                                               ctypes.byref(nfe), ptr(ws), stream_ptr())
+        if rc == -1:
+            raise _Declined()
+        _lib.check(rc, "cfm_ode_euler_cnf_reg_mlp_f32")
+        ctx.ts, ctx.dims, ctx.eps, ctx.mask, ctx.jsq = ts, dims, ed, mask, jsq
+        ctx.save_for_backward(traj, *params)
+        return traj[-1].clone()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        lib = _lib.load()
+        traj, *params = ctx.saved_tensors
+        dev = traj.device
+        Ws = [_lib.to_dev_f32(p, dev) for p in params[0::2]]
+        bs = [_lib.to_dev_f32(p, dev) for p in params[1::2]]
+        dWs = [torch.empty_like(w) for w in Ws]
+        dbs = [torch.empty_like(b) for b in bs]
+        Wp = (ctypes.c_void_p * 4)(*[w.data_ptr() for w in Ws])
+        bp = (ctypes.c_void_p * 4)(*[b.data_ptr() for b in bs])
+        dWp = (ctypes.c_void_p * 4)(*[w.data_ptr() for w in dWs])
+        dbp = (ctypes.c_void_p * 4)(*[b.data_ptr() for b in dbs])
+        cdims = (ctypes.c_int * 5)(*ctx.dims)
+        n_t, B, D = traj.shape
+        gd = _lib.to_dev_f32(g, dev)
+        g0 = torch.empty((B, D), dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
+        ws = _lib.workspace(_lib.OP_CNF_GRAD, B, n_t, 0, dev)
+        rc = lib.cfm_cnf_reg_euler_grad_f32(Wp, bp, cdims, 4, ptr(traj), B, ctx.ts.ctypes.data_as(ctypes.c_void_p), n_t,
+                                            0 if ctx.eps is None else 1, ptr(ctx.eps), ctx.mask, ptr(ctx.jsq), ptr(gd),
+                                            dWp, dbp, ptr(g0), ptr(ws), stream_ptr())
+        _lib.check(rc, "cfm_cnf_reg_euler_grad_f32")
+        grads = [None] * len(params)
+        grads[0::2] = dWs
+        grads[1::2] = dbs
+        return (g0, None, None, None, None, *grads)
+
+
+class RegularizedCNF(DifferentiableCNF):
+    """``DifferentiableCNF`` with the reference's path-integral regularisers (RNODE / TrajectoryNet): the state that
+    ``AugmentationModule`` builds (runner/src/models/components/augmentation.py:137-210) under ``AugmentedVectorField``
+    (:266-303), integrated and differentiated as ``CNFLitModule.step`` does (runner/src/models/cfm_module.py:1412-1454).
+
+    The state is ``[l, (e), (f), y]`` of width 1 + r + d.  A column is carried only if its coefficient is > 0, in the
+    reference's order (``names``): ``log_prob``; ``squared_L2`` (e += h |v|^2, ``SquaredL2Reg``); ``jacobian_frobenius``
+    (f += h ||dv/dx||_F / d, ``JacobianFrobeniusReg``).  With both coefficients 0 this is the parent class.
+
+    ``solve`` runs on the HIP kernels (``last_path == "hip"``: ``cfm_ode_euler_cnf_reg_mlp_f32`` forward, one launch of
+    ``cfm_cnf_reg_euler_grad_f32`` backward; columns l and y are bit-equal to the parent's solve) under the parent's
+    conditions, for the exact trace with either or both penalties and for a Hutchinson estimator with ``squared_L2``
+    alone.  Everything else runs the same recurrence in differentiable torch ops (``"generic"``): CPU, float64, other
+    fields, ``jacobian_frobenius`` with a Hutchinson estimator, the fused path switched off, a grid of more than
+    3 B (1 + r + d) points."""
+
+    def __init__(self, model, squared_l2_reg=0.0, jacobian_frobenius_reg=0.0, estimator="exact", noise=None):
+        super().__init__(model, estimator=estimator, noise=noise)
+        if squared_l2_reg < 0.0 or jacobian_frobenius_reg < 0.0:
+            raise ValueError("a regularisation coefficient is >= 0 (0: the column is not carried)")
+        self.reg_mask = (1 if squared_l2_reg > 0.0 else 0) | (2 if jacobian_frobenius_reg > 0.0 else 0)
+        self.names = ["log_prob"] + [n for k, n in enumerate(REG_NAMES) if self.reg_mask >> k & 1]
+        self.coeffs = torch.tensor([1.0] + [float(c) for c in (squared_l2_reg, jacobian_frobenius_reg) if c > 0.0])
+        self.aug_dims = len(self.names)
+
+    def solve(self, x_aug, t_span):
+        from .ode import _check_t_span
+        if self.reg_mask == 0:
+            return super().solve(x_aug, t_span)
+        a = self.aug_dims
+        if x_aug.dim() != 2 or x_aug.shape[1] < a + 1:
+            raise ValueError(f"the state is [B, {a} + d] ({', '.join(self.names)}, x); got {tuple(x_aug.shape)}")
+        ts = torch.as_tensor(t_span).detach().to(dtype=x_aug.dtype).cpu()
+        _check_t_span(ts)
+        y = x_aug[:, a:]
+        eps = None
+        if self.estimator != "exact":
+            eps = self.checked_noise(y) if self.noise is not None else self.draw_noise(y)
+        m = self.hip_mlp(y.shape[1])
+        if (m is not None and x_aug.is_cuda and x_aug.dtype == torch.float32
+                and (self.estimator == "exact" or self.reg_mask == 1)
+                and all(p.dtype == torch.float32 and p.device == x_aug.device for p in m.parameters())):
+            lins = m._linears()
+            params = [p for l in lins for p in (l.weight, l.bias)]
+            dims = [lins[0].in_features] + [l.out_features for l in lins]
+            try:
+                out = _CNFRegEulerFunction.apply(x_aug, ts.numpy().copy(), eps, dims, self.reg_mask, *params)
+                self.last_path = "hip"
+                return out
+            except _Declined:
+                pass
+        self.last_path = "generic"
+        return self._solve_generic(x_aug, ts, eps)
+
+    def _solve_generic(self, x_aug, ts, eps):
+        """The recurrence in differentiable torch ops, as the parent's (through the module graph, parameters cast to the
+        state's dtype); the Jacobian's norm is torch.norm's, so its gradient is 0 where the Jacobian is."""
+        if self.reg_mask == 0:
+            return super()._solve_generic(x_aug, ts, eps)
+        m = self.model
+        grad_field = isinstance(m, GradModel)        # v = d action / dx: GradModel.forward's autograd.grad has no torch.func rule
+        if grad_field:
+            m = m.action
+        net = m.net if isinstance(m, MLP) else m
+        a = self.aug_dims
+        cols = [x_aug[:, k] for k in range(a)]
+        y = x_aug[:, a:]
+        d = y.shape[1]
+        params = {k: p.to(device=y.device, dtype=y.dtype) for k, p in net.named_parameters()}
+        buffers = {k: b.to(device=y.device) for k, b in net.named_buffers()}
+        for n in range(ts.numel() - 1):
+            h = float(ts[n + 1] - ts[n])
+            tt = ts[n].to(device=y.device).reshape(1)
+
+            def net_of(z):
+                return torch.func.functional_call(net, (params, buffers), (z[None],))[0]
+
+            def f(yy):
+                z = torch.cat([yy, tt])
+                return torch.func.grad(lambda q: net_of(q).sum())(z)[:d] if grad_field else net_of(z)
+            jac = None
+            if eps is None or self.reg_mask & 2:
+                jac = torch.func.vmap(torch.func.jacrev(f))(y)
+            if eps is None:
+                v = torch.func.vmap(f)(y)
+                div = torch.diagonal(jac, dim1=-2, dim2=-1).sum(-1)
+            else:
+                v, jv = torch.func.vmap(lambda yy, ee: torch.func.jvp(f, (yy,), (ee,)))(y, eps)
+                div = (eps * jv).sum(-1)
+            cols[0] = cols[0] - h * div
+            k = 1
+            if self.reg_mask & 1:
+                cols[k] = cols[k] + h * (v * v).sum(1)
+                k += 1
+            if self.reg_mask & 2:
+                cols[k] = cols[k] + h * torch.norm(jac.reshape(jac.shape[0], -1), p=2, dim=1) / d
+            y = y + h * v
+        return torch.cat([torch.stack(cols, 1), y], 1)
+
+    def split(self, state):
+        """``(delta_logprob [B, 1], reg [B, r], x [B, d])`` as ``AugmentationModule.forward`` (augmentation.py:206-210):
+        the regulariser columns times their coefficients; ``zeros(1)`` when none is carried."""
+        a = self.aug_dims
+        delta_logprob, aug, x = state[:, :1], state[:, 1:a], state[:, a:]
+        reg = aug * self.coeffs[1:].to(aug)
+        if a == 1:
+            reg = torch.zeros(1).type_as(x)
+        return delta_logprob, reg, x
+
+    def loss(self, x, steps=100, t_span=None, prior_log_prob=None):
+        """``(reg, nll)`` as ``CNFLitModule.step`` for a single time point (cfm_module.py:1437-1454): the solve of
+        [0, .., 0, x] from t = 1 to t = 0 on `steps` uniform Euler steps (or on `t_span`); reg = -mean(aug * coeffs)
+        over rows and columns (negative because the integration runs backward), nll = -mean(prior(z) - l)."""
+        ts = torch.linspace(1.0, 0.0, int(steps) + 1, dtype=x.dtype) if t_span is None else t_span
+        out = self.solve(torch.cat([torch.zeros_like(x[:, :1]).expand(-1, self.aug_dims), x], 1), ts)
+        delta_logprob, reg, z = self.split(out)
+        logp0 = prior_log_prob(z) if prior_log_prob is not None else standard_normal_log_prob(z)
+        return torch.mean(-reg), -(logp0 - delta_logprob[:, 0]).mean()

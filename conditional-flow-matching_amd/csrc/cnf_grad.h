@@ -20,6 +20,17 @@
 // K = the 16 rows of the tile (cg_outer), kept across all steps and tiles of the workgroup; every workgroup writes one
 // partial gradient and ode_small_grad_reduce adds the partials in workgroup order: the same bits run to run.
 // Rows are independent: no cross-workgroup wait of any kind.
+//
+// REG (bit 0: squared_L2, bit 1: jacobian_frobenius) is the regularised solve of cnf_reg.h: the state is
+// [l, (e), (f), y], e += h |v|^2, f += h sqrt(S) / d with S = sum_k |J e_k|^2, J e_k = W_3 T_3^k.  With ce, cf the upstream
+// columns of e and f (constant along the solve, as c is):
+//   g_n = a . v - c div + ce |v|^2 + cf sqrt(S) / d
+//   bit 0: the primal output cotangent is h (a + 2 ce v) in place of h a: the last layer is evaluated for v
+//   bit 1: the cotangent of direction k's column J e_k is Jb_k = -h c e_k + (h cf / (d sqrt(S))) J e_k (no second term
+//          where S = 0, as torch.norm's backward has it), so Tb_3 = Jb_k W_3 and dW_3 += Jb_k^T T_3^k: one sm_gemm for
+//          J e_k, one cg_gemm_t and one cg_outer on a sixth tile buffer JB; S is read from the forward's side buffer
+//          jsq [n_t - 1, B].  Below Tb_3 the sweep is the one above.
+// REG = 0 is the kernel as it was: every REG branch is an `if constexpr`.
 #pragma once
 
 static_assert(SM_MB == 1, "the gradient kernel is written for one 16-row block per tile");
@@ -110,14 +121,21 @@ __device__ __forceinline__ void cg_store_partial(const SmArgs& A, int d, float* 
 // one staged net, the transposed copies of its two 64 x 64 layers, five tile buffers
 constexpr size_t cg_lds_bytes = small_lds_bytes(1, 5, false) + sizeof(float) * 2 * SM_W * SM_LD;
 static_assert(cg_lds_bytes == 127488, "the gradient kernel");
+// the sixth tile buffer (JB) of the jacobian_frobenius sweep: above 128 KB, inside the CU's 160 KB
+constexpr size_t cg_lds_bytes_jac = cg_lds_bytes + sizeof(float) * SM_ROWS * SM_LD;
+static_assert(cg_lds_bytes_jac == 131840 && cg_lds_bytes_jac <= 160 * 1024, "the gradient kernel with the Jacobian penalty");
+constexpr int cg_reg_cols(int REG) { return (REG & 1) + ((REG >> 1) & 1); }
 
-// traj [n_t, B, 1 + d]: the forward solve (y_n is read); G [B, 1 + d]; g0 [B, 1 + d] or null; part [gridDim.x][P]:
-// the workgroup's partial gradient in the order W0, b0, W1, b1, W2, b2, W3, b3 (each as the caller's tensor is laid out)
-template <int MODE>
+// traj [n_t, B, D]: the forward solve (y_n is read), D = 1 + cg_reg_cols(REG) + d; G [B, D]; g0 [B, D] or null;
+// part [gridDim.x][P]: the workgroup's partial gradient in the order W0, b0, W1, b1, W2, b2, W3, b3 (each as the caller's
+// tensor is laid out); jsq [n_t - 1, B]: S per (step, row) as the forward wrote it (read with REG bit 1 only)
+template <int MODE, int REG = 0>
 __global__ __launch_bounds__(256) void ode_small_euler_grad(SmArgs A, int B, int d, const float* __restrict__ tspan, int n_t,
                                                          const float* __restrict__ traj, const float* __restrict__ eps,
                                                          const float* __restrict__ G, float* __restrict__ g0,
-                                                         float* __restrict__ part, int P) {
+                                                         float* __restrict__ part, int P,
+                                                         const float* __restrict__ jsq) {
+    static_assert(REG >= 0 && REG <= 3 && (MODE == AUG_EXACT || !(REG & 2)), "the Jacobian penalty needs the exact directions");
     extern __shared__ __attribute__((aligned(16))) float small_lds[];
     constexpr int TS = SM_ROWS * SM_LD, WS = SM_W * SM_LD;
     float* Wl = small_lds;
@@ -129,10 +147,12 @@ __global__ __launch_bounds__(256) void ode_small_euler_grad(SmArgs A, int B, int
     float* X2 = X1 + TS;
     float* X3 = X2 + TS;
     float* Y3 = X3 + TS;
+    float* JB = Y3 + TS;                      // REG bit 1 only (cg_lds_bytes_jac)
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     sm_stage_weights(A, d, Wl, bl, wt, tid);
     cg_stage_transposed(A, WT, tid);
-    const int D = d + 1;
+    constexpr int c0 = 1 + cg_reg_cols(REG);  // the column of y_0 in a state row
+    const int D = d + c0;
     const size_t n = (size_t)B * D;
     const int col = wv * 16 + (lane & 15);
     const bool lw = wv == 0 && (lane & 15) == 0;
@@ -151,15 +171,17 @@ __global__ __launch_bounds__(256) void ode_small_euler_grad(SmArgs A, int B, int
 
     for (int row0 = blockIdx.x * SM_ROWS; row0 < B; row0 += gridDim.x * SM_ROWS) {
         const int nrows = B - row0;
-        SmTile a, cv, ep, yn;
+        SmTile a, cv, ep, yn, ce, cf;
 #pragma unroll
         for (int i = 0; i < SM_V; ++i) {
             const int gr = row0 + sm_row(i, lane);
             const bool ok = gr < B && col < d;
-            a.v[i] = ok ? G[(size_t)gr * D + 1 + col] : 0.f;
+            a.v[i] = ok ? G[(size_t)gr * D + c0 + col] : 0.f;
             cv.v[i] = gr < B ? G[(size_t)gr * D] : 0.f;
+            if constexpr (REG & 1) ce.v[i] = gr < B ? G[(size_t)gr * D + 1] : 0.f;
+            if constexpr (REG & 2) cf.v[i] = gr < B ? G[(size_t)gr * D + 1 + (REG & 1)] : 0.f;
             ep.v[i] = (MODE == AUG_HUTCH && ok) ? eps[(size_t)gr * d + col] : 0.f;
-            yn.v[i] = (ok && n_t >= 2) ? traj[(size_t)(n_t - 2) * n + (size_t)gr * D + 1 + col] : 0.f;
+            yn.v[i] = (ok && n_t >= 2) ? traj[(size_t)(n_t - 2) * n + (size_t)gr * D + c0 + col] : 0.f;
         }
         __syncthreads();
         for (int st = n_t - 2; st >= 0; --st) {
@@ -169,12 +191,21 @@ __global__ __launch_bounds__(256) void ode_small_euler_grad(SmArgs A, int B, int
 #pragma unroll
                 for (int i = 0; i < SM_V; ++i) {
                     const int gr = row0 + sm_row(i, lane);
-                    yn.v[i] = (gr < B && col < d) ? traj[(size_t)(st - 1) * n + (size_t)gr * D + 1 + col] : 0.f;
+                    yn.v[i] = (gr < B && col < d) ? traj[(size_t)(st - 1) * n + (size_t)gr * D + c0 + col] : 0.f;
                 }
             }
             SmTile ap, cp;
 #pragma unroll
             for (int i = 0; i < SM_V; ++i) { ap.v[i] = h * a.v[i]; cp.v[i] = -(h * cv.v[i]); }    // cp = -h c
+            SmTile rs;                                    // h cf / (d sqrt(S)) per row; 0 where S = 0
+            if constexpr (REG & 2) {
+#pragma unroll
+                for (int i = 0; i < SM_V; ++i) {
+                    const int gr = row0 + sm_row(i, lane);
+                    const float S = gr < B ? jsq[(size_t)st * B + gr] : 0.f;
+                    rs.v[i] = S > 0.f ? (h * cf.v[i]) / ((float)d * sqrtf(S)) : 0.f;
+                }
+            }
 
             // ---- primal forward: s_l, q_l, h_l (the arithmetic of sm_field_aug) ----
             SmTile s[3], q[3], hh[3];
@@ -202,6 +233,17 @@ __global__ __launch_bounds__(256) void ode_small_euler_grad(SmArgs A, int B, int
                         cg_put(dst, hh[l], lane, col);
                         sm_lds_barrier();
                         float* tmp = src; src = dst; dst = tmp;
+                    }
+                }
+                if constexpr (REG & 1) {                  // v = W3 h3 + b3: the seed of the output is h (a + 2 ce v)
+                    cg_put(dst, hh[2], lane, col);        // dst = X2: last read by layer 1, a barrier ago
+                    sm_lds_barrier();
+                    sm_gemm(dst, W3, wv, lane, c);
+                    const float bv = (col < d) ? bl[3 * SM_W + col] : 0.f;
+#pragma unroll
+                    for (int i = 0; i < SM_V; ++i) {
+                        const float v = (col < d) ? c[0][i] + bv : 0.f;
+                        ap.v[i] = h * (a.v[i] + 2.f * ce.v[i] * v);
                     }
                 }
             }
@@ -242,6 +284,26 @@ __global__ __launch_bounds__(256) void ode_small_euler_grad(SmArgs A, int B, int
                 cg_put(X2, tv, lane, col);                                                  // T2
                 sm_lds_barrier();
                 sm_gemm(X2, Wl + 2 * WS, wv, lane, c);
+                if constexpr (REG & 2) {
+#pragma unroll
+                    for (int i = 0; i < SM_V; ++i) { U3.v[i] = c[0][i]; tv.v[i] = s[2].v[i] * U3.v[i]; }
+                    cg_put(X3, tv, lane, col);                                              // T3
+                    sm_lds_barrier();
+                    sm_gemm(X3, W3, wv, lane, c);                                           // J e_k (columns >= d are 0)
+#pragma unroll
+                    for (int i = 0; i < SM_V; ++i)
+                        tv.v[i] = fmaf(rs.v[i], c[0][i], (col == k && sm_row(i, lane) < nrows) ? cp.v[i] : 0.f);
+                    cg_put(JB, tv, lane, col);                                              // Jb_k
+                    sm_lds_barrier();
+                    cg_outer(JB, X3, wv, lane, dWa[3]);
+                    cg_gemm_t(JB, W3, wv, lane, c[0]);                                      // Tb3 = Jb_k W3
+#pragma unroll
+                    for (int i = 0; i < SM_V; ++i) {
+                        const float tb = c[0][i];
+                        sb[2].v[i] = fmaf(tb, U3.v[i], sb[2].v[i]);
+                        tv.v[i] = s[2].v[i] * tb;
+                    }
+                } else {                  // the sweep without the Jacobian penalty: its lines as they were, indentation included
 #pragma unroll
                 for (int i = 0; i < SM_V; ++i) { U3.v[i] = c[0][i]; tv.v[i] = cp.v[i] * (s[2].v[i] * U3.v[i]); }
                 cg_put(X3, tv, lane, col);                                                  // -h c T3
@@ -258,6 +320,7 @@ __global__ __launch_bounds__(256) void ode_small_euler_grad(SmArgs A, int B, int
                     const float tb = cp.v[i] * c[0][i];
                     sb[2].v[i] = fmaf(tb, U3.v[i], sb[2].v[i]);
                     tv.v[i] = s[2].v[i] * tb;
+                }
                 }
                 cg_put(Y3, tv, lane, col);                                                  // Ub3
                 sm_lds_barrier();
@@ -327,8 +390,10 @@ __global__ __launch_bounds__(256) void ode_small_euler_grad(SmArgs A, int B, int
 #pragma unroll
             for (int i = 0; i < SM_V; ++i) {
                 const int gr = row0 + sm_row(i, lane);
-                if (gr < B && col < d) g0[(size_t)gr * D + 1 + col] = a.v[i];
+                if (gr < B && col < d) g0[(size_t)gr * D + c0 + col] = a.v[i];
                 if (gr < B && lw) g0[(size_t)gr * D] = cv.v[i];
+                if constexpr (REG & 1) { if (gr < B && lw) g0[(size_t)gr * D + 1] = ce.v[i]; }
+                if constexpr (REG & 2) { if (gr < B && lw) g0[(size_t)gr * D + 1 + (REG & 1)] = cf.v[i]; }
             }
         }
     }
@@ -356,13 +421,15 @@ __global__ __launch_bounds__(256) void ode_small_grad_reduce(const float* __rest
     if (tail && p == 0) *tail = sum;
 }
 
-template <int MODE>
+template <int MODE, int REG = 0>
 static int cnf_grad_launch(const SmArgs& A, int B, int d, const float* tspan_dev, int n_t, const float* traj,
-                           const float* eps, const float* G, float* g0, float* part, int P, const CgOut& O, hipStream_t s) {
-    const int grid = small_grid<ode_small_euler_grad<MODE>, 128 * 1024>(B, CG_MAXGRID);
+                           const float* eps, const float* G, float* g0, float* part, int P, const CgOut& O, hipStream_t s,
+                           const float* jsq = nullptr) {
+    constexpr size_t lds = (REG & 2) ? cg_lds_bytes_jac : cg_lds_bytes;
+    const int grid = small_grid<ode_small_euler_grad<MODE, REG>, ((REG & 2) ? 160 : 128) * 1024>(B, CG_MAXGRID);
     if (grid < 0) return CFM_EINVAL;
-    hipLaunchKernelGGL(ode_small_euler_grad<MODE>, dim3(grid), dim3(256), cg_lds_bytes, s, A, B, d, tspan_dev, n_t, traj, eps,
-                       G, g0, part, P);
+    hipLaunchKernelGGL((ode_small_euler_grad<MODE, REG>), dim3(grid), dim3(256), lds, s, A, B, d, tspan_dev, n_t, traj, eps,
+                       G, g0, part, P, jsq);
     int rc = cfm_status();
     if (rc) return rc;
     hipLaunchKernelGGL(ode_small_grad_reduce, dim3((P + 255) / 256), dim3(256), 0, s, (const float*)part, grid, P, A, O, 1.f, nullptr);

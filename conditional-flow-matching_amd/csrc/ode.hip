@@ -1221,6 +1221,10 @@ extern "C" int cfm_ode_adaptive_gradmlp_f32(const float* const* W, const float* 
 // ---- CNF training: the gradient of the Euler augmented solve (ode_small_euler_grad, cfm_cnf_euler_grad_f32) ----
 #include "cnf_grad.h"
 
+// ---- regularised CNF training: the Euler solve with the kinetic / Jacobian path integrals and its gradient
+// (ode_small_euler_reg, cfm_ode_euler_cnf_reg_mlp_f32, cfm_cnf_reg_euler_grad_f32) ----
+#include "cnf_reg.h"
+
 // ---- training through the sampler: the gradient of the plain fixed-step solves (ode_small_fixed_grad, cfm_ode_fixed_grad_f32) ----
 #include "ode_grad.h"
 

@@ -520,6 +520,35 @@ int cfm_cnf_euler_grad_f32(const float* const* W, const float* const* b, const i
                            const float* eps, const float* g_final, float* const* dW, float* const* db,
                            float* g_initial, void* ws, void* stream);
 
+/* Regularised CNF training (RNODE / TrajectoryNet): the Euler solve of the state that AugmentationModule builds
+ * (runner/src/models/components/augmentation.py:137-210) under AugmentedVectorField (:266-303), and its gradient: what
+ * CNFLitModule.step (runner/src/models/cfm_module.py:1412-1454) integrates and differentiates.
+ * reg_mask: bit 0 = squared_L2 (SquaredL2Reg, augmentation.py:31-34: |v|^2), bit 1 = jacobian_frobenius
+ * (JacobianFrobeniusReg, :64-73: ||dv/dx||_F / d); at least one bit (mask 0 is cfm_ode_fixed_cnf_mlp_f32 /
+ * cfm_cnf_euler_grad_f32).  State rows [l, (e), (f), x], D = 1 + popcount(reg_mask) + d, columns in the reference's order
+ * (:158-177); per step y += h v, l -= h div, e += h |v|^2, f += h ||J||_F / d, everything at (y_n, t_n); columns l and x
+ * are the bit patterns of cfm_ode_fixed_cnf_mlp_f32 at CFM_ODE_EULER.  mode / eps as cfm_mlp_divergence_f32; bit 1 needs
+ * mode 0 (the Jacobian's columns are the exact trace's directions), mode 1 takes reg_mask 1 only: CFM_EINVAL otherwise.
+ * Forward: x0 device [B,D], traj device [n_t,B,D]; jac_sq device [n_t-1,B], written with bit 1 (||J||_F^2 per step and row,
+ * which the gradient reads back), NULL allowed without it; t_span host float[n_t], strictly monotone either way;
+ * ws: cfm_workspace_bytes(CFM_OP_ODE, B, max width, D), CFM_EINVAL when n_t > 3 B D.
+ * Same envelope and CFM_EINVAL rule as cfm_mlp_divergence_f32. */
+int cfm_ode_euler_cnf_reg_mlp_f32(const float* const* W, const float* const* b, const int* dims, int n_layers,
+                                  const float* x0, int B, const float* t_span, int n_t, int mode,
+                                  const float* eps, int reg_mask, float* traj, float* jac_sq, int* nfe, void* ws,
+                                  void* stream);
+/* Its gradient, discretise-then-optimise as cfm_cnf_euler_grad_f32: replaces loss.backward() through the augmented solve
+ * of cfm_module.py:1443, which in autograd differentiates JacobianFrobeniusReg's d rows of
+ * autograd.grad(..., create_graph=True) (augmentation.py:37-61) a second time.  traj, t_span, mode, eps, reg_mask, jac_sq:
+ * as given to / written by the forward; g_final device [B,D] = dL/d(final state); outputs as cfm_cnf_euler_grad_f32, with
+ * g_initial device [B,D] or NULL (the columns of l, e and f pass through: each enters the recurrence linearly).  Where
+ * ||J||_F = 0 its term has gradient 0, as torch.norm's backward has it.
+ * ws: cfm_workspace_bytes(CFM_OP_CNF_GRAD, B, n_t, 0).  The result is the same bit pattern run to run. */
+int cfm_cnf_reg_euler_grad_f32(const float* const* W, const float* const* b, const int* dims, int n_layers,
+                               const float* traj, int B, const float* t_span, int n_t, int mode,
+                               const float* eps, int reg_mask, const float* jac_sq, const float* g_final,
+                               float* const* dW, float* const* db, float* g_initial, void* ws, void* stream);
+
 /* Gradient of the plain fixed-step solve that cfm_ode_fixed_mlp_f32(..., scheme) wrote into traj: what
  * sensitivity="adjoint" asks of NeuralODE(model, solver="euler", sensitivity="adjoint")
  * (examples/images/cifar10/utils_cifar.py:63; runner/src/models/cfm_module.py:290) when a loss is put on node(x, t_span).

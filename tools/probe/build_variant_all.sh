@@ -7,7 +7,7 @@ R="$(cd "$(dirname "$0")/../.." && pwd)"; C="$R/conditional-flow-matching_amd/cs
 NAME=$1; FL=$2; shift; shift
 FILES="${*:-cost mlp mlp_train ode}"
 objs=""
-for f in abi cost sinkhorn sinkhorn_pts assign transport sample elem mlp mlp_train ode unbalanced; do
+for f in abi cost sinkhorn sinkhorn_pts assign transport sample elem mlp mlp_train ode cnf_reg unbalanced; do
   if [[ " $FILES " == *" $f "* ]]; then
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -fvisibility=hidden -ffp-contract=off -Wno-unused-result $FL -c "$C/$f.hip" -o /tmp/${f}_$NAME.o &
     objs="$objs /tmp/${f}_$NAME.o"
