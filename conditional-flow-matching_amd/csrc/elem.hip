@@ -192,8 +192,9 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const unsigned char* _
 
 extern "C" int cfm_gather_rows(const void* src, const int64_t* idx, int n, size_t row_bytes, void* out,
                                void* stream) {
-    if (!src || !idx || !out || n < 0) return CFM_EINVAL;
-    if (n == 0 || row_bytes == 0) return 0;
+    if (n < 0) return CFM_EINVAL;
+    if (n == 0 || row_bytes == 0) return 0;      // (an empty index or output tensor has a null data pointer)
+    if (!src || !idx || !out) return CFM_EINVAL;
     const int w16 = (row_bytes % 16 == 0) && (((uintptr_t)src & 15) == 0) && (((uintptr_t)out & 15) == 0);
     const size_t total = (size_t)n * (w16 ? row_bytes / 16 : row_bytes);
     int blocks = (int)((total + 255) / 256);

@@ -615,7 +615,8 @@ extern "C" int cfm_mlp_sf2m_step_f32(const float* xt, const float* t, const floa
 // ------------------------------------------------------------------- Adam ----
 // torch.optim.Adam (amsgrad = False, maximize = False), single step on every tensor of the table:
 //   g      = grad (+ weight_decay * p)
-//   m      = lerp(m, g, 1 - beta1)            = m + (1 - beta1) * (g - m)
+//   m      = lerp(m, g, w = 1 - beta1)        = m + w * (g - m)          for |w| <  0.5
+//                                             = g - (g - m) * (1 - w)    for |w| >= 0.5   (ATen/native/Lerp.h)
 //   v      = v * beta2 + (1 - beta2) * g * g
 //   denom  = sqrt(v) / sqrt(bias_correction2) + eps
 //   p      = p - (lr / bias_correction1) * m / denom
@@ -625,8 +626,9 @@ struct AdamTable { float* p; const float* g; float* m; float* v; unsigned long l
 // (the contraction pattern below is the one that is bit-equal to torch's foreach kernels on ROCm 7 /
 //  torch 2.10, found by probing the alternatives: tools/probe/adam_probe.py)
 __global__ __launch_bounds__(256) void adam_multi(const AdamTable* __restrict__ tab, int n_tensors,
-                                                  float w1, float beta2, float w2, float bc2_sqrt, float eps,
-                                                  float step_size, float weight_decay, float grad_scale) {
+                                                  float w1, float omw1, int w1_small, float beta2, float w2,
+                                                  float bc2_sqrt, float eps, float step_size, float weight_decay,
+                                                  float grad_scale) {
     for (int q = blockIdx.y; q < n_tensors; q += gridDim.y) {
         const AdamTable T = tab[q];
         for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < T.n; e += (size_t)gridDim.x * 256) {
@@ -638,7 +640,8 @@ __global__ __launch_bounds__(256) void adam_multi(const AdamTable* __restrict__ 
             const float p = T.p[e];
             if (weight_decay != 0.f) g = fmaf(weight_decay, p, g);
             float m = T.m[e], v = T.v[e];
-            m = fmaf(w1, g - m, m);                                   // lerp
+            const float gm = g - m;                                   // lerp: the form is uniform over the launch
+            m = w1_small ? fmaf(w1, gm, m) : fmaf(-gm, omw1, g);
             v = fmaf(w2, __fmul_rn(g, g), __fmul_rn(v, beta2));       // mul_, then addcmul_
             const float denom = __fadd_rn(__fdiv_rn(sqrtf(v), bc2_sqrt), eps);
             T.m[e] = m; T.v[e] = v;
@@ -654,8 +657,10 @@ extern "C" int cfm_adam_step_f32(const void* table, int n_tensors, double lr, do
     if (n_tensors == 0) return 0;
     const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
     const double step_size = lr / bc1, bc2_sqrt = sqrt(bc2);
+    const float w1 = (float)(1.0 - beta1);       // ATen switches forms on the fp32 weight and takes 1 - w in fp32
     hipLaunchKernelGGL(adam_multi, dim3(256, n_tensors < 16 ? n_tensors : 16), dim3(256), 0, (hipStream_t)stream,
-                       (const AdamTable*)table, n_tensors, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2),
+                       (const AdamTable*)table, n_tensors, w1, 1.0f - w1, fabsf(w1) < 0.5f ? 1 : 0, (float)beta2,
+                       (float)(1.0 - beta2),
                        (float)bc2_sqrt, (float)eps, (float)step_size, (float)weight_decay, (float)grad_scale);
     return cfm_status();
 }

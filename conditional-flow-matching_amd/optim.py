@@ -1,8 +1,8 @@
 """One-launch Adam — counterpart of ``torch.optim.Adam`` as the reference's training loops use it
 (``torch.optim.Adam(model.parameters())``: examples/2D_tutorials/*.ipynb, ``lr=2e-4`` in
 examples/images/cifar10/train_cifar10.py:93).  Same state (``step``, ``exp_avg``, ``exp_avg_sq``),
-same arithmetic, one ``cfm_adam_step_f32`` launch for all fp32 CUDA parameters of a group instead of
-~10 foreach kernels.  amsgrad / maximize / capturable / sparse gradients are not built: they raise."""
+same arithmetic (both forms of ATen's ``lerp``, the switch at ``1 - beta1 >= 0.5`` included), one
+``cfm_adam_step_f32`` launch for all fp32 CUDA parameters of a group instead of ~10 foreach kernels.  amsgrad / maximize / capturable / sparse gradients are not built: they raise."""
 import ctypes
 import struct
 
