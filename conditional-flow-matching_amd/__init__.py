@@ -22,5 +22,6 @@ from .action_matching import action_matching_loss  # noqa: F401
 from .optim import FusedAdam  # noqa: F401
 from .train import RegressionStep, SF2MStep  # noqa: F401
 from .optimal_transport import OTPlanSampler, wasserstein  # noqa: F401
+from .trajectory import TrajectoryFlowMatcher  # noqa: F401
 
 __version__ = "0.1.0"

@@ -74,6 +74,7 @@ SIGNATURES = {
     "cfm_sample_xt_ut_f32": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _i, _i,
                                   _vp, _vp, _vp, _vp, _vp]),
     "cfm_gather_rows": (_i, [_vp, _vp, _i, _sz, _vp, _vp]),
+    "cfm_traj_xt_ut_f32": (_i, [_i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _d, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "cfm_mlp_forward_f32": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "cfm_mlp_forward_train_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "cfm_mlp_backward_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -698,6 +698,15 @@ class OTPlanSampler:
         row, rows in order, slices in order).
         """
         times = X.shape[1]
+        idx = self._trajectory_indices(X).cpu().numpy()     # [times, n]: the ONE device-to-host copy of the indices
+        Xh = np.asarray(X.detach().cpu() if isinstance(X, torch.Tensor) else X)
+        return np.stack([Xh[:, t][idx[t]] for t in range(times)], axis=1)
+
+    def _trajectory_indices(self, X):
+        """The chain of draws of ``sample_trajectory`` as device int64 indices [times, n]: trajectory b visits row
+        ``idx[t, b]`` of slice t.  Same couplings, ``np.random`` consumption, diagnostics and exceptions; the indices stay
+        on the device (``cfm_amd.TrajectoryFlowMatcher`` gathers through them inside its kernel)."""
+        times = X.shape[1]
         dev = _lib.require_gpu()
         n = X.shape[0]
         sols = self._solve_many([(X[:, t], X[:, t + 1]) for t in range(times - 1)])
@@ -756,9 +765,7 @@ class OTPlanSampler:
             rows = j
         if bool(massless):
             raise ValueError("probabilities contain NaN")
-        idx = torch.stack(chain).cpu().numpy()              # [times, n]: the ONE device-to-host copy of the indices
-        Xh = np.asarray(X.detach().cpu() if isinstance(X, torch.Tensor) else X)
-        return np.stack([Xh[:, t][idx[t]] for t in range(times)], axis=1)
+        return torch.stack(chain)
 
 
 def wasserstein(

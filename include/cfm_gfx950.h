@@ -297,6 +297,29 @@ int cfm_sample_xt_ut_f32(int variant, const float* x0, const float* x1,
 int cfm_gather_rows(const void* src, const int64_t* idx, int n, size_t row_bytes,
                     void* out, void* stream);
 
+/* K7t — multi-marginal flow matching on trajectories X [B,T,d]: interval select + gather + interpolant + noise +
+ * leave-out rule in one launch.  Replaces the per-row loops of
+ *   runner/src/models/cfm_module.py:173-193 (x0.append(tmp_ot_list[ti][0][i]) ...) and :225-242
+ *   (calc_loc_and_target: mu_t, x, ut, `ut /= 2`, `t *= 2`, t + t_select)                              mode 0, linear
+ *   runner/src/models/cfm_module.py:1372-1377 and the per-row torchcubicspline evaluate / derivative
+ *   of :1396-1397, x = mu_t + sigma * eps :1406                                                         mode 1, spline
+ * t_select [B] int64: the interval of each row (0 <= t_select <= T - 2; mode 1: the knot interval, 0 <= . <= Tp - 2);
+ * t [B]: the local time in [0, 1); eps [B,d].  leaveout: the left-out slice L, 1 <= L <= T - 2, or <= 0 for none.
+ * mode 0: variant CFM_VARIANT_ICFM or CFM_VARIANT_SB, in the arithmetic of cfm_sample_xt_ut_f32 (bit-equal to it on
+ *   the gathered pair); sigma_t [B] = sigma * sqrt(t (1 - t)) from the caller's library (SB; else NULL).
+ *   idx: NULL (identity) or int64 [T-1][2][B], the index pair (i, j) of every interval's coupling: row b of interval k
+ *   is (X[i[b], k], X[j[b], k'])  with k' = k + 1, or k + 2 when k + 1 == L; such rows get ut / 2 and t * 2.
+ *   t_net = t + t_select.  S is not read.
+ * mode 1: variant CFM_VARIANT_ICFM.  The knots are the slices of X without slice L (Tp = T or T - 1 of them, at most
+ *   32), at times tau = slice number.  idx: NULL or int64 [Tp][B], the row of X trajectory b visits at each knot.
+ *   S [Tp][Tp] fp32: second derivatives at the knots = S @ knot values, for the natural cubic spline on tau.
+ *   xt = spline(t_net) + sigma * eps, ut = spline'(t_net), t_net = tau_i + t (tau_{i+1} - tau_i).
+ * Outputs xt, ut [B,d], t_net [B]. */
+int cfm_traj_xt_ut_f32(int mode, int variant, const float* X, int B, int T, int d,
+                       const int64_t* idx, const int64_t* t_select, const float* t,
+                       const float* eps, double sigma, const float* sigma_t, int leaveout,
+                       const float* S, float* xt, float* ut, float* t_net, void* stream);
+
 /* K10 — MLP vector field  Linear-SELU x3 + Linear  with the time column folded
  * in.  Replaces MLP.forward + torch_wrapper.forward
  *   torchcfm/models/models.py:10-21, torchcfm/utils.py:51-52.
