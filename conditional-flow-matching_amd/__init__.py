@@ -10,12 +10,19 @@ from .conditional_flow_matching import *  # noqa: F401,F403
 from .conditional_flow_matching import (  # noqa: F401
     ConditionalFlowMatcher,
     ExactOptimalTransportConditionalFlowMatcher,
+    ScheduledBridgeConditionalFlowMatcher,
     SchrodingerBridgeConditionalFlowMatcher,
     TargetConditionalFlowMatcher,
     VariancePreservingConditionalFlowMatcher,
     pad_t_like_x,
 )
 from .models import MLP  # noqa: F401
+from .schedule import (  # noqa: F401
+    ConstantNoiseScheduler,
+    CosineNoiseScheduler,
+    LinearDecreasingNoiseScheduler,
+    NoiseScheduler,
+)
 from .cnf import CNF, DifferentiableCNF, RegularizedCNF, log_likelihood  # noqa: F401
 from .ode import DifferentiableNeuralODE  # noqa: F401
 from .action_matching import action_matching_loss  # noqa: F401

@@ -27,6 +27,7 @@ OP_CNF_GRAD = 10
 OP_ACTION_GRAD = 11
 OP_ODE_GRAD = 12
 VARIANT_ICFM, VARIANT_SB, VARIANT_TARGET, VARIANT_VP = 0, 1, 2, 3
+VARIANT_SCHED = 4      # the scheduled bridge: cfm_sample_xt_ut_sched_f32 and cfm_traj_xt_ut_f32 mode 0
 
 ERRORS = {
     -1: "CFM_EINVAL (bad shape / null pointer / unsupported size)",
@@ -73,6 +74,7 @@ SIGNATURES = {
     "cfm_plan_sample_rows_pi_f64": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp]),
     "cfm_sample_xt_ut_f32": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _i, _i,
                                   _vp, _vp, _vp, _vp, _vp]),
+    "cfm_sample_xt_ut_sched_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "cfm_gather_rows": (_i, [_vp, _vp, _i, _sz, _vp, _vp]),
     "cfm_traj_xt_ut_f32": (_i, [_i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _d, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "cfm_mlp_forward_f32": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),

@@ -7,6 +7,8 @@ order (``t`` from the CPU generator, then ``eps`` from x0's generator; the OT
 samplers consume ``np.random`` first) and error behaviour.  The elementwise chain
 (mu_t, sigma_t, xt, ut) and the OT-index gathers run in ONE fused HIP kernel
 (``cfm_sample_xt_ut_f32``) that reproduces eager fp32 bit for bit.
+``ScheduledBridgeConditionalFlowMatcher`` (not in torchcfm: the runner's SF2M bridge with a noise schedule sigma(t))
+runs on the same kernel through ``cfm_sample_xt_ut_sched_f32``.
 """
 import math
 import warnings
@@ -58,6 +60,30 @@ def _fused_xt_ut(variant, sigma, x0, x1, t, eps, idx=None, xt_in=None, want_xt=T
     check(lib.cfm_sample_xt_ut_f32(variant, ptr(a0), ptr(a1), ptr(gi), ptr(gj), ptr(td), ptr(ed),
                                    float(sigma), ptr(c0), ptr(c1), ptr(xin), B, d, ptr(xt), ptr(ut),
                                    ptr(None), ptr(None), stream_ptr()), "cfm_sample_xt_ut_f32")
+    fin = lambda z: None if z is None else z.reshape(shape).to(device=out_dev, dtype=out_dtype)
+    return fin(xt), fin(ut)
+
+
+def _fused_xt_ut_sched(coef, x0, x1, eps, idx=None, xt_in=None, want_xt=True):
+    """Run cfm_sample_xt_ut_sched_f32: the scheduled bridge on a packed [B, 4] table (r, sigma_t, a, g^2 / F(1)) that
+    the caller's tensor library evaluated on t's own device.  Otherwise as _fused_xt_ut."""
+    lib = _lib.load()
+    dev = _lib.require_gpu()
+    out_dev, out_dtype, shape = x0.device, x0.dtype, x0.shape
+    B = shape[0]
+    a0 = _lib.to_dev_f32(x0.reshape(x0.shape[0], -1), dev)
+    a1 = _lib.to_dev_f32(x1.reshape(x1.shape[0], -1), dev)
+    d = a0.shape[1]
+    if coef.shape[0] != B:
+        raise AssertionError("t has to have batch size dimension")
+    cd = _lib.to_dev_f32(coef, dev)
+    ed = _lib.to_dev_f32(eps.reshape(B, -1), dev) if eps is not None else None
+    xin = _lib.to_dev_f32(xt_in.reshape(B, -1), dev) if xt_in is not None else None
+    xt = torch.empty((B, d), dtype=torch.float32, device=dev) if want_xt else None
+    ut = torch.empty((B, d), dtype=torch.float32, device=dev)
+    gi, gj = (idx if idx is not None else (None, None))
+    check(lib.cfm_sample_xt_ut_sched_f32(ptr(a0), ptr(a1), ptr(gi), ptr(gj), ptr(cd), ptr(ed), ptr(xin), B, d,
+                                         ptr(xt), ptr(ut), stream_ptr()), "cfm_sample_xt_ut_sched_f32")
     fin = lambda z: None if z is None else z.reshape(shape).to(device=out_dev, dtype=out_dtype)
     return fin(xt), fin(ut)
 
@@ -146,8 +172,7 @@ class ConditionalFlowMatcher:
         """t * x1 + (1 - t) * x0 (ref:62-83): the kernel's xt with eps = 0 (mu + 0 = mu)."""
         if self._needs_eager(x0, x1, t):
             return self._eager_compute_mu_t(x0, x1, t)
-        xt, _ = _fused_xt_ut(self._variant, self.sigma, x0, x1, self._t_vec(t, x0),
-                             torch.zeros_like(x0))
+        xt, _ = self._fused(x0, x1, self._t_vec(t, x0), torch.zeros_like(x0))
         return xt
 
     @_native
@@ -161,7 +186,7 @@ class ConditionalFlowMatcher:
         """mu_t + sigma_t * epsilon (ref:104-129)."""
         if self._customised() or self._needs_eager(x0, x1, t, epsilon):
             return self._eager_sample_xt(x0, x1, t, epsilon)
-        xt, _ = _fused_xt_ut(self._variant, self.sigma, x0, x1, self._t_vec(t, x0), epsilon)
+        xt, _ = self._fused(x0, x1, self._t_vec(t, x0), epsilon)
         return xt
 
     @_native
@@ -169,12 +194,15 @@ class ConditionalFlowMatcher:
         """ut(x1|x0) (ref:131-154; overrides :370-394, :448-478, :591-618)."""
         if self._customised() or self._needs_eager(x0, x1, t, xt):
             return self._eager_compute_conditional_flow(x0, x1, t, xt)
-        _, ut = _fused_xt_ut(self._variant, self.sigma, x0, x1, self._t_vec(t, x0), None, xt_in=xt,
-                             want_xt=False)
+        _, ut = self._fused(x0, x1, self._t_vec(t, x0), None, xt_in=xt, want_xt=False)
         return ut
 
     def sample_noise_like(self, x):
         return torch.randn_like(x)
+
+    def _fused(self, x0, x1, t, eps, idx=None, xt_in=None, want_xt=True):
+        """The class's closed forms on the fused kernel: (xt, ut)."""
+        return _fused_xt_ut(self._variant, self.sigma, x0, x1, t, eps, idx=idx, xt_in=xt_in, want_xt=want_xt)
 
     @staticmethod
     def _t_vec(t, x):
@@ -198,7 +226,7 @@ class ConditionalFlowMatcher:
             ut = self._impl("compute_conditional_flow")(x0, x1, t, xt)
         else:
             eps = self.sample_noise_like(x0)
-            xt, ut = _fused_xt_ut(self._variant, self.sigma, x0, x1, t, eps, idx=idx)
+            xt, ut = self._fused(x0, x1, t, eps, idx=idx)
         if return_noise:
             return t, xt, ut, eps
         return t, xt, ut
@@ -297,3 +325,83 @@ class VariancePreservingConditionalFlowMatcher(ConditionalFlowMatcher):
     """Albergo et al. 2023 trigonometric interpolants (ref:559-618)."""
 
     _variant = _lib.VARIANT_VP
+
+
+class ScheduledBridgeConditionalFlowMatcher(_OTMixin, ConditionalFlowMatcher):
+    """[SF]2M with a noise schedule: the Brownian bridge of dX = g(t) dW pinned at (x0, x1), coupled by entropic (or
+    exact) OT with regularisation 2 F(1) (``run:LINE`` cites ``runner/src/models/cfm_module.py``: the SF2M module takes
+    ``sigma: NoiseScheduler``, run:749, :819-827, reg run:827).  With F(t) = int_0^t g^2 (``cfm_amd.schedule``):
+
+        r(t)  = F(t) / F(1)              mu_t = x0 + (x1 - x0) r          sigma_t = sqrt(F(t) - F(t)^2 / F(1))
+        x_t   = mu_t + sigma_t eps
+        u_t   = a(t) (x_t - mu_t) + (x1 - x0) g(t)^2 / F(1),   a(t) = g(t)^2 (1 - 2 F(t) / F(1)) / (2 sigma_t^2 + 1e-8)
+        lambda(t) = 2 sigma_t / g(t)^2   (the weight of the runner's score loss, run:905-908); the score target is eps.
+
+    ``a(t)`` is (d sigma_t / dt) / sigma_t, so ``u_t`` is the time derivative of ``x_t`` at fixed eps.  The runner's
+    ``calc_u`` (run:843-850) divides d(sigma_t^2)/dt by sigma_t instead, which is not the derivative of its own x_t; a
+    user who wants that form overrides ``compute_conditional_flow`` (and runs the eager composition).  With
+    ``ConstantNoiseScheduler(sigma)`` the path is ``SchrodingerBridgeConditionalFlowMatcher(sigma)``'s.
+
+    The per-row scalars (r, sigma_t, a, g^2 / F(1)) come from the caller's tensor library on ``t``'s own device — sin,
+    cos and sqrt match eager bit for bit; the ``[B, d]`` work (OT gather, mu, x_t, u_t) is one fused HIP launch
+    (``cfm_sample_xt_ut_sched_f32``), bit-equal to the eager composition of this class in fp32.  CPU tensors, non-fp32
+    inputs, inputs that require grad and subclasses that override a closed form run that eager composition."""
+
+    _variant = _lib.VARIANT_SCHED
+
+    def __init__(self, schedule, ot_method="exact"):
+        from .schedule import NoiseScheduler
+        if not isinstance(schedule, NoiseScheduler):
+            raise TypeError(f"schedule must be a cfm_amd.NoiseScheduler, got {type(schedule).__name__}")
+        F1 = float(schedule.F(1.0))
+        if not F1 > 0:
+            raise ValueError(f"The schedule's accumulated variance F(1) must be strictly positive, got {F1}.")
+        self.schedule = schedule
+        self.F1 = F1
+        self.ot_method = ot_method
+        self.ot_sampler = OTPlanSampler(method=ot_method, reg=2 * F1)
+
+    @staticmethod
+    def _needs_eager(*tensors):
+        # this class's kernel serves device tensors only: host data ([B, *dim]) takes the eager composition
+        if ConditionalFlowMatcher._needs_eager(*tensors):
+            return True
+        return any(isinstance(z, torch.Tensor) and z.dim() >= 2 and not z.is_cuda for z in tensors)
+
+    def _coefs(self, t):
+        """(r, sigma_t, a, g^2 / F(1)) at t, in t's dtype on t's device (numbers for a number)."""
+        g2 = self.schedule(t) ** 2
+        r = self.schedule.F(t) / self.F1
+        sigma_t = self.schedule.sigma_t(t)
+        a = g2 * (1 - 2 * r) / (2 * sigma_t ** 2 + 1e-8)
+        return r, sigma_t, a, g2 / self.F1
+
+    def _fused(self, x0, x1, t, eps, idx=None, xt_in=None, want_xt=True):
+        tt = t.reshape(-1)
+        if tt.numel() != x0.shape[0]:
+            raise AssertionError("t has to have batch size dimension")
+        coef = torch.stack([c.to(torch.float32) for c in self._coefs(tt)], dim=1)
+        return _fused_xt_ut_sched(coef, x0, x1, eps, idx=idx, xt_in=xt_in, want_xt=want_xt)
+
+    # -- eager restatements: the operation order the kernel reproduces --
+    def _eager_compute_mu_t(self, x0, x1, t):
+        t = pad_t_like_x(t, x0)
+        return x0 + (x1 - x0) * (self.schedule.F(t) / self.F1)
+
+    def _eager_compute_sigma_t(self, t):
+        return self.schedule.sigma_t(t)
+
+    def _eager_compute_conditional_flow(self, x0, x1, t, xt):
+        tp = pad_t_like_x(t, x0)
+        mu_t = self._impl("compute_mu_t")(x0, x1, tp)
+        _, _, a, c = self._coefs(tp)
+        return a * (xt - mu_t) + (x1 - x0) * c
+
+    @_native
+    def compute_sigma_t(self, t):
+        """sqrt(F(t) - F(t)^2 / F(1)): the schedule's ``sigma_t``."""
+        return self.schedule.sigma_t(t)
+
+    def compute_lambda(self, t):
+        """2 sigma_t / g(t)^2 (run:905-908)."""
+        return 2 * self.compute_sigma_t(t) / self.schedule(t) ** 2

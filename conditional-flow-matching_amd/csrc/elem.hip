@@ -6,6 +6,7 @@
 //   SB       :446 (sigma_t), :474-478 (ut)
 //   Target   :349-350, :368, :393-394
 //   VP       :588-589, :617-618
+// and, for the scheduled bridge (cfm_sample_xt_ut_sched_f32), the chain of runner/src/models/cfm_module.py:834-850, :856.
 // The reference's tests demand bit equality with eager fp32
 // (tests/test_conditional_flow_matcher.py:124-126), so every operation below is
 // a separately rounded IEEE op in the reference's operation order: the file is
@@ -53,6 +54,11 @@ __device__ __forceinline__ RowCoef row_coef(float t, float sigma_f, float oms_f,
         r.c1 = t; r.c0 = 0.f;
         r.sig = f_sub(1.0f, f_mul(oms_f, t));                         // 1 - (1-sigma) t
         r.a = r.sig;
+    } else if (VARIANT == CFM_VARIANT_SCHED) {
+        // the packed [B, 4] table of the caller's tensor library (sin, cos and sqrt as eager computes them):
+        // r = F(t)/F(1), sigma_t, a = g^2 (1 - 2r) / (2 sigma_t^2 + 1e-8), g^2 / F(1).  t is not read.
+        const float4 q = reinterpret_cast<const float4*>(c0p)[b];
+        r.c1 = q.x; r.sig = q.y; r.a = q.z; r.c0 = q.w;
     } else {  // VP
         r.c0 = c0p[b]; r.c1 = c1p[b]; r.sig = sigma_f; r.a = 0.f;
     }
@@ -75,6 +81,12 @@ __device__ __forceinline__ void point(const RowCoef& r, float oms_f, float a0, f
         const float mu = f_mul(r.c1, a1);
         xt = have_xt ? xin : f_add(mu, f_mul(r.sig, e));
         ut = f_div(f_sub(a1, f_mul(oms_f, xt)), r.a);
+    } else if (VARIANT == CFM_VARIANT_SCHED) {
+        // mu = x0 + (x1 - x0) r;  ut = a (xt - mu) + (x1 - x0) g^2/F(1): ScheduledBridgeConditionalFlowMatcher's order
+        const float dx = f_sub(a1, a0);
+        const float mu = f_add(a0, f_mul(dx, r.c1));
+        xt = have_xt ? xin : f_add(mu, f_mul(r.sig, e));
+        ut = f_add(f_mul(r.a, f_sub(xt, mu)), f_mul(dx, r.c0));
     } else {
         const float mu = f_add(f_mul(r.c0, a0), f_mul(r.c1, a1));
         xt = have_xt ? xin : f_add(mu, f_mul(r.sig, e));
@@ -103,7 +115,7 @@ __global__ __launch_bounds__(256) void xt_ut_kernel(const float* __restrict__ x0
         const size_t k = (g - (size_t)b * per_row) * W;
         const size_t r0 = gi ? (size_t)gi[b] : (size_t)b;
         const size_t r1 = gj ? (size_t)gj[b] : (size_t)b;
-        const RowCoef rc = row_coef<VARIANT>(t[b], sigma_f, oms_f, c0p, c1p, b);
+        const RowCoef rc = row_coef<VARIANT>(VARIANT == CFM_VARIANT_SCHED ? 0.f : t[b], sigma_f, oms_f, c0p, c1p, b);
         const size_t o = (size_t)b * d + k;
         if (VEC) {
             const float4 a0 = *reinterpret_cast<const float4*>(x0 + r0 * d + k);
@@ -165,6 +177,26 @@ extern "C" int cfm_sample_xt_ut_f32(int variant, const float* x0, const float* x
         case CFM_VARIANT_TARGET: launch_xt_ut<CFM_VARIANT_TARGET>(vec, blocks, s, x0, x1, i, j, t, eps, sf, of, c0, c1, xin, B, d, xt, ut, x0g, x1g); break;
         default:                 launch_xt_ut<CFM_VARIANT_VP>(vec, blocks, s, x0, x1, i, j, t, eps, sf, of, c0, c1, xin, B, d, xt, ut, x0g, x1g); break;
     }
+    return cfm_status();
+}
+
+// The scheduled bridge (ScheduledBridgeConditionalFlowMatcher: the [SF]2M path with a noise schedule g(t),
+// runner/src/models/cfm_module.py:834-850 with the flow coefficient (d sigma_t/dt)/sigma_t) on the same kernel: the four
+// per-row scalars arrive as one packed [B, 4] table, read with one 16-byte load per row.
+extern "C" int cfm_sample_xt_ut_sched_f32(const float* x0, const float* x1, const int64_t* i, const int64_t* j,
+                                          const float* coef, const float* eps, const float* xin, int B, int d,
+                                          float* xt, float* ut, void* stream) {
+    if (!x0 || !x1 || !coef || !ut || B < 0 || d <= 0) return CFM_EINVAL;
+    if (!xin && (!eps || !xt)) return CFM_EINVAL;
+    if (((uintptr_t)coef) & 15) return CFM_EALIGN;
+    if (B == 0) return 0;
+    auto al = [](const void* p) { return p == nullptr || (((uintptr_t)p) & 15) == 0; };
+    const bool vec = (d % 4 == 0) && al(x0) && al(x1) && al(eps) && al(xt) && al(ut) && al(xin);
+    const size_t total = (size_t)B * (size_t)(vec ? d / 4 : d);
+    int blocks = (int)((total + 255) / 256);
+    if (blocks > 8192) blocks = 8192;
+    launch_xt_ut<CFM_VARIANT_SCHED>(vec, blocks, (hipStream_t)stream, x0, x1, i, j, nullptr, eps, 0.f, 0.f, coef, nullptr,
+                                    xin, B, d, xt, ut, nullptr, nullptr);
     return cfm_status();
 }
 

@@ -7,8 +7,9 @@
 // Every row reads its interval from t_select and gathers its operands from X where they lie, through the index pairs
 // of the interval's coupling (linear) or the chain of draws (spline); nothing is materialised in between.
 //
-// Linear mode restates the ICFM and SB closed forms of elem.hip's xt_ut_kernel operation by operation (separately
-// rounded IEEE ops in the reference's order, contraction off), so it is bit-equal to that kernel on the gathered pair.
+// Linear mode restates the ICFM, SB and scheduled-bridge closed forms of elem.hip's xt_ut_kernel operation by operation
+// (separately rounded IEEE ops in the reference's order, contraction off), so it is bit-equal to that kernel on the
+// gathered pair.
 // Spline mode: all rows share the knots, so the map S from knot values to the natural spline's second derivatives is
 // ONE Tp x Tp matrix (host, float64, passed as fp32, staged in LDS); a row needs M_i and M_{i+1} only — two length-Tp
 // dot products per element — and then the standard piecewise cubic and its derivative.  Rows of S sum to zero (a
@@ -72,11 +73,15 @@ __global__ __launch_bounds__(256) void traj_linear_kernel(const float* __restric
         const size_t r1 = idx ? (size_t)idx[((size_t)2 * k + 1) * B + b] : (size_t)b;
         const float tb = t[b];
         const float omt = t_sub(1.0f, tb);
-        float sig = sigma_f, ratio = 0.f;
+        float sig = sigma_f, ratio = 0.f, rr = 0.f, cc = 0.f;
         if (VARIANT == CFM_VARIANT_SB) {
             sig = sigma_t[b];                                 // the caller's own sigma * sqrt(t (1 - t)) (elem.hip)
             const float two_t = t_mul(2.0f, tb);
             ratio = t_div(t_sub(1.0f, two_t), t_add(t_mul(two_t, omt), 1e-8f));
+        } else if (VARIANT == CFM_VARIANT_SCHED) {
+            // the caller's [B, 4] table at the row's local time: r, sigma_t, a, g^2 / F(1) (elem.hip)
+            const float4 q = reinterpret_cast<const float4*>(sigma_t)[b];
+            rr = q.x; sig = q.y; ratio = q.z; cc = q.w;
         }
         const Vec<W> a0 = ld<W>(X + r0 * row_stride + (size_t)k * d + c);
         const Vec<W> a1 = ld<W>(X + r1 * row_stride + (size_t)k1 * d + c);
@@ -85,10 +90,13 @@ __global__ __launch_bounds__(256) void traj_linear_kernel(const float* __restric
         Vec<W> vx, vu;
 #pragma unroll
         for (int q = 0; q < W; ++q) {
-            const float mu = t_add(t_mul(tb, a1.v[q]), t_mul(omt, a0.v[q]));
+            const float dx = t_sub(a1.v[q], a0.v[q]);
+            const float mu = VARIANT == CFM_VARIANT_SCHED ? t_add(a0.v[q], t_mul(dx, rr))
+                                                          : t_add(t_mul(tb, a1.v[q]), t_mul(omt, a0.v[q]));
             vx.v[q] = t_add(mu, t_mul(sig, e.v[q]));
             float u = VARIANT == CFM_VARIANT_SB ? t_sub(t_add(t_mul(ratio, t_sub(vx.v[q], mu)), a1.v[q]), a0.v[q])
-                                                : t_sub(a1.v[q], a0.v[q]);
+                    : VARIANT == CFM_VARIANT_SCHED ? t_add(t_mul(ratio, t_sub(vx.v[q], mu)), t_mul(dx, cc))
+                                                   : dx;
             if (halved) u = t_div(u, 2.0f);
             vu.v[q] = u;
         }
@@ -172,8 +180,9 @@ extern "C" int cfm_traj_xt_ut_f32(int mode, int variant, const float* X, int B, 
     if (mode != 0 && mode != 1) return CFM_EINVAL;
     if (leaveout > 0 && (leaveout > T - 2)) return CFM_EINVAL;      // an interior slice, 1 <= L <= T - 2
     if (leaveout < 0) leaveout = 0;
-    if (mode == 0 && variant != CFM_VARIANT_ICFM && variant != CFM_VARIANT_SB) return CFM_EINVAL;
-    if (mode == 0 && variant == CFM_VARIANT_SB && !sigma_t) return CFM_EINVAL;
+    if (mode == 0 && variant != CFM_VARIANT_ICFM && variant != CFM_VARIANT_SB && variant != CFM_VARIANT_SCHED) return CFM_EINVAL;
+    if (mode == 0 && variant != CFM_VARIANT_ICFM && !sigma_t) return CFM_EINVAL;
+    if (mode == 0 && variant == CFM_VARIANT_SCHED && (((uintptr_t)sigma_t) & 15)) return CFM_EALIGN;      // the [B, 4] table
     if (mode == 1) {
         const int Tp = T - (leaveout > 0 ? 1 : 0);
         if (variant != CFM_VARIANT_ICFM || !S || Tp < 2 || Tp > TRAJ_MAX_KNOTS) return CFM_EINVAL;
@@ -191,6 +200,7 @@ extern "C" int cfm_traj_xt_ut_f32(int mode, int variant, const float* X, int B, 
                        sigma_t, leaveout, xt, ut, t_net)
     if (mode == 0) {
         if (variant == CFM_VARIANT_SB) { if (vec) CFM_TRAJ_LINEAR(CFM_VARIANT_SB, 4); else CFM_TRAJ_LINEAR(CFM_VARIANT_SB, 1); }
+        else if (variant == CFM_VARIANT_SCHED) { if (vec) CFM_TRAJ_LINEAR(CFM_VARIANT_SCHED, 4); else CFM_TRAJ_LINEAR(CFM_VARIANT_SCHED, 1); }
         else                           { if (vec) CFM_TRAJ_LINEAR(CFM_VARIANT_ICFM, 4); else CFM_TRAJ_LINEAR(CFM_VARIANT_ICFM, 1); }
     } else {
         if (vec) hipLaunchKernelGGL((traj_spline_kernel<4>), dim3(blocks), dim3(256), 0, s, X, B, T, d, idx, t_select, t, eps,

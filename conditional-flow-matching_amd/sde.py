@@ -12,6 +12,10 @@ A script that relied on torchsde's default passes ``method="srk"`` explicitly.  
 ``cfm_amd.MLP`` fields the network evaluations run on the HIP inference kernels and the state update is one fused HIP
 kernel per step (``cfm_sde_em_step_f32``) or stage (``cfm_sde_srk_step_f32``); any other callable pair is stepped by
 the same scheme in eager torch.
+``sigma`` may be a noise schedule (``cfm_amd.schedule``, or any callable of the time with a scalar value): the same
+kernels run it — g is evaluated once per refined step on the host, at the SOLVER's time t_k at the start of the step,
+also for ``reverse=True`` (what the reference's SDE classes and the eager scheme here do); a user who wants g(1 - t) on
+the way back passes ``lambda t: schedule(1 - t)``.  ``srk`` with a schedule is not built.
 The Brownian increments come from ``torch.randn`` on the state's device (torchsde's BrownianInterval
 stream is not reproducible without torchsde: the noise stream is NOT bit-compatible, the scheme is).
 """
@@ -22,6 +26,9 @@ import torch
 from . import _lib
 from ._lib import check, ptr, stream_ptr
 from .models import MLP
+from .schedule import ConstantNoiseScheduler, CosineNoiseScheduler, LinearDecreasingNoiseScheduler
+
+_BUILTIN_SCHEDULES = (ConstantNoiseScheduler, LinearDecreasingNoiseScheduler, CosineNoiseScheduler)
 
 
 class FlowScoreSDE(torch.nn.Module):
@@ -33,6 +40,7 @@ class FlowScoreSDE(torch.nn.Module):
     def __init__(self, drift, score, sigma=1.0, reverse=False):
         super().__init__()
         self.drift, self.score, self.sigma, self.reverse = drift, score, sigma, reverse
+        self.last_path = None      # "hip" / "eager": what the last sdeint call on this object ran
 
     def _cat(self, t, y):
         tt = torch.as_tensor(t, dtype=y.dtype, device=y.device)
@@ -75,6 +83,43 @@ def _fused_fields(sde):
     return f, s, df
 
 
+_G_CACHE = {}         # (schedule type, parameters, grid) -> g(t_k): _schedule_values
+
+
+def _schedule_values(sigma, steps):
+    """g(t_k) of a callable ``sigma`` for every step of the refined grid, as Python floats: evaluated on the host at the
+    solver's time at the start of the step, in float32.  None when a value is not a scalar (state-dependent noise)."""
+    # the built-in schedules are pure functions of their numeric parameters: a loop that samples again and again on one
+    # grid pays the per-step host evaluations (about 9 us each) once
+    key = None
+    if type(sigma) in _BUILTIN_SCHEDULES and all(isinstance(p, (int, float)) for p in vars(sigma).values()):
+        key = (type(sigma), tuple(sorted(vars(sigma).items())), tuple(t for t, _, _ in steps))
+        if key in _G_CACHE:
+            return list(_G_CACHE[key])
+    vals = []
+    for t, _, _ in steps:
+        v = sigma(torch.as_tensor(t, dtype=torch.float32))
+        if isinstance(v, torch.Tensor) and v.numel() != 1:
+            return None
+        try:
+            vals.append(float(v))
+        except (TypeError, ValueError):
+            return None
+    if key is not None:
+        if len(_G_CACHE) >= 16:
+            _G_CACHE.pop(next(iter(_G_CACHE)))
+        _G_CACHE[key] = tuple(vals)
+    return vals
+
+
+def _em_records(steps, g, reverse):
+    """The EmStep records of cfm_sde_em_mlp_f32 (csrc/sde_small.h), 16 bytes per step: field time, step, g(t_k) sqrt|h_k|,
+    output flag — with the casts of the launch-per-step path: float32 time, float32 step, float32 (g sqrt|h|)."""
+    import struct
+    return b"".join(struct.pack("<fffi", (1.0 - t) if reverse else t, h, gk * math.sqrt(abs(h)), 1 if is_out else 0)
+                    for (t, h, is_out), gk in zip(steps, g))
+
+
 _SRK_SCOPE = ("sdeint method 'srk' is built for FlowScoreSDE with a constant (non-callable) sigma: for constant diagonal "
               "noise every diffusion-derivative term of the SRI2W1 tableau vanishes; a state- or time-dependent g needs "
               "the full tableau, which is not built")
@@ -111,7 +156,8 @@ def sdeint(sde, y0, ts, method="euler", dt=1e-3, generator=None, noise="philox",
     ``euler``, ``(2, B, d)`` = (xi1, xi2) for ``srk``) — same trajectory, bit for bit, as that scheme; a tensor: the
     caller's standard normals, ``[n_steps, B, d]`` for ``euler`` and ``[n_steps, 2, B, d]`` for ``srk`` with
     ``n_steps`` the length of the refined grid.  ``fused=False`` forces the launch-per-step scheme (measurement /
-    test switch)."""
+    test switch).  A callable ``sde.sigma`` with a scalar value (a noise schedule) runs on the same ``euler`` kernels,
+    evaluated per refined step at the solver's time t_k (module docstring); a non-scalar value keeps the eager scheme."""
     if method not in ("euler", "srk"):
         raise NotImplementedError(f"sdeint method {method!r}: 'euler' (Euler-Maruyama) and 'srk' (SRI2W1) are built")
     srk = method == "srk"
@@ -125,7 +171,18 @@ def sdeint(sde, y0, ts, method="euler", dt=1e-3, generator=None, noise="philox",
     steps = _grid(ts, float(dt))
     given = _noise_arg(noise, method, len(steps), y0)
     fast = (isinstance(sde, FlowScoreSDE) and isinstance(sde.drift, MLP) and isinstance(sde.score, MLP)
-            and not callable(sde.sigma) and y0.dim() == 2 and torch.cuda.is_available())
+            and y0.dim() == 2 and torch.cuda.is_available())
+    g_steps = None
+    if isinstance(sde, FlowScoreSDE) and callable(sde.sigma) and (fast or fused is True):
+        # a schedule: one scalar per step (srk with a callable sigma was refused above)
+        g_steps = _schedule_values(sde.sigma, steps)
+        if g_steps is None:
+            if fused is True:
+                raise ValueError("sdeint(fused=True): sigma(t) must be a scalar (a noise schedule); state-dependent noise "
+                                 "is stepped in eager torch")
+            fast = False
+    if isinstance(sde, FlowScoreSDE):
+        sde.last_path = "hip" if fast else "eager"
     out = [y0]
     if fast:
         lib = _lib.load()
@@ -142,25 +199,28 @@ def sdeint(sde, y0, ts, method="euler", dt=1e-3, generator=None, noise="philox",
             fields = None
         if fused is True and fields is None:
             raise ValueError("sdeint(fused=True): needs two 4-layer time-varying cfm_amd.MLP fields of widths <= 64")
-        sigma = float(sde.sigma)
+        if g_steps is None:
+            g_steps = [float(sde.sigma)] * len(steps)
+        sigma = g_steps[0] if steps else 0.0          # (srk: constant)
         if fields is not None:
             import ctypes
             import struct
             f, s, dims = fields
             B, d = y.shape
-            recs, n_out = [], 0
-            for t, h, is_out in steps:
-                # the casts of the launch-per-step path: float32 time, float32 step, float32 (g sqrt|h|)
-                gs = sigma * math.sqrt(abs(h))
-                if srk:
+            n_out = sum(1 for st in steps if st[2])
+            if srk:
+                recs = []
+                for t, h, is_out in steps:
+                    # the casts of the launch-per-step path: float32 time, float32 step, float32 (g sqrt|h|)
+                    gs = sigma * math.sqrt(abs(h))
                     te = [(1.0 - u) if sde.reverse else u for u in (t, t + h, t + 0.5 * h)]
                     recs.append(struct.pack("<ffffffii", te[0], te[1], te[2], h, gs, 0.75 * sigma * math.sqrt(abs(h)),
                                             1 if is_out else 0, 0))
-                else:
-                    recs.append(struct.pack("<fffi", (1.0 - t) if sde.reverse else t, h, gs, 1 if is_out else 0))
-                n_out += 1 if is_out else 0
+                blob = b"".join(recs)
+            else:
+                blob = _em_records(steps, g_steps, sde.reverse)
             rec = 32 if srk else 16
-            host = (ctypes.c_char * (rec * len(steps))).from_buffer_copy(b"".join(recs))
+            host = (ctypes.c_char * (rec * len(steps))).from_buffer_copy(blob)
             xi = given
             seed = 0
             if xi is None and noise == "torch":
@@ -209,7 +269,7 @@ def sdeint(sde, y0, ts, method="euler", dt=1e-3, generator=None, noise="philox",
             if sde.reverse:
                 v = -v
             xi = given[k] if given is not None else torch.randn(y.shape, device=dev, dtype=torch.float32, generator=generator)
-            check(lib.cfm_sde_em_step_f32(ptr(y), ptr(v), ptr(s), ptr(xi), float(h), sigma, sign,
+            check(lib.cfm_sde_em_step_f32(ptr(y), ptr(v), ptr(s), ptr(xi), float(h), g_steps[k], sign,
                                           y.numel(), stream_ptr()), "cfm_sde_em_step_f32")
             if is_out:
                 out.append(y.clone().to(y0.device))
@@ -240,7 +300,9 @@ class FlowSolver(torch.nn.Module):
     """Subset of runner/src/models/components/solver.py:44-230 on this backend: a flow field and an
     optional score field (separate networks, or one network whose output is [flow, score]) behind
     ``odeint`` (NeuralODE) and ``sdeint`` (Euler-Maruyama; ``srk`` needs a constant sigma: ``sde.sdeint``).  vector_field / score_field are called as
-    f(t, x) like torchdyn vector fields."""
+    f(t, x) like torchdyn vector fields.  ``sdeint`` with ``sde_solver="euler"`` and two separate fields that unwrap to
+    time-varying ``cfm_amd.MLP``s (a ``torch_wrapper`` around one, or a bare one) runs ``sde.sdeint``'s HIP paths with the
+    schedule ``sigma``; ``last_path`` says ``"hip"`` or ``"eager"`` after a call."""
 
     def __init__(self, vector_field, dim, score_field=None, sigma=None, ode_solver="euler", sde_solver="euler",
                  dt=0.01, atol=1e-5, rtol=1e-5, **kwargs):
@@ -249,6 +311,7 @@ class FlowSolver(torch.nn.Module):
         self.separate_score = score_field is not None
         self.sigma, self.ode_solver, self.sde_solver = sigma, ode_solver, sde_solver
         self.dt, self.atol, self.rtol, self.nfe = dt, atol, rtol, 0
+        self.last_path = None
 
     def forward_flow_and_score(self, t, x, only_flow=False):       # solver.py:103-121
         if self.separate_score:
@@ -282,12 +345,36 @@ class FlowSolver(torch.nn.Module):
                          return_t_eval=False)
         return node(x0, t_span)
 
+    def _hip_fields(self):
+        """(flow MLP, score MLP) when sdeint's HIP paths can take the pair (the rule of NeuralODE._hip_mlp), else None."""
+        from .utils import torch_wrapper
+        if self.sde_solver != "euler" or not self.separate_score or self.sigma is None:
+            return None
+        pair = []
+        for f in (self.net, self.score_net):
+            m = f.model if isinstance(f, torch_wrapper) else f
+            if not (isinstance(m, MLP) and m.time_varying):
+                return None
+            lins = m._linears()
+            if lins[-1].out_features + 1 != lins[0].in_features:
+                return None
+            pair.append(m)
+        return tuple(pair)
+
     def sdeint(self, x0, t_span, reverse=False, generator=None):
         if self.sde_solver == "srk":
             raise NotImplementedError("FlowSolver(sde_solver='srk'): sigma is a schedule sigma(t) here, and 'srk' is built "
                                       "for constant diagonal noise only (the full SRI2W1 tableau is not built)")
         self.nfe = 0
         outer = self
+        fields = self._hip_fields()
+        if fields is not None:
+            sde = FlowScoreSDE(fields[0], fields[1], sigma=self.sigma, reverse=reverse)
+            out = sdeint(sde, x0, t_span, method="euler", dt=self.dt, generator=generator)
+            self.last_path = sde.last_path
+            self.nfe = len(_grid(t_span, float(self.dt)))          # one evaluation of the field pair per refined step
+            return out
+        self.last_path = "eager"
 
         class _S:
             def f(self, t, y):

@@ -13,10 +13,13 @@ import torch
 from . import _lib
 from ._lib import check, ptr, stream_ptr
 from .conditional_flow_matching import (ConditionalFlowMatcher, ExactOptimalTransportConditionalFlowMatcher,
+                                        ScheduledBridgeConditionalFlowMatcher,
                                         SchrodingerBridgeConditionalFlowMatcher, pad_t_like_x)
 
 MAX_FUSED_KNOTS = 32        # TRAJ_MAX_KNOTS of csrc/traj.hip: more knots take the eager path
-_ACCEPTED = (ConditionalFlowMatcher, ExactOptimalTransportConditionalFlowMatcher, SchrodingerBridgeConditionalFlowMatcher)
+_ACCEPTED = (ConditionalFlowMatcher, ExactOptimalTransportConditionalFlowMatcher, SchrodingerBridgeConditionalFlowMatcher,
+             ScheduledBridgeConditionalFlowMatcher)
+_BRIDGES = (_lib.VARIANT_SB, _lib.VARIANT_SCHED)      # Brownian-bridge paths: linear interpolant only
 _ONE_WORKGROUP_ROWS = 256   # batches up to this size are solved by one workgroup (optimal_transport._solve_many)
 _S_CACHE = {}
 
@@ -52,7 +55,8 @@ class TrajectoryFlowMatcher:
     ``FM`` fixes coupling and path: ``ConditionalFlowMatcher(sigma)`` — no coupling;
     ``ExactOptimalTransportConditionalFlowMatcher(sigma)`` — consecutive slices coupled by its ``ot_sampler``;
     ``SchrodingerBridgeConditionalFlowMatcher(sigma, ...)`` — its coupling and the Brownian-bridge path (linear
-    interpolant only).  (An ``FM`` whose ``ot_sampler`` attribute is ``None`` does not couple, like ``self.ot_sampler
+    interpolant only); ``ScheduledBridgeConditionalFlowMatcher(schedule, ...)`` — the same with a noise schedule, read at
+    the row's local time (linear interpolant only).  (An ``FM`` whose ``ot_sampler`` attribute is ``None`` does not couple, like ``self.ot_sampler
     is None`` at run:158.)  ``leaveout_timepoint`` ``L`` holds slice ``L`` out of TRAINING calls (run:152-160, :167-170):
     ``-1`` for none, else ``1 <= L <= T - 2`` (checked against every ``X``).
 
@@ -92,15 +96,15 @@ class TrajectoryFlowMatcher:
 
     def __init__(self, FM, interpolant="linear", leaveout_timepoint=-1):
         if type(FM) not in _ACCEPTED and not (isinstance(FM, _ACCEPTED) and
-                                              FM._variant in (_lib.VARIANT_ICFM, _lib.VARIANT_SB)):
+                                              FM._variant in (_lib.VARIANT_ICFM,) + _BRIDGES):
             raise ValueError("TrajectoryFlowMatcher takes a ConditionalFlowMatcher, an "
-                             "ExactOptimalTransportConditionalFlowMatcher or a SchrodingerBridgeConditionalFlowMatcher; "
-                             f"got {type(FM).__name__}")
+                             "ExactOptimalTransportConditionalFlowMatcher, a SchrodingerBridgeConditionalFlowMatcher or a "
+                             f"ScheduledBridgeConditionalFlowMatcher; got {type(FM).__name__}")
         if interpolant not in ("linear", "spline"):
             raise ValueError(f"interpolant must be 'linear' or 'spline', got {interpolant!r}")
-        if interpolant == "spline" and FM._variant == _lib.VARIANT_SB:
+        if interpolant == "spline" and FM._variant in _BRIDGES:
             raise ValueError("interpolant='spline' has no Schrodinger-bridge path: use interpolant='linear' with a "
-                             "SchrodingerBridgeConditionalFlowMatcher")
+                             f"{type(FM).__name__}")
         L = int(leaveout_timepoint)
         if L != -1 and L < 1:
             raise ValueError(f"leaveout_timepoint must be -1 or 1 <= L <= T - 2, got {leaveout_timepoint}")
@@ -165,9 +169,10 @@ class TrajectoryFlowMatcher:
         xt = torch.empty((B, d), dtype=torch.float32, device=Xf.device)
         ut = torch.empty((B, d), dtype=torch.float32, device=Xf.device)
         t_net = torch.empty(B, dtype=torch.float32, device=Xf.device)
+        sigma = 0.0 if self.FM._variant == _lib.VARIANT_SCHED else float(self.FM.sigma)      # (the schedule is in the table)
         with torch.cuda.device(Xf.device):
             check(lib.cfm_traj_xt_ut_f32(mode, self.FM._variant, ptr(Xc), B, T, d, ptr(idx), ptr(t_select),
-                                         ptr(tc), ptr(ec), float(self.FM.sigma), ptr(sigma_t),
+                                         ptr(tc), ptr(ec), sigma, ptr(sigma_t),
                                          leave, ptr(S), ptr(xt), ptr(ut), ptr(t_net), stream_ptr()), "cfm_traj_xt_ut_f32")
         return t_net, xt, ut
 
@@ -207,6 +212,8 @@ class TrajectoryFlowMatcher:
             sigma_t = None
             if self.FM._variant == _lib.VARIANT_SB:
                 sigma_t = (self.FM.sigma * torch.sqrt(t * (1 - t))).contiguous()      # ref:446, eager, on t's device
+            elif self.FM._variant == _lib.VARIANT_SCHED:
+                sigma_t = torch.stack(self.FM._coefs(t), dim=1).contiguous()          # [B, 4] at the local times, on t's device
             t_net, xt, ut = self._launch(0, Xf, None if idx is None else idx.to(Xf.device), t_select, t, eps, sigma_t,
                                          leave, None)
             return t_net, xt, ut, eps, t, t_select

@@ -66,6 +66,8 @@ extern "C" {
 #define CFM_VARIANT_SB     1  /* SchrodingerBridgeConditionalFlowMatcher      */
 #define CFM_VARIANT_TARGET 2  /* TargetConditionalFlowMatcher                 */
 #define CFM_VARIANT_VP     3  /* VariancePreservingConditionalFlowMatcher     */
+/* the scheduled bridge (cfm_sample_xt_ut_sched_f32, cfm_traj_xt_ut_f32 mode 0 only; cfm_sample_xt_ut_f32 refuses it) */
+#define CFM_VARIANT_SCHED  4  /* ScheduledBridgeConditionalFlowMatcher (runner's SF2M with a NoiseScheduler) */
 
 int cfm_abi_version(void);
 
@@ -292,6 +294,20 @@ int cfm_sample_xt_ut_f32(int variant, const float* x0, const float* x1,
                          const float* c1, const float* xt_in, int B, int d, float* xt,
                          float* ut, float* x0g, float* x1g, void* stream);
 
+/* K7+K8 (scheduled bridge) — the same fused gather + sample + flow for the Brownian bridge of dX = g(t) dW with a
+ * noise schedule g(t), F(t) = int_0^t g^2.  Replaces x0[i], x1[j] and the eager chain of
+ *   runner/src/models/cfm_module.py:819-827 (sigma: NoiseScheduler, OT reg 2 F(1)), :834-841 (mu_t, sigma_t), :856 (x_t),
+ *   :843-850 (calc_u — here with the coefficient (d sigma_t/dt) / sigma_t, the time derivative of x_t)
+ * coef [B,4] (16-byte aligned, else CFM_EALIGN), per row and evaluated by the caller's tensor library on t's device (so
+ * sin, cos and sqrt match eager bit for bit):  r = F(t)/F(1),  sigma_t,  a = g^2 (1 - 2r) / (2 sigma_t^2 + 1e-8),
+ * c = g^2/F(1).  Separately rounded ops, no contraction, in this order:
+ *   mu = x0 + (x1 - x0) r;   xt = mu + sigma_t eps  (or xt_in);   ut = a (xt - mu) + (x1 - x0) c.
+ * i, j, eps, xt_in, xt as for cfm_sample_xt_ut_f32. */
+int cfm_sample_xt_ut_sched_f32(const float* x0, const float* x1, const int64_t* i,
+                               const int64_t* j, const float* coef, const float* eps,
+                               const float* xt_in, int B, int d, float* xt, float* ut,
+                               void* stream);
+
 /* Row gather  out[b,:] = src[idx[b],:]  (labels y0[i], y1[j]; :215-218).
  * elem_bytes = bytes per row. */
 int cfm_gather_rows(const void* src, const int64_t* idx, int n, size_t row_bytes,
@@ -307,6 +323,8 @@ int cfm_gather_rows(const void* src, const int64_t* idx, int n, size_t row_bytes
  * t [B]: the local time in [0, 1); eps [B,d].  leaveout: the left-out slice L, 1 <= L <= T - 2, or <= 0 for none.
  * mode 0: variant CFM_VARIANT_ICFM or CFM_VARIANT_SB, in the arithmetic of cfm_sample_xt_ut_f32 (bit-equal to it on
  *   the gathered pair); sigma_t [B] = sigma * sqrt(t (1 - t)) from the caller's library (SB; else NULL).
+ *   Variant CFM_VARIANT_SCHED: the arithmetic of cfm_sample_xt_ut_sched_f32; sigma_t is then its [B,4] coefficient
+ *   table (16-byte aligned) at the rows' local times and sigma is not read.
  *   idx: NULL (identity) or int64 [T-1][2][B], the index pair (i, j) of every interval's coupling: row b of interval k
  *   is (X[i[b], k], X[j[b], k'])  with k' = k + 1, or k + 2 when k + 1 == L; such rows get ut / 2 and t * 2.
  *   t_net = t + t_select.  S is not read.
