@@ -9,6 +9,7 @@ TorchCFM API (``torchcfm.OTPlanSampler`` / ``ConditionalFlowMatcher`` family).
 from .conditional_flow_matching import *  # noqa: F401,F403
 from .conditional_flow_matching import (  # noqa: F401
     ConditionalFlowMatcher,
+    DSBMConditionalFlowMatcher,
     ExactOptimalTransportConditionalFlowMatcher,
     ScheduledBridgeConditionalFlowMatcher,
     SchrodingerBridgeConditionalFlowMatcher,
@@ -27,7 +28,8 @@ from .cnf import CNF, DifferentiableCNF, RegularizedCNF, log_likelihood  # noqa:
 from .ode import DifferentiableNeuralODE  # noqa: F401
 from .action_matching import action_matching_loss  # noqa: F401
 from .optim import FusedAdam  # noqa: F401
-from .train import RegressionStep, SF2MStep  # noqa: F401
+from .train import DSBMStep, RegressionStep, SF2MStep  # noqa: F401
+from .sde import DSBMFlowSolver  # noqa: F401
 from .optimal_transport import OTPlanSampler, wasserstein  # noqa: F401
 from .trajectory import TrajectoryFlowMatcher  # noqa: F401
 

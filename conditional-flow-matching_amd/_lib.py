@@ -75,6 +75,7 @@ SIGNATURES = {
     "cfm_sample_xt_ut_f32": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _i, _i,
                                   _vp, _vp, _vp, _vp, _vp]),
     "cfm_sample_xt_ut_sched_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "cfm_sample_dsbm_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "cfm_gather_rows": (_i, [_vp, _vp, _i, _sz, _vp, _vp]),
     "cfm_traj_xt_ut_f32": (_i, [_i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _d, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "cfm_mlp_forward_f32": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
@@ -83,6 +84,7 @@ SIGNATURES = {
     "cfm_sde_em_mlp_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _vp, ctypes.c_ulonglong, _vp, _vp, _vp]),
     "cfm_mlp_regression_step_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cfm_mlp_sf2m_step_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _f, _vp, _vp]),
+    "cfm_mlp_dsbm_step_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "cfm_adam_step_f32": (_i, [_vp, _i, _d, _d, _d, _d, _d, _i, _d, _vp]),
     "cfm_sde_em_step_f32": (_i, [_vp, _vp, _vp, _vp, _d, _d, _d, _sz, _vp]),
     "cfm_sde_srk_mlp_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _vp, ctypes.c_ulonglong, _vp, _vp, _vp]),
@@ -97,6 +99,7 @@ SIGNATURES = {
                                        _vp, _vp]),
     "cfm_ode_adaptive_mlp_f32": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp]),
     "cfm_ode_fixed_mlp_f32": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "cfm_ode_fixed_pair_mlp_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "cfm_ode_adaptive_cnf_mlp_f32": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _f, _f, _vp, _vp, _vp,
                                          _vp, _vp]),
     "cfm_ode_fixed_cnf_mlp_f32": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),

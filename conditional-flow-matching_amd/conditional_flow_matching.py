@@ -8,7 +8,8 @@ samplers consume ``np.random`` first) and error behaviour.  The elementwise chai
 (mu_t, sigma_t, xt, ut) and the OT-index gathers run in ONE fused HIP kernel
 (``cfm_sample_xt_ut_f32``) that reproduces eager fp32 bit for bit.
 ``ScheduledBridgeConditionalFlowMatcher`` (not in torchcfm: the runner's SF2M bridge with a noise schedule sigma(t))
-runs on the same kernel through ``cfm_sample_xt_ut_sched_f32``.
+runs on the same kernel through ``cfm_sample_xt_ut_sched_f32``; ``DSBMConditionalFlowMatcher`` (the runner's DSBM: that
+bridge with the forward and backward SDE drifts as targets) on its three-output sibling ``cfm_sample_dsbm_f32``.
 """
 import math
 import warnings
@@ -405,3 +406,122 @@ class ScheduledBridgeConditionalFlowMatcher(_OTMixin, ConditionalFlowMatcher):
     def compute_lambda(self, t):
         """2 sigma_t / g(t)^2 (run:905-908)."""
         return 2 * self.compute_sigma_t(t) / self.schedule(t) ** 2
+
+
+def _fused_dsbm(coef, x0, x1, eps, idx=None):
+    """Run cfm_sample_dsbm_f32 on a packed [B, 4] table (r, sigma_t, cf, cb) that the caller's tensor library evaluated on
+    t's own device: (xt, forward_target, backward_target) on x0's device/dtype, in eps's shape."""
+    lib = _lib.load()
+    dev = _lib.require_gpu()
+    out_dev, out_dtype, shape = x0.device, x0.dtype, eps.shape
+    B = shape[0]
+    a0 = _lib.to_dev_f32(x0.reshape(x0.shape[0], -1), dev)
+    a1 = _lib.to_dev_f32(x1.reshape(x1.shape[0], -1), dev)
+    d = a0.shape[1]
+    if coef.shape[0] != B:
+        raise AssertionError("t has to have batch size dimension")
+    cd = _lib.to_dev_f32(coef, dev)
+    ed = _lib.to_dev_f32(eps.reshape(B, -1), dev)
+    xt, ft, bt = (torch.empty((B, d), dtype=torch.float32, device=dev) for _ in range(3))
+    gi, gj = (idx if idx is not None else (None, None))
+    check(lib.cfm_sample_dsbm_f32(ptr(a0), ptr(a1), ptr(gi), ptr(gj), ptr(cd), ptr(ed), B, d, ptr(xt), ptr(ft), ptr(bt),
+                                  stream_ptr()), "cfm_sample_dsbm_f32")
+    fin = lambda z: z.reshape(shape).to(device=out_dev, dtype=out_dtype)
+    return fin(xt), fin(ft), fin(bt)
+
+
+class DSBMConditionalFlowMatcher:
+    """DSBM (diffusion Schrodinger bridge matching / iterative Markovian fitting): the scheduled bridge's x_t with the
+    drifts of the forward and of the backward SDE as regression targets, and the row weights of the two losses
+    (``run:LINE`` cites ``runner/src/models/cfm_module.py``: DSBMLitModule, run:1183-1227, on run:834-841, :856).  With
+    ``g = schedule(t)``, ``F(t) = int_0^t g^2``:
+
+        r = F(t) / F(1)    mu_t = x0 + (x1 - x0) r    sigma_t = sqrt(F(t) - F(t)^2 / F(1))    x_t = mu_t + sigma_t eps
+        forward_target   = (x1 - x0) - g sqrt(t / (1 - t + 1e-6)) eps          (run:1192-1194)
+        backward_target  = (x0 - x1) - g sqrt((1 - t) / (t + 1e-6)) eps        (run:1195-1199)
+        forward_scaling  = (1 + g^2 t / (1 - t + 1e-6)) ** -1                  (run:1215)   one per row
+        backward_scaling = (1 + g^2 (1 - t) / (t + 1e-6)) ** -1                (run:1216)
+
+    ``schedule``: a ``cfm_amd.NoiseScheduler``, or a number sigma for ``ConstantNoiseScheduler(sigma)``.  ``ot_method``:
+    ``None`` pairs the rows as given (the refreshed pairs of the outer loop, run:1212); ``"exact"`` / ``"sinkhorn"``
+    couple through ``OTPlanSampler(reg=2 F(1))`` as ``ScheduledBridgeConditionalFlowMatcher`` does.  ``t = 0`` and
+    ``t = 1`` are legal: the ``1e-6`` keeps both targets finite.
+
+    The per-row scalars come from the caller's tensor library on ``t``'s own device; the ``[B, d]`` work (OT gather,
+    mu_t, x_t, both targets) is one fused HIP launch (``cfm_sample_dsbm_f32``), bit-equal to the eager composition of
+    this class in fp32.  CPU tensors, non-fp32 inputs, inputs that require grad and subclasses that override a closed
+    form (``compute_mu_t``, ``compute_sigma_t``, ``compute_targets``) run that eager composition."""
+
+    def __init__(self, schedule, ot_method=None):
+        from .schedule import ConstantNoiseScheduler, NoiseScheduler
+        if isinstance(schedule, (int, float)) and not isinstance(schedule, bool):
+            schedule = ConstantNoiseScheduler(schedule)
+        if not isinstance(schedule, NoiseScheduler):
+            raise TypeError(f"schedule must be a cfm_amd.NoiseScheduler or a number, got {type(schedule).__name__}")
+        F1 = float(schedule.F(1.0))
+        if not F1 > 0:
+            raise ValueError(f"The schedule's accumulated variance F(1) must be strictly positive, got {F1}.")
+        self.schedule, self.F1, self.ot_method = schedule, F1, ot_method
+        self.ot_sampler = OTPlanSampler(method=ot_method, reg=2 * F1) if ot_method is not None else None
+
+    _needs_eager = staticmethod(ScheduledBridgeConditionalFlowMatcher._needs_eager)
+
+    def _customised(self):
+        cls = type(self)
+        return any(not getattr(getattr(cls, m), "_cfm_native", False) for m in ("compute_mu_t", "compute_sigma_t", "compute_targets"))
+
+    # -- the closed forms: the eager composition, and the operation order the kernel reproduces --
+    def _target_coefs(self, t):
+        """(cf, cb) at t: the noise coefficients of the forward and of the backward target"""
+        g = self.schedule(t)
+        return g * torch.sqrt(t / (1 - t + 1e-6)), g * torch.sqrt((1 - t) / (t + 1e-6))
+
+    @_native
+    def compute_mu_t(self, x0, x1, t):
+        """x0 + (x1 - x0) F(t) / F(1) (run:836-838)."""
+        t = pad_t_like_x(t, x0)
+        return x0 + (x1 - x0) * (self.schedule.F(t) / self.F1)
+
+    @_native
+    def compute_sigma_t(self, t):
+        """sqrt(F(t) - F(t)^2 / F(1)) (run:840): the schedule's ``sigma_t``."""
+        return self.schedule.sigma_t(t)
+
+    @_native
+    def compute_targets(self, x0, x1, t, eps):
+        """(forward_target, backward_target) (run:1192-1199)."""
+        cf, cb = self._target_coefs(pad_t_like_x(t, x0))
+        return (x1 - x0) - cf * eps, (x0 - x1) - cb * eps
+
+    def compute_scalings(self, t):
+        """(forward_scaling, backward_scaling), one value per row (run:1215-1216)."""
+        g2 = self.schedule(t) ** 2
+        return (1 + g2 * t / (1 - t + 1e-6)) ** -1, (1 + g2 * (1 - t) / (t + 1e-6)) ** -1
+
+    def sample_noise_like(self, x):
+        return torch.randn_like(x)
+
+    def sample_location_and_targets(self, x0, x1, t=None, return_noise=False):
+        """(t, xt, forward_target, backward_target, forward_scaling, backward_scaling[, eps]); RNG order as the other
+        matchers: the OT sampler's draws, then ``t`` from the CPU generator, then ``eps`` from x0's."""
+        idx = self.ot_sampler._sample_indices(x0, x1) if self.ot_sampler is not None else None
+        if t is None:
+            t = torch.rand(x0.shape[0]).type_as(x0)
+        assert len(t) == x0.shape[0], "t has to have batch size dimension"
+        tt = t.reshape(-1)
+        fs, bs = self.compute_scalings(tt)
+        if self._customised() or self._needs_eager(x0, x1, t):
+            if idx is not None:
+                i, j = idx
+                x0, x1 = x0[i.to(x0.device)], x1[j.to(x1.device)]
+            eps = self.sample_noise_like(x0)
+            xt = self.compute_mu_t(x0, x1, t) + pad_t_like_x(self.compute_sigma_t(t), x0) * eps
+            ft, bt = self.compute_targets(x0, x1, t, eps)
+        else:
+            eps = self.sample_noise_like(x0)
+            cf, cb = self._target_coefs(tt)
+            coef = torch.stack([c.to(torch.float32) for c in (self.schedule.F(tt) / self.F1, self.schedule.sigma_t(tt), cf, cb)], dim=1)
+            xt, ft, bt = _fused_dsbm(coef, x0, x1, eps, idx=idx)
+        if return_noise:
+            return t, xt, ft, bt, fs, bs, eps
+        return t, xt, ft, bt, fs, bs

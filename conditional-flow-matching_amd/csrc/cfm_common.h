@@ -47,7 +47,10 @@ static inline int cfm_device_cus() {
 struct MlpNetLayer {
     const float* X; const float* W; const float* bias; float* out; float* zout;
     const float* target; const float* lam; float scale; float* partial;      // last layer: loss target, row weights, seed scale, loss partials
+    int lam_mode;                                                            // what lam does, per net: LAM_RESIDUAL or LAM_ROW_WEIGHT
 };
+// lam of a loss epilogue: LAM_RESIDUAL (lam v + target)^2, the SF2M score loss; LAM_ROW_WEIGHT lam (v - target)^2, the DSBM losses
+enum { LAM_RESIDUAL = 0, LAM_ROW_WEIGHT = 1 };
 
 // XCD-aware block remap: the dispatcher places block b on XCD b % 8; give each
 // XCD a contiguous range of logical ids so neighbouring tiles share its L2.

@@ -200,6 +200,69 @@ extern "C" int cfm_sample_xt_ut_sched_f32(const float* x0, const float* x1, cons
     return cfm_status();
 }
 
+// DSBM (DSBMConditionalFlowMatcher): the scheduled bridge's x_t and the two drift targets that the forward and the backward
+// net regress, runner/src/models/cfm_module.py:834-841 (mu_t, sigma_t), :1187-1200 (x_t, the targets).  The xt_ut_kernel
+// loop with three outputs: the per-row scalars arrive as one packed [B, 4] table (r, sigma_t, cf, cb), one 16-byte load
+// per row; every op separately rounded, in the matcher's eager order:
+//   dx = x1 - x0;  mu = x0 + dx r;  xt = mu + sigma_t eps;  ft = dx - cf eps;  bt = (x0 - x1) - cb eps
+__device__ __forceinline__ void dsbm_point(const float4& q, float a0, float a1, float e, float& xt, float& ft, float& bt) {
+    const float dx = f_sub(a1, a0);
+    const float mu = f_add(a0, f_mul(dx, q.x));
+    xt = f_add(mu, f_mul(q.y, e));
+    ft = f_sub(dx, f_mul(q.z, e));
+    bt = f_sub(f_sub(a0, a1), f_mul(q.w, e));
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void dsbm_kernel(const float* __restrict__ x0, const float* __restrict__ x1,
+                                                   const int64_t* __restrict__ gi, const int64_t* __restrict__ gj,
+                                                   const float* __restrict__ coef, const float* __restrict__ eps, int B, int d,
+                                                   float* __restrict__ xt, float* __restrict__ ft, float* __restrict__ bt) {
+    constexpr int W = VEC ? 4 : 1;
+    const size_t per_row = (size_t)d / W;
+    const size_t total = (size_t)B * per_row;
+    for (size_t g = (size_t)blockIdx.x * 256 + threadIdx.x; g < total; g += (size_t)gridDim.x * 256) {
+        const int b = (int)(g / per_row);
+        const size_t k = (g - (size_t)b * per_row) * W;
+        const size_t r0 = gi ? (size_t)gi[b] : (size_t)b;
+        const size_t r1 = gj ? (size_t)gj[b] : (size_t)b;
+        const float4 q = reinterpret_cast<const float4*>(coef)[b];
+        const size_t o = (size_t)b * d + k;
+        if (VEC) {
+            const float4 a0 = *reinterpret_cast<const float4*>(x0 + r0 * d + k);
+            const float4 a1 = *reinterpret_cast<const float4*>(x1 + r1 * d + k);
+            const float4 e = *reinterpret_cast<const float4*>(eps + o);
+            float4 vx, vf, vb;
+            dsbm_point(q, a0.x, a1.x, e.x, vx.x, vf.x, vb.x);
+            dsbm_point(q, a0.y, a1.y, e.y, vx.y, vf.y, vb.y);
+            dsbm_point(q, a0.z, a1.z, e.z, vx.z, vf.z, vb.z);
+            dsbm_point(q, a0.w, a1.w, e.w, vx.w, vf.w, vb.w);
+            *reinterpret_cast<float4*>(xt + o) = vx;
+            *reinterpret_cast<float4*>(ft + o) = vf;
+            *reinterpret_cast<float4*>(bt + o) = vb;
+        } else {
+            float vx, vf, vb;
+            dsbm_point(q, x0[r0 * d + k], x1[r1 * d + k], eps[o], vx, vf, vb);
+            xt[o] = vx; ft[o] = vf; bt[o] = vb;
+        }
+    }
+}
+
+extern "C" int cfm_sample_dsbm_f32(const float* x0, const float* x1, const int64_t* i, const int64_t* j, const float* coef,
+                                   const float* eps, int B, int d, float* xt, float* ft, float* bt, void* stream) {
+    if (!x0 || !x1 || !coef || !eps || !xt || !ft || !bt || B < 0 || d <= 0) return CFM_EINVAL;
+    if (((uintptr_t)coef) & 15) return CFM_EALIGN;
+    if (B == 0) return 0;
+    auto al = [](const void* p) { return (((uintptr_t)p) & 15) == 0; };
+    const bool vec = (d % 4 == 0) && al(x0) && al(x1) && al(eps) && al(xt) && al(ft) && al(bt);
+    const size_t total = (size_t)B * (size_t)(vec ? d / 4 : d);
+    int blocks = (int)((total + 255) / 256);
+    if (blocks > 8192) blocks = 8192;
+    if (vec) hipLaunchKernelGGL(dsbm_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x0, x1, i, j, coef, eps, B, d, xt, ft, bt);
+    else     hipLaunchKernelGGL(dsbm_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x0, x1, i, j, coef, eps, B, d, xt, ft, bt);
+    return cfm_status();
+}
+
 // generic row gather (labels y0[i], y1[j]; also x0[i], x1[j] for sample_plan)
 __global__ __launch_bounds__(256) void gather_rows_kernel(const unsigned char* __restrict__ src,
                                                           const int64_t* __restrict__ idx, int n,

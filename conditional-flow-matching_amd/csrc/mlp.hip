@@ -37,7 +37,8 @@ struct LayerEpi {
     const float* W; int ldw; const float* bias; const float* tptr; float tval; int t_per_row, tcol, B, N;
     float* out; float* zout; const float* mse_u; float mse_scale, mse_inv_n; float* mse_partial;
     const float* lam;      // weighted residual (the score loss of the SF2M step): r = lam[row] * v + mse_u, seed (r * mse_scale) * lam[row]
-};
+    int lam_mode;          // LAM_ROW_WEIGHT (the DSBM losses): lam[row] weights the plain residual's square instead, sum w (v - mse_u)^2,
+};                         // seed ((v - mse_u) * mse_scale) * w
 // wg: the workgroup's index inside its net's grid (blockIdx.x when one net runs alone) — the slot of its loss partial
 template <bool ACT, typename G>
 __device__ __forceinline__ void layer_epilogue(const G& g, int row0, int col0, const LayerEpi& E, unsigned wg) {
@@ -74,7 +75,11 @@ __device__ __forceinline__ void layer_epilogue(const G& g, int row0, int col0, c
                 v[u] = ACT ? selu_f(x) : x;
                 if (!ACT && mse_u != nullptr && gc + u < N) {
                     const float tgt = mse_u[(size_t)gr * N + gc + u];
-                    if (lam != nullptr) {       // (lam = 1: fmaf(1, v, e) = v - (-e) and (r * scale) * 1 — the bits of the plain mode on u = -e)
+                    if (lam != nullptr && E.lam_mode == LAM_ROW_WEIGHT) {   // (w = 1: w * dlt = dlt and (dlt * scale) * 1 — the bits of the plain mode)
+                        const float dlt = v[u] - tgt;
+                        lsum = fmaf(lw * dlt, dlt, lsum);
+                        v[u] = (dlt * E.mse_scale) * lw;
+                    } else if (lam != nullptr) {       // (lam = 1: fmaf(1, v, e) = v - (-e) and (r * scale) * 1 — the bits of the plain mode on u = -e)
                         const float rr = fmaf(lw, v[u], tgt);
                         lsum = fmaf(rr, rr, lsum);
                         v[u] = (rr * E.mse_scale) * lw;
@@ -289,7 +294,7 @@ static int launch_net_layer(const MlpNetLayer* net, int nets, int lda, int ldw, 
     for (int q = 0; q < nets; ++q) {
         P[q] = plan_layer(net[q].X, lda, net[q].W, ldw, B, K, N);
         const LayerEpi E = {net[q].W, ldw, net[q].bias, t, tval, t_per_row, tcol, B, N, net[q].out, net[q].zout,
-                            net[q].target, net[q].scale, net[q].partial ? inv_n : 0.f, net[q].partial, net[q].lam};
+                            net[q].target, net[q].scale, net[q].partial ? inv_n : 0.f, net[q].partial, net[q].lam, net[q].lam_mode};
         A[q] = LayerArgs{net[q].X, lda, K, P[q].tn, E};
     }
     if (n_partials) *n_partials = P[0].tm * P[0].tn;      // (the tile follows from the sizes alone: equal for both nets)

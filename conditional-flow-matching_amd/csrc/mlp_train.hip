@@ -488,6 +488,7 @@ __global__ __launch_bounds__(256) void mse_grad(float* __restrict__ v, const flo
 struct NetForward {
     const float* const* W; const float* const* b; float* const* hidden; float* const* preact; float* g;
     const float* target; const float* lam; float scale; float* lpart;
+    int lam_mode;      // what the row weights do (cfm_common.h): LAM_RESIDUAL, or LAM_ROW_WEIGHT for the DSBM step
 };
 
 // one loss partial per workgroup of the last layer (an upper bound: the 128 x 128 form has fewer)
@@ -507,7 +508,7 @@ static int mlp_train_forward(const NetForward* nf, int nets, const float* xt, co
         for (int q = 0; q < nets; ++q) {
             float* dst = last ? nf[q].g : nf[q].hidden[l];
             net[q] = MlpNetLayer{cur[q], nf[q].W[l], nf[q].b[l], dst, last ? nullptr : nf[q].preact[l], nullptr, nullptr, 0.f, nullptr};
-            if (last && fuse_loss) { net[q].target = nf[q].target; net[q].lam = nf[q].lam; net[q].scale = nf[q].scale; net[q].partial = nf[q].lpart; }
+            if (last && fuse_loss) { net[q].target = nf[q].target; net[q].lam = nf[q].lam; net[q].scale = nf[q].scale; net[q].partial = nf[q].lpart; net[q].lam_mode = nf[q].lam_mode; }
             cur[q] = dst;
         }
         const int rc = cfm_mlp_launch_layer(net, nets, K, dims[l], first_t ? t : nullptr, first_t ? 1 : 0, first_t ? K : -1, B, K,
@@ -603,6 +604,45 @@ extern "C" int cfm_mlp_sf2m_step_f32(const float* xt, const float* t, const floa
         tw[q] = carve_train_ws((char*)ws + q * ws_pitch, B, maxw, maxp);
         nf[q] = NetForward{W + q * n_layers, b + q * n_layers, hidden + q * (n_layers - 1), preact + q * (n_layers - 1), q ? g_score : g_flow,
                            q ? eps : ut, q ? lam : nullptr, q ? (2.0f * inv_n) * score_weight : 2.0f * inv_n, tw[q].lpart};
+    }
+    int n_lpart = 0;
+    const int rc = mlp_train_forward(nf, 2, xt, t, dims, n_layers, B, inv_n, true, s, &n_lpart);
+    if (rc) return rc;
+    NetBackward nb[2];
+    for (int q = 0; q < 2; ++q) net_backward_of(&nb[q], nf[q], xt, n_layers, dW + q * n_layers, db + q * n_layers, tw[q], losses + q, n_lpart);
+    return mlp_backward_impl(nb, 2, dims, n_layers, B, s, t, nullptr, nullptr);
+}
+
+// ------------------------------------------------------------ the DSBM step: two nets ----
+// One DSBM (diffusion Schrodinger bridge matching) training step for a forward and a backward drift net of equal layer sizes,
+// everything but the optimizer update:
+//     f = fwd([xt, t]);  b = bwd([xt, t])
+//     losses = {mean(wf[:, None] * (f - ft)^2), mean(wb[:, None] * (b - bt)^2)};  dW, db of both nets = d (losses[0] + losses[1]) / d parameters
+// — runner/src/models/cfm_module.py:1203-1227 (DSBMLitModule.step: the two row-scaled MSEs and their sum).  The two-net driver
+// of cfm_mlp_sf2m_step_f32 with the row-weighted loss epilogue (LAM_ROW_WEIGHT) on both nets: the launch count of ONE
+// regression step, and with wf = wb = 1 each net's loss and gradients are the bits cfm_mlp_regression_step_f32 gives it alone.
+extern "C" int cfm_mlp_dsbm_step_f32(const float* xt, const float* t, const float* ft, const float* bt, const float* wf,
+                                     const float* wb, const float* const* W, const float* const* b, float* const* hidden,
+                                     float* const* preact, float* const* dW, float* const* db, const int* dims,
+                                     int n_layers, int B, float* g_fwd, float* g_bwd, float* losses, void* ws, void* stream) {
+    if (!xt || !ft || !bt || !wf || !wb || !W || !b || !dims || !g_fwd || !g_bwd || !dW || !db || !losses || !ws || n_layers < 1 || B < 1)
+        return CFM_EINVAL;
+    if (n_layers > SF2M_MAX_LAYERS) return CFM_EINVAL;      // the one reduction's table is full at two nets of 7 layers
+    if (n_layers > 1 && (!hidden || !preact)) return CFM_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    if (t && dims[0] < 2) return CFM_EINVAL;
+    if (!loss_partials_fit(B, dims[n_layers])) return CFM_EINVAL;
+    int maxw; size_t maxp;
+    mlp_widest(dims, n_layers, &maxw, &maxp);
+    // two CFM_OP_MLP_TRAIN workspaces back to back: the forward net's, then the backward net's
+    const size_t ws_pitch = cfm_align_up(cfm_mlp_train_ws_bytes_internal(B, maxw, (int)maxp), 256);
+    const size_t nel = (size_t)B * dims[n_layers];
+    const float inv_n = 1.0f / (float)nel;
+    TrainWs tw[2]; NetForward nf[2];
+    for (int q = 0; q < 2; ++q) {
+        tw[q] = carve_train_ws((char*)ws + q * ws_pitch, B, maxw, maxp);
+        nf[q] = NetForward{W + q * n_layers, b + q * n_layers, hidden + q * (n_layers - 1), preact + q * (n_layers - 1), q ? g_bwd : g_fwd,
+                           q ? bt : ft, q ? wb : wf, 2.0f * inv_n, tw[q].lpart, LAM_ROW_WEIGHT};
     }
     int n_lpart = 0;
     const int rc = mlp_train_forward(nf, 2, xt, t, dims, n_layers, B, inv_n, true, s, &n_lpart);

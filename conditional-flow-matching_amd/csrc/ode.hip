@@ -960,6 +960,146 @@ static int ode_fixed_small(int scheme, const float* const* W, const float* const
     return ode_fixed_small_m<AUG_NONE>(scheme, W, b, dims, B, d, t_span, n_t, traj, tspan_dev, nullptr, s);
 }
 
+// ---- DSBM: the probability-flow ODE of a forward and a backward drift net, dx/dt = (f(t, x) - b(t, x)) / 2 ----------
+// runner/src/models/components/solver.py:259-263 (DSBMFlowSolver.forward_ode_drift).  ode_small_fixed with two fields: both
+// nets' weights in LDS in the layout of the SDE kernels (sde_small.h: small_lds_bytes(2, 2, false)), every stage derivative
+// k = 0.5f * (f - b) — one rounded subtraction and an exact halving, so `/ 2` and `* 0.5f` agree — and the stage and step
+// arithmetic of ode_small_fixed.  Bit-equal to the layer driver below (two forward passes on mlp_layer, ode_half_diff,
+// ode_combine).
+template <int SCHEME>
+__global__ __launch_bounds__(256) void ode_small_fixed_pair(SmArgs F, SmArgs S, int B, int d, const float* __restrict__ tspan,
+                                                            int n_t, float* __restrict__ traj) {
+    constexpr int NS = fx_stages<SCHEME>();
+    extern __shared__ __attribute__((aligned(16))) float small_lds[];
+    float* WlF = small_lds;
+    float* blF = WlF + 4 * SM_W * SM_LD;
+    float* wtF = blF + 4 * SM_W;
+    float* WlS = wtF + SM_W;
+    float* blS = WlS + 4 * SM_W * SM_LD;
+    float* wtS = blS + 4 * SM_W;
+    float* Ab0 = wtS + SM_W;
+    float* Ab1 = Ab0 + SM_ROWS * SM_LD;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    sm_stage_weights(F, d, WlF, blF, wtF, tid);
+    sm_stage_weights(S, d, WlS, blS, wtS, tid);
+    const size_t n = (size_t)B * d;
+    const int col = wv * 16 + (lane & 15);
+    for (int row0 = blockIdx.x * SM_ROWS; row0 < B; row0 += gridDim.x * SM_ROWS) {
+        SmTile x;
+#pragma unroll
+        for (int i = 0; i < SM_V; ++i) {
+            const int gr = row0 + sm_row(i, lane);
+            x.v[i] = (gr < B && col < d) ? traj[(size_t)gr * d + col] : 0.f;
+        }
+        __syncthreads();
+        for (int k = 0; k + 1 < n_t; ++k) {
+            const float t = tspan[k], dt = tspan[k + 1] - tspan[k];
+            SmTile f[NS];
+#pragma unroll
+            for (int sg = 0; sg < NS; ++sg) {
+                SmTile y = x;
+                float tsg = t;
+                if (sg > 0) {
+#pragma unroll
+                    for (int i = 0; i < SM_V; ++i) {
+                        float acc = (float)fx_a<SCHEME>(sg - 1, 0) * f[0].v[i];
+#pragma unroll
+                        for (int q = 1; q < NS - 1; ++q)
+                            if (q < sg) acc = fmaf((float)fx_a<SCHEME>(sg - 1, q), f[q].v[i], acc);
+                        y.v[i] = fmaf(dt, acc, x.v[i]);
+                    }
+                    tsg = t + (float)fx_c<SCHEME>(sg - 1) * dt;
+                }
+                const SmTile fv = sm_field(y, tsg, F, d, Ab0, Ab1, WlF, blF, wtF, wv, lane);
+                const SmTile bv = sm_field(y, tsg, S, d, Ab0, Ab1, WlS, blS, wtS, wv, lane);
+#pragma unroll
+                for (int i = 0; i < SM_V; ++i) f[sg].v[i] = 0.5f * (fv.v[i] - bv.v[i]);
+            }
+#pragma unroll
+            for (int i = 0; i < SM_V; ++i) {
+                float acc = (float)fx_b<SCHEME>(0) * f[0].v[i];
+#pragma unroll
+                for (int q = 1; q < NS; ++q) acc = fmaf((float)fx_b<SCHEME>(q), f[q].v[i], acc);
+                x.v[i] = fmaf(dt, acc, x.v[i]);
+                const int gr = row0 + sm_row(i, lane);
+                if (gr < B && col < d) traj[(size_t)(k + 1) * n + (size_t)gr * d + col] = x.v[i];
+            }
+        }
+        __syncthreads();
+    }
+}
+
+template <int SCHEME>
+static int ode_fixed_pair_small_t(const SmArgs& F, const SmArgs& S, int B, int d, const float* t_span, int n_t, float* traj,
+                                  float* tspan_dev, hipStream_t s) {
+    const int grid = small_grid<ode_small_fixed_pair<SCHEME>, 160 * 1024>(B);
+    if (grid < 0) return CFM_EINVAL;
+    int rc = cfm_hip(hipMemcpyAsync(tspan_dev, t_span, sizeof(float) * n_t, hipMemcpyHostToDevice, s));
+    if (rc) return rc;
+    hipLaunchKernelGGL((ode_small_fixed_pair<SCHEME>), dim3(grid), dim3(256), small_lds_bytes(2, 2, false), s, F, S, B, d,
+                       tspan_dev, n_t, traj);
+    return cfm_status();
+}
+
+// k <- 0.5f * (k - kb): the stage derivative of the pair from the two nets' outputs (layer driver)
+__global__ __launch_bounds__(256) void ode_half_diff(size_t n, float* __restrict__ k, const float* __restrict__ kb) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) k[i] = 0.5f * (k[i] - kb[i]);
+}
+
+extern "C" int cfm_ode_fixed_pair_mlp_f32(const float* const* Wf, const float* const* bf, const float* const* Wb,
+                                          const float* const* bb, const int* dims, int n_layers, const float* x0, int B,
+                                          const float* t_span, int n_t, int scheme, float* traj, int* nfe, void* ws,
+                                          void* stream) {
+    int d;
+    if (!Wf || !bf || !Wb || !bb || !x0 || !t_span || !traj || !ws || B <= 0 || n_t < 1 || !fx_known(scheme)) return CFM_EINVAL;
+    int rc = check_mlp(dims, n_layers, &d);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const int width = maxwidth(dims, n_layers);
+    OdeWs w = ode_carve(ws, B, width, d);
+    const size_t n = (size_t)B * d;
+    const int ns = fx_stages_host(scheme);
+    rc = cfm_hip(hipMemcpyAsync(traj, x0, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (rc) return rc;
+    if (ode_small_enabled() && small_envelope(dims, n_layers, nullptr) == 0 && d + 1 <= SM_W && n >= (size_t)n_t && n_t >= 2) {
+        const SmArgs F = small_args(Wf, bf, dims), S = small_args(Wb, bb, dims);
+        if (scheme == CFM_ODE_RK4) rc = ode_fixed_pair_small_t<CFM_ODE_RK4>(F, S, B, d, t_span, n_t, traj, w.xt, s);
+        else if (scheme == CFM_ODE_MIDPOINT) rc = ode_fixed_pair_small_t<CFM_ODE_MIDPOINT>(F, S, B, d, t_span, n_t, traj, w.xt, s);
+        else rc = ode_fixed_pair_small_t<CFM_ODE_EULER>(F, S, B, d, t_span, n_t, traj, w.xt, s);
+        if (nfe) *nfe = ns * (n_t - 1);
+        return rc;
+    }
+    // the layer driver of cfm_ode_fixed_mlp_f32 with two forward passes and the halved difference per stage
+    int evals = 0;
+    for (int k = 0; k + 1 < n_t; ++k) {
+        const float t = t_span[k], dt = t_span[k + 1] - t_span[k];
+        const float* xk = traj + (size_t)k * n;
+        for (int sg = 0; sg < ns; ++sg) {
+            const float* yin = xk;
+            float tsg = t;
+            if (sg > 0) {
+                Stages st{}; st.n = sg;
+                for (int q = 0; q < 7; ++q) { st.k[q] = w.k[q < sg ? q : 0]; st.c[q] = q < sg ? (float)fx_a_host(scheme, sg - 1, q) : 0.f; }
+                hipLaunchKernelGGL(ode_combine, dim3(ode_blocks(n)), dim3(256), 0, s, n, xk, dt, st, w.xt, (float*)nullptr);
+                yin = w.xt;
+                tsg = t + (float)fx_c_host(scheme, sg - 1) * dt;
+            }
+            rc = cfm_mlp_forward_impl(yin, nullptr, tsg, 1, 0, Wf, bf, dims, n_layers, B, w.k[sg], w.act, s);
+            if (rc) return rc;
+            rc = cfm_mlp_forward_impl(yin, nullptr, tsg, 1, 0, Wb, bb, dims, n_layers, B, w.x, w.act, s);
+            if (rc) return rc;
+            hipLaunchKernelGGL(ode_half_diff, dim3(ode_blocks(n)), dim3(256), 0, s, n, w.k[sg], w.x);
+            ++evals;
+        }
+        Stages st{}; st.n = ns;
+        for (int q = 0; q < 7; ++q) { st.k[q] = w.k[q < ns ? q : 0]; st.c[q] = q < ns ? (float)fx_b_host(scheme, q) : 0.f; }
+        hipLaunchKernelGGL(ode_combine, dim3(ode_blocks(n)), dim3(256), 0, s, n, xk, dt, st,
+                           traj + (size_t)(k + 1) * n, (float*)nullptr);
+    }
+    if (nfe) *nfe = evals;
+    return cfm_status();
+}
+
 // ---- CNF: one evaluation of [v, div] (the tile kernel of the augmented solves, once) --------------------------
 // x: rows of stride ldx (d values each); v: rows of stride ldv; div[row * lddiv] = dsign * div.
 // FIELD_GRAD: v = grad_x s and div = its Laplacian (AUG_EXACT), or v alone (AUG_NONE: div is not touched).

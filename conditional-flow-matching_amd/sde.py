@@ -36,6 +36,7 @@ class FlowScoreSDE(torch.nn.Module):
     (``reverse=True``: backward drift -drift + score evaluated at 1 - t, solver.py:129-139,32-35)."""
     noise_type = "diagonal"
     sde_type = "ito"
+    negate_reverse = True      # reverse=True flips the sign of the drift net (DriftSDE does not)
 
     def __init__(self, drift, score, sigma=1.0, reverse=False):
         super().__init__()
@@ -59,6 +60,31 @@ class FlowScoreSDE(torch.nn.Module):
         return torch.ones_like(y) * s
 
 
+class DriftSDE(torch.nn.Module):
+    """dy = drift([y, t]) dt + sigma dW — ONE drift net, as DSBM trains them (runner/src/models/components/solver.py:249-257
+    behind the SDE class of :35-41).  ``reverse=True``: the drift is evaluated at 1 - t and enters with a PLUS sign (the
+    backward net IS the drift of the time-reversed process); ``sigma`` is read at the solver's time, as for
+    ``FlowScoreSDE``."""
+    noise_type = "diagonal"
+    sde_type = "ito"
+    score = None               # (sdeint's HIP paths: no second field)
+    negate_reverse = False     # (and no sign flip on the way back)
+
+    def __init__(self, drift, sigma=1.0, reverse=False):
+        super().__init__()
+        self.drift, self.sigma, self.reverse = drift, sigma, reverse
+        self.last_path = None      # "hip" / "eager": what the last sdeint call on this object ran
+
+    _cat = FlowScoreSDE._cat
+    g = FlowScoreSDE.g
+
+    def f(self, t, y):
+        return self.drift(self._cat(1 - t if self.reverse else t, y))
+
+
+_SDE_CLASSES = (FlowScoreSDE, DriftSDE)      # what sdeint's HIP paths know how to take apart
+
+
 def _grid(ts, dt):
     """The ts grid refined so that no step exceeds dt; returns [(t, h, is_output)]."""
     pts = [float(x) for x in ts]
@@ -71,8 +97,11 @@ def _grid(ts, dt):
 
 
 def _fused_fields(sde):
-    """(drift, score) as two 4-layer time-varying MLPs of widths <= 64 with identical layer sizes, or None."""
+    """(drift, score) as two 4-layer time-varying MLPs of widths <= 64 with identical layer sizes, or None.  A DriftSDE:
+    (drift, None), the kernel's single-field mode."""
     f, s = sde.drift, sde.score
+    if s is None:
+        s = f
     if not (isinstance(f, MLP) and isinstance(s, MLP) and f.time_varying and s.time_varying):
         return None
     lf, ls = f._linears(), s._linears()
@@ -80,7 +109,7 @@ def _fused_fields(sde):
     ds = [ls[0].in_features] + [l.out_features for l in ls]
     if len(lf) != 4 or df != ds or max(df[1:]) > 64 or df[0] != df[4] + 1:
         return None
-    return f, s, df
+    return f, sde.score, df
 
 
 _G_CACHE = {}         # (schedule type, parameters, grid) -> g(t_k): _schedule_values
@@ -120,6 +149,12 @@ def _em_records(steps, g, reverse):
                     for (t, h, is_out), gk in zip(steps, g))
 
 
+def _kernel_reverse_flag(sde):
+    """The ``reverse`` argument of the one-launch kernels: it NEGATES the first field, which is FlowScoreSDE's way back;
+    a DriftSDE's reverse lives in the records' te = 1 - t alone (flag 0 in both directions)."""
+    return 1 if (sde.reverse and sde.negate_reverse) else 0
+
+
 _SRK_SCOPE = ("sdeint method 'srk' is built for FlowScoreSDE with a constant (non-callable) sigma: for constant diagonal "
               "noise every diffusion-derivative term of the SRI2W1 tableau vanishes; a state- or time-dependent g needs "
               "the full tableau, which is not built")
@@ -149,7 +184,8 @@ def sdeint(sde, y0, ts, method="euler", dt=1e-3, generator=None, noise="philox",
 
     Two small ``cfm_amd.MLP`` fields (4 layers, widths <= 64: the SF2M tutorial's and the single-cell models) run the
     WHOLE trajectory in one launch (``cfm_sde_em_mlp_f32`` / ``cfm_sde_srk_mlp_f32``: weights of both fields in LDS,
-    state in registers).
+    state in registers).  A ``DriftSDE`` (one drift net: DSBM's forward or backward SDE) takes the same ``euler`` paths
+    with one field, the one-launch kernel in its single-field mode.
     ``noise="philox"`` (default): N(0, 1) from Philox4x32-10 inside the kernel, seeded from ``generator`` (or torch's
     default CUDA generator), so ``torch.manual_seed`` makes runs repeatable; ``noise="torch"``: the increments are
     drawn with ``torch.randn`` step by step exactly as the launch-per-step scheme draws them (``(B, d)`` per step for
@@ -170,10 +206,11 @@ def sdeint(sde, y0, ts, method="euler", dt=1e-3, generator=None, noise="philox",
                              "FlowScoreSDE(..., reverse=True))")
     steps = _grid(ts, float(dt))
     given = _noise_arg(noise, method, len(steps), y0)
-    fast = (isinstance(sde, FlowScoreSDE) and isinstance(sde.drift, MLP) and isinstance(sde.score, MLP)
+    known = isinstance(sde, _SDE_CLASSES)
+    fast = (known and isinstance(sde.drift, MLP) and (sde.score is None or isinstance(sde.score, MLP))
             and y0.dim() == 2 and torch.cuda.is_available())
     g_steps = None
-    if isinstance(sde, FlowScoreSDE) and callable(sde.sigma) and (fast or fused is True):
+    if known and callable(sde.sigma) and (fast or fused is True):
         # a schedule: one scalar per step (srk with a callable sigma was refused above)
         g_steps = _schedule_values(sde.sigma, steps)
         if g_steps is None:
@@ -181,7 +218,7 @@ def sdeint(sde, y0, ts, method="euler", dt=1e-3, generator=None, noise="philox",
                 raise ValueError("sdeint(fused=True): sigma(t) must be a scalar (a noise schedule); state-dependent noise "
                                  "is stepped in eager torch")
             fast = False
-    if isinstance(sde, FlowScoreSDE):
+    if known:
         sde.last_path = "hip" if fast else "eager"
     out = [y0]
     if fast:
@@ -198,7 +235,8 @@ def sdeint(sde, y0, ts, method="euler", dt=1e-3, generator=None, noise="philox",
                 raise ValueError(f"sdeint(fused=True): y0 has {y.shape[1]} columns, the fields map {fields[2][4]}")
             fields = None
         if fused is True and fields is None:
-            raise ValueError("sdeint(fused=True): needs two 4-layer time-varying cfm_amd.MLP fields of widths <= 64")
+            raise ValueError("sdeint(fused=True): needs two 4-layer time-varying cfm_amd.MLP fields of widths <= 64 "
+                             "(FlowScoreSDE; one for a DriftSDE)")
         if g_steps is None:
             g_steps = [float(sde.sigma)] * len(steps)
         sigma = g_steps[0] if steps else 0.0          # (srk: constant)
@@ -229,12 +267,12 @@ def sdeint(sde, y0, ts, method="euler", dt=1e-3, generator=None, noise="philox",
             elif xi is None:
                 seed = int(torch.randint(0, 2 ** 62, (1,), device=dev, generator=generator).item())
             Wf, bf, _, keep_f = f.hip_params(dev)
-            Ws, bs, _, keep_s = s.hip_params(dev)
+            Ws, bs, _, keep_s = s.hip_params(dev) if s is not None else (None, None, None, None)      # one field: Ws = bs = NULL
             cd = (ctypes.c_int * 5)(*dims)
             traj = torch.empty((n_out, B, d), dtype=torch.float32, device=dev)
             ws = torch.empty(rec * len(steps) + 256, dtype=torch.uint8, device=dev)
             entry, name = (lib.cfm_sde_srk_mlp_f32, "cfm_sde_srk_mlp_f32") if srk else (lib.cfm_sde_em_mlp_f32, "cfm_sde_em_mlp_f32")
-            check(entry(Wf, bf, Ws, bs, cd, 4, ptr(y), B, host, len(steps), 1 if sde.reverse else 0,
+            check(entry(Wf, bf, Ws, bs, cd, 4, ptr(y), B, host, len(steps), _kernel_reverse_flag(sde),
                         ptr(xi), seed, ptr(traj), ptr(ws), stream_ptr()), name)
             torch.cuda.current_stream().synchronize()          # `host` (pageable) must outlive the copy
             return torch.cat([y0.to(torch.float32)[None].to(y0.device), traj.to(y0.device)])
@@ -265,8 +303,8 @@ def sdeint(sde, y0, ts, method="euler", dt=1e-3, generator=None, noise="philox",
         for k, (t, h, is_out) in enumerate(steps):
             te = (1.0 - t) if sde.reverse else t
             v = sde.drift.forward_hip(y, te)
-            s = sde.score.forward_hip(y, te)
-            if sde.reverse:
+            s = sde.score.forward_hip(y, te) if sde.score is not None else None
+            if sde.reverse and sde.negate_reverse:
                 v = -v
             xi = given[k] if given is not None else torch.randn(y.shape, device=dev, dtype=torch.float32, generator=generator)
             check(lib.cfm_sde_em_step_f32(ptr(y), ptr(v), ptr(s), ptr(xi), float(h), g_steps[k], sign,
@@ -383,3 +421,141 @@ class FlowSolver(torch.nn.Module):
             def g(self, t, y):
                 return outer.sigma(t) * torch.ones_like(y)
         return sdeint(_S(), x0, t_span, method=self.sde_solver, dt=self.dt, generator=generator)
+
+
+class DSBMFlowSolver(FlowSolver):
+    """runner/src/models/components/solver.py:225-269 on this backend: ``vector_field`` is the FORWARD SDE drift net and
+    ``score_field`` the BACKWARD one (two separate nets, called as f(t, x); the single-net split output is not built).
+    ``sigma``: a noise schedule (``cfm_amd.schedule``) or a number for a constant one.
+
+    ``sdeint``: forward ``dy = f(t, y) dt + g(t) dW``; ``reverse=True`` has drift ``+b(1 - t, y)`` with g read at the
+    solver's time (solver.py:249-257, :35-41).  Time-varying ``cfm_amd.MLP`` nets run ``sde.sdeint``'s HIP paths on a
+    ``DriftSDE``: 4 layers of widths <= 64 the one-launch kernel in its single-field mode (``cfm_sde_em_mlp_f32`` with
+    ``Ws = NULL``), wider ones a launch per step; anything else the eager scheme.  ``sde_solver="srk"`` is refused.
+
+    ``odeint``: ``dx/dt = (f(t, x) - b(t, x)) / 2`` (solver.py:259-263).  MLP pairs of equal sizes under ``euler``,
+    ``midpoint`` or ``rk4`` run ``cfm_ode_fixed_pair_mlp_f32`` (one launch for 4 layers of widths <= 64;
+    ``fused=False`` forces its launch-per-stage form: two forward passes, the halved difference, the stage combine —
+    the same bits); ``dopri5`` / ``tsit5`` and every other field run ``NeuralODE``'s generic path on the combined
+    callable.  ``nfe`` counts one evaluation of the pair per stage.  ``last_path``: ``"hip"`` or ``"eager"``."""
+
+    def __init__(self, vector_field, dim, score_field=None, sigma=None, ode_solver="euler", sde_solver="euler", dt=0.01,
+                 **kwargs):
+        if score_field is None:
+            raise TypeError("DSBMFlowSolver needs the backward drift net as score_field (one net with a split "
+                            "[forward, backward] output is not built)")
+        if isinstance(sigma, (int, float)) and not isinstance(sigma, bool):
+            sigma = ConstantNoiseScheduler(sigma)
+        super().__init__(vector_field, dim, score_field=score_field, sigma=sigma, ode_solver=ode_solver,
+                         sde_solver=sde_solver, dt=dt, **kwargs)
+
+    def forward_sde_drift(self, t, x):                              # solver.py:249-252
+        self.nfe += 1
+        return self.net(t, x)
+
+    def backward_sde_drift(self, t, x):                             # solver.py:254-257
+        self.nfe += 1
+        return self.score_net(t, x)
+
+    def forward_ode_drift(self, t, x):                              # solver.py:259-263
+        self.nfe += 1
+        return (self.net(t, x) - self.score_net(t, x)) / 2
+
+    def _hip_pair(self):
+        """(forward MLP, backward MLP) when the HIP paths can take them (the rule of NeuralODE._hip_mlp), else None."""
+        from .utils import torch_wrapper
+        pair = []
+        for f in (self.net, self.score_net):
+            m = f.model if isinstance(f, torch_wrapper) else f
+            if not (isinstance(m, MLP) and m.time_varying):
+                return None
+            lins = m._linears()
+            if lins[-1].out_features + 1 != lins[0].in_features:
+                return None
+            pair.append(m)
+        return tuple(pair)
+
+    def sdeint(self, x0, t_span, reverse=False, generator=None, noise="philox", fused=None):
+        if self.sde_solver == "srk":
+            raise NotImplementedError("DSBMFlowSolver(sde_solver='srk'): sigma is a schedule sigma(t) here, and 'srk' is built "
+                                      "for constant diagonal noise only (the full SRI2W1 tableau is not built)")
+        if self.sigma is None:
+            raise ValueError("DSBMFlowSolver.sdeint needs sigma (a noise schedule or a number)")
+        self.nfe = 0
+        pair = self._hip_pair()
+        if pair is not None:
+            sde = DriftSDE(pair[1] if reverse else pair[0], sigma=self.sigma, reverse=reverse)
+            out = sdeint(sde, x0, t_span, method="euler", dt=self.dt, generator=generator, noise=noise, fused=fused)
+            self.last_path = sde.last_path
+            self.nfe = len(_grid(t_span, float(self.dt)))          # one drift evaluation per refined step
+            return out
+        self.last_path = "eager"
+        outer = self
+
+        class _S:
+            def f(self, t, y):
+                return outer.backward_sde_drift(1 - t, y) if reverse else outer.forward_sde_drift(t, y)
+
+            def g(self, t, y):
+                return outer.sigma(t) * torch.ones_like(y)
+        return sdeint(_S(), x0, t_span, method="euler", dt=self.dt, generator=generator, noise=noise)
+
+    @torch.no_grad()
+    def odeint(self, x0, t_span, fused=None):
+        from .ode import NeuralODE, _check_t_span
+        self.nfe = 0
+        pair = self._hip_pair()
+        if (pair is not None and self.ode_solver in _lib.ODE_SCHEME and x0.dim() == 2 and x0.dtype == torch.float32
+                and torch.cuda.is_available()):
+            dims = [[l.in_features for l in m._linears()] + [m._linears()[-1].out_features] for m in pair]
+            if dims[0] == dims[1] and x0.shape[1] == dims[0][-1]:
+                _check_t_span(torch.as_tensor(t_span, dtype=torch.float32).cpu())
+                self.last_path = "hip"
+                return self._odeint_hip(pair, x0, t_span, fused)
+        self.last_path = "eager"
+        node = NeuralODE(self.forward_ode_drift, solver=self.ode_solver, atol=self.atol, rtol=self.rtol, return_t_eval=False)
+        return node(x0, t_span)
+
+    def _odeint_hip(self, pair, x0, t_span, fused):
+        import ctypes
+
+        import numpy as np
+        lib = _lib.load()
+        dev = _lib.require_gpu()
+        Wf, bf, dims, keep_f = pair[0].hip_params(dev)
+        Wb, bb, _, keep_b = pair[1].hip_params(dev)
+        n = len(dims) - 1
+        xd = _lib.to_dev_f32(x0, dev)
+        B, d = xd.shape
+        ts = np.ascontiguousarray(torch.as_tensor(t_span, dtype=torch.float32).cpu().numpy())
+        n_t = ts.shape[0]
+        traj = torch.empty((n_t, B, d), dtype=torch.float32, device=dev)
+        ws = _lib.workspace(_lib.OP_ODE, B, max(dims[1:n]) if n > 1 else 1, d, dev)
+        nfe = ctypes.c_int(0)
+        if fused is False:
+            lib.cfm_ode_set_fused(0)
+        try:
+            rc = lib.cfm_ode_fixed_pair_mlp_f32(Wf, bf, Wb, bb, dims, n, ptr(xd), B, ts.ctypes.data_as(ctypes.c_void_p), n_t,
+                                                _lib.ODE_SCHEME[self.ode_solver], ptr(traj), ctypes.byref(nfe), ptr(ws),
+                                                stream_ptr())
+        finally:
+            if fused is False:
+                lib.cfm_ode_set_fused(1)
+        check(rc, "cfm_ode_fixed_pair_mlp_f32")
+        torch.cuda.current_stream().synchronize()          # `ts` (pageable) must outlive the copy
+        self.nfe = nfe.value
+        return traj.to(x0.device)
+
+    @torch.no_grad()
+    def resample_pairs(self, x0, x1, generator=None, noise="philox"):
+        """The outer-loop refresh of DSBM / iterative Markovian fitting (runner/src/models/cfm_module.py:1018-1033): the
+        forward SDE from ``x0[:B // 2]`` and the reverse SDE from ``x1[B // 2:]`` over ``t_span = (0, 1)``, the latter
+        flipped in time; returns ``[B, 2, *dim]`` with ``[:, 0]`` the time-0 end and ``[:, 1]`` the time-1 end of every
+        pair.  ``noise``: as ``sdeint``; a tensor ``[n_steps, B, *dim]`` is split by rows between the two solves.  A pure
+        composition of ``sdeint``."""
+        half = x0.shape[0] // 2
+        t_span = torch.linspace(0, 1, 2)
+        nf, nb = (noise[:, :half], noise[:, half:]) if torch.is_tensor(noise) else (noise, noise)
+        forward_traj = self.sdeint(x0[:half], t_span, generator=generator, noise=nf)
+        backward_traj = torch.flip(self.sdeint(x1[half:], t_span, reverse=True, generator=generator, noise=nb), (0,))
+        return torch.cat([forward_traj, backward_traj], dim=1).transpose(0, 1)

@@ -26,6 +26,10 @@ its launches) while the remaining layers' products still run; the compute stream
 (examples/2D_tutorials/SF2M_tutorial.ipynb cell 3, single-cell_example.ipynb, runner/src/models/cfm_module.py:896-909):
 a flow net and a score net of equal layer sizes under one optimizer, ``cfm_mlp_sf2m_step_f32`` — every launch of the
 regression step serving both nets — followed by one ``cfm_adam_step_f32`` over all parameters of both.
+
+``DSBMStep(forward_model, backward_model, optimizer)(t, xt, forward_target, backward_target, forward_scaling,
+backward_scaling)`` is the same driver for DSBM (runner/src/models/cfm_module.py:1215-1227): a forward and a backward drift
+net, each under a row-weighted MSE, ``cfm_mlp_dsbm_step_f32``.
 """
 import ctypes
 
@@ -188,20 +192,22 @@ class SF2MStep:
 
     MAX_LAYERS = 7      # cfm_mlp_sf2m_step_f32: the one final reduction holds the jobs of two 7-layer nets
 
+    _WHO, _FIRST, _SECOND = "SF2MStep", "flow", "score"      # how the refusals name the step and its two nets
+
     def __init__(self, model, score_model, optimizer, score_weight=1.0):
-        who = "SF2MStep"
-        self.net, self.score_net = _as_mlp(model, who, "the flow model"), _as_mlp(score_model, who, "the score model")
+        who, first, second = self._WHO, self._FIRST, self._SECOND
+        self.net, self.score_net = _as_mlp(model, who, f"the {first} model"), _as_mlp(score_model, who, f"the {second} model")
         flins, slins = self.net._linears(), self.score_net._linears()
         dims = [flins[0].in_features] + [l.out_features for l in flins]
         sdims = [slins[0].in_features] + [l.out_features for l in slins]
         if dims != sdims or bool(self.net.time_varying) != bool(self.score_net.time_varying):
-            raise TypeError(f"{who}: the nets' layer sizes differ (flow {dims}, score {sdims}): one launch serves both "
+            raise TypeError(f"{who}: the nets' layer sizes differ ({first} {dims}, {second} {sdims}): one launch serves both "
                             "nets only when their layers have equal sizes")
-        _need_fp32_gpu(who, ((flins, "the flow model"), (slins, "the score model")))
+        _need_fp32_gpu(who, ((flins, f"the {first} model"), (slins, f"the {second} model")))
         if slins[0].weight.device != flins[0].weight.device:
-            raise TypeError(f"{who}: the score model is not on the GPU of the flow model")
+            raise TypeError(f"{who}: the {second} model is not on the GPU of the {first} model")
         if self.net is self.score_net:
-            raise TypeError(f"{who}: the flow and the score model are the same module")
+            raise TypeError(f"{who}: the {first} and the {second} model are the same module")
         self.opt, self.score_weight = optimizer, float(score_weight)
         self.dims, self.n, self.dev = dims, len(flins), flins[0].weight.device
         self.lins = flins + slins                                     # flow first, score second: the order of every table
@@ -230,6 +236,18 @@ class SF2MStep:
             self.cd = (ctypes.c_int * (n + 1))(*d)
             self._B = B
 
+    def _tables(self):
+        """(W, b, dW, db): host tables of 2 n device pointers, the first net's layers first; a replaced .grad is put back"""
+        params = [q for l in self.lins for q in (l.weight, l.bias)]
+        for v, p in zip(self._gviews, params):
+            if p.grad is not v:
+                p.grad = v
+        N2 = 2 * self.n
+        return ((ctypes.c_void_p * N2)(*[l.weight.data_ptr() for l in self.lins]),
+                (ctypes.c_void_p * N2)(*[l.bias.data_ptr() for l in self.lins]),
+                (ctypes.c_void_p * N2)(*[self._gviews[2 * l].data_ptr() for l in range(N2)]),
+                (ctypes.c_void_p * N2)(*[self._gviews[2 * l + 1].data_ptr() for l in range(N2)]))
+
     def backward_only(self, t, xt, ut, eps, lambda_t):
         """forward + both losses + backward of both nets; returns ``[flow_loss, score_loss]`` (device tensor)"""
         if self.n > self.MAX_LAYERS:
@@ -253,15 +271,7 @@ class SF2MStep:
         if tv and tt.numel() != B:
             raise RuntimeError("SF2MStep: one time per row is required")
         self._buffers(B)
-        params = [q for l in self.lins for q in (l.weight, l.bias)]
-        for v, p in zip(self._gviews, params):
-            if p.grad is not v:
-                p.grad = v
-        N2 = 2 * n
-        Wp = (ctypes.c_void_p * N2)(*[l.weight.data_ptr() for l in self.lins])
-        bp = (ctypes.c_void_p * N2)(*[l.bias.data_ptr() for l in self.lins])
-        dWp = (ctypes.c_void_p * N2)(*[self._gviews[2 * l].data_ptr() for l in range(N2)])
-        dbp = (ctypes.c_void_p * N2)(*[self._gviews[2 * l + 1].data_ptr() for l in range(N2)])
+        Wp, bp, dWp, dbp = self._tables()
         check(lib.cfm_mlp_sf2m_step_f32(ptr(xt), ptr(tt), ptr(ut), ptr(eps), ptr(lam), Wp, bp, self.hp, self.zp, dWp, dbp,
                                         self.cd, n, B, ptr(self.g[0]), ptr(self.g[1]), ptr(self.losses),
                                         self.score_weight, ptr(self.ws), stream_ptr()),
@@ -278,5 +288,68 @@ class SF2MStep:
             raise NotImplementedError("SF2MStep is not built for data parallel runs (its gradients would be stepped on "
                                       "unreduced); use one process, or RegressionStep for the flow net alone")
         losses = self.backward_only(t, xt, ut, eps, lambda_t)
+        self.opt.step()
+        return losses
+
+
+class DSBMStep(SF2MStep):
+    """The DSBM (diffusion Schrodinger bridge matching) training step for a forward and a backward drift ``MLP`` of equal
+    layer sizes (runner/src/models/cfm_module.py:1215-1227; the batch is ``DSBMConditionalFlowMatcher``'s):
+
+        f = forward_model(torch.cat([xt, t[:, None]], dim=-1)); b = backward_model(torch.cat([xt, t[:, None]], dim=-1))
+        forward_loss = torch.mean(forward_scaling[:, None] * (f - forward_target) ** 2)
+        backward_loss = torch.mean(backward_scaling[:, None] * (b - backward_target) ** 2)
+        (forward_loss + backward_loss).backward(); optimizer.step()
+
+    ``step(t, xt, forward_target, backward_target, forward_scaling, backward_scaling)`` returns the device tensor
+    ``[forward_loss, backward_loss]`` (overwritten by the next call).  One ``cfm_mlp_dsbm_step_f32``: the two-net driver of
+    ``SF2MStep`` with a row-weighted loss in the last layer's epilogue, the launch count of one regression step.  The
+    reference raises "Loss Not Finite" on a non-finite loss (run:1224-1225); that check reads the loss on the host, a
+    synchronisation the step does not make: it stays with the caller (``torch.isfinite(losses).all()`` when wanted)."""
+
+    _WHO, _FIRST, _SECOND = "DSBMStep", "forward", "backward"
+
+    def __init__(self, forward_model, backward_model, optimizer):
+        n = len(_as_mlp(forward_model, self._WHO, "the forward model")._linears())
+        if n > self.MAX_LAYERS:      # (refused here, not at the first step: nothing about it depends on the batch)
+            raise TypeError(f"DSBMStep: the nets have {n} Linear layers; the fused step takes at most "
+                            f"{self.MAX_LAYERS} (two nets' reduction jobs fill its one table)")
+        super().__init__(forward_model, backward_model, optimizer, score_weight=1.0)
+        self.backward_net = self.score_net
+
+    def backward_only(self, t, xt, forward_target, backward_target, forward_scaling, backward_scaling):
+        """forward + both losses + backward of both nets; returns ``[forward_loss, backward_loss]`` (device tensor)"""
+        lib = _lib.load()
+        xt = xt.detach().reshape(xt.shape[0], -1)
+        B, n = xt.shape[0], self.n
+        ft = forward_target.detach().reshape(forward_target.shape[0], -1)
+        bt = backward_target.detach().reshape(backward_target.shape[0], -1)
+        tv = self.net.time_varying
+        if xt.shape[1] != self.dims[0] - int(bool(tv)) or ft.shape != (B, self.dims[n]) or bt.shape != ft.shape:
+            raise RuntimeError(f"DSBMStep: xt has shape {tuple(xt.shape)}, the targets {tuple(ft.shape)} and {tuple(bt.shape)}; "
+                               f"the nets map {self.dims[0] - int(bool(tv))} (+ time) -> {self.dims[n]}")
+        if forward_scaling.numel() != B or backward_scaling.numel() != B:
+            raise RuntimeError(f"DSBMStep: the scalings have {forward_scaling.numel()} and {backward_scaling.numel()} values "
+                               f"for {B} rows (one per row is required)")
+        xt = _lib.to_dev_f32(xt, self.dev); ft = _lib.to_dev_f32(ft, self.dev); bt = _lib.to_dev_f32(bt, self.dev)
+        wf = _lib.to_dev_f32(forward_scaling.detach().reshape(-1), self.dev)
+        wb = _lib.to_dev_f32(backward_scaling.detach().reshape(-1), self.dev)
+        tt = _lib.to_dev_f32(t.detach().reshape(-1), self.dev) if tv else None
+        if tv and tt.numel() != B:
+            raise RuntimeError("DSBMStep: one time per row is required")
+        self._buffers(B)
+        Wp, bp, dWp, dbp = self._tables()
+        check(lib.cfm_mlp_dsbm_step_f32(ptr(xt), ptr(tt), ptr(ft), ptr(bt), ptr(wf), ptr(wb), Wp, bp, self.hp, self.zp, dWp, dbp,
+                                        self.cd, n, B, ptr(self.g[0]), ptr(self.g[1]), ptr(self.losses), ptr(self.ws),
+                                        stream_ptr()),
+              "cfm_mlp_dsbm_step_f32")
+        return self.losses
+
+    def __call__(self, t, xt, forward_target, backward_target, forward_scaling, backward_scaling):
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise NotImplementedError("DSBMStep is not built for data parallel runs (its gradients would be stepped on "
+                                      "unreduced); use one process")
+        losses = self.backward_only(t, xt, forward_target, backward_target, forward_scaling, backward_scaling)
         self.opt.step()
         return losses

@@ -308,6 +308,18 @@ int cfm_sample_xt_ut_sched_f32(const float* x0, const float* x1, const int64_t* 
                                const float* xt_in, int B, int d, float* xt, float* ut,
                                void* stream);
 
+/* K7+K8 (DSBM) — the scheduled bridge's x_t with the two drift targets of diffusion Schrodinger bridge matching: fused
+ * gather + sample + both targets, three outputs in one launch.  Replaces x0[i], x1[j] and the eager chain of
+ *   runner/src/models/cfm_module.py:834-841 (mu_t, sigma_t), :1187-1200 (x_t, forward and backward target).
+ * coef [B,4] (16-byte aligned, else CFM_EALIGN), per row and evaluated by the caller's tensor library on t's device:
+ *   r = F(t)/F(1),  sigma_t,  cf = g sqrt(t / (1 - t + 1e-6)),  cb = g sqrt((1 - t) / (t + 1e-6)).
+ * Separately rounded ops, no contraction, in this order:
+ *   dx = x1 - x0;  mu = x0 + dx r;  xt = mu + sigma_t eps;  ft = dx - cf eps;  bt = (x0 - x1) - cb eps.
+ * i, j as for cfm_sample_xt_ut_f32 (NULL: identity); eps, xt, ft, bt [B,d], all required. */
+int cfm_sample_dsbm_f32(const float* x0, const float* x1, const int64_t* i, const int64_t* j,
+                        const float* coef, const float* eps, int B, int d, float* xt, float* ft,
+                        float* bt, void* stream);
+
 /* Row gather  out[b,:] = src[idx[b],:]  (labels y0[i], y1[j]; :215-218).
  * elem_bytes = bytes per row. */
 int cfm_gather_rows(const void* src, const int64_t* idx, int n, size_t row_bytes,
@@ -420,6 +432,23 @@ int cfm_mlp_sf2m_step_f32(const float* xt, const float* t, const float* ut, cons
                           const float* const* W, const float* const* b, float* const* hidden, float* const* preact,
                           float* const* dW, float* const* db, const int* dims, int n_layers, int B,
                           float* g_flow, float* g_score, float* losses, float score_weight, void* ws, void* stream);
+/* One DSBM training step — a forward and a backward drift net of EQUAL layer sizes on one bridge batch, everything but
+ * the optimizer update, in the launch count of ONE cfm_mlp_regression_step_f32 (the two-net driver of
+ * cfm_mlp_sf2m_step_f32 with a row-weighted loss epilogue on both nets):
+ *     f = fwd([xt, t]);  b = bwd([xt, t])
+ *     losses[0] = mean(wf[:, None] * (f - ft)^2);  losses[1] = mean(wb[:, None] * (b - bt)^2)
+ *     dW, db = d (losses[0] + losses[1]) / d parameters
+ * Replaces runner/src/models/cfm_module.py:1203-1227 (DSBMLitModule.step: both nets on [xt, t], the two row-scaled
+ * MSEs, their sum's backward).  The reference's "Loss Not Finite" check needs a host read of the loss: the caller's.
+ * xt, t, dims, n_layers, B as in cfm_mlp_regression_step_f32; ft, bt [B, dims[n_layers]]; wf, wb [B] (the matcher's
+ * forward_scaling, backward_scaling).  W, b, dW, db, hidden, preact: HOST tables as in cfm_mlp_sf2m_step_f32, the
+ * forward net's layers first.  g_fwd, g_bwd receive d loss / d f, d loss / d b: ((f - ft) * 2 / (B N)) * wf.  With
+ * wf = wb = 1 each net's loss and gradients are the bits of cfm_mlp_regression_step_f32 on its own target.
+ * Deterministic.  Limits and ws as for cfm_mlp_sf2m_step_f32. */
+int cfm_mlp_dsbm_step_f32(const float* xt, const float* t, const float* ft, const float* bt, const float* wf,
+                          const float* wb, const float* const* W, const float* const* b, float* const* hidden,
+                          float* const* preact, float* const* dW, float* const* db, const int* dims, int n_layers,
+                          int B, float* g_fwd, float* g_bwd, float* losses, void* ws, void* stream);
 /* One torch.optim.Adam step (amsgrad=False, maximize=False) on n_tensors fp32 tensors in ONE launch.
  * table: DEVICE array of n_tensors records {float* param; const float* grad; float* exp_avg;
  * float* exp_avg_sq; uint64 numel} (40 bytes each).  step >= 1 is the step count AFTER this update
@@ -514,6 +543,19 @@ int cfm_ode_adaptive_mlp_f32(const float* const* W, const float* const* b, const
 int cfm_ode_fixed_mlp_f32(const float* const* W, const float* const* b, const int* dims,
                           int n_layers, const float* x0, int B, const float* t_span,
                           int n_t, int scheme, float* traj, int* nfe, void* ws, void* stream);
+/* DSBM sampling — the probability-flow ODE of a forward and a backward drift net of EQUAL layer sizes,
+ *     dx/dt = (f(t, x) - b(t, x)) / 2,
+ * on the fixed-step schemes.  Replaces NeuralODE(forward_ode_drift).trajectory of the reference's DSBMFlowSolver:
+ * runner/src/models/components/solver.py:259-263.  Every stage derivative is k = 0.5f * (f - b) (one rounded
+ * subtraction, an exact halving); stages, steps, t_span (either direction) and nfe (one evaluation of the PAIR per
+ * stage) as cfm_ode_fixed_mlp_f32.  4-layer nets of widths <= 64 run the whole solve in one launch with both nets'
+ * weights in LDS; any other size, or with the fused small-field path disabled (cfm_ode_set_fused(0)), the layer
+ * driver steps it (two forward passes, the halved difference and the stage combine per stage) — the same bits.
+ * ws: cfm_workspace_bytes(CFM_OP_ODE, B, max hidden width, d). */
+int cfm_ode_fixed_pair_mlp_f32(const float* const* Wf, const float* const* bf, const float* const* Wb,
+                               const float* const* bb, const int* dims, int n_layers, const float* x0, int B,
+                               const float* t_span, int n_t, int scheme, float* traj, int* nfe, void* ws,
+                               void* stream);
 
 /* K12 — continuous normalising flow of an MLP field v = MLP([x, t]) (4 linear layers, widths <= 64, dims[0] = d + 1).
  * mode 0: div = tr(dv/dx) (exact); mode 1: div = eps^T (dv/dx) eps (Hutchinson; eps device [B,d], fixed for a solve).
