@@ -10,6 +10,7 @@ import os
 import subprocess
 import threading
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -258,3 +259,29 @@ def to_dev_f32(x, device=None):
     """Contiguous fp32 copy/view of `x` on the GPU."""
     device = device or require_gpu()
     return x.detach().to(device=device, dtype=torch.float32).contiguous()
+
+
+def param_tables(params, device):
+    """(Ws, bs, W_ptrs, b_ptrs) of a flat (W_0, b_0, W_1, b_1, ...) parameter sequence: contiguous fp32 device tensors and
+    their pointer tables for the C ABI.  The tables hold raw addresses: keep Ws and bs referenced for as long as a call
+    may read them."""
+    Ws = [to_dev_f32(p, device) for p in params[0::2]]
+    bs = [to_dev_f32(p, device) for p in params[1::2]]
+    n = len(Ws)
+    return Ws, bs, (ctypes.c_void_p * n)(*[w.data_ptr() for w in Ws]), (ctypes.c_void_p * n)(*[b.data_ptr() for b in bs])
+
+
+def grad_tables(Ws, bs):
+    """(dWs, dbs, dW_ptrs, db_ptrs): uninitialised gradient tensors shaped like Ws and bs, and their pointer tables."""
+    dWs = [torch.empty_like(w) for w in Ws]
+    dbs = [torch.empty_like(b) for b in bs]
+    n = len(Ws)
+    return dWs, dbs, (ctypes.c_void_p * n)(*[w.data_ptr() for w in dWs]), (ctypes.c_void_p * n)(*[b.data_ptr() for b in dbs])
+
+
+def t_span_f32(t_span):
+    """(ts, pointer, n_t): t_span as a contiguous float32 numpy array on the host.  The pointer is into ts: keep ts
+    referenced until the call that reads it has returned (and, where the entry copies it asynchronously, until the
+    stream has been synchronised)."""
+    ts = np.ascontiguousarray(torch.as_tensor(t_span, dtype=torch.float32).cpu().numpy())
+    return ts, ts.ctypes.data_as(ctypes.c_void_p), ts.shape[0]

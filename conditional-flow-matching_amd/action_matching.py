@@ -20,10 +20,7 @@ import torch
 from . import _lib
 from ._lib import ptr, stream_ptr
 from .models import MLP, GradModel, hip_action
-
-
-class _Declined(Exception):
-    """cfm_action_matching_grad_f32 answered CFM_EINVAL inside the envelope: the fused small-field path is switched off."""
+from .ode import _Declined
 
 
 class _ActionMatchingFunction(torch.autograd.Function):
@@ -110,9 +107,8 @@ def action_matching_loss(action, x0, x1, t, xt=None):
         given = (x0, x1, t) if xt is None else (x0, x1, t, xt)
         if (all(v.dtype == torch.float32 and v.device == x0.device for v in given)
                 and all(p.device == x0.device for p in params)):
-            dims = [lins[0].in_features] + [l.out_features for l in lins]
             try:
-                loss = _ActionMatchingFunction.apply(x0, x1, xt, t, dims, *params)
+                loss = _ActionMatchingFunction.apply(x0, x1, xt, t, m.dims(), *params)
                 action_matching_loss.last_path = "hip"
                 return loss
             except _Declined:

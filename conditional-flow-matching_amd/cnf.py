@@ -32,7 +32,6 @@ Hutchinson probes are fixed for a whole solve (FFJORD's convention, model-compar
 slot): ``cnf.noise`` if set, else one draw per ``NeuralODE.trajectory`` call, kept as
 ``cnf.last_noise``.  The ML-CNF tutorial redraws the probe at every evaluation; that is not replicated.
 """
-import ctypes
 import math
 
 import torch
@@ -40,6 +39,7 @@ import torch
 from . import _lib
 from ._lib import ptr, stream_ptr
 from .models import MLP, GradModel
+from .ode import _check_t_span, _Declined, _solve_backward, _solve_forward
 from .utils import torch_wrapper
 
 ESTIMATORS = ("exact", "hutch_gaussian", "hutch_rademacher")
@@ -197,9 +197,9 @@ def log_likelihood(model, x, t_span=None, solver="dopri5", atol=1e-5, rtol=1e-5,
     return (out, z) if return_z else out
 
 
-class _Declined(Exception):
-    """The forward solve answered CFM_EINVAL inside the envelope: the fused small-field path is switched off, or the
-    grid has more points than the solve's workspace holds (n_t > 3 B (1 + d))."""
+def _probe_args(ed):
+    """(mode, eps) of the augmented entries: 0 / NULL for the exact trace, 1 / the probe for a Hutchinson estimate."""
+    return 0 if ed is None else 1, ptr(ed)
 
 
 class _CNFEulerFunction(torch.autograd.Function):
@@ -207,57 +207,15 @@ class _CNFEulerFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x_aug, ts, eps, dims, *params):
-        lib = _lib.load()
-        dev = x_aug.device
-        Ws = [_lib.to_dev_f32(p, dev) for p in params[0::2]]
-        bs = [_lib.to_dev_f32(p, dev) for p in params[1::2]]
-        Wp = (ctypes.c_void_p * 4)(*[w.data_ptr() for w in Ws])
-        bp = (ctypes.c_void_p * 4)(*[b.data_ptr() for b in bs])
-        cdims = (ctypes.c_int * 5)(*dims)
-        xd = _lib.to_dev_f32(x_aug, dev)
-        B, D = xd.shape
-        n_t = ts.shape[0]
-        traj = torch.empty((n_t, B, D), dtype=torch.float32, device=dev)
-        ws = _lib.workspace(_lib.OP_ODE, B, max(dims[1:4]), D, dev)
-        ed = _lib.to_dev_f32(eps, dev) if eps is not None else None
-        nfe = ctypes.c_int(0)
-        rc = lib.cfm_ode_fixed_cnf_mlp_f32(Wp, bp, cdims, 4, ptr(xd), B, ts.ctypes.data_as(ctypes.c_void_p), n_t,
-                                           0 if eps is None else 1, ptr(ed), _lib.ODE_SCHEME["euler"], ptr(traj),
-                                           ctypes.byref(nfe), ptr(ws), stream_ptr())
-        if rc == -1:
-            raise _Declined()
-        _lib.check(rc, "cfm_ode_fixed_cnf_mlp_f32")
-        ctx.ts, ctx.dims, ctx.eps = ts, dims, ed
-        ctx.save_for_backward(traj, *params)
+        ctx.eps = _lib.to_dev_f32(eps, x_aug.device) if eps is not None else None
+        traj = _solve_forward(ctx, "cfm_ode_fixed_cnf_mlp_f32", x_aug, ts, dims, params,
+                              (*_probe_args(ctx.eps), _lib.ODE_SCHEME["euler"]), declines=True)
         return traj[-1].clone()
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        lib = _lib.load()
-        traj, *params = ctx.saved_tensors
-        dev = traj.device
-        Ws = [_lib.to_dev_f32(p, dev) for p in params[0::2]]
-        bs = [_lib.to_dev_f32(p, dev) for p in params[1::2]]
-        dWs = [torch.empty_like(w) for w in Ws]
-        dbs = [torch.empty_like(b) for b in bs]
-        Wp = (ctypes.c_void_p * 4)(*[w.data_ptr() for w in Ws])
-        bp = (ctypes.c_void_p * 4)(*[b.data_ptr() for b in bs])
-        dWp = (ctypes.c_void_p * 4)(*[w.data_ptr() for w in dWs])
-        dbp = (ctypes.c_void_p * 4)(*[b.data_ptr() for b in dbs])
-        cdims = (ctypes.c_int * 5)(*ctx.dims)
-        n_t, B, D = traj.shape
-        gd = _lib.to_dev_f32(g, dev)
-        g0 = torch.empty((B, D), dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
-        ws = _lib.workspace(_lib.OP_CNF_GRAD, B, n_t, 0, dev)
-        rc = lib.cfm_cnf_euler_grad_f32(Wp, bp, cdims, 4, ptr(traj), B, ctx.ts.ctypes.data_as(ctypes.c_void_p), n_t,
-                                        0 if ctx.eps is None else 1, ptr(ctx.eps), ptr(gd), dWp, dbp, ptr(g0), ptr(ws),
-                                        stream_ptr())
-        _lib.check(rc, "cfm_cnf_euler_grad_f32")
-        grads = [None] * len(params)
-        grads[0::2] = dWs
-        grads[1::2] = dbs
-        return (g0, None, None, None, *grads)
+        return _solve_backward(ctx, "cfm_cnf_euler_grad_f32", _lib.OP_CNF_GRAD, g, _probe_args(ctx.eps), 3)
 
 
 class DifferentiableCNF(CNF):
@@ -282,23 +240,26 @@ class DifferentiableCNF(CNF):
         self.last_path = None
 
     def solve(self, x_aug, t_span):
-        from .ode import _check_t_span
         if x_aug.dim() != 2 or x_aug.shape[1] < 2:
             raise ValueError(f"the state is [B, 1 + d]; got {tuple(x_aug.shape)}")
+        return self._solve(x_aug, t_span, 1, _CNFEulerFunction, True, ())
+
+    def _solve(self, x_aug, t_span, a, function, fused_ok, extra):
+        """The solve of a checked state [B, a + d] whose first ``a`` columns are augmented: ``function`` (one of the
+        autograd.Function pairs above, called with ``extra`` between dims and the parameters) where the HIP kernels take
+        it and ``fused_ok`` holds, the generic recurrence otherwise."""
         ts = torch.as_tensor(t_span).detach().to(dtype=x_aug.dtype).cpu()
         _check_t_span(ts)
-        y = x_aug[:, 1:]
+        y = x_aug[:, a:]
         eps = None
         if self.estimator != "exact":
             eps = self.checked_noise(y) if self.noise is not None else self.draw_noise(y)
         m = self.hip_mlp(y.shape[1])
-        if (m is not None and x_aug.is_cuda and x_aug.dtype == torch.float32
+        if (m is not None and x_aug.is_cuda and x_aug.dtype == torch.float32 and fused_ok
                 and all(p.dtype == torch.float32 and p.device == x_aug.device for p in m.parameters())):
-            lins = m._linears()
-            params = [p for l in lins for p in (l.weight, l.bias)]
-            dims = [lins[0].in_features] + [l.out_features for l in lins]
+            params = [p for l in m._linears() for p in (l.weight, l.bias)]
             try:
-                out = _CNFEulerFunction.apply(x_aug, ts.numpy().copy(), eps, dims, *params)
+                out = function.apply(x_aug, ts.numpy().copy(), eps, m.dims(), *extra, *params)
                 self.last_path = "hip"
                 return out
             except _Declined:
@@ -351,58 +312,19 @@ class _CNFRegEulerFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x_aug, ts, eps, dims, mask, *params):
-        lib = _lib.load()
         dev = x_aug.device
-        Ws = [_lib.to_dev_f32(p, dev) for p in params[0::2]]
-        bs = [_lib.to_dev_f32(p, dev) for p in params[1::2]]
-        Wp = (ctypes.c_void_p * 4)(*[w.data_ptr() for w in Ws])
-        bp = (ctypes.c_void_p * 4)(*[b.data_ptr() for b in bs])
-        cdims = (ctypes.c_int * 5)(*dims)
-        xd = _lib.to_dev_f32(x_aug, dev)
-        B, D = xd.shape
-        n_t = ts.shape[0]
-        traj = torch.empty((n_t, B, D), dtype=torch.float32, device=dev)
-        jsq = torch.empty((max(n_t - 1, 1), B), dtype=torch.float32, device=dev) if mask & 2 else None
-        ws = _lib.workspace(_lib.OP_ODE, B, max(dims[1:4]), D, dev)
-        ed = _lib.to_dev_f32(eps, dev) if eps is not None else None
-        nfe = ctypes.c_int(0)
-        rc = lib.cfm_ode_euler_cnf_reg_mlp_f32(Wp, bp, cdims, 4, ptr(xd), B, ts.ctypes.data_as(ctypes.c_void_p), n_t,
-                                               0 if eps is None else 1, ptr(ed), mask, ptr(traj), ptr(jsq),
-                                               ctypes.byref(nfe), ptr(ws), stream_ptr())
-        if rc == -1:
-            raise _Declined()
-        _lib.check(rc, "cfm_ode_euler_cnf_reg_mlp_f32")
-        ctx.ts, ctx.dims, ctx.eps, ctx.mask, ctx.jsq = ts, dims, ed, mask, jsq
-        ctx.save_for_backward(traj, *params)
+        ctx.eps = _lib.to_dev_f32(eps, dev) if eps is not None else None
+        ctx.mask = mask
+        ctx.jsq = torch.empty((max(ts.shape[0] - 1, 1), x_aug.shape[0]), dtype=torch.float32, device=dev) if mask & 2 else None
+        traj = _solve_forward(ctx, "cfm_ode_euler_cnf_reg_mlp_f32", x_aug, ts, dims, params, (*_probe_args(ctx.eps), mask),
+                              after=(ptr(ctx.jsq),), declines=True)
         return traj[-1].clone()
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        lib = _lib.load()
-        traj, *params = ctx.saved_tensors
-        dev = traj.device
-        Ws = [_lib.to_dev_f32(p, dev) for p in params[0::2]]
-        bs = [_lib.to_dev_f32(p, dev) for p in params[1::2]]
-        dWs = [torch.empty_like(w) for w in Ws]
-        dbs = [torch.empty_like(b) for b in bs]
-        Wp = (ctypes.c_void_p * 4)(*[w.data_ptr() for w in Ws])
-        bp = (ctypes.c_void_p * 4)(*[b.data_ptr() for b in bs])
-        dWp = (ctypes.c_void_p * 4)(*[w.data_ptr() for w in dWs])
-        dbp = (ctypes.c_void_p * 4)(*[b.data_ptr() for b in dbs])
-        cdims = (ctypes.c_int * 5)(*ctx.dims)
-        n_t, B, D = traj.shape
-        gd = _lib.to_dev_f32(g, dev)
-        g0 = torch.empty((B, D), dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
-        ws = _lib.workspace(_lib.OP_CNF_GRAD, B, n_t, 0, dev)
-        rc = lib.cfm_cnf_reg_euler_grad_f32(Wp, bp, cdims, 4, ptr(traj), B, ctx.ts.ctypes.data_as(ctypes.c_void_p), n_t,
-                                            0 if ctx.eps is None else 1, ptr(ctx.eps), ctx.mask, ptr(ctx.jsq), ptr(gd),
-                                            dWp, dbp, ptr(g0), ptr(ws), stream_ptr())
-        _lib.check(rc, "cfm_cnf_reg_euler_grad_f32")
-        grads = [None] * len(params)
-        grads[0::2] = dWs
-        grads[1::2] = dbs
-        return (g0, None, None, None, None, *grads)
+        return _solve_backward(ctx, "cfm_cnf_reg_euler_grad_f32", _lib.OP_CNF_GRAD, g,
+                               (*_probe_args(ctx.eps), ctx.mask, ptr(ctx.jsq)), 4)
 
 
 class RegularizedCNF(DifferentiableCNF):
@@ -431,33 +353,13 @@ class RegularizedCNF(DifferentiableCNF):
         self.aug_dims = len(self.names)
 
     def solve(self, x_aug, t_span):
-        from .ode import _check_t_span
         if self.reg_mask == 0:
             return super().solve(x_aug, t_span)
         a = self.aug_dims
         if x_aug.dim() != 2 or x_aug.shape[1] < a + 1:
             raise ValueError(f"the state is [B, {a} + d] ({', '.join(self.names)}, x); got {tuple(x_aug.shape)}")
-        ts = torch.as_tensor(t_span).detach().to(dtype=x_aug.dtype).cpu()
-        _check_t_span(ts)
-        y = x_aug[:, a:]
-        eps = None
-        if self.estimator != "exact":
-            eps = self.checked_noise(y) if self.noise is not None else self.draw_noise(y)
-        m = self.hip_mlp(y.shape[1])
-        if (m is not None and x_aug.is_cuda and x_aug.dtype == torch.float32
-                and (self.estimator == "exact" or self.reg_mask == 1)
-                and all(p.dtype == torch.float32 and p.device == x_aug.device for p in m.parameters())):
-            lins = m._linears()
-            params = [p for l in lins for p in (l.weight, l.bias)]
-            dims = [lins[0].in_features] + [l.out_features for l in lins]
-            try:
-                out = _CNFRegEulerFunction.apply(x_aug, ts.numpy().copy(), eps, dims, self.reg_mask, *params)
-                self.last_path = "hip"
-                return out
-            except _Declined:
-                pass
-        self.last_path = "generic"
-        return self._solve_generic(x_aug, ts, eps)
+        return self._solve(x_aug, t_span, a, _CNFRegEulerFunction, self.estimator == "exact" or self.reg_mask == 1,
+                           (self.reg_mask,))
 
     def _solve_generic(self, x_aug, ts, eps):
         """The recurrence in differentiable torch ops, as the parent's (through the module graph, parameters cast to the

@@ -13,6 +13,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr, stream_ptr
+from .utils import torch_wrapper
 
 
 class _MLPTrainFunction(torch.autograd.Function):
@@ -77,8 +78,7 @@ class _MLPTrainFunction(torch.autograd.Function):
         if tuple(dout.shape) != (acts[0].shape[0], dims[n]):
             raise RuntimeError(f"MLP backward: upstream gradient has shape {tuple(dout.shape)}, expected {(acts[0].shape[0], dims[n])}")
         dout = dout.contiguous().float()
-        dW = [torch.empty_like(w) for w in Ws]
-        db = [torch.empty(w.shape[0], dtype=torch.float32, device=dev) for w in Ws]
+        dW, db, dWp, dbp = _lib.grad_tables(Ws, [params[2 * l + 1].detach() for l in range(n)])
         dx = torch.empty_like(acts[0]) if ctx.needs_input_grad[0] else None
         maxw = max(dims)
         maxp = max(dims[l] * dims[l + 1] for l in range(n))
@@ -86,8 +86,6 @@ class _MLPTrainFunction(torch.autograd.Function):
         ap = (ctypes.c_void_p * n)(*[a.data_ptr() for a in acts])
         zp = (ctypes.c_void_p * n)(*([0] + [z.data_ptr() for z in preact]))
         Wp = (ctypes.c_void_p * n)(*[w.data_ptr() for w in Ws])
-        dWp = (ctypes.c_void_p * n)(*[g.data_ptr() for g in dW])
-        dbp = (ctypes.c_void_p * n)(*[g.data_ptr() for g in db])
         cd = (ctypes.c_int * (n + 1))(*dims)
         check(lib.cfm_mlp_backward_f32(ap, zp, Wp, cd, n, B, ptr(dout), dWp, dbp, ptr(dx), ptr(ws), stream_ptr()),
               "cfm_mlp_backward_f32")
@@ -116,17 +114,17 @@ class MLP(torch.nn.Module):
     def _linears(self):
         return [m for m in self.net if isinstance(m, torch.nn.Linear)]
 
+    def dims(self):
+        """[in, h_1, ..., out]: the layer widths as a Python list."""
+        lins = self._linears()
+        return [lins[0].in_features] + [l.out_features for l in lins]
+
     def hip_params(self, device=None):
         """(W_ptrs, b_ptrs, dims, keepalive) as ctypes arrays for the C ABI."""
         dev = device or _lib.require_gpu()
-        lins = self._linears()
-        Ws = [_lib.to_dev_f32(l.weight, dev) for l in lins]
-        bs = [_lib.to_dev_f32(l.bias, dev) for l in lins]
-        n = len(lins)
-        Wp = (ctypes.c_void_p * n)(*[w.data_ptr() for w in Ws])
-        bp = (ctypes.c_void_p * n)(*[b.data_ptr() for b in bs])
-        dims = (ctypes.c_int * (n + 1))(*([lins[0].in_features] + [l.out_features for l in lins]))
-        return Wp, bp, dims, (Ws, bs)
+        dims = self.dims()
+        Ws, bs, Wp, bp = _lib.param_tables([p for l in self._linears() for p in (l.weight, l.bias)], dev)
+        return Wp, bp, (ctypes.c_int * len(dims))(*dims), (Ws, bs)
 
     @torch.no_grad()
     def forward_hip(self, x, t=None):
@@ -193,6 +191,22 @@ class MLP(torch.nn.Module):
             lead = x.shape[:-1]
             return self.forward_hip(x.reshape(-1, x.shape[-1])).reshape(*lead, -1).to(x.dtype)
         return self.forward_hip(x).to(x.dtype)
+
+
+def time_mlp(f, bare=False):
+    """The time-varying ``MLP`` that ``f`` wraps in a ``torch_wrapper`` (bare: or is) when its output width + 1 equals its
+    input width — a field x' = v([x, t]) that the HIP solvers take apart — else None."""
+    if isinstance(f, torch_wrapper):
+        m = f.model
+    elif bare:
+        m = f
+    else:
+        return None
+    if isinstance(m, MLP) and m.time_varying:
+        dims = m.dims()
+        if dims[-1] + 1 == dims[0]:
+            return m
+    return None
 
 
 def hip_action(a, d):

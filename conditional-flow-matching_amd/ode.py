@@ -33,7 +33,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr, stream_ptr
-from .models import MLP, GradModel
+from .models import GradModel, time_mlp
 from .utils import torch_wrapper
 
 # Adaptive pairs: c, a (rows 2..7; row 7 = b, so stage 7's state is the solution), e (x_err = dt * sum e_i k_i).
@@ -87,6 +87,51 @@ def _check_t_span(ts):
     raise ValueError("t_span must be strictly increasing or strictly decreasing")
 
 
+def _solve_hip(kind, m, x, t_span, solver, atol=None, rtol=None, probe=None, second=None, fused=None):
+    """One call of cfm_ode_{fixed,adaptive}_<kind>_f32 (fixed for the ODE_SCHEME solvers, adaptive for the ODE_TABLEAU ones)
+    on the net ``m``: parameters, state and ``t_span`` marshalled, trajectory and workspace allocated.
+
+    probe: ``(eps,)`` for the augmented (CNF) entries, which take ``(mode, eps)`` after the grid: eps None is the exact
+    trace.  second: the other net of the pair entries, its tables after the first net's.  fused=False switches the
+    one-launch form off around the call.  Returns ``(rc, entry name, traj [n_t, B, width], nfe, n_steps, ts)`` and checks
+    nothing: which ``rc`` is a decline is the caller's rule.  ``ts`` is the pageable host grid the entry read: a caller
+    whose entry copies it asynchronously keeps it until it has synchronised the stream."""
+    lib = _lib.load()
+    dev = _lib.require_gpu()
+    Wp, bp, dims, keep = m.hip_params(dev)
+    tables = (Wp, bp)
+    if second is not None:
+        Wb, bb, _, keep_b = second.hip_params(dev)
+        tables += (Wb, bb)
+    n = len(dims) - 1
+    xd = _lib.to_dev_f32(x, dev)
+    B, d = xd.shape
+    ts, tsp, n_t = _lib.t_span_f32(t_span)
+    traj = torch.empty((n_t, B, d), dtype=torch.float32, device=dev)
+    ws = _lib.workspace(_lib.OP_ODE, B, max(dims[1:n]) if n > 1 else 1, d, dev)
+    args = [*tables, dims, n, ptr(xd), B, tsp, n_t]
+    if probe is not None:
+        ed = _lib.to_dev_f32(probe[0], dev) if probe[0] is not None else None
+        args += [0 if ed is None else 1, ptr(ed)]
+    nfe = ctypes.c_int(0)
+    steps = ctypes.c_int(0)
+    if solver in _lib.ODE_SCHEME:
+        what = f"cfm_ode_fixed_{kind}_f32"
+        steps.value = n_t - 1
+        args += [_lib.ODE_SCHEME[solver], ptr(traj), ctypes.byref(nfe), ptr(ws), stream_ptr()]
+    else:
+        what = f"cfm_ode_adaptive_{kind}_f32"
+        args += [_lib.ODE_TABLEAU[solver], atol, rtol, ptr(traj), ctypes.byref(steps), ctypes.byref(nfe), ptr(ws), stream_ptr()]
+    if fused is False:
+        lib.cfm_ode_set_fused(0)
+    try:
+        rc = getattr(lib, what)(*args)
+    finally:
+        if fused is False:
+            lib.cfm_ode_set_fused(1)
+    return rc, what, traj, nfe.value, steps.value, ts
+
+
 class NeuralODE(torch.nn.Module):
     def __init__(self, vector_field, solver="dopri5", order=1, atol=1e-3, rtol=1e-3,
                  sensitivity="autograd", return_t_eval=True, **kwargs):
@@ -103,13 +148,7 @@ class NeuralODE(torch.nn.Module):
 
     # ---- dispatch ----
     def _hip_mlp(self):
-        vf = self.vf
-        if isinstance(vf, torch_wrapper) and isinstance(vf.model, MLP) and vf.model.time_varying:
-            m = vf.model
-            lins = m._linears()
-            if lins[-1].out_features + 1 == lins[0].in_features:
-                return m
-        return None
+        return time_mlp(self.vf)
 
     def _hip_grad(self, x):
         """The action MLP of torch_wrapper(GradModel(mlp)) when the gradient-field drivers take the solve, else None."""
@@ -167,36 +206,15 @@ class NeuralODE(torch.nn.Module):
         """Augmented solve in cfm_ode_{fixed,adaptive}_cnf_mlp_f32 (grad: m is the action net of a GradModel, fixed
         steps, cfm_ode_fixed_cnf_gradmlp_f32); None when the library declines it (CFM_EINVAL: the fused small-field
         path is switched off) so the caller steps it generically."""
-        lib = _lib.load()
-        dev = _lib.require_gpu()
-        Wp, bp, dims, keep = m.hip_params(dev)
-        xd = _lib.to_dev_f32(x, dev)
-        B, D = xd.shape
-        ts = np.ascontiguousarray(torch.as_tensor(t_span, dtype=torch.float32).cpu().numpy())
-        n_t = ts.shape[0]
-        traj = torch.empty((n_t, B, D), dtype=torch.float32, device=dev)
-        ws = _lib.workspace(_lib.OP_ODE, B, max(dims[1:4]), D, dev)
-        mode = 0 if eps is None else 1
+        B, D = x.shape
         if eps is not None and tuple(eps.shape) != (B, D - 1):
             raise ValueError(f"probe of shape {tuple(eps.shape)} for a state of {B} rows and {D - 1} columns")
-        ed = _lib.to_dev_f32(eps, dev) if eps is not None else None
-        nfe = ctypes.c_int(0)
-        steps = ctypes.c_int(0)
-        tsp = ts.ctypes.data_as(ctypes.c_void_p)
-        if self.solver in _lib.ODE_SCHEME:
-            what = "cfm_ode_fixed_cnf_gradmlp_f32" if grad else "cfm_ode_fixed_cnf_mlp_f32"
-            rc = getattr(lib, what)(Wp, bp, dims, 4, ptr(xd), B, tsp, n_t, mode, ptr(ed), _lib.ODE_SCHEME[self.solver],
-                                    ptr(traj), ctypes.byref(nfe), ptr(ws), stream_ptr())
-            steps.value = n_t - 1
-        else:
-            rc = lib.cfm_ode_adaptive_cnf_mlp_f32(Wp, bp, dims, 4, ptr(xd), B, tsp, n_t, mode, ptr(ed),
-                                                  _lib.ODE_TABLEAU[self.solver], self.atol, self.rtol, ptr(traj),
-                                                  ctypes.byref(steps), ctypes.byref(nfe), ptr(ws), stream_ptr())
-            what = "cfm_ode_adaptive_cnf_mlp_f32"
+        rc, what, traj, nfe, steps, _ = _solve_hip("cnf_gradmlp" if grad else "cnf_mlp", m, x, t_span, self.solver,
+                                                   self.atol, self.rtol, probe=(eps,))
         if rc == -1:
             return None
         check(rc, what)
-        self.nfe, self.n_steps = nfe.value, steps.value
+        self.nfe, self.n_steps = nfe, steps
         return traj.to(x.device)
 
     def forward(self, x, t_span):
@@ -208,34 +226,11 @@ class NeuralODE(torch.nn.Module):
         """grad: m is the action net of a GradModel and the solve runs in the cfm_ode_*_gradmlp_f32 drivers; these have
         no layer-per-kernel form, so None comes back when the library declines (CFM_EINVAL: the fused small-field path
         is switched off, or t_span has more points than the workspace holds) and the caller steps it generically."""
-        lib = _lib.load()
-        dev = _lib.require_gpu()
-        Wp, bp, dims, keep = m.hip_params(dev)
-        n = len(dims) - 1
-        xd = _lib.to_dev_f32(x, dev)
-        B, d = xd.shape
-        ts = np.ascontiguousarray(torch.as_tensor(t_span, dtype=torch.float32).cpu().numpy())
-        n_t = ts.shape[0]
-        traj = torch.empty((n_t, B, d), dtype=torch.float32, device=dev)
-        maxw = max(dims[1:n]) if n > 1 else 1
-        ws = _lib.workspace(_lib.OP_ODE, B, maxw, d, dev)
-        nfe = ctypes.c_int(0)
-        steps = ctypes.c_int(0)
-        tsp = ts.ctypes.data_as(ctypes.c_void_p)
-        kind = "gradmlp" if grad else "mlp"
-        if self.solver in _lib.ODE_SCHEME:
-            what = f"cfm_ode_fixed_{kind}_f32"
-            rc = getattr(lib, what)(Wp, bp, dims, n, ptr(xd), B, tsp, n_t, _lib.ODE_SCHEME[self.solver], ptr(traj),
-                                    ctypes.byref(nfe), ptr(ws), stream_ptr())
-            steps.value = n_t - 1
-        else:
-            what = f"cfm_ode_adaptive_{kind}_f32"
-            rc = getattr(lib, what)(Wp, bp, dims, n, ptr(xd), B, tsp, n_t, _lib.ODE_TABLEAU[self.solver], self.atol,
-                                    self.rtol, ptr(traj), ctypes.byref(steps), ctypes.byref(nfe), ptr(ws), stream_ptr())
+        rc, what, traj, nfe, steps, _ = _solve_hip("gradmlp" if grad else "mlp", m, x, t_span, self.solver, self.atol, self.rtol)
         if grad and rc == -1:
             return None
         check(rc, what)
-        self.nfe, self.n_steps = nfe.value, steps.value
+        self.nfe, self.n_steps = nfe, steps
         return traj.to(x.device)
 
     # ---- generic vector fields: same algorithm at tensor level ----
@@ -329,56 +324,70 @@ class NeuralODE(torch.nn.Module):
         return torch.stack(sol)
 
 
+class _Declined(Exception):
+    """A fused entry answered CFM_EINVAL inside its envelope: the fused small-field path is switched off, or (the solves)
+    the grid has more points than the solve's workspace holds (n_t > 3 B width).  The caller runs its generic path."""
+
+
+def _solve_forward(ctx, what, x, ts, dims, params, mid, after=(), declines=False):
+    """The forward of a differentiable fixed-step solve of a 4-layer net: one call of the entry ``what`` with ``mid``
+    between the grid and the trajectory and ``after`` behind it.  params: the flat (W_0, b_0, W_1, ...) inputs of the
+    Function; ts: the float32 host grid.  Saves the trajectory [n_t, B, width] and the parameters on ctx for
+    ``_solve_backward`` and returns the trajectory.  declines: CFM_EINVAL raises ``_Declined`` instead of an error."""
+    lib = _lib.load()
+    dev = x.device
+    Ws, bs, Wp, bp = _lib.param_tables(params, dev)
+    cdims = (ctypes.c_int * 5)(*dims)
+    xd = _lib.to_dev_f32(x, dev)
+    B, width = xd.shape
+    n_t = ts.shape[0]
+    traj = torch.empty((n_t, B, width), dtype=torch.float32, device=dev)
+    ws = _lib.workspace(_lib.OP_ODE, B, max(dims[1:4]), width, dev)
+    nfe = ctypes.c_int(0)
+    rc = getattr(lib, what)(Wp, bp, cdims, 4, ptr(xd), B, ts.ctypes.data_as(ctypes.c_void_p), n_t, *mid, ptr(traj), *after,
+                            ctypes.byref(nfe), ptr(ws), stream_ptr())
+    if declines and rc == -1:
+        raise _Declined()
+    check(rc, what)
+    ctx.ts, ctx.dims = ts, dims
+    ctx.save_for_backward(traj, *params)
+    return traj
+
+
+def _solve_backward(ctx, what, op, g, mid, n_other):
+    """The backward of ``_solve_forward``: one call of the entry ``what`` over the saved trajectory, with ``mid`` between
+    the grid and the upstream gradient g; ``op`` sizes its workspace.  Returns the Function's gradients: the state's (if
+    needed), None for its ``n_other`` further non-parameter inputs, then (dW_0, db_0, dW_1, ...)."""
+    lib = _lib.load()
+    traj, *params = ctx.saved_tensors
+    dev = traj.device
+    Ws, bs, Wp, bp = _lib.param_tables(params, dev)
+    dWs, dbs, dWp, dbp = _lib.grad_tables(Ws, bs)
+    cdims = (ctypes.c_int * 5)(*ctx.dims)
+    n_t, B, width = traj.shape
+    gd = _lib.to_dev_f32(g, dev)
+    g0 = torch.empty((B, width), dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
+    ws = _lib.workspace(op, B, n_t, 0, dev)
+    check(getattr(lib, what)(Wp, bp, cdims, 4, ptr(traj), B, ctx.ts.ctypes.data_as(ctypes.c_void_p), n_t, *mid, ptr(gd),
+                             dWp, dbp, ptr(g0), ptr(ws), stream_ptr()), what)
+    grads = [None] * len(params)
+    grads[0::2] = dWs
+    grads[1::2] = dbs
+    return (g0, *[None] * n_other, *grads)
+
+
 class _FixedStepODEFunction(torch.autograd.Function):
     """The trajectory [n_t, B, d] of a fixed-step solve (cfm_ode_fixed_mlp_f32); backward: cfm_ode_fixed_grad_f32."""
 
     @staticmethod
     def forward(ctx, x, ts, scheme, dims, *params):
-        lib = _lib.load()
-        dev = x.device
-        Ws = [_lib.to_dev_f32(p, dev) for p in params[0::2]]
-        bs = [_lib.to_dev_f32(p, dev) for p in params[1::2]]
-        Wp = (ctypes.c_void_p * 4)(*[w.data_ptr() for w in Ws])
-        bp = (ctypes.c_void_p * 4)(*[b.data_ptr() for b in bs])
-        cdims = (ctypes.c_int * 5)(*dims)
-        xd = _lib.to_dev_f32(x, dev)
-        B, d = xd.shape
-        n_t = ts.shape[0]
-        traj = torch.empty((n_t, B, d), dtype=torch.float32, device=dev)
-        ws = _lib.workspace(_lib.OP_ODE, B, max(dims[1:4]), d, dev)
-        nfe = ctypes.c_int(0)
-        check(lib.cfm_ode_fixed_mlp_f32(Wp, bp, cdims, 4, ptr(xd), B, ts.ctypes.data_as(ctypes.c_void_p), n_t, scheme,
-                                        ptr(traj), ctypes.byref(nfe), ptr(ws), stream_ptr()), "cfm_ode_fixed_mlp_f32")
-        ctx.ts, ctx.scheme, ctx.dims = ts, scheme, dims
-        ctx.save_for_backward(traj, *params)
-        return traj
+        ctx.scheme = scheme
+        return _solve_forward(ctx, "cfm_ode_fixed_mlp_f32", x, ts, dims, params, (scheme,))
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        lib = _lib.load()
-        traj, *params = ctx.saved_tensors
-        dev = traj.device
-        Ws = [_lib.to_dev_f32(p, dev) for p in params[0::2]]
-        bs = [_lib.to_dev_f32(p, dev) for p in params[1::2]]
-        dWs = [torch.empty_like(w) for w in Ws]
-        dbs = [torch.empty_like(b) for b in bs]
-        Wp = (ctypes.c_void_p * 4)(*[w.data_ptr() for w in Ws])
-        bp = (ctypes.c_void_p * 4)(*[b.data_ptr() for b in bs])
-        dWp = (ctypes.c_void_p * 4)(*[w.data_ptr() for w in dWs])
-        dbp = (ctypes.c_void_p * 4)(*[b.data_ptr() for b in dbs])
-        cdims = (ctypes.c_int * 5)(*ctx.dims)
-        n_t, B, d = traj.shape
-        gd = _lib.to_dev_f32(g, dev)
-        g0 = torch.empty((B, d), dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
-        ws = _lib.workspace(_lib.OP_ODE_GRAD, B, n_t, 0, dev)
-        check(lib.cfm_ode_fixed_grad_f32(Wp, bp, cdims, 4, ptr(traj), B, ctx.ts.ctypes.data_as(ctypes.c_void_p), n_t,
-                                         ctx.scheme, ptr(gd), dWp, dbp, ptr(g0), ptr(ws), stream_ptr()),
-              "cfm_ode_fixed_grad_f32")
-        grads = [None] * len(params)
-        grads[0::2] = dWs
-        grads[1::2] = dbs
-        return (g0, None, None, None, *grads)
+        return _solve_backward(ctx, "cfm_ode_fixed_grad_f32", _lib.OP_ODE_GRAD, g, (ctx.scheme,), 3)
 
 
 class DifferentiableNeuralODE(NeuralODE):
@@ -413,8 +422,7 @@ class DifferentiableNeuralODE(NeuralODE):
         lins = m._linears()
         if lins[3].bias is None or not all(p.dtype == torch.float32 and p.device == x.device for p in m.parameters()):
             return None
-        dims = [lins[0].in_features] + [l.out_features for l in lins]
-        if _lib.load().cfm_ode_fixed_grad_available((ctypes.c_int * 5)(*dims), 4) != 0:
+        if _lib.load().cfm_ode_fixed_grad_available((ctypes.c_int * 5)(*m.dims()), 4) != 0:
             return None
         return m
 
@@ -427,7 +435,7 @@ class DifferentiableNeuralODE(NeuralODE):
             return self._trajectory_generic(x, ts)
         lins = m._linears()
         params = [p for l in lins for p in (l.weight, l.bias)]
-        dims = [lins[0].in_features] + [l.out_features for l in lins]
+        dims = m.dims()
         scheme = _lib.ODE_SCHEME[self.solver]
         self.last_path = "hip"
         self.n_steps = ts.numel() - 1

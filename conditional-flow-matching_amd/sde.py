@@ -25,7 +25,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr, stream_ptr
-from .models import MLP
+from .models import MLP, time_mlp
 from .schedule import ConstantNoiseScheduler, CosineNoiseScheduler, LinearDecreasingNoiseScheduler
 
 _BUILTIN_SCHEDULES = (ConstantNoiseScheduler, LinearDecreasingNoiseScheduler, CosineNoiseScheduler)
@@ -104,10 +104,8 @@ def _fused_fields(sde):
         s = f
     if not (isinstance(f, MLP) and isinstance(s, MLP) and f.time_varying and s.time_varying):
         return None
-    lf, ls = f._linears(), s._linears()
-    df = [lf[0].in_features] + [l.out_features for l in lf]
-    ds = [ls[0].in_features] + [l.out_features for l in ls]
-    if len(lf) != 4 or df != ds or max(df[1:]) > 64 or df[0] != df[4] + 1:
+    df, ds = f.dims(), s.dims()
+    if len(df) != 5 or df != ds or max(df[1:]) > 64 or df[0] != df[4] + 1:
         return None
     return f, sde.score, df
 
@@ -149,6 +147,20 @@ def _em_records(steps, g, reverse):
                     for (t, h, is_out), gk in zip(steps, g))
 
 
+def _srk_records(steps, sigma, reverse):
+    """The SrkStep records of cfm_sde_srk_mlp_f32 (csrc/sde_small.h), 32 bytes per step: the field times of the three stages
+    (t, t + h, t + h / 2), step, sigma sqrt|h|, 3/4 sigma sqrt|h|, output flag, padding — with the casts of the
+    launch-per-step path, as ``_em_records``."""
+    import struct
+    recs = []
+    for t, h, is_out in steps:
+        gs = sigma * math.sqrt(abs(h))
+        te = [(1.0 - u) if reverse else u for u in (t, t + h, t + 0.5 * h)]
+        recs.append(struct.pack("<ffffffii", te[0], te[1], te[2], h, gs, 0.75 * sigma * math.sqrt(abs(h)),
+                                1 if is_out else 0, 0))
+    return b"".join(recs)
+
+
 def _kernel_reverse_flag(sde):
     """The ``reverse`` argument of the one-launch kernels: it NEGATES the first field, which is FlowScoreSDE's way back;
     a DriftSDE's reverse lives in the records' te = 1 - t alone (flag 0 in both directions)."""
@@ -173,6 +185,109 @@ def _noise_arg(noise, method, n_steps, y0):
         raise ValueError(f"sdeint(method={method!r}): the noise tensor must have shape {list(want)} "
                          f"([n_steps{', 2' if method == 'srk' else ''}, B, d] on the grid refined to dt), got {list(noise.shape)}")
     return noise
+
+
+def _run_one_launch(sde, fields, y0, y, steps, g_steps, srk, given, noise, generator):
+    """The whole trajectory in one launch of cfm_sde_em_mlp_f32 / cfm_sde_srk_mlp_f32.  fields: ``_fused_fields(sde)``; y:
+    the fp32 device copy of y0; given: the caller's normals on the device, or None for ``noise`` "torch" / "philox"."""
+    import ctypes
+    lib = _lib.load()
+    dev = y.device
+    f, s, dims = fields
+    B, d = y.shape
+    n_out = sum(1 for st in steps if st[2])
+    if srk:
+        blob, rec = _srk_records(steps, g_steps[0] if steps else 0.0, sde.reverse), 32          # (srk: sigma is constant)
+    else:
+        blob, rec = _em_records(steps, g_steps, sde.reverse), 16
+    host = (ctypes.c_char * (rec * len(steps))).from_buffer_copy(blob)
+    xi = given
+    seed = 0
+    if xi is None and noise == "torch":
+        shape = (2, B, d) if srk else (B, d)
+        xi = torch.stack([torch.randn(shape, device=dev, dtype=torch.float32, generator=generator) for _ in steps])
+    elif xi is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,), device=dev, generator=generator).item())
+    Wf, bf, _, keep_f = f.hip_params(dev)
+    Ws, bs, _, keep_s = s.hip_params(dev) if s is not None else (None, None, None, None)      # one field: Ws = bs = NULL
+    cd = (ctypes.c_int * 5)(*dims)
+    traj = torch.empty((n_out, B, d), dtype=torch.float32, device=dev)
+    ws = torch.empty(rec * len(steps) + 256, dtype=torch.uint8, device=dev)
+    name = "cfm_sde_srk_mlp_f32" if srk else "cfm_sde_em_mlp_f32"
+    check(getattr(lib, name)(Wf, bf, Ws, bs, cd, 4, ptr(y), B, host, len(steps), _kernel_reverse_flag(sde),
+                             ptr(xi), seed, ptr(traj), ptr(ws), stream_ptr()), name)
+    torch.cuda.current_stream().synchronize()          # `host` (pageable) must outlive the copy
+    return torch.cat([y0.to(torch.float32)[None].to(y0.device), traj.to(y0.device)])
+
+
+def _run_stepped(sde, y0, y, steps, g_steps, srk, given, generator):
+    """A launch per step: the fields through ``MLP.forward_hip``, the state update in cfm_sde_em_step_f32 (``euler``) or
+    one cfm_sde_srk_step_f32 per stage (``srk``).  y: the fp32 device copy of y0, updated in place; the increments are
+    drawn inside the loop unless ``given``."""
+    lib = _lib.load()
+    dev = y.device
+    out = [y0]
+    sign = 1.0
+    if srk:
+        sigma = g_steps[0] if steps else 0.0          # (srk: constant)
+
+        def pair(yy, u):
+            te = (1.0 - u) if sde.reverse else u
+            v = sde.drift.forward_hip(yy, te)
+            return (-v if sde.reverse else v), sde.score.forward_hip(yy, te)
+        ys = torch.empty_like(y)
+    for k, (t, h, is_out) in enumerate(steps):
+        if srk:
+            xi = given[k] if given is not None else torch.randn((2,) + tuple(y.shape), device=dev, dtype=torch.float32,
+                                                                generator=generator)
+            xi1, xi2 = xi[0], xi[1]
+            v1, s1 = pair(y, t)
+            v2 = s2 = v3 = s3 = None
+            for stage in (1, 2, 3):
+                check(lib.cfm_sde_srk_step_f32(stage, ptr(y), ptr(ys), ptr(v1), ptr(s1), ptr(v2), ptr(s2), ptr(v3),
+                                               ptr(s3), ptr(xi1), ptr(xi2), float(h), sigma, sign, y.numel(),
+                                               stream_ptr()), "cfm_sde_srk_step_f32")
+                if stage == 1:
+                    v2, s2 = pair(ys, t + h)
+                elif stage == 2:
+                    v3, s3 = pair(ys, t + 0.5 * h)
+        else:
+            te = (1.0 - t) if sde.reverse else t
+            v = sde.drift.forward_hip(y, te)
+            s = sde.score.forward_hip(y, te) if sde.score is not None else None
+            if sde.reverse and sde.negate_reverse:
+                v = -v
+            xi = given[k] if given is not None else torch.randn(y.shape, device=dev, dtype=torch.float32, generator=generator)
+            check(lib.cfm_sde_em_step_f32(ptr(y), ptr(v), ptr(s), ptr(xi), float(h), g_steps[k], sign,
+                                          y.numel(), stream_ptr()), "cfm_sde_em_step_f32")
+        if is_out:
+            out.append(y.clone().to(y0.device))
+    return torch.stack([o.to(torch.float32) for o in out])
+
+
+def _run_eager(sde, y0, steps, srk, given, generator):
+    """The same schemes in eager torch ops on ``sde.f`` / ``sde.g``, in the caller's dtype and on its device."""
+    out = [y0]
+    y = y0
+    if given is not None:
+        given = given.to(device=y.device, dtype=y.dtype)
+    for k, (t, h, is_out) in enumerate(steps):
+        tt = torch.as_tensor(t, dtype=y.dtype, device=y.device)
+        if srk:
+            # the scheme of csrc/sde_srk.h in the caller's dtype
+            xi = given[k] if given is not None else torch.randn((2,) + tuple(y.shape), device=y.device, dtype=y.dtype,
+                                                                generator=generator)
+            gs = float(sde.sigma) * math.sqrt(abs(h))
+            k1 = sde.f(tt, y)
+            k2 = sde.f(tt + h, y + h * k1)
+            k3 = sde.f(tt + 0.5 * h, y + (0.25 * h) * (k1 + k2) + (0.75 * gs) * (xi[0] + xi[1] / math.sqrt(3.0)))
+            y = y + (h / 6.0) * ((k1 + k2) + 4.0 * k3) + gs * xi[0]
+        else:
+            xi = given[k] if given is not None else torch.randn(y.shape, device=y.device, dtype=y.dtype, generator=generator)
+            y = y + h * sde.f(tt, y) + sde.g(tt, y) * math.sqrt(abs(h)) * xi
+        if is_out:
+            out.append(y)
+    return torch.stack(out)
 
 
 @torch.no_grad()
@@ -220,118 +335,53 @@ def sdeint(sde, y0, ts, method="euler", dt=1e-3, generator=None, noise="philox",
             fast = False
     if known:
         sde.last_path = "hip" if fast else "eager"
-    out = [y0]
-    if fast:
-        lib = _lib.load()
-        dev = _lib.require_gpu()
-        y = _lib.to_dev_f32(y0, dev).clone()
-        if given is not None:
-            given = _lib.to_dev_f32(given, dev).contiguous()
-        fields = _fused_fields(sde) if (y.shape[1] <= 64 and fused is not False) else None
-        if fields is not None and y.shape[1] != fields[2][4]:
-            # the one-launch kernel reads y0 with the fields' output width as its pitch: a state of another width
-            # must not reach it (the stepping path below raises the layer's shape error instead)
-            if fused is True:
-                raise ValueError(f"sdeint(fused=True): y0 has {y.shape[1]} columns, the fields map {fields[2][4]}")
-            fields = None
-        if fused is True and fields is None:
-            raise ValueError("sdeint(fused=True): needs two 4-layer time-varying cfm_amd.MLP fields of widths <= 64 "
-                             "(FlowScoreSDE; one for a DriftSDE)")
-        if g_steps is None:
-            g_steps = [float(sde.sigma)] * len(steps)
-        sigma = g_steps[0] if steps else 0.0          # (srk: constant)
-        if fields is not None:
-            import ctypes
-            import struct
-            f, s, dims = fields
-            B, d = y.shape
-            n_out = sum(1 for st in steps if st[2])
-            if srk:
-                recs = []
-                for t, h, is_out in steps:
-                    # the casts of the launch-per-step path: float32 time, float32 step, float32 (g sqrt|h|)
-                    gs = sigma * math.sqrt(abs(h))
-                    te = [(1.0 - u) if sde.reverse else u for u in (t, t + h, t + 0.5 * h)]
-                    recs.append(struct.pack("<ffffffii", te[0], te[1], te[2], h, gs, 0.75 * sigma * math.sqrt(abs(h)),
-                                            1 if is_out else 0, 0))
-                blob = b"".join(recs)
-            else:
-                blob = _em_records(steps, g_steps, sde.reverse)
-            rec = 32 if srk else 16
-            host = (ctypes.c_char * (rec * len(steps))).from_buffer_copy(blob)
-            xi = given
-            seed = 0
-            if xi is None and noise == "torch":
-                shape = (2, B, d) if srk else (B, d)
-                xi = torch.stack([torch.randn(shape, device=dev, dtype=torch.float32, generator=generator) for _ in steps])
-            elif xi is None:
-                seed = int(torch.randint(0, 2 ** 62, (1,), device=dev, generator=generator).item())
-            Wf, bf, _, keep_f = f.hip_params(dev)
-            Ws, bs, _, keep_s = s.hip_params(dev) if s is not None else (None, None, None, None)      # one field: Ws = bs = NULL
-            cd = (ctypes.c_int * 5)(*dims)
-            traj = torch.empty((n_out, B, d), dtype=torch.float32, device=dev)
-            ws = torch.empty(rec * len(steps) + 256, dtype=torch.uint8, device=dev)
-            entry, name = (lib.cfm_sde_srk_mlp_f32, "cfm_sde_srk_mlp_f32") if srk else (lib.cfm_sde_em_mlp_f32, "cfm_sde_em_mlp_f32")
-            check(entry(Wf, bf, Ws, bs, cd, 4, ptr(y), B, host, len(steps), _kernel_reverse_flag(sde),
-                        ptr(xi), seed, ptr(traj), ptr(ws), stream_ptr()), name)
-            torch.cuda.current_stream().synchronize()          # `host` (pageable) must outlive the copy
-            return torch.cat([y0.to(torch.float32)[None].to(y0.device), traj.to(y0.device)])
-        sign = 1.0
-        if srk:
-            def pair(yy, u):
-                te = (1.0 - u) if sde.reverse else u
-                v = sde.drift.forward_hip(yy, te)
-                return (-v if sde.reverse else v), sde.score.forward_hip(yy, te)
-            ys = torch.empty_like(y)
-            for k, (t, h, is_out) in enumerate(steps):
-                xi = given[k] if given is not None else torch.randn((2,) + tuple(y.shape), device=dev, dtype=torch.float32,
-                                                                    generator=generator)
-                xi1, xi2 = xi[0], xi[1]
-                v1, s1 = pair(y, t)
-                v2 = s2 = v3 = s3 = None
-                for stage in (1, 2, 3):
-                    check(lib.cfm_sde_srk_step_f32(stage, ptr(y), ptr(ys), ptr(v1), ptr(s1), ptr(v2), ptr(s2), ptr(v3),
-                                                   ptr(s3), ptr(xi1), ptr(xi2), float(h), sigma, sign, y.numel(),
-                                                   stream_ptr()), "cfm_sde_srk_step_f32")
-                    if stage == 1:
-                        v2, s2 = pair(ys, t + h)
-                    elif stage == 2:
-                        v3, s3 = pair(ys, t + 0.5 * h)
-                if is_out:
-                    out.append(y.clone().to(y0.device))
-            return torch.stack([o.to(torch.float32) for o in out])
-        for k, (t, h, is_out) in enumerate(steps):
-            te = (1.0 - t) if sde.reverse else t
-            v = sde.drift.forward_hip(y, te)
-            s = sde.score.forward_hip(y, te) if sde.score is not None else None
-            if sde.reverse and sde.negate_reverse:
-                v = -v
-            xi = given[k] if given is not None else torch.randn(y.shape, device=dev, dtype=torch.float32, generator=generator)
-            check(lib.cfm_sde_em_step_f32(ptr(y), ptr(v), ptr(s), ptr(xi), float(h), g_steps[k], sign,
-                                          y.numel(), stream_ptr()), "cfm_sde_em_step_f32")
-            if is_out:
-                out.append(y.clone().to(y0.device))
-        return torch.stack([o.to(torch.float32) for o in out])
-    y = y0
+    if not fast:
+        return _run_eager(sde, y0, steps, srk, given, generator)
+    _lib.load()
+    dev = _lib.require_gpu()
+    y = _lib.to_dev_f32(y0, dev).clone()
     if given is not None:
-        given = given.to(device=y.device, dtype=y.dtype)
-    for k, (t, h, is_out) in enumerate(steps):
-        tt = torch.as_tensor(t, dtype=y.dtype, device=y.device)
-        if srk:
-            # the scheme of csrc/sde_srk.h in the caller's dtype
-            xi = given[k] if given is not None else torch.randn((2,) + tuple(y.shape), device=y.device, dtype=y.dtype,
-                                                                generator=generator)
-            gs = float(sde.sigma) * math.sqrt(abs(h))
-            k1 = sde.f(tt, y)
-            k2 = sde.f(tt + h, y + h * k1)
-            k3 = sde.f(tt + 0.5 * h, y + (0.25 * h) * (k1 + k2) + (0.75 * gs) * (xi[0] + xi[1] / math.sqrt(3.0)))
-            y = y + (h / 6.0) * ((k1 + k2) + 4.0 * k3) + gs * xi[0]
-        else:
-            xi = given[k] if given is not None else torch.randn(y.shape, device=y.device, dtype=y.dtype, generator=generator)
-            y = y + h * sde.f(tt, y) + sde.g(tt, y) * math.sqrt(abs(h)) * xi
-        if is_out:
-            out.append(y)
-    return torch.stack(out)
+        given = _lib.to_dev_f32(given, dev).contiguous()
+    fields = _fused_fields(sde) if (y.shape[1] <= 64 and fused is not False) else None
+    if fields is not None and y.shape[1] != fields[2][4]:
+        # the one-launch kernel reads y0 with the fields' output width as its pitch: a state of another width
+        # must not reach it (the stepping path raises the layer's shape error instead)
+        if fused is True:
+            raise ValueError(f"sdeint(fused=True): y0 has {y.shape[1]} columns, the fields map {fields[2][4]}")
+        fields = None
+    if fused is True and fields is None:
+        raise ValueError("sdeint(fused=True): needs two 4-layer time-varying cfm_amd.MLP fields of widths <= 64 "
+                         "(FlowScoreSDE; one for a DriftSDE)")
+    if g_steps is None:
+        g_steps = [float(sde.sigma)] * len(steps)
+    if fields is not None:
+        return _run_one_launch(sde, fields, y0, y, steps, g_steps, srk, given, noise, generator)
+    return _run_stepped(sde, y0, y, steps, g_steps, srk, given, generator)
+
+
+def _mlp_pair(first, second):
+    """(MLP, MLP) when both fields are, or wrap, time-varying MLPs that the HIP paths take (``models.time_mlp``), else None."""
+    pair = (time_mlp(first, bare=True), time_mlp(second, bare=True))
+    return None if None in pair else pair
+
+
+def _refuse_srk(who):
+    raise NotImplementedError(f"{who}(sde_solver='srk'): sigma is a schedule sigma(t) here, and 'srk' is built "
+                              "for constant diagonal noise only (the full SRI2W1 tableau is not built)")
+
+
+class _SolverSDE:
+    """The eager SDE of a FlowSolver for ``sdeint``: f(t, y) from the solver's drift methods (so ``nfe`` counts), g from
+    its schedule."""
+
+    def __init__(self, solver, reverse):
+        self.solver, self.reverse = solver, reverse
+
+    def f(self, t, y):
+        return self.solver.backward_sde_drift(1 - t, y) if self.reverse else self.solver.forward_sde_drift(t, y)
+
+    def g(self, t, y):
+        return self.solver.sigma(t) * torch.ones_like(y)
 
 
 class FlowSolver(torch.nn.Module):
@@ -385,26 +435,14 @@ class FlowSolver(torch.nn.Module):
 
     def _hip_fields(self):
         """(flow MLP, score MLP) when sdeint's HIP paths can take the pair (the rule of NeuralODE._hip_mlp), else None."""
-        from .utils import torch_wrapper
         if self.sde_solver != "euler" or not self.separate_score or self.sigma is None:
             return None
-        pair = []
-        for f in (self.net, self.score_net):
-            m = f.model if isinstance(f, torch_wrapper) else f
-            if not (isinstance(m, MLP) and m.time_varying):
-                return None
-            lins = m._linears()
-            if lins[-1].out_features + 1 != lins[0].in_features:
-                return None
-            pair.append(m)
-        return tuple(pair)
+        return _mlp_pair(self.net, self.score_net)
 
     def sdeint(self, x0, t_span, reverse=False, generator=None):
         if self.sde_solver == "srk":
-            raise NotImplementedError("FlowSolver(sde_solver='srk'): sigma is a schedule sigma(t) here, and 'srk' is built "
-                                      "for constant diagonal noise only (the full SRI2W1 tableau is not built)")
+            _refuse_srk("FlowSolver")
         self.nfe = 0
-        outer = self
         fields = self._hip_fields()
         if fields is not None:
             sde = FlowScoreSDE(fields[0], fields[1], sigma=self.sigma, reverse=reverse)
@@ -413,14 +451,7 @@ class FlowSolver(torch.nn.Module):
             self.nfe = len(_grid(t_span, float(self.dt)))          # one evaluation of the field pair per refined step
             return out
         self.last_path = "eager"
-
-        class _S:
-            def f(self, t, y):
-                return outer.backward_sde_drift(1 - t, y) if reverse else outer.forward_sde_drift(t, y)
-
-            def g(self, t, y):
-                return outer.sigma(t) * torch.ones_like(y)
-        return sdeint(_S(), x0, t_span, method=self.sde_solver, dt=self.dt, generator=generator)
+        return sdeint(_SolverSDE(self, reverse), x0, t_span, method=self.sde_solver, dt=self.dt, generator=generator)
 
 
 class DSBMFlowSolver(FlowSolver):
@@ -463,22 +494,11 @@ class DSBMFlowSolver(FlowSolver):
 
     def _hip_pair(self):
         """(forward MLP, backward MLP) when the HIP paths can take them (the rule of NeuralODE._hip_mlp), else None."""
-        from .utils import torch_wrapper
-        pair = []
-        for f in (self.net, self.score_net):
-            m = f.model if isinstance(f, torch_wrapper) else f
-            if not (isinstance(m, MLP) and m.time_varying):
-                return None
-            lins = m._linears()
-            if lins[-1].out_features + 1 != lins[0].in_features:
-                return None
-            pair.append(m)
-        return tuple(pair)
+        return _mlp_pair(self.net, self.score_net)
 
     def sdeint(self, x0, t_span, reverse=False, generator=None, noise="philox", fused=None):
         if self.sde_solver == "srk":
-            raise NotImplementedError("DSBMFlowSolver(sde_solver='srk'): sigma is a schedule sigma(t) here, and 'srk' is built "
-                                      "for constant diagonal noise only (the full SRI2W1 tableau is not built)")
+            _refuse_srk("DSBMFlowSolver")
         if self.sigma is None:
             raise ValueError("DSBMFlowSolver.sdeint needs sigma (a noise schedule or a number)")
         self.nfe = 0
@@ -490,15 +510,7 @@ class DSBMFlowSolver(FlowSolver):
             self.nfe = len(_grid(t_span, float(self.dt)))          # one drift evaluation per refined step
             return out
         self.last_path = "eager"
-        outer = self
-
-        class _S:
-            def f(self, t, y):
-                return outer.backward_sde_drift(1 - t, y) if reverse else outer.forward_sde_drift(t, y)
-
-            def g(self, t, y):
-                return outer.sigma(t) * torch.ones_like(y)
-        return sdeint(_S(), x0, t_span, method="euler", dt=self.dt, generator=generator, noise=noise)
+        return sdeint(_SolverSDE(self, reverse), x0, t_span, method="euler", dt=self.dt, generator=generator, noise=noise)
 
     @torch.no_grad()
     def odeint(self, x0, t_span, fused=None):
@@ -507,7 +519,7 @@ class DSBMFlowSolver(FlowSolver):
         pair = self._hip_pair()
         if (pair is not None and self.ode_solver in _lib.ODE_SCHEME and x0.dim() == 2 and x0.dtype == torch.float32
                 and torch.cuda.is_available()):
-            dims = [[l.in_features for l in m._linears()] + [m._linears()[-1].out_features] for m in pair]
+            dims = [m.dims() for m in pair]
             if dims[0] == dims[1] and x0.shape[1] == dims[0][-1]:
                 _check_t_span(torch.as_tensor(t_span, dtype=torch.float32).cpu())
                 self.last_path = "hip"
@@ -517,33 +529,11 @@ class DSBMFlowSolver(FlowSolver):
         return node(x0, t_span)
 
     def _odeint_hip(self, pair, x0, t_span, fused):
-        import ctypes
-
-        import numpy as np
-        lib = _lib.load()
-        dev = _lib.require_gpu()
-        Wf, bf, dims, keep_f = pair[0].hip_params(dev)
-        Wb, bb, _, keep_b = pair[1].hip_params(dev)
-        n = len(dims) - 1
-        xd = _lib.to_dev_f32(x0, dev)
-        B, d = xd.shape
-        ts = np.ascontiguousarray(torch.as_tensor(t_span, dtype=torch.float32).cpu().numpy())
-        n_t = ts.shape[0]
-        traj = torch.empty((n_t, B, d), dtype=torch.float32, device=dev)
-        ws = _lib.workspace(_lib.OP_ODE, B, max(dims[1:n]) if n > 1 else 1, d, dev)
-        nfe = ctypes.c_int(0)
-        if fused is False:
-            lib.cfm_ode_set_fused(0)
-        try:
-            rc = lib.cfm_ode_fixed_pair_mlp_f32(Wf, bf, Wb, bb, dims, n, ptr(xd), B, ts.ctypes.data_as(ctypes.c_void_p), n_t,
-                                                _lib.ODE_SCHEME[self.ode_solver], ptr(traj), ctypes.byref(nfe), ptr(ws),
-                                                stream_ptr())
-        finally:
-            if fused is False:
-                lib.cfm_ode_set_fused(1)
-        check(rc, "cfm_ode_fixed_pair_mlp_f32")
+        from .ode import _solve_hip
+        rc, what, traj, nfe, _, ts = _solve_hip("pair_mlp", pair[0], x0, t_span, self.ode_solver, second=pair[1], fused=fused)
+        check(rc, what)
         torch.cuda.current_stream().synchronize()          # `ts` (pageable) must outlive the copy
-        self.nfe = nfe.value
+        self.nfe = nfe
         return traj.to(x0.device)
 
     @torch.no_grad()

@@ -40,7 +40,83 @@ from ._lib import check, ptr, stream_ptr
 from .models import MLP
 
 
-class RegressionStep:
+class _FusedStep:
+    """What the fused steps share, for one net or two of equal layer sizes: the flat gradient buffer with every ``.grad``
+    a view of it, the activation buffers and workspaces per batch size, the pointer tables, the batch checks."""
+
+    def _setup(self, nets):
+        """nets: one or two checked MLPs (fp32, biased, on one GPU, equal layer sizes); the first one's layers come first
+        in ``lins`` and in every table."""
+        self.net, self.n_nets = nets[0], len(nets)
+        self.dims = nets[0].dims()
+        self.n = len(self.dims) - 1
+        self.lins = [l for net in nets for l in net._linears()]
+        self.dev = self.lins[0].weight.device
+        # ONE flat gradient buffer; every parameter's .grad is a view of it (one all-reduce for data parallel runs)
+        self.flat_grad = torch.zeros(sum(l.weight.numel() + l.bias.numel() for l in self.lins), dtype=torch.float32, device=self.dev)
+        self._gviews, off = [], 0
+        for l in self.lins:
+            for p in (l.weight, l.bias):
+                v = self.flat_grad[off:off + p.numel()].view_as(p); off += p.numel()
+                p.grad = v
+                self._gviews.append(v)
+        self._B = None
+
+    def _buffers(self, B):
+        """hidden / preact (the first net's layers first), one loss-gradient seed g and one workspace per net, and their
+        host tables; rebuilt only when the batch size changes."""
+        if self._B != B:
+            d, n, dev, nets = self.dims, self.n, self.dev, range(self.n_nets)
+            self.hidden = [torch.empty((B, d[l + 1]), dtype=torch.float32, device=dev) for _ in nets for l in range(n - 1)]
+            self.preact = [torch.empty((B, d[l + 1]), dtype=torch.float32, device=dev) for _ in nets for l in range(n - 1)]
+            self.g = [torch.empty((B, d[n]), dtype=torch.float32, device=dev) for _ in nets]      # own allocations: aligned alike
+            one = _lib.load().cfm_workspace_bytes(_lib.OP_MLP_TRAIN, B, max(d), max(d[l] * d[l + 1] for l in range(n)))
+            self.ws = torch.empty(self.n_nets * one, dtype=torch.uint8, device=dev)      # the nets' workspaces back to back
+            m = max(1, self.n_nets * (n - 1))
+            self.hp = (ctypes.c_void_p * m)(*([h.data_ptr() for h in self.hidden] or [0]))
+            self.zp = (ctypes.c_void_p * m)(*([z.data_ptr() for z in self.preact] or [0]))
+            self.cd = (ctypes.c_int * (n + 1))(*d)
+            self._B = B
+
+    def _tables(self):
+        """(W, b, dW, db): host tables of n_nets * n device pointers, the first net's layers first.  The parameters' storage
+        may have moved (load_state_dict keeps it, .to() does not), so the pointers are taken per call; a replaced .grad is
+        put back."""
+        for v, p in zip(self._gviews, (q for l in self.lins for q in (l.weight, l.bias))):
+            if p.grad is not v:
+                p.grad = v
+        N = len(self.lins)
+        return ((ctypes.c_void_p * N)(*[l.weight.data_ptr() for l in self.lins]),
+                (ctypes.c_void_p * N)(*[l.bias.data_ptr() for l in self.lins]),
+                (ctypes.c_void_p * N)(*[self._gviews[2 * l].data_ptr() for l in range(N)]),
+                (ctypes.c_void_p * N)(*[self._gviews[2 * l + 1].data_ptr() for l in range(N)]))
+
+    def _in_width(self):
+        """columns of xt: the first layer's input without the time column"""
+        return self.dims[0] - int(bool(self.net.time_varying))
+
+    def _xt_ut(self, who, xt, ut, same_rows):
+        """(xt, ut, B) with xt and ut detached and reshaped to [B, -1], their columns checked against the layer sizes
+        (same_rows: and ut's rows against xt's)."""
+        xt = xt.detach().reshape(xt.shape[0], -1)
+        ut = ut.detach().reshape(ut.shape[0], -1)
+        B = xt.shape[0]
+        if xt.shape[1] != self._in_width() or ut.shape[1] != self.dims[self.n] or (same_rows and ut.shape[0] != B):
+            raise RuntimeError(f"{who}: xt has {xt.shape[1]} / ut has {ut.shape[1]} columns, the "
+                               f"{'net maps' if self.n_nets == 1 else 'nets map'} {self._in_width()} (+ time) -> {self.dims[self.n]}")
+        return xt, ut, B
+
+    def _times(self, who, t, B):
+        """t as a device vector with one time per row, or None for a net without a time column"""
+        if not self.net.time_varying:
+            return None
+        tt = _lib.to_dev_f32(t.detach().reshape(-1), self.dev)
+        if tt.numel() != B:
+            raise RuntimeError(f"{who}: one time per row is required")
+        return tt
+
+
+class RegressionStep(_FusedStep):
     def __init__(self, model, optimizer, data_parallel=None):
         """data_parallel: None — the bucketed gradient all-reduce runs iff torch.distributed is initialised with more than
         one rank; True — whenever a process group exists, also with ONE rank (the N > 1 composition — communication
@@ -49,49 +125,20 @@ class RegressionStep:
         net = model.module if hasattr(model, "module") and isinstance(model.module, MLP) else model
         if not isinstance(net, MLP):
             raise TypeError("RegressionStep drives a cfm_amd.MLP vector field")
-        self.net, self.opt = net, optimizer
+        self.opt = optimizer
         from .optim import FusedAdam
         self._fused_opt = isinstance(optimizer, FusedAdam)           # its step() takes the 1 / world of the mean (grad_scale)
-        self.lins = net._linears()
-        self.n = len(self.lins)
-        dev = self.lins[0].weight.device
-        if dev.type != "cuda" or any(l.weight.dtype != torch.float32 or l.bias is None for l in self.lins):
+        lins = net._linears()
+        if lins[0].weight.device.type != "cuda" or any(l.weight.dtype != torch.float32 or l.bias is None for l in lins):
             raise TypeError("RegressionStep needs an fp32 MLP with biases on the GPU")
-        self.dev = dev
-        self.dims = [self.lins[0].in_features] + [l.out_features for l in self.lins]
-        # ONE flat gradient buffer; every parameter's .grad is a view of it (one all-reduce for data parallel runs)
-        sizes = []
-        for l in self.lins:
-            sizes += [l.weight.numel(), l.bias.numel()]
-        self.flat_grad = torch.zeros(sum(sizes), dtype=torch.float32, device=dev)
-        views, off = [], 0
-        for l in self.lins:
-            for p in (l.weight, l.bias):
-                v = self.flat_grad[off:off + p.numel()].view_as(p); off += p.numel()
-                p.grad = v
-                views.append(v)
-        self._gviews = views
+        self._setup([net])
         # per-layer buckets of the flat buffer ([W_l, b_l] are adjacent) + one event per layer for the data-parallel form
         self._buckets, off = [], 0
         for l in self.lins:
             nl = l.weight.numel() + l.bias.numel()
             self._buckets.append(self.flat_grad[off:off + nl]); off += nl
         self._events = self._comm = self._evp = None
-        self._B = None
-        self.loss = torch.zeros((), dtype=torch.float32, device=dev)
-
-    def _buffers(self, B):
-        if self._B != B:
-            d, n, dev = self.dims, self.n, self.dev
-            self.hidden = [torch.empty((B, d[l + 1]), dtype=torch.float32, device=dev) for l in range(n - 1)]
-            self.preact = [torch.empty((B, d[l + 1]), dtype=torch.float32, device=dev) for l in range(n - 1)]
-            self.g = torch.empty((B, d[n]), dtype=torch.float32, device=dev)
-            self.ws = torch.empty(_lib.load().cfm_workspace_bytes(_lib.OP_MLP_TRAIN, B, max(d), max(d[l] * d[l + 1] for l in range(n))),
-                                  dtype=torch.uint8, device=dev)
-            self.hp = (ctypes.c_void_p * max(1, n - 1))(*([h.data_ptr() for h in self.hidden] or [0]))
-            self.zp = (ctypes.c_void_p * max(1, n - 1))(*([z.data_ptr() for z in self.preact] or [0]))
-            self.cd = (ctypes.c_int * (n + 1))(*d)
-            self._B = B
+        self.loss = torch.zeros((), dtype=torch.float32, device=self.dev)
 
     def _dp_setup(self):
         """events (created by a first record: torch makes the HIP event lazily) and the communication stream"""
@@ -108,29 +155,13 @@ class RegressionStep:
         """forward + loss + backward; returns the loss (0-dim device tensor, overwritten by the next call).
         layer_events: ctypes array of n hipEvent_t (see ``cfm_mlp_regression_step_f32``: ``layer_done``) or None."""
         lib = _lib.load()
-        xt = xt.detach().reshape(xt.shape[0], -1)
-        ut = ut.detach().reshape(ut.shape[0], -1)
-        B = xt.shape[0]
-        tv = self.net.time_varying
-        if xt.shape[1] != self.dims[0] - int(bool(tv)) or ut.shape[1] != self.dims[self.n]:
-            raise RuntimeError(f"RegressionStep: xt has {xt.shape[1]} / ut has {ut.shape[1]} columns, the net maps "
-                               f"{self.dims[0] - int(bool(tv))} (+ time) -> {self.dims[self.n]}")
+        xt, ut, B = self._xt_ut("RegressionStep", xt, ut, same_rows=False)
         xt = _lib.to_dev_f32(xt, self.dev); ut = _lib.to_dev_f32(ut, self.dev)
-        tt = _lib.to_dev_f32(t.detach().reshape(-1), self.dev) if tv else None
-        if tv and tt.numel() != B:
-            raise RuntimeError("RegressionStep: one time per row is required")
+        tt = self._times("RegressionStep", t, B)
         self._buffers(B)
-        n = self.n
-        # the parameters' storage may have moved (load_state_dict keeps it, .to() does not): pointers are taken per call
-        for v, p in zip(self._gviews, (q for l in self.lins for q in (l.weight, l.bias))):
-            if p.grad is not v:
-                p.grad = v
-        Wp = (ctypes.c_void_p * n)(*[l.weight.data_ptr() for l in self.lins])
-        bp = (ctypes.c_void_p * n)(*[l.bias.data_ptr() for l in self.lins])
-        dWp = (ctypes.c_void_p * n)(*[self._gviews[2 * l].data_ptr() for l in range(n)])
-        dbp = (ctypes.c_void_p * n)(*[self._gviews[2 * l + 1].data_ptr() for l in range(n)])
-        check(lib.cfm_mlp_regression_step_f32(ptr(xt), ptr(tt), ptr(ut), Wp, bp, self.cd, n, B, self.hp, self.zp,
-                                              ptr(self.g), dWp, dbp, ptr(self.loss), layer_events, ptr(self.ws),
+        Wp, bp, dWp, dbp = self._tables()
+        check(lib.cfm_mlp_regression_step_f32(ptr(xt), ptr(tt), ptr(ut), Wp, bp, self.cd, self.n, B, self.hp, self.zp,
+                                              ptr(self.g[0]), dWp, dbp, ptr(self.loss), layer_events, ptr(self.ws),
                                               stream_ptr()),
               "cfm_mlp_regression_step_f32")
         return self.loss
@@ -180,7 +211,7 @@ def _need_fp32_gpu(who, nets):
             raise TypeError(f"{who}: {what} is not on the GPU")
 
 
-class SF2MStep:
+class SF2MStep(_FusedStep):
     """The [SF]2M training step for a flow ``MLP`` and a score ``MLP`` of equal layer sizes:
 
         vt = model(torch.cat([xt, t[:, None]], dim=-1)); st = score_model(torch.cat([xt, t[:, None]], dim=-1))
@@ -196,57 +227,20 @@ class SF2MStep:
 
     def __init__(self, model, score_model, optimizer, score_weight=1.0):
         who, first, second = self._WHO, self._FIRST, self._SECOND
-        self.net, self.score_net = _as_mlp(model, who, f"the {first} model"), _as_mlp(score_model, who, f"the {second} model")
-        flins, slins = self.net._linears(), self.score_net._linears()
-        dims = [flins[0].in_features] + [l.out_features for l in flins]
-        sdims = [slins[0].in_features] + [l.out_features for l in slins]
-        if dims != sdims or bool(self.net.time_varying) != bool(self.score_net.time_varying):
+        net, self.score_net = _as_mlp(model, who, f"the {first} model"), _as_mlp(score_model, who, f"the {second} model")
+        flins, slins = net._linears(), self.score_net._linears()
+        dims, sdims = net.dims(), self.score_net.dims()
+        if dims != sdims or bool(net.time_varying) != bool(self.score_net.time_varying):
             raise TypeError(f"{who}: the nets' layer sizes differ ({first} {dims}, {second} {sdims}): one launch serves both "
                             "nets only when their layers have equal sizes")
         _need_fp32_gpu(who, ((flins, f"the {first} model"), (slins, f"the {second} model")))
         if slins[0].weight.device != flins[0].weight.device:
             raise TypeError(f"{who}: the {second} model is not on the GPU of the {first} model")
-        if self.net is self.score_net:
+        if net is self.score_net:
             raise TypeError(f"{who}: the {first} and the {second} model are the same module")
         self.opt, self.score_weight = optimizer, float(score_weight)
-        self.dims, self.n, self.dev = dims, len(flins), flins[0].weight.device
-        self.lins = flins + slins                                     # flow first, score second: the order of every table
-        # ONE flat gradient buffer for both nets; every parameter's .grad is a view of it
-        self.flat_grad = torch.zeros(sum(l.weight.numel() + l.bias.numel() for l in self.lins), dtype=torch.float32, device=self.dev)
-        self._gviews, off = [], 0
-        for l in self.lins:
-            for p in (l.weight, l.bias):
-                v = self.flat_grad[off:off + p.numel()].view_as(p); off += p.numel()
-                p.grad = v
-                self._gviews.append(v)
-        self._B = None
+        self._setup([net, self.score_net])                            # flow first, score second: the order of every table
         self.losses = torch.zeros(2, dtype=torch.float32, device=self.dev)
-
-    def _buffers(self, B):
-        if self._B != B:
-            d, n, dev = self.dims, self.n, self.dev
-            self.hidden = [torch.empty((B, d[l + 1]), dtype=torch.float32, device=dev) for _ in range(2) for l in range(n - 1)]
-            self.preact = [torch.empty((B, d[l + 1]), dtype=torch.float32, device=dev) for _ in range(2) for l in range(n - 1)]
-            self.g = [torch.empty((B, d[n]), dtype=torch.float32, device=dev) for _ in range(2)]      # own allocations: aligned as RegressionStep's
-            one = _lib.load().cfm_workspace_bytes(_lib.OP_MLP_TRAIN, B, max(d), max(d[l] * d[l + 1] for l in range(n)))
-            self.ws = torch.empty(2 * one, dtype=torch.uint8, device=dev)      # two workspaces back to back
-            m = max(1, 2 * (n - 1))
-            self.hp = (ctypes.c_void_p * m)(*([h.data_ptr() for h in self.hidden] or [0]))
-            self.zp = (ctypes.c_void_p * m)(*([z.data_ptr() for z in self.preact] or [0]))
-            self.cd = (ctypes.c_int * (n + 1))(*d)
-            self._B = B
-
-    def _tables(self):
-        """(W, b, dW, db): host tables of 2 n device pointers, the first net's layers first; a replaced .grad is put back"""
-        params = [q for l in self.lins for q in (l.weight, l.bias)]
-        for v, p in zip(self._gviews, params):
-            if p.grad is not v:
-                p.grad = v
-        N2 = 2 * self.n
-        return ((ctypes.c_void_p * N2)(*[l.weight.data_ptr() for l in self.lins]),
-                (ctypes.c_void_p * N2)(*[l.bias.data_ptr() for l in self.lins]),
-                (ctypes.c_void_p * N2)(*[self._gviews[2 * l].data_ptr() for l in range(N2)]),
-                (ctypes.c_void_p * N2)(*[self._gviews[2 * l + 1].data_ptr() for l in range(N2)]))
 
     def backward_only(self, t, xt, ut, eps, lambda_t):
         """forward + both losses + backward of both nets; returns ``[flow_loss, score_loss]`` (device tensor)"""
@@ -254,26 +248,18 @@ class SF2MStep:
             raise RuntimeError(f"SF2MStep: the nets have {self.n} Linear layers; the fused step takes at most "
                                f"{self.MAX_LAYERS} (two nets' reduction jobs fill its one table)")
         lib = _lib.load()
-        xt = xt.detach().reshape(xt.shape[0], -1)
-        ut = ut.detach().reshape(ut.shape[0], -1)
-        B, n = xt.shape[0], self.n
-        tv = self.net.time_varying
-        if xt.shape[1] != self.dims[0] - int(bool(tv)) or ut.shape[1] != self.dims[n] or ut.shape[0] != B:
-            raise RuntimeError(f"SF2MStep: xt has {xt.shape[1]} / ut has {ut.shape[1]} columns, the nets map "
-                               f"{self.dims[0] - int(bool(tv))} (+ time) -> {self.dims[n]}")
+        xt, ut, B = self._xt_ut("SF2MStep", xt, ut, same_rows=True)
         if eps.numel() != ut.numel() or eps.shape[0] != B:
             raise RuntimeError(f"SF2MStep: eps has shape {tuple(eps.shape)}, ut {tuple(ut.shape)}")
         if lambda_t.numel() != B:
             raise RuntimeError(f"SF2MStep: lambda_t has {lambda_t.numel()} values for {B} rows (one per row is required)")
         xt = _lib.to_dev_f32(xt, self.dev); ut = _lib.to_dev_f32(ut, self.dev)
         eps = _lib.to_dev_f32(eps.reshape(B, -1), self.dev); lam = _lib.to_dev_f32(lambda_t.reshape(-1), self.dev)
-        tt = _lib.to_dev_f32(t.detach().reshape(-1), self.dev) if tv else None
-        if tv and tt.numel() != B:
-            raise RuntimeError("SF2MStep: one time per row is required")
+        tt = self._times("SF2MStep", t, B)
         self._buffers(B)
         Wp, bp, dWp, dbp = self._tables()
         check(lib.cfm_mlp_sf2m_step_f32(ptr(xt), ptr(tt), ptr(ut), ptr(eps), ptr(lam), Wp, bp, self.hp, self.zp, dWp, dbp,
-                                        self.cd, n, B, ptr(self.g[0]), ptr(self.g[1]), ptr(self.losses),
+                                        self.cd, self.n, B, ptr(self.g[0]), ptr(self.g[1]), ptr(self.losses),
                                         self.score_weight, ptr(self.ws), stream_ptr()),
               "cfm_mlp_sf2m_step_f32")
         return self.losses
@@ -324,19 +310,16 @@ class DSBMStep(SF2MStep):
         B, n = xt.shape[0], self.n
         ft = forward_target.detach().reshape(forward_target.shape[0], -1)
         bt = backward_target.detach().reshape(backward_target.shape[0], -1)
-        tv = self.net.time_varying
-        if xt.shape[1] != self.dims[0] - int(bool(tv)) or ft.shape != (B, self.dims[n]) or bt.shape != ft.shape:
+        if xt.shape[1] != self._in_width() or ft.shape != (B, self.dims[n]) or bt.shape != ft.shape:
             raise RuntimeError(f"DSBMStep: xt has shape {tuple(xt.shape)}, the targets {tuple(ft.shape)} and {tuple(bt.shape)}; "
-                               f"the nets map {self.dims[0] - int(bool(tv))} (+ time) -> {self.dims[n]}")
+                               f"the nets map {self._in_width()} (+ time) -> {self.dims[n]}")
         if forward_scaling.numel() != B or backward_scaling.numel() != B:
             raise RuntimeError(f"DSBMStep: the scalings have {forward_scaling.numel()} and {backward_scaling.numel()} values "
                                f"for {B} rows (one per row is required)")
         xt = _lib.to_dev_f32(xt, self.dev); ft = _lib.to_dev_f32(ft, self.dev); bt = _lib.to_dev_f32(bt, self.dev)
         wf = _lib.to_dev_f32(forward_scaling.detach().reshape(-1), self.dev)
         wb = _lib.to_dev_f32(backward_scaling.detach().reshape(-1), self.dev)
-        tt = _lib.to_dev_f32(t.detach().reshape(-1), self.dev) if tv else None
-        if tv and tt.numel() != B:
-            raise RuntimeError("DSBMStep: one time per row is required")
+        tt = self._times("DSBMStep", t, B)
         self._buffers(B)
         Wp, bp, dWp, dbp = self._tables()
         check(lib.cfm_mlp_dsbm_step_f32(ptr(xt), ptr(tt), ptr(ft), ptr(bt), ptr(wf), ptr(wb), Wp, bp, self.hp, self.zp, dWp, dbp,
