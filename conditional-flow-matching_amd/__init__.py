@@ -25,7 +25,7 @@ from .schedule import (  # noqa: F401
     NoiseScheduler,
 )
 from .cnf import CNF, DifferentiableCNF, RegularizedCNF, log_likelihood  # noqa: F401
-from .ode import DifferentiableNeuralODE  # noqa: F401
+from .ode import AdaptiveDifferentiableNeuralODE, DifferentiableNeuralODE  # noqa: F401
 from .action_matching import action_matching_loss  # noqa: F401
 from .optim import FusedAdam  # noqa: F401
 from .train import DSBMStep, RegressionStep, SF2MStep  # noqa: F401

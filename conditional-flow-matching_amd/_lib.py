@@ -114,6 +114,10 @@ SIGNATURES = {
     "cfm_action_matching_grad_f32": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "cfm_ode_fixed_grad_f32": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cfm_ode_fixed_grad_available": (_i, [_vp, _i]),
+    "cfm_ode_adaptive_rec_mlp_f32": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _f, _f, _vp, _vp, _vp, _i, _vp, _vp, _vp,
+                                         _vp, _vp]),
+    "cfm_ode_adaptive_grad_f32": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cfm_ode_adaptive_grad_available": (_i, [_vp, _i]),
 }
 # solver selectors of the cfm_ode_adaptive_* / cfm_ode_fixed_* entries (include/cfm_gfx950.h)
 ODE_TABLEAU = {"dopri5": 0, "tsit5": 1}
@@ -143,6 +147,7 @@ EXTRA_SIGNATURES = {
     "cfm_ode_set_fused": (None, [_i]),
     "cfm_mlp_set_glds": (None, [_i]),
     "cfm_mlp_get_glds": (_i, []),
+    "cfm_ode_rec_resident_rows": (_i, [_i]),
     "cfm_set_blocking_sync": (None, [_i]),
 }
 

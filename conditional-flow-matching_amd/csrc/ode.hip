@@ -329,17 +329,31 @@ static int read_red(hipStream_t s, const double* dev, int count, double* host) {
     return 0;
 }
 
-template <int TAB, int MODE, int FIELD>
+// The record of an accepted step that the recording solve keeps (cfm_ode_adaptive_rec_mlp_f32) and its gradient replays
+// (ode_adaptive_grad.h): solver-space t and dt of the stages, the time k_1 was evaluated at (FSAL: the previous step's
+// last stage time, which is not t in general after a landing step), the t_span index the step end lands on or -1.
+struct OdeStepRec { float t, dt, t_k1; int out; };
+static_assert(sizeof(OdeStepRec) == 16, "the step log's record");
+struct OdeRec { OdeStepRec* log; float* ysteps; int max_steps; };   // log [max_steps], ysteps [max_steps, B, d]: device
+
+template <int TAB, int MODE, int FIELD, bool REC = false>
 static int ode_dopri5_small(const float* const* W, const float* const* b, const int* dims, int B, int d,
                             const float* t_span, int n_t, float tsign, const float* eps, float atol, float rtol,
                             float* traj, int* n_steps, int* nfe, float* xbuf, float* kbuf, float* tspan_dev,
-                            void* state_dev, char* sync_dev, float t0, float dt0, int evals0, hipStream_t s);
+                            void* state_dev, char* sync_dev, float t0, float dt0, int evals0, hipStream_t s,
+                            OdeRec rec = OdeRec{nullptr, nullptr, 0}, int* n_accepted = nullptr);
 
 // the tableau selector (validated by the entry points) picks the instantiation
 template <int MODE, int FIELD = FIELD_MLP, class... Args>
 static int ode_adaptive_small(int tab, Args... args) {
     return tab == CFM_ODE_TSIT5 ? ode_dopri5_small<CFM_ODE_TSIT5, MODE, FIELD>(args...)
                                 : ode_dopri5_small<CFM_ODE_DOPRI5, MODE, FIELD>(args...);
+}
+// the recording variant: the plain MLP field only
+template <class... Args>
+static int ode_adaptive_small_rec(int tab, Args... args) {
+    return tab == CFM_ODE_TSIT5 ? ode_dopri5_small<CFM_ODE_TSIT5, AUG_NONE, FIELD_MLP, true>(args...)
+                                : ode_dopri5_small<CFM_ODE_DOPRI5, AUG_NONE, FIELD_MLP, true>(args...);
 }
 
 // Time direction of a t_span (torchdyn's rule): a strictly decreasing grid is integrated as
@@ -394,7 +408,8 @@ static int ode_init_step(F&& f, size_t n, float t, float hsign, float atol, floa
 
 static int ode_dopri5_layers(int tab, const float* const* W, const float* const* b, const int* dims, int n_layers, int d,
                              const float* x0, int B, const float* t_span, int n_t, float tsign, float atol,
-                             float rtol, float* traj, int* n_steps, int* nfe, void* ws, void* stream);
+                             float rtol, float* traj, int* n_steps, int* nfe, void* ws, void* stream,
+                             const OdeRec* rec = nullptr, int* n_accepted = nullptr);
 
 extern "C" int cfm_ode_adaptive_mlp_f32(const float* const* W, const float* const* b, const int* dims,
                                         int n_layers, const float* x0, int B, const float* t_span,
@@ -420,14 +435,43 @@ extern "C" int cfm_ode_dopri5_mlp_f32(const float* const* W, const float* const*
     return cfm_ode_adaptive_mlp_f32(W, b, dims, n_layers, x0, B, t_span, n_t, CFM_ODE_DOPRI5, atol, rtol, traj, n_steps, nfe, ws, stream);
 }
 
+// cfm_ode_adaptive_mlp_f32 on the recording instantiation of the one-launch kernel: the same arithmetic (traj, n_steps and
+// nfe are its bits), plus the starting state and the record of every accepted step.  CFM_EINVAL wherever the plain entry
+// would leave that kernel; CFM_ENOCONV when the log filled up before the end of the grid.
+extern "C" int cfm_ode_adaptive_rec_mlp_f32(const float* const* W, const float* const* b, const int* dims,
+                                            int n_layers, const float* x0, int B, const float* t_span,
+                                            int n_t, int tableau, float atol, float rtol, float* traj, int* n_steps,
+                                            int* nfe, int max_steps, void* log, float* ysteps, int* n_accepted, void* ws,
+                                            void* stream) {
+    int d;
+    if (!W || !b || !x0 || !t_span || !traj || !ws || B <= 0 || n_t < 2 || !rk_adaptive_known(tableau)) return CFM_EINVAL;
+    if (max_steps < 1 || !log || !ysteps || !n_accepted) return CFM_EINVAL;
+    int rc = check_mlp(dims, n_layers, &d);
+    if (rc) return rc;
+    float* ts = (float*)malloc(sizeof(float) * (size_t)n_t);
+    if (!ts) return CFM_EINVAL;
+    const float tsign = ode_direction(t_span, n_t, ts);
+    if (tsign == 0.f) { free(ts); return CFM_EINVAL; }
+    const OdeRec rec{(OdeStepRec*)log, ysteps, max_steps};
+    *n_accepted = 0;
+    rc = ode_dopri5_layers(tableau, W, b, dims, n_layers, d, x0, B, ts, n_t, tsign, atol, rtol, traj, n_steps, nfe, ws, stream,
+                           &rec, n_accepted);
+    free(ts);
+    return rc;
+}
+
 static int ode_dopri5_layers(int tab, const float* const* W, const float* const* b, const int* dims, int n_layers, int d,
                              const float* x0, int B, const float* t_span, int n_t, float tsign, float atol,
-                             float rtol, float* traj, int* n_steps, int* nfe, void* ws, void* stream) {
+                             float rtol, float* traj, int* n_steps, int* nfe, void* ws, void* stream,
+                             const OdeRec* rec, int* n_accepted) {
     int rc;
     hipStream_t s = (hipStream_t)stream;
     const int width = maxwidth(dims, n_layers);
     OdeWs w = ode_carve(ws, B, width, d);
     const size_t n = (size_t)B * d;
+    // small vector fields: the whole step attempt in one kernel, controller on the device
+    const bool small = ode_small_enabled() && small_envelope(dims, n_layers, nullptr) == 0 && d + 1 <= SM_W && n >= (size_t)n_t;
+    if (rec && !small) return CFM_EINVAL;              // only the one-launch kernel records its steps
     const int nb = ode_blocks(n);
     int evals = 0, steps = 0;
 
@@ -451,8 +495,10 @@ static int ode_dopri5_layers(int tab, const float* const* W, const float* const*
     rc = ode_init_step(f, n, t, tsign, atol, rtol, w, s, &dt);
     if (rc) return rc;
 
-    // small vector fields: the whole step attempt in one kernel, controller on the device
-    if (ode_small_enabled() && small_envelope(dims, n_layers, nullptr) == 0 && d + 1 <= SM_W && n >= (size_t)n_t)
+    if (small && rec)
+        return ode_adaptive_small_rec(tab, W, b, dims, B, d, t_span, n_t, tsign, nullptr, atol, rtol, traj, n_steps, nfe, w.x,
+                                      w.k[0], w.xt, (void*)(w.red + 16), w.sync, t, dt, evals, s, *rec, n_accepted);
+    if (small)
         return ode_adaptive_small<0>(tab, W, b, dims, B, d, t_span, n_t, tsign, nullptr, atol, rtol, traj, n_steps, nfe, w.x,
                                    w.k[0], w.xt, (void*)(w.red + 16), w.sync, t, dt, evals, s);
 
@@ -578,13 +624,18 @@ __device__ __forceinline__ bool sm_grid_allsum(double* __restrict__ row, double 
 // decision and next step size from that sum (the fp32 controller of the host loop above).  `lines` is only
 // touched by SM_PROF builds (phase stamps).  FIELD: what the stage evaluations call (FIELD_GRAD: grad_field.h, plain
 // solves only); everything around the call is the same code.
-template <int TAB, bool RESIDENT, int MODE, int FIELD = FIELD_MLP>
+// REC (plain MLP field): every accepted step n leaves the state it started from in R.ysteps[n] (each workgroup its own rows)
+// and its record in R.log[n] (workgroup 0, lane 0); the accepted count nacc and the FSAL time tk1 are functions of the
+// replicated SmState history, so every workgroup holds the same values.  A full log (nacc == R.max_steps before done) ends
+// the loop in every workgroup at the same attempt, before its re-arm and rendezvous, as max_attempts does: err = 3.
+template <int TAB, bool RESIDENT, int MODE, int FIELD = FIELD_MLP, bool REC = false>
 __global__ __launch_bounds__(256) void ode_small_dopri(SmArgs A, int B, int d, SmState* __restrict__ st_io,
                                                     float* __restrict__ xbuf, float* __restrict__ kbuf,
                                                     const float* __restrict__ tspan, int n_t, float atol, float rtol,
                                                     float* __restrict__ traj, double* __restrict__ partial,
                                                     unsigned long long* __restrict__ lines, int max_attempts,
-                                                    float tsign, const float* __restrict__ eps) {
+                                                    float tsign, const float* __restrict__ eps, OdeRec R) {
+    static_assert(!REC || (MODE == AUG_NONE && FIELD == FIELD_MLP), "the plain MLP field records its steps");
     // MODE != AUG_NONE: the state is [B, 1 + d] (column 0 = l, the log-density accumulator, d l / dt = -div); each
     // row's l and its stage values sit in the registers of every lane that holds the row
     constexpr bool AUG = MODE != AUG_NONE;
@@ -626,8 +677,11 @@ __global__ __launch_bounds__(256) void ode_small_dopri(SmArgs A, int B, int d, S
     }
     __syncthreads();                                  // weights staged
     int attempt = 0, err = 0;
+    int nacc = 0;                                     // REC: accepted steps so far
+    float tk1 = st.t;                                 // REC: the time k_1 of the next accepted step was evaluated at
     for (; !st.done; ++attempt) {
         if (attempt >= max_attempts) { err = 1; break; }
+        if (REC && nacc >= R.max_steps) { err = 3; break; }
         if (tid == 0)                                 // re-arm this workgroup's slot of the next attempt
             __hip_atomic_store(&partial[(size_t)((attempt + 1) % 3) * SM_MAXGRID + blockIdx.x], __longlong_as_double(-1ll),
                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -749,6 +803,14 @@ __global__ __launch_bounds__(256) void ode_small_dopri(SmArgs A, int B, int d, S
                         }
                     }
                 }
+                if constexpr (REC) {
+                    float* ys = R.ysteps + (size_t)nacc * n;
+#pragma unroll
+                    for (int i = 0; i < SM_V; ++i) {
+                        const int gr = blockIdx.x * SM_ROWS + sm_row(i, lane);
+                        if (gr < B && col < d) ys[(size_t)gr * D + col] = x.v[i];
+                    }
+                }
                 x = y; k0 = k6;                       // FSAL
                 if constexpr (AUG) { xl = yl; l0 = l6; }
             }
@@ -759,6 +821,23 @@ __global__ __launch_bounds__(256) void ode_small_dopri(SmArgs A, int B, int d, S
                 const int rows = (B - row0 < SM_ROWS) ? B - row0 : SM_ROWS;
                 const size_t base = (size_t)row0 * D;
                 for (int e = tid; e < rows * D; e += 256) dst[base + e] = xn[base + e];   // own rows, written above
+            }
+        }
+        if constexpr (REC && !RESIDENT) {
+            if (accept) {
+                float* ys = R.ysteps + (size_t)nacc * n;
+                for (int row0 = blockIdx.x * SM_ROWS; row0 < B; row0 += gridDim.x * SM_ROWS) {
+                    const int rows = (B - row0 < SM_ROWS) ? B - row0 : SM_ROWS;
+                    const size_t base = (size_t)row0 * D;
+                    for (int e = tid; e < rows * D; e += 256) ys[base + e] = x_in[base + e];   // own rows
+                }
+            }
+        }
+        if constexpr (REC) {
+            if (accept) {
+                if (blockIdx.x == 0 && tid == 0) R.log[nacc] = OdeStepRec{st.t, dt, tk1, lands ? st.ckpt : -1};
+                tk1 = st.t + rk_c<TAB>(5) * dt;       // the stage time of k_7, the next accepted step's k_1
+                ++nacc;
             }
         }
         SmState nx = st;
@@ -776,30 +855,53 @@ __global__ __launch_bounds__(256) void ode_small_dopri(SmArgs A, int B, int d, S
         nx.done = (nx.t < T) ? 0 : 1;
         st = nx;
     }
-    if (blockIdx.x == 0 && tid == 0) { st.pad = err; st_io[1] = st; }
+    if (blockIdx.x == 0 && tid == 0) {
+        st.pad = err; st_io[1] = st;
+        if constexpr (REC) { SmState cnt = st; cnt.steps = nacc; st_io[2] = cnt; }
+    }
 }
 
-template <int TAB, int MODE, int FIELD>
-static int ode_dopri5_small(const float* const* W, const float* const* b, const int* dims, int B, int d,
-                            const float* t_span, int n_t, float tsign, const float* eps, float atol, float rtol,
-                            float* traj, int* n_steps, int* nfe, float* xbuf, float* kbuf, float* tspan_dev,
-                            void* state_dev, char* sync_dev, float t0, float dt0, int evals0, hipStream_t s) {
-    const SmArgs A = small_args(W, b, dims);
+// Workgroups of ode_small_dopri<TAB, ., MODE, FIELD, REC> that can be resident at once (the grid rendezvous needs grid <= this);
+// -1: the query failed.  One result per device and instantiation: the grid is sized from the occupancy of the kernel launched.
+template <int TAB, int MODE, int FIELD, bool REC>
+static int ode_dopri_resident() {
     constexpr size_t lds = small_lds_bytes(1, 2, MODE != AUG_NONE);
-    // (one result per TAB, MODE and FIELD: the grid is sized from the occupancy of the instantiation that is launched)
-    const int resident = cfm_once_per_device([] {
-        hipError_t e = hipFuncSetAttribute((const void*)ode_small_dopri<TAB, true, MODE, FIELD>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-        hipError_t e2 = hipFuncSetAttribute((const void*)ode_small_dopri<TAB, false, MODE, FIELD>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-        // workgroups that can be resident at once: the grid rendezvous needs grid <= this
+    return cfm_once_per_device([] {
+        hipError_t e = hipFuncSetAttribute((const void*)ode_small_dopri<TAB, true, MODE, FIELD, REC>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+        hipError_t e2 = hipFuncSetAttribute((const void*)ode_small_dopri<TAB, false, MODE, FIELD, REC>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
         int pa = 0, pb = 0;
         if (e == hipSuccess && e2 == hipSuccess &&
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&pa, (const void*)ode_small_dopri<TAB, true, MODE, FIELD>, 256, lds) == hipSuccess &&
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&pb, (const void*)ode_small_dopri<TAB, false, MODE, FIELD>, 256, lds) == hipSuccess &&
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&pa, (const void*)ode_small_dopri<TAB, true, MODE, FIELD, REC>, 256, lds) == hipSuccess &&
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&pb, (const void*)ode_small_dopri<TAB, false, MODE, FIELD, REC>, 256, lds) == hipSuccess &&
             pa > 0 && pb > 0)
             return cfm_device_cus() * (pa < pb ? pa : pb);
         return -1;
     });
-    if (resident < 0) return CFM_EINVAL;
+}
+
+// Rows up to which the recording solve keeps its state in registers (one 16-row tile per resident workgroup); above, x and
+// k_1 travel through the parity buffers.  For tests and measurements that must sit on either side of that limit; < 0: the
+// occupancy query failed or the tableau is unknown.
+extern "C" int cfm_ode_rec_resident_rows(int tableau) {
+    if (!rk_adaptive_known(tableau)) return CFM_EINVAL;
+    int g = tableau == CFM_ODE_TSIT5 ? ode_dopri_resident<CFM_ODE_TSIT5, AUG_NONE, FIELD_MLP, true>()
+                                     : ode_dopri_resident<CFM_ODE_DOPRI5, AUG_NONE, FIELD_MLP, true>();
+    if (g < 0) return CFM_EINVAL;
+    return SM_ROWS * (g < SM_MAXGRID ? g : SM_MAXGRID);
+}
+
+template <int TAB, int MODE, int FIELD, bool REC>
+static int ode_dopri5_small(const float* const* W, const float* const* b, const int* dims, int B, int d,
+                            const float* t_span, int n_t, float tsign, const float* eps, float atol, float rtol,
+                            float* traj, int* n_steps, int* nfe, float* xbuf, float* kbuf, float* tspan_dev,
+                            void* state_dev, char* sync_dev, float t0, float dt0, int evals0, hipStream_t s,
+                            OdeRec rec, int* n_accepted) {
+    const SmArgs A = small_args(W, b, dims);
+    constexpr size_t lds = small_lds_bytes(1, 2, MODE != AUG_NONE);
+    const int resident = ode_dopri_resident<TAB, MODE, FIELD, REC>();
+    // (the recording entry answers CFM_EINVAL only before any GPU work, as a decline its caller may act on: a query that
+    // fails here, after the first evaluations, is an error of its own)
+    if (resident < 0) return REC ? (int)hipErrorInvalidDeviceFunction : CFM_EINVAL;
     int rc = cfm_hip(hipMemcpyAsync(tspan_dev, t_span, sizeof(float) * n_t, hipMemcpyHostToDevice, s));
     if (rc) return rc;
     SmState h[2];
@@ -820,22 +922,27 @@ static int ode_dopri5_small(const float* const* W, const float* const* b, const 
     // CFM_ETIMEOUT after 4 s).  The call is synchronous anyway: the lock is held until the solve has finished.
     std::lock_guard<std::mutex> persistent_lock(g_persistent_mu);
     if (tiles <= grid)
-        hipLaunchKernelGGL((ode_small_dopri<TAB, true, MODE, FIELD>), dim3(grid), dim3(256), lds, s, A, B, d, st, xbuf, kbuf, tspan_dev, n_t,
-                           atol, rtol, traj, partial, lines, 1000000, tsign, eps);
+        hipLaunchKernelGGL((ode_small_dopri<TAB, true, MODE, FIELD, REC>), dim3(grid), dim3(256), lds, s, A, B, d, st, xbuf, kbuf, tspan_dev, n_t,
+                           atol, rtol, traj, partial, lines, 1000000, tsign, eps, rec);
     else
-        hipLaunchKernelGGL((ode_small_dopri<TAB, false, MODE, FIELD>), dim3(grid), dim3(256), lds, s, A, B, d, st, xbuf, kbuf, tspan_dev, n_t,
-                           atol, rtol, traj, partial, lines, 1000000, tsign, eps);
+        hipLaunchKernelGGL((ode_small_dopri<TAB, false, MODE, FIELD, REC>), dim3(grid), dim3(256), lds, s, A, B, d, st, xbuf, kbuf, tspan_dev, n_t,
+                           atol, rtol, traj, partial, lines, 1000000, tsign, eps, rec);
     rc = cfm_status();
     if (rc) return rc;
-    SmState cur;
+    SmState cur, cnt;
     rc = cfm_hip(hipMemcpyAsync(&cur, st + 1, sizeof(SmState), hipMemcpyDeviceToHost, s));
     if (rc) return rc;
+    if (REC) {
+        rc = cfm_hip(hipMemcpyAsync(&cnt, st + 2, sizeof(SmState), hipMemcpyDeviceToHost, s));
+        if (rc) return rc;
+    }
     rc = cfm_hip(hipStreamSynchronize(s));
     if (rc) return rc;
+    if (REC && n_accepted) *n_accepted = cnt.steps;
     if (n_steps) *n_steps = cur.steps;
     if (nfe) *nfe = cur.evals;
     if (cur.pad == 2) return CFM_ETIMEOUT;
-    return cur.done && cur.pad == 0 ? 0 : CFM_ENOCONV;
+    return cur.done && cur.pad == 0 ? 0 : CFM_ENOCONV;     // (pad 1: max_attempts, pad 3: the step log is full)
 }
 
 #include "sde_small.h"
@@ -1367,6 +1474,10 @@ extern "C" int cfm_ode_adaptive_gradmlp_f32(const float* const* W, const float* 
 
 // ---- training through the sampler: the gradient of the plain fixed-step solves (ode_small_fixed_grad, cfm_ode_fixed_grad_f32) ----
 #include "ode_grad.h"
+
+// ---- training through the adaptive sampler: the gradient of the accepted steps of the recording solve
+// (ode_small_adaptive_grad, cfm_ode_adaptive_grad_f32) ----
+#include "ode_adaptive_grad.h"
 
 // ---- action-matching training: loss and parameter gradient in one launch (cfm_action_matching_grad_f32) ----
 #include "action_grad.h"

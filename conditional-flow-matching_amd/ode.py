@@ -22,6 +22,8 @@ attempts for the adaptive ones.
 
 ``NeuralODE.trajectory`` carries no graph.  ``DifferentiableNeuralODE`` (fixed-step solvers) returns the same values with
 one: forward ``cfm_ode_fixed_mlp_f32``, backward ``cfm_ode_fixed_grad_f32``, the gradient of the recurrence.
+``AdaptiveDifferentiableNeuralODE`` does the same for ``dopri5`` / ``tsit5``: forward ``cfm_ode_adaptive_rec_mlp_f32``, which
+records its accepted steps, backward ``cfm_ode_adaptive_grad_f32`` over them, the step sequence a constant.
 
 ``t_span`` is strictly monotone.  A decreasing one integrates backward in time as torchdyn does
 (SURVEY.md A.4): ``g(s, x) = -f(-s, x)`` on ``s = -t_span``.
@@ -70,7 +72,8 @@ SOLVERS = ("euler", "midpoint", "rk4", "dopri5", "tsit5")
 
 
 def _hairer_norm(x):
-    return x.abs().pow(2).mean().sqrt()
+    """RMS norm, for the step controller alone: detached, so the step sequence is a constant of any graph."""
+    return x.detach().abs().pow(2).mean().sqrt()
 
 
 def _check_t_span(ts):
@@ -234,7 +237,9 @@ class NeuralODE(torch.nn.Module):
         return traj.to(x.device)
 
     # ---- generic vector fields: same algorithm at tensor level ----
-    def _trajectory_generic(self, x, t_span):
+    def _trajectory_generic(self, x, t_span, record=None, max_steps=None):
+        """record (adaptive solvers): a list that receives (t, dt, t_k1, out) of every accepted step, the step log of
+        AdaptiveDifferentiableNeuralODE; more than max_steps of them raise."""
         f = self.vf
         ts = torch.as_tensor(t_span, dtype=torch.float32)
         sol = [x]
@@ -289,7 +294,11 @@ class NeuralODE(torch.nn.Module):
             h1 = f32(f32(0.01) / max(d1, d2)) ** (f32(1.0) / (order + f32(1.0)))
         dt = f32(min(f32(100) * h0, h1))
         ckpt, steps = 1, 0
+        tk1 = t                     # where k1 was evaluated (FSAL: the accepted step's last stage time, not t after a landing)
         while t < T:
+            if record is not None and len(record) >= max_steps:
+                raise RuntimeError(f"the step log is full: max_steps = {max_steps} accepted steps did not reach the end "
+                                   f"of t_span (t = {float(sign * t)}); raise max_steps")
             if t + dt > T:
                 dt = f32(T - t)
             dt_old, flag = dt, False
@@ -305,6 +314,9 @@ class NeuralODE(torch.nn.Module):
             ratio = f32(float(_hairer_norm(err / (atol + rtol * torch.max(x.abs(), x_new.abs())))))
             steps += 1
             if ratio <= 1:
+                if record is not None:
+                    record.append((float(t), float(dt), float(tk1), ckpt if lands else -1))
+                    tk1 = f32(t + f32(tab_c[5]) * dt)
                 if lands:
                     t = f32(ts[ckpt]); sol.append(x_new); ckpt += 1
                 else:
@@ -329,11 +341,14 @@ class _Declined(Exception):
     the grid has more points than the solve's workspace holds (n_t > 3 B width).  The caller runs its generic path."""
 
 
-def _solve_forward(ctx, what, x, ts, dims, params, mid, after=(), declines=False):
-    """The forward of a differentiable fixed-step solve of a 4-layer net: one call of the entry ``what`` with ``mid``
+def _solve_forward(ctx, what, x, ts, dims, params, mid, after=(), declines=False, tail=None):
+    """The forward of a differentiable solve of a 4-layer net: one call of the entry ``what`` with ``mid``
     between the grid and the trajectory and ``after`` behind it.  params: the flat (W_0, b_0, W_1, ...) inputs of the
     Function; ts: the float32 host grid.  Saves the trajectory [n_t, B, width] and the parameters on ctx for
-    ``_solve_backward`` and returns the trajectory.  declines: CFM_EINVAL raises ``_Declined`` instead of an error."""
+    ``_solve_backward`` and returns the trajectory.  declines: CFM_EINVAL raises ``_Declined`` instead of an error.
+    tail: a recording solve's ``(alloc, done)``: ``alloc(B, width, dev)`` gives the entry's arguments between nfe and the
+    workspace, ``done(rc, nfe)`` looks at the return code before it is checked and gives the tensors that are saved in
+    the trajectory's place."""
     lib = _lib.load()
     dev = x.device
     Ws, bs, Wp, bp = _lib.param_tables(params, dev)
@@ -345,31 +360,34 @@ def _solve_forward(ctx, what, x, ts, dims, params, mid, after=(), declines=False
     ws = _lib.workspace(_lib.OP_ODE, B, max(dims[1:4]), width, dev)
     nfe = ctypes.c_int(0)
     rc = getattr(lib, what)(Wp, bp, cdims, 4, ptr(xd), B, ts.ctypes.data_as(ctypes.c_void_p), n_t, *mid, ptr(traj), *after,
-                            ctypes.byref(nfe), ptr(ws), stream_ptr())
+                            ctypes.byref(nfe), *(tail[0](B, width, dev) if tail else ()), ptr(ws), stream_ptr())
     if declines and rc == -1:
         raise _Declined()
+    state = tail[1](rc, nfe.value) if tail else (traj,)
     check(rc, what)
-    ctx.ts, ctx.dims = ts, dims
-    ctx.save_for_backward(traj, *params)
+    ctx.ts, ctx.dims, ctx.n_state = ts, dims, len(state)
+    ctx.save_for_backward(*state, *params)
     return traj
 
 
-def _solve_backward(ctx, what, op, g, mid, n_other):
+def _solve_backward(ctx, what, op, g, mid, n_other, head=None):
     """The backward of ``_solve_forward``: one call of the entry ``what`` over the saved trajectory, with ``mid`` between
     the grid and the upstream gradient g; ``op`` sizes its workspace.  Returns the Function's gradients: the state's (if
-    needed), None for its ``n_other`` further non-parameter inputs, then (dW_0, db_0, dW_1, ...)."""
+    needed), None for its ``n_other`` further non-parameter inputs, then (dW_0, db_0, dW_1, ...).
+    head: a recording solve's ``head(state, B, n_t)``: the entry's arguments between the layer count and ``mid``, from the
+    tensors its forward saved (the first of them [., B, width]), in place of (trajectory, B, grid, n_t)."""
     lib = _lib.load()
-    traj, *params = ctx.saved_tensors
-    dev = traj.device
+    state, params = ctx.saved_tensors[:ctx.n_state], ctx.saved_tensors[ctx.n_state:]
+    dev = state[0].device
     Ws, bs, Wp, bp = _lib.param_tables(params, dev)
     dWs, dbs, dWp, dbp = _lib.grad_tables(Ws, bs)
     cdims = (ctypes.c_int * 5)(*ctx.dims)
-    n_t, B, width = traj.shape
+    n_t, (B, width) = ctx.ts.shape[0], state[0].shape[1:]
     gd = _lib.to_dev_f32(g, dev)
     g0 = torch.empty((B, width), dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
     ws = _lib.workspace(op, B, n_t, 0, dev)
-    check(getattr(lib, what)(Wp, bp, cdims, 4, ptr(traj), B, ctx.ts.ctypes.data_as(ctypes.c_void_p), n_t, *mid, ptr(gd),
-                             dWp, dbp, ptr(g0), ptr(ws), stream_ptr()), what)
+    first = head(state, B, n_t) if head else (ptr(state[0]), B, ctx.ts.ctypes.data_as(ctypes.c_void_p), n_t)
+    check(getattr(lib, what)(Wp, bp, cdims, 4, *first, *mid, ptr(gd), dWp, dbp, ptr(g0), ptr(ws), stream_ptr()), what)
     grads = [None] * len(params)
     grads[0::2] = dWs
     grads[1::2] = dbs
@@ -441,3 +459,107 @@ class DifferentiableNeuralODE(NeuralODE):
         self.n_steps = ts.numel() - 1
         self.nfe = len(FIXED_TABLEAUS[self.solver]["b"]) * self.n_steps
         return _FixedStepODEFunction.apply(x, np.ascontiguousarray(ts.numpy()), scheme, dims, *params)
+
+
+class _AdaptiveODEFunction(torch.autograd.Function):
+    """The trajectory [n_t, B, d] of an adaptive solve that records its accepted steps (cfm_ode_adaptive_rec_mlp_f32);
+    backward: cfm_ode_adaptive_grad_f32 over ysteps[:n_accepted] and the log.  ``out`` (a dict) receives nfe, n_steps,
+    n_accepted and step_log."""
+
+    @staticmethod
+    def forward(ctx, x, ts, tab, atol, rtol, max_steps, out, dims, *params):
+        steps, n_acc = ctypes.c_int(0), ctypes.c_int(0)
+        bufs = []
+
+        def alloc(B, width, dev):
+            bufs.append(torch.empty((max_steps, 4), dtype=torch.float32, device=dev))            # 16-byte records
+            bufs.append(torch.empty((max_steps, B, width), dtype=torch.float32, device=dev))
+            return max_steps, ptr(bufs[0]), ptr(bufs[1]), ctypes.byref(n_acc)
+
+        def done(rc, nfe):
+            if rc == -3 and n_acc.value >= max_steps:
+                raise RuntimeError(f"cfm_ode_adaptive_rec_mlp_f32: the step log is full: max_steps = {max_steps} accepted "
+                                   "steps did not reach the end of t_span; raise max_steps")
+            n = n_acc.value
+            log = bufs[0][:n].clone()
+            host = log.cpu()
+            out.update(nfe=nfe, n_steps=steps.value, n_accepted=n, step_log=torch.cat(
+                [host[:, :3].double(), host.view(torch.int32)[:, 3:].double()], 1))
+            return bufs[1][:n].clone(), log          # (copies: the max_steps buffers go back to the allocator)
+
+        ctx.tab, ctx.tsign = tab, (-1.0 if ts[1] < ts[0] else 1.0)
+        return _solve_forward(ctx, "cfm_ode_adaptive_rec_mlp_f32", x, ts, dims, params, (tab, atol, rtol),
+                              (ctypes.byref(steps),), declines=True, tail=(alloc, done))
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        def head(state, B, n_t):
+            return ptr(state[0]), ptr(state[1]), state[0].shape[0], B, n_t
+        return _solve_backward(ctx, "cfm_ode_adaptive_grad_f32", _lib.OP_ODE_GRAD, g, (ctx.tab, ctx.tsign), 7, head=head)
+
+
+class AdaptiveDifferentiableNeuralODE(NeuralODE):
+    """``NeuralODE`` on ``dopri5`` / ``tsit5`` whose trajectory carries a gradient: the reference's standard sampler call
+    ``NeuralODE(torch_wrapper(model), solver="dopri5", sensitivity="adjoint", atol, rtol)`` with a loss on it.
+
+    ``trajectory(x, t_span)`` returns ``[n_t, B, d]`` (n_t >= 2, either direction), differentiable with respect to ``x`` and
+    the field's parameters.  The gradient is that of the recurrence of ACCEPTED steps the forward ran, the step sequence
+    taken as a constant (discretise-then-optimise): rejected attempts contribute nothing and nothing flows
+    through the controller, ``t_span``, ``atol`` or ``rtol``.  It is autograd through ``NeuralODE._trajectory_generic``,
+    whose controller reads Python floats only.
+
+    After a call: ``last_path``, ``nfe``, ``n_steps`` (attempts), ``n_accepted`` and ``step_log``, a ``[n_accepted, 4]``
+    float64 CPU tensor of ``t, dt, t_k1, out`` per accepted step: solver-space (sign * t) start and size, the time its
+    first slope was evaluated at, the ``t_span`` index its end lands on or -1.  More than ``max_steps`` accepted steps
+    raise a ``RuntimeError``; there is no second solve.
+
+    ``last_path == "hip"``: the envelope of ``DifferentiableNeuralODE`` and the one-launch adaptive kernel takes the solve
+    (``B d >= n_t``).  Forward ``cfm_ode_adaptive_rec_mlp_f32``, bit-equal to ``NeuralODE(vf, solver).trajectory``; backward
+    one call of ``cfm_ode_adaptive_grad_f32``, once differentiable.  ``"generic"``: everything else, the parent's loop in
+    differentiable torch ops."""
+
+    def __init__(self, vector_field, solver="dopri5", atol=1e-3, rtol=1e-3, max_steps=512, **kwargs):
+        if solver not in ADAPTIVE_TABLEAUS:
+            raise NotImplementedError(f"solver {solver!r}: the adaptive pairs, one of {tuple(ADAPTIVE_TABLEAUS)} "
+                                      "(DifferentiableNeuralODE has the fixed-step schemes)")
+        super().__init__(vector_field, solver=solver, atol=atol, rtol=rtol, **kwargs)
+        if int(max_steps) < 1:
+            raise ValueError("max_steps must be at least 1")
+        self.max_steps = int(max_steps)
+        self.n_accepted = 0
+        self.step_log = None
+
+    def _hip_grad_mlp(self, x):
+        """The MLP when cfm_ode_adaptive_grad_f32 takes the solve of this state, else None: the envelope test of
+        DifferentiableNeuralODE._hip_grad_mlp (borrowed, not restated), then the adaptive entry's own answer."""
+        m = DifferentiableNeuralODE._hip_grad_mlp(self, x)
+        if m is None or _lib.load().cfm_ode_adaptive_grad_available((ctypes.c_int * 5)(*m.dims()), 4) != 0:
+            return None
+        return m
+
+    def trajectory(self, x, t_span):
+        ts = torch.as_tensor(t_span).detach().to(dtype=torch.float32).cpu()
+        _check_t_span(ts)
+        if ts.numel() < 2:
+            raise ValueError("an adaptive solve needs at least two t_span points")
+        m = self._hip_grad_mlp(x)
+        if m is not None:
+            params = [p for l in m._linears() for p in (l.weight, l.bias)]
+            out = {}
+            try:
+                traj = _AdaptiveODEFunction.apply(x, np.ascontiguousarray(ts.numpy()), _lib.ODE_TABLEAU[self.solver], self.atol,
+                                                  self.rtol, self.max_steps, out, m.dims(), *params)
+            except _Declined:             # B d < n_t, or the fused path was switched off after the envelope test: the entry
+                                          # declines before any GPU work; whatever fails later is an error, not a decline
+                traj = None
+            if traj is not None:
+                self.last_path = "hip"
+                self.nfe, self.n_steps, self.n_accepted, self.step_log = out["nfe"], out["n_steps"], out["n_accepted"], out["step_log"]
+                return traj
+        self.last_path = "generic"
+        record = []
+        traj = self._trajectory_generic(x, ts, record=record, max_steps=self.max_steps)
+        self.n_accepted = len(record)
+        self.step_log = torch.tensor(record, dtype=torch.float64).reshape(-1, 4)
+        return traj

@@ -59,7 +59,7 @@ extern "C" {
 #define CFM_OP_TRANSPORT     9   /* cfm_transport_exact_f32 (B0, B1, 0) */
 #define CFM_OP_CNF_GRAD     10   /* cfm_cnf_euler_grad_f32 (B, n_t, 0): per-workgroup partial gradients + t_span */
 #define CFM_OP_ACTION_GRAD  11   /* cfm_action_matching_grad_f32 (B, 0, 0): per-workgroup partial gradients + loss terms */
-#define CFM_OP_ODE_GRAD     12   /* cfm_ode_fixed_grad_f32 (B, n_t, 0): per-workgroup partial gradients + t_span */
+#define CFM_OP_ODE_GRAD     12   /* cfm_ode_fixed_grad_f32, cfm_ode_adaptive_grad_f32 (B, n_t, 0): per-workgroup partial gradients + t_span */
 
 /* variants for cfm_sample_xt_ut_f32 (reference class in parentheses) */
 #define CFM_VARIANT_ICFM   0  /* ConditionalFlowMatcher / ExactOT...          */
@@ -652,6 +652,36 @@ int cfm_ode_fixed_grad_f32(const float* const* W, const float* const* b, const i
  * caller that differentiates through the solve (utils_cifar.py:63) asks before the forward, since a backward pass cannot
  * fall back. */
 int cfm_ode_fixed_grad_available(const int* dims, int n_layers);
+
+/* Training through the adaptive sampler: NeuralODE(model, solver="dopri5" | "tsit5", sensitivity="adjoint", atol, rtol)
+ * with a loss on node(x, t_span) (examples/images/cifar10/utils_cifar.py:63-68; the reference's standard sampler call).
+ * Discretise-then-optimise: the gradient of the recurrence of ACCEPTED steps the forward ran, the step sequence taken as
+ * a constant; rejected attempts contribute nothing.
+ * Forward, cfm_ode_adaptive_rec_mlp_f32: cfm_ode_adaptive_mlp_f32 (same arguments; traj, n_steps and nfe are its bits)
+ * that also records its accepted steps.  log: device, max_steps records {float t, dt, t_k1; int out} (16 bytes): solver-space
+ * (s = sign * t) start and size of the step as its stages used them, the time its first slope was evaluated at (FSAL: the
+ * previous accepted step's last stage time; t_span[0] for the first), and the t_span index its end lands on or -1.
+ * ysteps: device [max_steps,B,d], the state every accepted step started from (ysteps[0] = x0).  n_accepted: host int.
+ * CFM_EINVAL wherever cfm_ode_adaptive_mlp_f32 would leave its one-launch kernel (a net outside the small-field envelope,
+ * B d < n_t, the fused path switched off: cfm_ode_set_fused) — only that kernel records — and then before any GPU work, so
+ * a caller may step the solve another way at no cost; a failure after that is a hipError_t; CFM_ENOCONV when max_steps
+ * accepted steps did not reach the end of the grid (the records written so far are valid, traj is not complete). */
+int cfm_ode_adaptive_rec_mlp_f32(const float* const* W, const float* const* b, const int* dims,
+                                 int n_layers, const float* x0, int B, const float* t_span,
+                                 int n_t, int tableau, float atol, float rtol, float* traj, int* n_steps,
+                                 int* nfe, int max_steps, void* log, float* ysteps, int* n_accepted, void* ws,
+                                 void* stream);
+/* Its gradient.  ysteps, log, n_accepted: as the forward left them; tsign: +1 for an increasing t_span, -1 for a decreasing
+ * one; g_traj: device [n_t,B,d] = dL/d traj, every slice.  Outputs (overwritten): dW[l], db[l] device, laid out as W[l],
+ * b[l]; g_initial device [B,d] = dL/d x0, or NULL.  Every step's six stages are recomputed from ysteps[n] in the forward's
+ * arithmetic.  ws: cfm_workspace_bytes(CFM_OP_ODE_GRAD, B, n_t, 0).  Envelope and CFM_EINVAL rule of
+ * cfm_ode_fixed_grad_f32.  The result is the same bit pattern run to run. */
+int cfm_ode_adaptive_grad_f32(const float* const* W, const float* const* b, const int* dims, int n_layers,
+                              const float* ysteps, const void* log, int n_accepted, int B, int n_t, int tableau,
+                              float tsign, const float* g_traj, float* const* dW, float* const* db, float* g_initial,
+                              void* ws, void* stream);
+/* Whether cfm_ode_adaptive_grad_f32 takes a field of these dims: 0, or CFM_EINVAL.  No GPU work. */
+int cfm_ode_adaptive_grad_available(const int* dims, int n_layers);
 
 /* K13 — action matching: the field v = grad_x s(x, t) of a scalar action net s = MLP([x, t]) with one output
  * (4 linear layers, dims = [d + 1, n1, n2, n3, 1], 1 <= every width <= 64, d + 1 <= 64), and the solves over it.

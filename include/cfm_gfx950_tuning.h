@@ -45,6 +45,7 @@ void cfm_set_blocking_sync(int on);              /* THIS host thread's solver wa
 void cfm_ode_set_fused(int on);                  /* 0: layer-per-kernel ODE stages instead of the fused small-field drivers */
 void cfm_mlp_set_glds(int mode);               /* MLP layers on 64 x 64 tiles: 0 = register-staged operand loads (gemm_core.h: the plain ascending-k chain, bit-equal to the fused small-field ODE drivers), 1 = direct-to-LDS DMA (gemm_glds64.h) when the rows are 16-byte aligned, 2 (default) = for 4-byte aligned rows too */
 int cfm_mlp_get_glds(void);                    /* the mode in force (tests restore what they changed) */
+int cfm_ode_rec_resident_rows(int tableau);    /* rows up to which cfm_ode_adaptive_rec_mlp_f32 keeps its state in registers (16 x the workgroups of its kernel that are resident at once; above it the streamed instantiation runs); < 0: query failed.  Needs the GPU */
 
 /* read-backs (blocking) */
 int cfm_assign_debug_times(const void* ws, double* us32);          /* microseconds per mode of the last solve on ws */
