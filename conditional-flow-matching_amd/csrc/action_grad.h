@@ -1,6 +1,6 @@
-// action_grad.h — the action-matching loss and its parameter gradient in one launch (included by ode.hip after cnf_grad.h;
-// SmTile, sm_gemm, cg_gemm_t, selu_f, selu_slope, small_grid come from small_field.h, cg_put, cg_outer, cg_sum4, CgOut,
-// CG_MAXGRID and ode_small_grad_reduce from cnf_grad.h, grad_check from ode.hip).
+// action_grad.h — the action-matching loss and its parameter gradient in one launch (included by small_grad.hip after
+// cnf_grad.h; SmTile, sm_gemm, cg_gemm_t, selu_f, selu_slope come from small_field.h, cg_put, cg_outer, cg_sum4 from
+// cnf_grad.h, the host tail and the reduce launch from small_grad.hip, grad_check from ode_envelope.h).
 //
 // Counterpart of ActionMatchingLitModule.step (runner/src/models/cfm_module.py:670-694) and the loss.backward() that
 // follows it: per row  l = s(x0, 0) - s(x1, 1) + 1/2 |grad_x s(xt, t)|^2 + d/dt s(xt, t),  loss = mean l, for the action net
@@ -319,21 +319,10 @@ extern "C" int cfm_action_matching_grad_f32(const float* const* W, const float* 
     if (!x0 || !x1 || !t || !loss || !dW || !db || !ws) return CFM_EINVAL;
     int rc = grad_check(W, b, dims, n_layers, B, &d, &A);
     if (rc) return rc;
+    for (int l = 0; l < 4; ++l) if (!W[l] || !b[l]) return CFM_EINVAL;
     CgOut O;
-    int P = 1;                                                          // the loss term behind the gradient
-    for (int l = 0; l < 4; ++l) {
-        if (!W[l] || !b[l] || !dW[l] || !db[l]) return CFM_EINVAL;
-        O.dW[l] = dW[l]; O.db[l] = db[l];
-        P += dims[l + 1] * (dims[l] + 1);
-    }
-    hipStream_t s = (hipStream_t)stream;
-    float* part = (float*)ws;
-    const int grid = small_grid<action_matching_grad, 128 * 1024>(B, CG_MAXGRID);
-    if (grid < 0) return CFM_EINVAL;
-    hipLaunchKernelGGL(action_matching_grad, dim3(grid), dim3(256), am_lds_bytes, s, A, B, d, x0, x1, xt, t, part, P);
-    rc = cfm_status();
-    if (rc) return rc;
-    hipLaunchKernelGGL(ode_small_grad_reduce, dim3((P + 255) / 256), dim3(256), 0, s, (const float*)part, grid, P, A, O,
-                       1.f / (float)B, loss);
-    return cfm_status();
+    const int P = cg_out(dims, dW, db, &O) + 1;                         // the loss term behind the gradient
+    if (P < 1) return CFM_EINVAL;
+    return cg_launch<action_matching_grad, 128 * 1024>(am_lds_bytes, (hipStream_t)stream, B, (float*)ws, P, A, O, 1.f / (float)B, loss,
+                                                       A, B, d, x0, x1, xt, t, (float*)ws, P);
 }

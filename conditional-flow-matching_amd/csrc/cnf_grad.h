@@ -1,5 +1,6 @@
-// cnf_grad.h — gradient of the Euler solve of the augmented CNF state (included by ode.hip; the tile engine it runs on
-// comes from small_field.h: SmTile, sm_gemm, cg_gemm_t, sm_stage_weights, selu_f, selu_slope, small_grid; cnf_check from ode.hip).
+// cnf_grad.h — gradient of the Euler solve of the augmented CNF state (included by small_grad.hip, whose host tail and
+// reduce launch it ends on; the tile engine it runs on comes from small_field.h: SmTile, sm_gemm, cg_gemm_t,
+// sm_stage_weights, selu_f, selu_slope; cnf_check, cnf_reg_check and cg_reg_cols from ode_envelope.h).
 //
 // Forward (ode_small_fixed<CFM_ODE_EULER, MODE>):  y_{n+1} = y_n + h_n v(y_n, t_n),  l_{n+1} = l_n - h_n div(y_n, t_n).
 // Given G = dL/d[l_N, y_N]:  c = G[:, 0] never changes (l enters linearly), a_N = G[:, 1:], and for n = N-1 .. 0
@@ -21,7 +22,7 @@
 // partial gradient and ode_small_grad_reduce adds the partials in workgroup order: the same bits run to run.
 // Rows are independent: no cross-workgroup wait of any kind.
 //
-// REG (bit 0: squared_L2, bit 1: jacobian_frobenius) is the regularised solve of cnf_reg.h: the state is
+// REG (bit 0: squared_L2, bit 1: jacobian_frobenius) is the regularised solve of cnf_reg.hip: the state is
 // [l, (e), (f), y], e += h |v|^2, f += h sqrt(S) / d with S = sum_k |J e_k|^2, J e_k = W_3 T_3^k.  With ce, cf the upstream
 // columns of e and f (constant along the solve, as c is):
 //   g_n = a . v - c div + ce |v|^2 + cf sqrt(S) / d
@@ -34,18 +35,6 @@
 #pragma once
 
 static_assert(SM_MB == 1, "the gradient kernel is written for one 16-row block per tile");
-#define CG_MAXGRID 256                                 // workgroups (= partial gradients) at most
-#define CG_PMAX (4 * SM_W * SM_W + 4 * SM_W)           // floats of one partial gradient at most
-
-struct CgOut { float* dW[4]; float* db[4]; };
-
-extern "C" size_t cfm_cnf_grad_ws_bytes_internal(int B, int n_t) {
-    if (B <= 0 || n_t < 1) return 0;
-    const size_t tiles = ((size_t)B + SM_ROWS - 1) / SM_ROWS;
-    const size_t g = tiles < CG_MAXGRID ? tiles : CG_MAXGRID;
-    return cfm_align_up(sizeof(float) * (size_t)n_t, 256) + sizeof(float) * g * CG_PMAX;
-}
-
 __device__ __forceinline__ void cg_put(float* __restrict__ buf, const SmTile& v, int lane, int col) {
 #pragma unroll
     for (int i = 0; i < SM_V; ++i) buf[sm_row(i, lane) * SM_LD + col] = v.v[i];
@@ -124,7 +113,6 @@ static_assert(cg_lds_bytes == 127488, "the gradient kernel");
 // the sixth tile buffer (JB) of the jacobian_frobenius sweep: above 128 KB, inside the CU's 160 KB
 constexpr size_t cg_lds_bytes_jac = cg_lds_bytes + sizeof(float) * SM_ROWS * SM_LD;
 static_assert(cg_lds_bytes_jac == 131840 && cg_lds_bytes_jac <= 160 * 1024, "the gradient kernel with the Jacobian penalty");
-constexpr int cg_reg_cols(int REG) { return (REG & 1) + ((REG >> 1) & 1); }
 
 // traj [n_t, B, D]: the forward solve (y_n is read), D = 1 + cg_reg_cols(REG) + d; G [B, D]; g0 [B, D] or null;
 // part [gridDim.x][P]: the workgroup's partial gradient in the order W0, b0, W1, b1, W2, b2, W3, b3 (each as the caller's
@@ -401,39 +389,13 @@ __global__ __launch_bounds__(256) void ode_small_euler_grad(SmArgs A, int B, int
     cg_store_partial(A, d, part + (size_t)blockIdx.x * P, dWa, dba, dwt, lane, col);
 }
 
-// dW[], db[] = scale * the partials added in workgroup order (scale = 1 changes no bit); tail: null, or where the one
-// element that a partial carries behind db[3] goes (action_grad.h: the loss)
-__global__ __launch_bounds__(256) void ode_small_grad_reduce(const float* __restrict__ part, int nparts, int P, SmArgs A,
-                                                          CgOut O, float scale, float* __restrict__ tail) {
-    int p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= P) return;
-    float sum = 0.f;
-    for (int g = 0; g < nparts; ++g) sum += part[(size_t)g * P + p];
-    sum *= scale;
-#pragma unroll
-    for (int l = 0; l < 4; ++l) {
-        const int nw = A.dims[l + 1] * A.dims[l], nb = A.dims[l + 1];
-        if (p >= 0 && p < nw) O.dW[l][p] = sum;
-        p -= nw;
-        if (p >= 0 && p < nb) O.db[l][p] = sum;
-        p -= nb;
-    }
-    if (tail && p == 0) *tail = sum;
-}
-
 template <int MODE, int REG = 0>
 static int cnf_grad_launch(const SmArgs& A, int B, int d, const float* tspan_dev, int n_t, const float* traj,
                            const float* eps, const float* G, float* g0, float* part, int P, const CgOut& O, hipStream_t s,
                            const float* jsq = nullptr) {
-    constexpr size_t lds = (REG & 2) ? cg_lds_bytes_jac : cg_lds_bytes;
-    const int grid = small_grid<ode_small_euler_grad<MODE, REG>, ((REG & 2) ? 160 : 128) * 1024>(B, CG_MAXGRID);
-    if (grid < 0) return CFM_EINVAL;
-    hipLaunchKernelGGL((ode_small_euler_grad<MODE, REG>), dim3(grid), dim3(256), lds, s, A, B, d, tspan_dev, n_t, traj, eps,
-                       G, g0, part, P, jsq);
-    int rc = cfm_status();
-    if (rc) return rc;
-    hipLaunchKernelGGL(ode_small_grad_reduce, dim3((P + 255) / 256), dim3(256), 0, s, (const float*)part, grid, P, A, O, 1.f, nullptr);
-    return cfm_status();
+    return cg_launch<ode_small_euler_grad<MODE, REG>, ((REG & 2) ? 160 : 128) * 1024>(
+        (REG & 2) ? cg_lds_bytes_jac : cg_lds_bytes, s, B, part, P, A, O, 1.f, nullptr, A, B, d, tspan_dev, n_t, traj, eps, G, g0,
+        part, P, jsq);
 }
 
 extern "C" int cfm_cnf_euler_grad_f32(const float* const* W, const float* const* b, const int* dims, int n_layers,
@@ -445,17 +407,35 @@ extern "C" int cfm_cnf_euler_grad_f32(const float* const* W, const float* const*
     int rc = cnf_check(W, b, dims, n_layers, B, mode, eps, &d, &A);
     if (rc) return rc;
     CgOut O;
-    int P = 0;
-    for (int l = 0; l < 4; ++l) {
-        if (!dW[l] || !db[l]) return CFM_EINVAL;
-        O.dW[l] = dW[l]; O.db[l] = db[l];
-        P += dims[l + 1] * (dims[l] + 1);
-    }
+    const int P = cg_out(dims, dW, db, &O);
+    if (P < 0) return CFM_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    float* tspan_dev = (float*)ws;
-    float* part = (float*)((char*)ws + cfm_align_up(sizeof(float) * (size_t)n_t, 256));
-    rc = cfm_hip(hipMemcpyAsync(tspan_dev, t_span, sizeof(float) * n_t, hipMemcpyHostToDevice, s));
+    const CgWs w = cg_carve(ws, n_t);
+    rc = cfm_hip(hipMemcpyAsync(w.tspan, t_span, sizeof(float) * n_t, hipMemcpyHostToDevice, s));
     if (rc) return rc;
-    return mode == 0 ? cnf_grad_launch<AUG_EXACT>(A, B, d, tspan_dev, n_t, traj, eps, g_final, g_initial, part, P, O, s)
-                     : cnf_grad_launch<AUG_HUTCH>(A, B, d, tspan_dev, n_t, traj, eps, g_final, g_initial, part, P, O, s);
+    return mode == 0 ? cnf_grad_launch<AUG_EXACT>(A, B, d, w.tspan, n_t, traj, eps, g_final, g_initial, w.part, P, O, s)
+                     : cnf_grad_launch<AUG_HUTCH>(A, B, d, w.tspan, n_t, traj, eps, g_final, g_initial, w.part, P, O, s);
+}
+
+// the gradient of the regularised solve (cfm_ode_euler_cnf_reg_mlp_f32, cnf_reg.h): traj, g_final, g_initial [., B, D] with
+// D = 1 + cg_reg_cols(reg_mask) + d; jac_sq: the forward's side buffer (reg_mask bit 1)
+extern "C" int cfm_cnf_reg_euler_grad_f32(const float* const* W, const float* const* b, const int* dims, int n_layers,
+                                          const float* traj, int B, const float* t_span, int n_t, int mode, const float* eps,
+                                          int reg_mask, const float* jac_sq, const float* g_final, float* const* dW,
+                                          float* const* db, float* g_initial, void* ws, void* stream) {
+    int d; SmArgs A;
+    if (!traj || !t_span || !g_final || !dW || !db || !ws || n_t < 1 || cnf_reg_check(mode, reg_mask, jac_sq)) return CFM_EINVAL;
+    int rc = cnf_check(W, b, dims, n_layers, B, mode, eps, &d, &A);
+    if (rc) return rc;
+    CgOut O;
+    const int P = cg_out(dims, dW, db, &O);
+    if (P < 0) return CFM_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const CgWs w = cg_carve(ws, n_t);
+    rc = cfm_hip(hipMemcpyAsync(w.tspan, t_span, sizeof(float) * n_t, hipMemcpyHostToDevice, s));
+    if (rc) return rc;
+    if (mode == 1) return cnf_grad_launch<AUG_HUTCH, 1>(A, B, d, w.tspan, n_t, traj, eps, g_final, g_initial, w.part, P, O, s, jac_sq);
+    if (reg_mask == 1) return cnf_grad_launch<AUG_EXACT, 1>(A, B, d, w.tspan, n_t, traj, eps, g_final, g_initial, w.part, P, O, s, jac_sq);
+    if (reg_mask == 2) return cnf_grad_launch<AUG_EXACT, 2>(A, B, d, w.tspan, n_t, traj, eps, g_final, g_initial, w.part, P, O, s, jac_sq);
+    return cnf_grad_launch<AUG_EXACT, 3>(A, B, d, w.tspan, n_t, traj, eps, g_final, g_initial, w.part, P, O, s, jac_sq);
 }

@@ -1,6 +1,6 @@
 // cnf_reg.hip — the regularised CNF solve (RNODE / TrajectoryNet): the Euler solve of the augmented state with the kinetic
-// and Jacobian penalties as path integrals, on the tile engine of small_field.h.  The C entries and the
-// gradient are ode.hip's (cnf_reg.h, cnf_grad.h: ode_small_euler_grad<MODE, REG>).  A translation unit of its own: with
+// and Jacobian penalties as path integrals, on the tile engine of small_field.h.  The C entry is
+// ode.hip's (cnf_reg.h), the gradient small_grad.hip's (cnf_grad.h: ode_small_euler_grad<MODE, REG>).  A unit of its own: with
 // these kernels inside ode.hip the compiler gave two of that unit's existing kernels four more registers each.
 //
 // State [l, (e), (f), y], D = 1 + r + d; REG bit 0 carries e (squared_L2), bit 1 carries f (jacobian_frobenius), in the

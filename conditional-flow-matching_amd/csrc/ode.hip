@@ -17,6 +17,8 @@
 #include "cfm_common.h"
 #include "small_field.h"
 #include "grad_field.h"
+#include "ode_tableau.h"
+#include "ode_envelope.h"
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -153,108 +155,9 @@ static int check_mlp(const int* dims, int n_layers, int* d_out) {
 
 static int g_ode_fused = -1;     // -1: from the environment (CFM_ODE_FUSED=0 disables), else 0 / 1
 extern "C" void cfm_ode_set_fused(int on) { g_ode_fused = on ? 1 : 0; }
-static int ode_small_enabled() {
+extern "C" int cfm_ode_fused_internal() {       // not exported: small_grad.hip's entries read the switch through it
     if (g_ode_fused < 0) { const char* e = getenv("CFM_ODE_FUSED"); g_ode_fused = (e && e[0] == '0') ? 0 : 1; }
     return g_ode_fused;
-}
-// ---- tableaus ----------------------------------------------------------------------------------------------------
-// Entries as compile-time constants: in the kernels every index is a constant after unrolling, the host drivers
-// read the same tables.  Every use casts the fp64 constant: (float)rk_a<TAB>(s, q), (float)rk_e<TAB>(q).
-// Adaptive pairs (7 stages, FSAL, row 6 of a = b, so stage 6's y is x_new; e = b - b_alt):
-//   CFM_ODE_DOPRI5: Dormand-Prince 5(4);  CFM_ODE_TSIT5: Tsitouras 5(4) (Tsitouras 2011, the
-//   coefficients torchdyn's default solver carries).
-template <int TAB>
-__host__ __device__ __forceinline__ double rk_a(int s, int q) {
-    if constexpr (TAB == CFM_ODE_TSIT5) {
-        constexpr double A[6][6] = {
-            {0.161, 0, 0, 0, 0, 0},
-            {-0.008480655492356989, 0.335480655492357, 0, 0, 0, 0},
-            {2.8971530571054935, -6.359448489975075, 4.3622954328695815, 0, 0, 0},
-            {5.325864828439257, -11.748883564062828, 7.4955393428898365, -0.09249506636175525, 0, 0},
-            {5.86145544294642, -12.92096931784711, 8.159367898576159, -0.071584973281401, -0.028269050394068383, 0},
-            {0.09646076681806523, 0.01, 0.4798896504144996, 1.379008574103742, -3.290069515436081, 2.324710524099774}};
-        return A[s][q];
-    } else {
-        constexpr double A[6][6] = {
-            {1.0 / 5, 0, 0, 0, 0, 0},
-            {3.0 / 40, 9.0 / 40, 0, 0, 0, 0},
-            {44.0 / 45, -56.0 / 15, 32.0 / 9, 0, 0, 0},
-            {19372.0 / 6561, -25360.0 / 2187, 64448.0 / 6561, -212.0 / 729, 0, 0},
-            {9017.0 / 3168, -355.0 / 33, 46732.0 / 5247, 49.0 / 176, -5103.0 / 18656, 0},
-            {35.0 / 384, 0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784, 11.0 / 84}};
-        return A[s][q];
-    }
-}
-template <int TAB>
-__host__ __device__ __forceinline__ float rk_c(int s) {
-    if constexpr (TAB == CFM_ODE_TSIT5) {
-        constexpr float C[6] = {(float)0.161, (float)0.327, (float)0.9, (float)0.9800255409045097, 1.f, 1.f};
-        return C[s];
-    } else {
-        constexpr float C[6] = {1.f / 5, 3.f / 10, 4.f / 5, 8.f / 9, 1.f, 1.f};
-        return C[s];
-    }
-}
-template <int TAB>
-__host__ __device__ __forceinline__ double rk_e(int q) {
-    if constexpr (TAB == CFM_ODE_TSIT5) {
-        constexpr double E[7] = {0.001780011052226, 0.000816434459657, -0.007880878010262, 0.144711007173263,
-                                 -0.582357165452555, 0.458082105929187, -1.0 / 66};
-        return E[q];
-    } else {
-        constexpr double BS[7] = {35.0 / 384, 0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784, 11.0 / 84, 0};
-        constexpr double BA[7] = {1951.0 / 21600, 0, 22642.0 / 50085, 451.0 / 720, -12231.0 / 42400, 649.0 / 6300, 1.0 / 60};
-        return BS[q] - BA[q];
-    }
-}
-static double rk_a_host(int tab, int s, int q) { return tab == CFM_ODE_TSIT5 ? rk_a<CFM_ODE_TSIT5>(s, q) : rk_a<CFM_ODE_DOPRI5>(s, q); }
-static float rk_c_host(int tab, int s) { return tab == CFM_ODE_TSIT5 ? rk_c<CFM_ODE_TSIT5>(s) : rk_c<CFM_ODE_DOPRI5>(s); }
-static double rk_e_host(int tab, int q) { return tab == CFM_ODE_TSIT5 ? rk_e<CFM_ODE_TSIT5>(q) : rk_e<CFM_ODE_DOPRI5>(q); }
-static int rk_adaptive_known(int tab) { return tab == CFM_ODE_DOPRI5 || tab == CFM_ODE_TSIT5; }
-
-// Fixed-step schemes: stage s >= 1 is y = x + dt * sum_{q<s} a[s-1][q] k_q at t + c[s-1] dt; x_new = x + dt * sum b k.
-//   CFM_ODE_EULER;  CFM_ODE_MIDPOINT: x + dt f(t + dt/2, x + dt/2 k1);  CFM_ODE_RK4: the 3/8 rule.
-template <int SCHEME>
-__host__ __device__ __forceinline__ constexpr int fx_stages() { return SCHEME == CFM_ODE_RK4 ? 4 : SCHEME == CFM_ODE_MIDPOINT ? 2 : 1; }
-template <int SCHEME>
-__host__ __device__ __forceinline__ double fx_a(int s, int q) {
-    if constexpr (SCHEME == CFM_ODE_RK4) {
-        constexpr double A[3][3] = {{1.0 / 3, 0, 0}, {-1.0 / 3, 1, 0}, {1, -1, 1}};
-        return A[s][q];
-    } else {
-        constexpr double A[3][3] = {{1.0 / 2, 0, 0}, {0, 0, 0}, {0, 0, 0}};
-        return A[s][q];
-    }
-}
-template <int SCHEME>
-__host__ __device__ __forceinline__ double fx_c(int s) {
-    if constexpr (SCHEME == CFM_ODE_RK4) {
-        constexpr double C[3] = {1.0 / 3, 2.0 / 3, 1};
-        return C[s];
-    } else {
-        constexpr double C[3] = {1.0 / 2, 0, 0};
-        return C[s];
-    }
-}
-template <int SCHEME>
-__host__ __device__ __forceinline__ double fx_b(int q) {
-    if constexpr (SCHEME == CFM_ODE_RK4) {
-        constexpr double Bv[4] = {1.0 / 8, 3.0 / 8, 3.0 / 8, 1.0 / 8};
-        return Bv[q];
-    } else if constexpr (SCHEME == CFM_ODE_MIDPOINT) {
-        constexpr double Bv[4] = {0, 1, 0, 0};
-        return Bv[q];
-    } else {
-        constexpr double Bv[4] = {1, 0, 0, 0};
-        return Bv[q];
-    }
-}
-static int fx_known(int scheme) { return scheme == CFM_ODE_EULER || scheme == CFM_ODE_MIDPOINT || scheme == CFM_ODE_RK4; }
-static int fx_stages_host(int scheme) { return scheme == CFM_ODE_RK4 ? 4 : scheme == CFM_ODE_MIDPOINT ? 2 : 1; }
-static double fx_a_host(int sc, int s, int q) { return sc == CFM_ODE_RK4 ? fx_a<CFM_ODE_RK4>(s, q) : fx_a<CFM_ODE_MIDPOINT>(s, q); }
-static double fx_c_host(int sc, int s) { return sc == CFM_ODE_RK4 ? fx_c<CFM_ODE_RK4>(s) : fx_c<CFM_ODE_MIDPOINT>(s); }
-static double fx_b_host(int sc, int q) {
-    return sc == CFM_ODE_RK4 ? fx_b<CFM_ODE_RK4>(q) : sc == CFM_ODE_MIDPOINT ? fx_b<CFM_ODE_MIDPOINT>(q) : fx_b<CFM_ODE_EULER>(q);
 }
 
 static int ode_fixed_small(int scheme, const float* const* W, const float* const* b, const int* dims, int B, int d,
@@ -276,7 +179,7 @@ extern "C" int cfm_ode_fixed_mlp_f32(const float* const* W, const float* const* 
     if (rc) return rc;
     // small vector fields: rows are independent and the steps are fixed, so ONE launch integrates the
     // whole t_span (a workgroup walks its 64-row tile through every step, weights resident in LDS)
-    if (ode_small_enabled() && small_envelope(dims, n_layers, nullptr) == 0 && d + 1 <= SM_W && n >= (size_t)n_t && n_t >= 2) {
+    if (cfm_ode_fused_internal() && small_envelope(dims, n_layers, nullptr) == 0 && d + 1 <= SM_W && n >= (size_t)n_t && n_t >= 2) {
         rc = ode_fixed_small(scheme, W, b, dims, B, d, t_span, n_t, traj, w.xt, s);
         if (nfe) *nfe = ns * (n_t - 1);
         return rc;
@@ -329,11 +232,7 @@ static int read_red(hipStream_t s, const double* dev, int count, double* host) {
     return 0;
 }
 
-// The record of an accepted step that the recording solve keeps (cfm_ode_adaptive_rec_mlp_f32) and its gradient replays
-// (ode_adaptive_grad.h): solver-space t and dt of the stages, the time k_1 was evaluated at (FSAL: the previous step's
-// last stage time, which is not t in general after a landing step), the t_span index the step end lands on or -1.
-struct OdeStepRec { float t, dt, t_k1; int out; };
-static_assert(sizeof(OdeStepRec) == 16, "the step log's record");
+// OdeStepRec (ode_envelope.h): the record of an accepted step that the recording solve keeps
 struct OdeRec { OdeStepRec* log; float* ysteps; int max_steps; };   // log [max_steps], ysteps [max_steps, B, d]: device
 
 template <int TAB, int MODE, int FIELD, bool REC = false>
@@ -470,7 +369,7 @@ static int ode_dopri5_layers(int tab, const float* const* W, const float* const*
     OdeWs w = ode_carve(ws, B, width, d);
     const size_t n = (size_t)B * d;
     // small vector fields: the whole step attempt in one kernel, controller on the device
-    const bool small = ode_small_enabled() && small_envelope(dims, n_layers, nullptr) == 0 && d + 1 <= SM_W && n >= (size_t)n_t;
+    const bool small = cfm_ode_fused_internal() && small_envelope(dims, n_layers, nullptr) == 0 && d + 1 <= SM_W && n >= (size_t)n_t;
     if (rec && !small) return CFM_EINVAL;              // only the one-launch kernel records its steps
     const int nb = ode_blocks(n);
     int evals = 0, steps = 0;
@@ -1168,7 +1067,7 @@ extern "C" int cfm_ode_fixed_pair_mlp_f32(const float* const* Wf, const float* c
     const int ns = fx_stages_host(scheme);
     rc = cfm_hip(hipMemcpyAsync(traj, x0, n * sizeof(float), hipMemcpyDeviceToDevice, s));
     if (rc) return rc;
-    if (ode_small_enabled() && small_envelope(dims, n_layers, nullptr) == 0 && d + 1 <= SM_W && n >= (size_t)n_t && n_t >= 2) {
+    if (cfm_ode_fused_internal() && small_envelope(dims, n_layers, nullptr) == 0 && d + 1 <= SM_W && n >= (size_t)n_t && n_t >= 2) {
         const SmArgs F = small_args(Wf, bf, dims), S = small_args(Wb, bb, dims);
         if (scheme == CFM_ODE_RK4) rc = ode_fixed_pair_small_t<CFM_ODE_RK4>(F, S, B, d, t_span, n_t, traj, w.xt, s);
         else if (scheme == CFM_ODE_MIDPOINT) rc = ode_fixed_pair_small_t<CFM_ODE_MIDPOINT>(F, S, B, d, t_span, n_t, traj, w.xt, s);
@@ -1256,20 +1155,6 @@ static int cnf_eval(const SmArgs& A, int B, int d, const float* x, int ldx, floa
     hipLaunchKernelGGL((ode_small_div<MODE, FIELD>), dim3(grid), dim3(256), small_lds_bytes(1, 2, true), s, A, B, d, x, ldx, t, eps, v, ldv,
                        div, lddiv, dsign);
     return cfm_status();
-}
-
-// the envelope of the CNF entries: the small-field kernels (small_envelope, every width >= 1, d + 1 <= SM_W), fused path
-// on, mode 0 (exact trace) or 1 (Hutchinson, eps given)
-static int cnf_check(const float* const* W, const float* const* b, const int* dims, int n_layers, int B, int mode,
-                     const float* eps, int* d_out, SmArgs* A) {
-    int d;
-    if (!W || !b || B <= 0 || (mode != 0 && mode != 1) || (mode == 1 && !eps)) return CFM_EINVAL;
-    if (small_envelope(dims, n_layers, &d)) return CFM_EINVAL;
-    for (int l = 1; l <= 3; ++l) if (dims[l] < 1) return CFM_EINVAL;
-    if (d < 1 || d + 1 > SM_W || !ode_small_enabled()) return CFM_EINVAL;
-    *A = small_args(W, b, dims);
-    *d_out = d;
-    return 0;
 }
 
 // a fixed-step grid: strictly monotone, either way
@@ -1385,20 +1270,7 @@ extern "C" int cfm_ode_dopri5_cnf_mlp_f32(const float* const* W, const float* co
 }
 
 // ---- action matching: v = grad_x s(x, t) of a scalar action net (grad_field.h) -------------------------------------
-// The envelope of the gradient-field entries: 4 layers [d + 1, n1, n2, n3, 1], 1 <= every width <= SM_W, d + 1 <= SM_W,
-// fused path on.  There is no layer-per-kernel form of this field.
-static int grad_check(const float* const* W, const float* const* b, const int* dims, int n_layers, int B, int* d_out,
-                      SmArgs* A) {
-    if (!W || !b || !dims || B <= 0 || n_layers != 4) return CFM_EINVAL;
-    const int d = dims[0] - 1;
-    if (dims[4] != 1 || d < 1 || d + 1 > SM_W) return CFM_EINVAL;
-    for (int l = 1; l <= 3; ++l) if (dims[l] < 1 || dims[l] > SM_W) return CFM_EINVAL;
-    if (!ode_small_enabled()) return CFM_EINVAL;
-    *A = small_args(W, b, dims);
-    *d_out = d;
-    return 0;
-}
-
+// (the envelope of these entries: grad_check, ode_envelope.h)
 extern "C" int cfm_mlp_grad_field_f32(const float* const* W, const float* const* b, const int* dims, int n_layers,
                                       const float* x, int ldx, int B, float t, float* v, float* lap, void* ws,
                                       void* stream) {
@@ -1465,19 +1337,9 @@ extern "C" int cfm_ode_adaptive_gradmlp_f32(const float* const* W, const float* 
     return rc;
 }
 
-// ---- CNF training: the gradient of the Euler augmented solve (ode_small_euler_grad, cfm_cnf_euler_grad_f32) ----
-#include "cnf_grad.h"
-
-// ---- regularised CNF training: the Euler solve with the kinetic / Jacobian path integrals and its gradient
-// (ode_small_euler_reg, cfm_ode_euler_cnf_reg_mlp_f32, cfm_cnf_reg_euler_grad_f32) ----
+// ---- regularised CNF training: the Euler solve with the kinetic / Jacobian path integrals (ode_small_euler_reg of
+// cnf_reg.hip, cfm_ode_euler_cnf_reg_mlp_f32) ----
 #include "cnf_reg.h"
 
-// ---- training through the sampler: the gradient of the plain fixed-step solves (ode_small_fixed_grad, cfm_ode_fixed_grad_f32) ----
-#include "ode_grad.h"
-
-// ---- training through the adaptive sampler: the gradient of the accepted steps of the recording solve
-// (ode_small_adaptive_grad, cfm_ode_adaptive_grad_f32) ----
-#include "ode_adaptive_grad.h"
-
-// ---- action-matching training: loss and parameter gradient in one launch (cfm_action_matching_grad_f32) ----
-#include "action_grad.h"
+// The gradients of these solves (CNF, regularised CNF, fixed-step, adaptive, action matching) are a translation unit of
+// their own, small_grad.hip: folding or moving their code cannot perturb the kernels above.

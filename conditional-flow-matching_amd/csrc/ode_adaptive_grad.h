@@ -1,6 +1,6 @@
 // ode_adaptive_grad.h — gradient of the adaptive solves (dopri5, tsit5) of ode_small_dopri<TAB, ., AUG_NONE, FIELD_MLP, true>
-// with respect to the field's parameters and the initial state (included by ode.hip after ode_grad.h; it runs on the helpers
-// of cnf_grad.h as ode_grad.h does, and on the tile engine of small_field.h).
+// with respect to the field's parameters and the initial state (included by small_grad.hip after ode_grad.h; it runs on the
+// helpers of cnf_grad.h and on the reverse step of ode_reverse.h as ode_grad.h does, and on the tile engine of small_field.h).
 //
 // The accepted step sequence is a constant of the gradient (discretise-then-optimise): rejected attempts
 // contribute nothing, and the controller's scalars are not differentiated.  Row 6 of a is b and the seventh slope feeds
@@ -29,25 +29,12 @@ __global__ __launch_bounds__(256) void ode_small_adaptive_grad(SmArgs A, int B, 
                                                             int n_acc, const float* __restrict__ ysteps, float tsign,
                                                             const float* __restrict__ G, int n_t, float* __restrict__ g0,
                                                             float* __restrict__ part, int P) {
-    constexpr int NS = 6;
+    using T = RkCoef<TAB>;
     extern __shared__ __attribute__((aligned(16))) float small_lds[];
-    constexpr int TS = SM_ROWS * SM_LD, WS = SM_W * SM_LD;
-    float* Wl = small_lds;
-    float* WT = Wl + 4 * WS;                  // W1^T, W2^T
-    float* bl = WT + 2 * WS;
-    float* wt = bl + 4 * SM_W;
-    float* P0 = wt + SM_W;
-    float* P1 = P0 + TS;
-    float* Q0 = P1 + TS;
-    float* Q1 = Q0 + TS;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    sm_stage_weights(A, d, Wl, bl, wt, tid);
-    cg_stage_transposed(A, WT, tid);
+    const OgLds L = og_prologue(A, d, small_lds, tid);
     const size_t n = (size_t)B * d;
     const int col = wv * 16 + (lane & 15);
-    const float* W1T = WT;
-    const float* W2T = WT + WS;
-    const float* W3 = Wl + 3 * WS;
 
     f32x4 dWa[4][4];
     float dba[4], dwt = 0.f;
@@ -91,104 +78,11 @@ __global__ __launch_bounds__(256) void ode_small_adaptive_grad(SmArgs A, int B, 
                 }
             }
 
-            // ---- the stages forward: s_l, h_l, Y_s (the arithmetic of sm_field and of ode_small_dopri's SM_COMBINE) ----
-            SmTile s[NS][3], hh[NS][3], Y[NS], f[NS];
-            float tsg[NS];
-            f32x4 c[SM_MB];
+            float tsg[T::NS];
+            tsg[0] = tsign * r.t_k1;                       // k_1 is the previous step's k_7 (FSAL): evaluated there
 #pragma unroll
-            for (int sg = 0; sg < NS; ++sg) {
-                Y[sg] = y;
-                tsg[sg] = tsign * r.t_k1;                  // k_1 is the previous step's k_7 (FSAL): evaluated there
-                if (sg > 0) {
-#pragma unroll
-                    for (int i = 0; i < SM_V; ++i) {
-                        float acc = (float)rk_a<TAB>(sg - 1, 0) * f[0].v[i];
-#pragma unroll
-                        for (int q = 1; q < NS - 1; ++q)
-                            if (q < sg) acc = fmaf((float)rk_a<TAB>(sg - 1, q), f[q].v[i], acc);
-                        Y[sg].v[i] = fmaf(hdt, acc, y.v[i]);
-                    }
-                    tsg[sg] = tsign * (r.t + rk_c<TAB>(sg - 1) * r.dt);
-                }
-                cg_put(P0, Y[sg], lane, col);
-                sm_lds_barrier();
-                float* src = P0; float* dst = P1;
-#pragma unroll
-                for (int l = 0; l < (sg < NS - 1 ? 4 : 3); ++l) {          // no Y depends on the last stage's slope
-                    const int N = A.dims[l + 1];
-                    sm_gemm(src, Wl + l * WS, wv, lane, c);
-                    const float bv = (col < N) ? bl[l * SM_W + col] : 0.f;
-                    const float wtc = (l == 0 && col < N) ? wt[col] : 0.f;
-#pragma unroll
-                    for (int i = 0; i < SM_V; ++i) {
-                        float z = c[0][i] + bv;
-                        if (l == 0) z = fmaf(tsg[sg], wtc, z);
-                        if (l < 3) {
-                            s[sg][l].v[i] = (col < N && sm_row(i, lane) < nrows) ? selu_slope(z) : 0.f;
-                            hh[sg][l].v[i] = (col < N) ? selu_f(z) : 0.f;
-                        } else {
-                            f[sg].v[i] = (col < N) ? z : 0.f;
-                        }
-                    }
-                    if (l < 2 || (l == 2 && sg < NS - 1)) {
-                        cg_put(dst, hh[sg][l], lane, col);
-                        sm_lds_barrier();
-                        float* tmp = src; src = dst; dst = tmp;
-                    }
-                }
-            }
-
-            // ---- the stages backward: one vector-Jacobian product each ----
-            SmTile Yb[NS], lamn = lam;
-#pragma unroll
-            for (int sg = NS - 1; sg >= 0; --sg) {
-                SmTile kb, zb;
-#pragma unroll
-                for (int i = 0; i < SM_V; ++i) {
-                    float acc = (float)rk_a<TAB>(NS - 1, sg) * lam.v[i];
-#pragma unroll
-                    for (int rr = sg + 1; rr < NS; ++rr) acc = fmaf((float)rk_a<TAB>(rr - 1, sg), Yb[rr].v[i], acc);
-                    kb.v[i] = hdt * acc;
-                }
-                cg_put(Q0, kb, lane, col);
-                cg_put(Q1, hh[sg][2], lane, col);
-                sm_lds_barrier();
-                dba[3] += cg_sum4(kb);
-                cg_outer(Q0, Q1, wv, lane, dWa[3]);
-                cg_gemm_t(Q0, W3, wv, lane, c[0]);
-#pragma unroll
-                for (int i = 0; i < SM_V; ++i) zb.v[i] = c[0][i] * s[sg][2].v[i];
-                dba[2] += cg_sum4(zb);
-                cg_put(P0, zb, lane, col);
-                cg_put(P1, hh[sg][1], lane, col);
-                sm_lds_barrier();
-                cg_outer(P0, P1, wv, lane, dWa[2]);
-                sm_gemm(P0, W2T, wv, lane, c);
-#pragma unroll
-                for (int i = 0; i < SM_V; ++i) zb.v[i] = c[0][i] * s[sg][1].v[i];
-                dba[1] += cg_sum4(zb);
-                cg_put(Q0, zb, lane, col);
-                cg_put(Q1, hh[sg][0], lane, col);
-                sm_lds_barrier();
-                cg_outer(Q0, Q1, wv, lane, dWa[1]);
-                sm_gemm(Q0, W1T, wv, lane, c);
-#pragma unroll
-                for (int i = 0; i < SM_V; ++i) zb.v[i] = c[0][i] * s[sg][0].v[i];
-                {
-                    const float zs = cg_sum4(zb);
-                    dba[0] += zs;
-                    dwt = fmaf(tsg[sg], zs, dwt);
-                }
-                cg_put(P0, zb, lane, col);
-                cg_put(P1, Y[sg], lane, col);
-                sm_lds_barrier();
-                cg_outer(P0, P1, wv, lane, dWa[0]);
-                cg_gemm_t(P0, Wl, wv, lane, c[0]);                                          // zb1 W0[:, :d]
-#pragma unroll
-                for (int i = 0; i < SM_V; ++i) { Yb[sg].v[i] = c[0][i]; lamn.v[i] += c[0][i]; }
-            }
-            lam = lamn;
-            sm_lds_barrier();       // the last product read (P0, P1): the next step writes y_n there first
+            for (int sg = 1; sg < T::NS; ++sg) tsg[sg] = tsign * (r.t + rk_c<TAB>(sg - 1) * r.dt);
+            og_reverse_step<T>(A, L, nrows, wv, lane, col, y, lam, hdt, tsg, dWa, dba, dwt);
         }
         if (g0) {
 #pragma unroll
@@ -205,14 +99,8 @@ template <int TAB>
 static int ode_adaptive_grad_launch(const SmArgs& A, int B, int d, const OdeStepRec* log, int n_acc, const float* ysteps,
                                     float tsign, const float* G, int n_t, float* g0, float* part, int P, const CgOut& O,
                                     hipStream_t s) {
-    const int grid = small_grid<ode_small_adaptive_grad<TAB>, 128 * 1024>(B, CG_MAXGRID);
-    if (grid < 0) return CFM_EINVAL;
-    hipLaunchKernelGGL(ode_small_adaptive_grad<TAB>, dim3(grid), dim3(256), og_lds_bytes, s, A, B, d, log, n_acc, ysteps, tsign, G,
-                       n_t, g0, part, P);
-    int rc = cfm_status();
-    if (rc) return rc;
-    hipLaunchKernelGGL(ode_small_grad_reduce, dim3((P + 255) / 256), dim3(256), 0, s, (const float*)part, grid, P, A, O, 1.f, nullptr);
-    return cfm_status();
+    return cg_launch<ode_small_adaptive_grad<TAB>, 128 * 1024>(og_lds_bytes, s, B, part, P, A, O, 1.f, nullptr, A, B, d, log, n_acc,
+                                                               ysteps, tsign, G, n_t, g0, part, P);
 }
 
 // the envelope of the gradient of the adaptive solves: that of the fixed-step gradient.  No GPU work.
@@ -230,15 +118,10 @@ extern "C" int cfm_ode_adaptive_grad_f32(const float* const* W, const float* con
     const int d = dims[4];
     const SmArgs A = small_args(W, b, dims);
     CgOut O;
-    int P = 0;
-    for (int l = 0; l < 4; ++l) {
-        if (!dW[l] || !db[l]) return CFM_EINVAL;
-        O.dW[l] = dW[l]; O.db[l] = db[l];
-        P += dims[l + 1] * (dims[l] + 1);
-    }
+    const int P = cg_out(dims, dW, db, &O);
+    if (P < 0) return CFM_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    // the layout of cfm_ode_grad_ws_bytes_internal: the t_span area (not used: the log carries the times), then the partials
-    float* part = (float*)((char*)ws + cfm_align_up(sizeof(float) * (size_t)n_t, 256));
+    float* part = cg_carve(ws, n_t).part;          // the t_span area is not used: the log carries the times
     const OdeStepRec* lg = (const OdeStepRec*)log;
     if (tableau == CFM_ODE_TSIT5)
         return ode_adaptive_grad_launch<CFM_ODE_TSIT5>(A, B, d, lg, n_accepted, ysteps, tsign, g_traj, n_t, g_initial, part, P, O, s);

@@ -1,6 +1,7 @@
 // ode_grad.h — gradient of the fixed-step solves of ode_small_fixed<SCHEME, AUG_NONE> (euler, midpoint, rk4) with respect
-// to the field's parameters and the initial state (included by ode.hip after cnf_grad.h, whose cg_put, cg_outer, cg_sum4,
-// cg_stage_transposed, cg_store_partial, CgOut, CG_MAXGRID, CG_PMAX and ode_small_grad_reduce it runs on; the tile engine is small_field.h's).
+// to the field's parameters and the initial state (included by small_grad.hip after cnf_grad.h, whose cg_put, cg_outer,
+// cg_sum4, cg_stage_transposed and cg_store_partial it runs on; the host tail is small_grad.hip's, the tile engine
+// small_field.h's, the reverse step ode_reverse.h's: one text for this kernel and ode_small_adaptive_grad).
 //
 // Forward, per step n with h = tspan[n + 1] - tspan[n]:  Y_1 = y_n,  Y_s = fmaf(h, sum_{q<s} a_sq k_q, y_n),
 // k_s = f(t_n + c_s h, Y_s),  y_{n+1} = fmaf(h, sum_s b_s k_s, y_n).  Given G = dL/d traj [n_t, B, d]:  lam_N = G[N], and for
@@ -29,9 +30,7 @@
 // reads, and one barrier at the end of the step separates the last phase's reads of (P0, P1) from the next step's y_n.
 #pragma once
 
-// one staged net, the transposed copies of its two 64 x 64 layers, four tile buffers
-constexpr size_t og_lds_bytes = small_lds_bytes(1, 4, false) + sizeof(float) * 2 * SM_W * SM_LD;
-static_assert(og_lds_bytes == 123136 && og_lds_bytes <= cg_lds_bytes, "the ODE gradient kernel");
+#include "ode_reverse.h"
 
 // the layout of cfm_cnf_grad_ws_bytes_internal: the device copy of t_span, then one partial gradient per workgroup
 extern "C" size_t cfm_ode_grad_ws_bytes_internal(int B, int n_t) { return cfm_cnf_grad_ws_bytes_internal(B, n_t); }
@@ -42,25 +41,12 @@ template <int SCHEME>
 __global__ __launch_bounds__(256) void ode_small_fixed_grad(SmArgs A, int B, int d, const float* __restrict__ tspan, int n_t,
                                                          const float* __restrict__ traj, const float* __restrict__ G,
                                                          float* __restrict__ g0, float* __restrict__ part, int P) {
-    constexpr int NS = fx_stages<SCHEME>();
+    using T = FxCoef<SCHEME>;
     extern __shared__ __attribute__((aligned(16))) float small_lds[];
-    constexpr int TS = SM_ROWS * SM_LD, WS = SM_W * SM_LD;
-    float* Wl = small_lds;
-    float* WT = Wl + 4 * WS;                  // W1^T, W2^T
-    float* bl = WT + 2 * WS;
-    float* wt = bl + 4 * SM_W;
-    float* P0 = wt + SM_W;
-    float* P1 = P0 + TS;
-    float* Q0 = P1 + TS;
-    float* Q1 = Q0 + TS;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    sm_stage_weights(A, d, Wl, bl, wt, tid);
-    cg_stage_transposed(A, WT, tid);
+    const OgLds L = og_prologue(A, d, small_lds, tid);
     const size_t n = (size_t)B * d;
     const int col = wv * 16 + (lane & 15);
-    const float* W1T = WT;
-    const float* W2T = WT + WS;
-    const float* W3 = Wl + 3 * WS;
 
     f32x4 dWa[4][4];
     float dba[4], dwt = 0.f;
@@ -96,105 +82,13 @@ __global__ __launch_bounds__(256) void ode_small_fixed_grad(SmArgs A, int B, int
                 }
             }
 
-            // ---- the stages forward: s_l, h_l, Y_s (the arithmetic of sm_field and of ode_small_fixed) ----
-            SmTile s[NS][3], hh[NS][3], Y[NS], f[NS];
-            float tsg[NS];
-            f32x4 c[SM_MB];
+            float tsg[T::NS];
+            tsg[0] = t;
 #pragma unroll
-            for (int sg = 0; sg < NS; ++sg) {
-                Y[sg] = y;
-                tsg[sg] = t;
-                if (sg > 0) {
+            for (int sg = 1; sg < T::NS; ++sg) tsg[sg] = t + (float)fx_c<SCHEME>(sg - 1) * h;
+            og_reverse_step<T>(A, L, nrows, wv, lane, col, y, lam, h, tsg, dWa, dba, dwt);
 #pragma unroll
-                    for (int i = 0; i < SM_V; ++i) {
-                        float acc = (float)fx_a<SCHEME>(sg - 1, 0) * f[0].v[i];
-#pragma unroll
-                        for (int q = 1; q < NS - 1; ++q)
-                            if (q < sg) acc = fmaf((float)fx_a<SCHEME>(sg - 1, q), f[q].v[i], acc);
-                        Y[sg].v[i] = fmaf(h, acc, y.v[i]);
-                    }
-                    tsg[sg] = t + (float)fx_c<SCHEME>(sg - 1) * h;
-                }
-                cg_put(P0, Y[sg], lane, col);
-                sm_lds_barrier();
-                float* src = P0; float* dst = P1;
-#pragma unroll
-                for (int l = 0; l < (sg < NS - 1 ? 4 : 3); ++l) {          // no Y depends on the last stage's slope
-                    const int N = A.dims[l + 1];
-                    sm_gemm(src, Wl + l * WS, wv, lane, c);
-                    const float bv = (col < N) ? bl[l * SM_W + col] : 0.f;
-                    const float wtc = (l == 0 && col < N) ? wt[col] : 0.f;
-#pragma unroll
-                    for (int i = 0; i < SM_V; ++i) {
-                        float z = c[0][i] + bv;
-                        if (l == 0) z = fmaf(tsg[sg], wtc, z);
-                        if (l < 3) {
-                            s[sg][l].v[i] = (col < N && sm_row(i, lane) < nrows) ? selu_slope(z) : 0.f;
-                            hh[sg][l].v[i] = (col < N) ? selu_f(z) : 0.f;
-                        } else {
-                            f[sg].v[i] = (col < N) ? z : 0.f;
-                        }
-                    }
-                    if (l < 2 || (l == 2 && sg < NS - 1)) {
-                        cg_put(dst, hh[sg][l], lane, col);
-                        sm_lds_barrier();
-                        float* tmp = src; src = dst; dst = tmp;
-                    }
-                }
-            }
-
-            // ---- the stages backward: one vector-Jacobian product each ----
-            SmTile Yb[NS], lamn = lam;
-#pragma unroll
-            for (int sg = NS - 1; sg >= 0; --sg) {
-                SmTile kb, zb;
-#pragma unroll
-                for (int i = 0; i < SM_V; ++i) {
-                    float acc = (float)fx_b<SCHEME>(sg) * lam.v[i];
-#pragma unroll
-                    for (int r = sg + 1; r < NS; ++r) acc = fmaf((float)fx_a<SCHEME>(r - 1, sg), Yb[r].v[i], acc);
-                    kb.v[i] = h * acc;
-                }
-                cg_put(Q0, kb, lane, col);
-                cg_put(Q1, hh[sg][2], lane, col);
-                sm_lds_barrier();
-                dba[3] += cg_sum4(kb);
-                cg_outer(Q0, Q1, wv, lane, dWa[3]);
-                cg_gemm_t(Q0, W3, wv, lane, c[0]);
-#pragma unroll
-                for (int i = 0; i < SM_V; ++i) zb.v[i] = c[0][i] * s[sg][2].v[i];
-                dba[2] += cg_sum4(zb);
-                cg_put(P0, zb, lane, col);
-                cg_put(P1, hh[sg][1], lane, col);
-                sm_lds_barrier();
-                cg_outer(P0, P1, wv, lane, dWa[2]);
-                sm_gemm(P0, W2T, wv, lane, c);
-#pragma unroll
-                for (int i = 0; i < SM_V; ++i) zb.v[i] = c[0][i] * s[sg][1].v[i];
-                dba[1] += cg_sum4(zb);
-                cg_put(Q0, zb, lane, col);
-                cg_put(Q1, hh[sg][0], lane, col);
-                sm_lds_barrier();
-                cg_outer(Q0, Q1, wv, lane, dWa[1]);
-                sm_gemm(Q0, W1T, wv, lane, c);
-#pragma unroll
-                for (int i = 0; i < SM_V; ++i) zb.v[i] = c[0][i] * s[sg][0].v[i];
-                {
-                    const float zs = cg_sum4(zb);
-                    dba[0] += zs;
-                    dwt = fmaf(tsg[sg], zs, dwt);
-                }
-                cg_put(P0, zb, lane, col);
-                cg_put(P1, Y[sg], lane, col);
-                sm_lds_barrier();
-                cg_outer(P0, P1, wv, lane, dWa[0]);
-                cg_gemm_t(P0, Wl, wv, lane, c[0]);                                          // zb1 W0[:, :d]
-#pragma unroll
-                for (int i = 0; i < SM_V; ++i) { Yb[sg].v[i] = c[0][i]; lamn.v[i] += c[0][i]; }
-            }
-#pragma unroll
-            for (int i = 0; i < SM_V; ++i) lam.v[i] = lamn.v[i] + g.v[i];
-            sm_lds_barrier();       // the last product read (P0, P1): the next step writes y_n there first
+            for (int i = 0; i < SM_V; ++i) lam.v[i] = lam.v[i] + g.v[i];
         }
         if (g0) {
 #pragma unroll
@@ -210,14 +104,8 @@ __global__ __launch_bounds__(256) void ode_small_fixed_grad(SmArgs A, int B, int
 template <int SCHEME>
 static int ode_grad_launch(const SmArgs& A, int B, int d, const float* tspan_dev, int n_t, const float* traj, const float* G,
                            float* g0, float* part, int P, const CgOut& O, hipStream_t s) {
-    const int grid = small_grid<ode_small_fixed_grad<SCHEME>, 128 * 1024>(B, CG_MAXGRID);
-    if (grid < 0) return CFM_EINVAL;
-    hipLaunchKernelGGL(ode_small_fixed_grad<SCHEME>, dim3(grid), dim3(256), og_lds_bytes, s, A, B, d, tspan_dev, n_t, traj, G, g0,
-                       part, P);
-    int rc = cfm_status();
-    if (rc) return rc;
-    hipLaunchKernelGGL(ode_small_grad_reduce, dim3((P + 255) / 256), dim3(256), 0, s, (const float*)part, grid, P, A, O, 1.f, nullptr);
-    return cfm_status();
+    return cg_launch<ode_small_fixed_grad<SCHEME>, 128 * 1024>(og_lds_bytes, s, B, part, P, A, O, 1.f, nullptr, A, B, d, tspan_dev,
+                                                               n_t, traj, G, g0, part, P);
 }
 
 // the envelope of the gradient of the fixed-step solves: the small-field kernels (every width >= 1, d + 1 <= SM_W), fused
@@ -226,7 +114,7 @@ extern "C" int cfm_ode_fixed_grad_available(const int* dims, int n_layers) {
     int d;
     if (small_envelope(dims, n_layers, &d)) return CFM_EINVAL;
     for (int l = 1; l <= 3; ++l) if (dims[l] < 1) return CFM_EINVAL;
-    return (d < 1 || d + 1 > SM_W || !ode_small_enabled()) ? CFM_EINVAL : 0;
+    return (d < 1 || d + 1 > SM_W || !cfm_ode_fused_internal()) ? CFM_EINVAL : 0;
 }
 
 extern "C" int cfm_ode_fixed_grad_f32(const float* const* W, const float* const* b, const int* dims, int n_layers,
@@ -239,18 +127,13 @@ extern "C" int cfm_ode_fixed_grad_f32(const float* const* W, const float* const*
     const int d = dims[4];
     const SmArgs A = small_args(W, b, dims);
     CgOut O;
-    int P = 0;
-    for (int l = 0; l < 4; ++l) {
-        if (!dW[l] || !db[l]) return CFM_EINVAL;
-        O.dW[l] = dW[l]; O.db[l] = db[l];
-        P += dims[l + 1] * (dims[l] + 1);
-    }
+    const int P = cg_out(dims, dW, db, &O);
+    if (P < 0) return CFM_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    float* tspan_dev = (float*)ws;
-    float* part = (float*)((char*)ws + cfm_align_up(sizeof(float) * (size_t)n_t, 256));
-    rc = cfm_hip(hipMemcpyAsync(tspan_dev, t_span, sizeof(float) * n_t, hipMemcpyHostToDevice, s));
+    const CgWs w = cg_carve(ws, n_t);
+    rc = cfm_hip(hipMemcpyAsync(w.tspan, t_span, sizeof(float) * n_t, hipMemcpyHostToDevice, s));
     if (rc) return rc;
-    if (scheme == CFM_ODE_RK4) return ode_grad_launch<CFM_ODE_RK4>(A, B, d, tspan_dev, n_t, traj, g_traj, g_initial, part, P, O, s);
-    if (scheme == CFM_ODE_MIDPOINT) return ode_grad_launch<CFM_ODE_MIDPOINT>(A, B, d, tspan_dev, n_t, traj, g_traj, g_initial, part, P, O, s);
-    return ode_grad_launch<CFM_ODE_EULER>(A, B, d, tspan_dev, n_t, traj, g_traj, g_initial, part, P, O, s);
+    if (scheme == CFM_ODE_RK4) return ode_grad_launch<CFM_ODE_RK4>(A, B, d, w.tspan, n_t, traj, g_traj, g_initial, w.part, P, O, s);
+    if (scheme == CFM_ODE_MIDPOINT) return ode_grad_launch<CFM_ODE_MIDPOINT>(A, B, d, w.tspan, n_t, traj, g_traj, g_initial, w.part, P, O, s);
+    return ode_grad_launch<CFM_ODE_EULER>(A, B, d, w.tspan, n_t, traj, g_traj, g_initial, w.part, P, O, s);
 }

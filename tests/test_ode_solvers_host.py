@@ -91,11 +91,11 @@ def test_package_tableaus_equal_the_restatements_copy():
 
 
 def test_kernel_source_carries_the_same_tsit5_constants():
-    """csrc/ode.hip spells every tsit5 entry with the digits of the package's table (the casts to float happen at the
-    use, from these float64 constants)."""
+    """csrc/ode_tableau.h (the one table of ode.hip's solvers and small_grad.hip's gradient kernels) spells every tsit5
+    entry with the digits of the package's table (the casts to float happen at the use, from these float64 constants)."""
     adaptive, _ = _package_tableaus()
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = open(os.path.join(root, "conditional-flow-matching_amd", "csrc", "ode.hip")).read()
+    src = open(os.path.join(root, "conditional-flow-matching_amd", "csrc", "ode_tableau.h")).read()
     tab = adaptive["tsit5"]
     for v in [x for row in tab["a"] for x in row] + list(tab["c"][:4]) + list(tab["e"][:6]):
         assert repr(abs(v)) in src, v
