@@ -286,7 +286,7 @@ def grad_tables(Ws, bs):
 
 def t_span_f32(t_span):
     """(ts, pointer, n_t): t_span as a contiguous float32 numpy array on the host.  The pointer is into ts: keep ts
-    referenced until the call that reads it has returned (and, where the entry copies it asynchronously, until the
-    stream has been synchronised)."""
+    referenced until the call that reads it has returned — no longer: the library has consumed a host array by then
+    (include/cfm_gfx950.h; tests/test_gpu_stream_contract.py overwrites it behind a busy stream)."""
     ts = np.ascontiguousarray(torch.as_tensor(t_span, dtype=torch.float32).cpu().numpy())
     return ts, ts.ctypes.data_as(ctypes.c_void_p), ts.shape[0]

@@ -217,18 +217,24 @@ extern "C" int cfm_ode_euler_mlp_f32(const float* const* W, const float* const* 
     return cfm_ode_fixed_mlp_f32(W, b, dims, n_layers, x0, B, t_span, n_t, CFM_ODE_EULER, traj, nfe, ws, stream);
 }
 
-static double* g_ode_pinned = nullptr;
+// Read-back buffer of the adaptive host drivers (pinned host memory, 64 bytes): one per HOST THREAD, as the assignment
+// driver's poll buffer (assign_driver.h, AsgThread) — two threads in adaptive solves on their own streams read their own
+// norms and controller words, never each other's.  Allocated by the thread's first read and kept for its lifetime.
+static thread_local double* g_ode_pinned = nullptr;
 
 static int read_red(hipStream_t s, const double* dev, int count, double* host) {
-    if (!g_ode_pinned) {
-        int rc = cfm_hip(hipHostMalloc((void**)&g_ode_pinned, 64, hipHostMallocDefault));
+    if (count < 1 || count > 8) return CFM_EINVAL;
+    double* pinned = g_ode_pinned;
+    if (!pinned) {
+        int rc = cfm_hip(hipHostMalloc((void**)&pinned, 64, hipHostMallocDefault));
         if (rc) return rc;
+        g_ode_pinned = pinned;
     }
-    int rc = cfm_hip(hipMemcpyAsync(g_ode_pinned, dev, sizeof(double) * count, hipMemcpyDeviceToHost, s));
+    int rc = cfm_hip(hipMemcpyAsync(pinned, dev, sizeof(double) * count, hipMemcpyDeviceToHost, s));
     if (rc) return rc;
     rc = cfm_hip(hipStreamSynchronize(s));
     if (rc) return rc;
-    for (int i = 0; i < count; ++i) host[i] = g_ode_pinned[i];
+    for (int i = 0; i < count; ++i) host[i] = pinned[i];
     return 0;
 }
 

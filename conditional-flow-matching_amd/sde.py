@@ -216,7 +216,7 @@ def _run_one_launch(sde, fields, y0, y, steps, g_steps, srk, given, noise, gener
     name = "cfm_sde_srk_mlp_f32" if srk else "cfm_sde_em_mlp_f32"
     check(getattr(lib, name)(Wf, bf, Ws, bs, cd, 4, ptr(y), B, host, len(steps), _kernel_reverse_flag(sde),
                              ptr(xi), seed, ptr(traj), ptr(ws), stream_ptr()), name)
-    torch.cuda.current_stream().synchronize()          # `host` (pageable) must outlive the copy
+    # (no synchronisation: a host array may be dropped as soon as the call returns, include/cfm_gfx950.h)
     return torch.cat([y0.to(torch.float32)[None].to(y0.device), traj.to(y0.device)])
 
 
@@ -531,8 +531,7 @@ class DSBMFlowSolver(FlowSolver):
     def _odeint_hip(self, pair, x0, t_span, fused):
         from .ode import _solve_hip
         rc, what, traj, nfe, _, ts = _solve_hip("pair_mlp", pair[0], x0, t_span, self.ode_solver, second=pair[1], fused=fused)
-        check(rc, what)
-        torch.cuda.current_stream().synchronize()          # `ts` (pageable) must outlive the copy
+        check(rc, what)          # (`ts` may go when the call has returned: include/cfm_gfx950.h, host arrays)
         self.nfe = nfe
         return traj.to(x0.device)
 

@@ -10,18 +10,28 @@
  * Conventions (all entry points):
  *   - every pointer is a DEVICE pointer owned by the caller (contiguous,
  *     row-major) unless the parameter is documented "host";
- *   - `stream` is a hipStream_t passed as void*; work is enqueued on it and the
- *     call returns without synchronising, EXCEPT cfm_assign_exact_f32,
- *     cfm_assign_exact_batch_f32 and cfm_ode_*_mlp_f32 whose control flow is data dependent: they pump their
- *     step kernels on `stream` and poll a few bytes of device state, so they
- *     return only when the result is resident in the output buffers;
+ *   - `stream` is a hipStream_t passed as void*; ALL work (launches, memsets, copies) is enqueued on it and the
+ *     call returns without synchronising, EXCEPT cfm_assign_exact_f32, cfm_assign_exact_batch_f32 and the ADAPTIVE
+ *     solves (cfm_ode_dopri5_mlp_f32, cfm_ode_adaptive_mlp_f32, cfm_ode_adaptive_rec_mlp_f32,
+ *     cfm_ode_dopri5_cnf_mlp_f32, cfm_ode_adaptive_cnf_mlp_f32, cfm_ode_adaptive_gradmlp_f32) whose control flow is
+ *     data dependent: they pump their step kernels on `stream` and read a few bytes of device state back, so they
+ *     return only when the result is resident in the output buffers.  The fixed-step solves (cfm_ode_euler_*,
+ *     cfm_ode_fixed_*), the SDE trajectories and every gradient entry are asynchronous like the rest: their nfe is
+ *     known on the host, their trajectory is ready when `stream` reaches it;
+ *   - a HOST array passed to an entry (pointer tables, dims, t_span, step records) may be overwritten or freed as
+ *     soon as the call returns, also by the asynchronous entries: the tables are read during the call, and the
+ *     data arrays are copied with hipMemcpyAsync from pageable memory, which the runtime stages before it returns
+ *     (tests/test_gpu_stream_contract.py overwrites each behind a busy stream, at up to 640 KB);
  *   - no entry point allocates or frees device memory: scratch comes from the
  *     caller through `ws` (size from cfm_workspace_bytes);
  *   - return value: 0 = ok, <0 = invalid argument (CFM_E*), >0 = hipError_t;
  *   - no exceptions cross the boundary; no global state except a lazily
  *     initialised per-device properties cache, per HOST THREAD the captured launch
  *     programs (hipGraphs) of the exact solver's last four (workspace, size, batch,
- *     stream) combinations + 2 KiB of pinned memory, and the solver-parameter table
+ *     stream) combinations + 2 KiB of pinned memory, per HOST THREAD 64 bytes of pinned memory the adaptive ODE
+ *     drivers read their norms and controller words back through (allocated by the thread's first adaptive solve;
+ *     host threads on their own streams never share a read-back buffer), one process-wide mutex that lets ONE
+ *     persistent adaptive solve run at a time, and the solver-parameter table
  *     of include/cfm_gfx950_tuning.h (measurement / tuning exports that no
  *     binding needs; a solve snapshots the table under a mutex when it starts).
  */
