@@ -24,12 +24,12 @@ from .schedule import (  # noqa: F401
     LinearDecreasingNoiseScheduler,
     NoiseScheduler,
 )
-from .cnf import CNF, DifferentiableCNF, RegularizedCNF, log_likelihood  # noqa: F401
+from .cnf import CNF, AugmentationModule, DifferentiableCNF, RegularizedCNF, log_likelihood  # noqa: F401
 from .ode import AdaptiveDifferentiableNeuralODE, DifferentiableNeuralODE  # noqa: F401
 from .action_matching import action_matching_loss  # noqa: F401
 from .optim import FusedAdam  # noqa: F401
 from .train import DSBMStep, RegressionStep, SF2MStep  # noqa: F401
-from .sde import DSBMFlowSolver  # noqa: F401
+from .sde import DSBMFlowSolver, FlowSolver  # noqa: F401
 from .optimal_transport import OTPlanSampler, wasserstein  # noqa: F401
 from .trajectory import TrajectoryFlowMatcher  # noqa: F401
 

@@ -26,12 +26,19 @@ unpinned, as the forward solvers are.
 
 ``RegularizedCNF`` adds the reference's kinetic and Jacobian penalties (``AugmentationModule`` with ``squared_l2_reg`` /
 ``jacobian_frobenius_reg``, ``CNFLitModule.step``) as further state columns ``[l, (e), (f), y]``: forward
-``cfm_ode_euler_cnf_reg_mlp_f32``, backward one launch of ``cfm_cnf_reg_euler_grad_f32``.
+``cfm_ode_euler_cnf_reg_mlp_f32``, backward one launch of ``cfm_cnf_reg_euler_grad_f32``.  It takes the
+``L1`` and ``L2`` path lengths as penalties too (``l1_reg``, ``l2_reg``: state ``[l, (L1), (L2), (e), (f), y]``).
+
+``AugmentationModule`` is the reference's class of that name: which of these columns a solve carries, with or without
+the trace.  ``FlowSolver.odeint`` (sde.py) integrates them next to the trajectory, for ``ode_solver="euler"`` in one
+launch of the same forward entry in its "no trace" mode.
 
 Hutchinson probes are fixed for a whole solve (FFJORD's convention, model-comparison's ``CNF.noise``
 slot): ``cnf.noise`` if set, else one draw per ``NeuralODE.trajectory`` call, kept as
 ``cnf.last_noise``.  The ML-CNF tutorial redraws the probe at every evaluation; that is not replicated.
 """
+import contextlib
+import ctypes
 import math
 
 import torch
@@ -304,6 +311,111 @@ class DifferentiableCNF(CNF):
 
 # ---- regularised CNF training: the kinetic and Jacobian penalties as path integrals ----------------
 REG_NAMES = ("squared_L2", "jacobian_frobenius")        # bit 0, bit 1 of reg_mask; the reference's order
+# every regulariser column in the reference's order (augmentation.py:158-177), which is not bit order, with its reg_mask
+# bit (include/cfm_gfx950.h: CFM_REG_*)
+AUG_REG_BITS = (("L1", 4), ("L2", 8), ("squared_L2", 1), ("jacobian_frobenius", 2))
+TRACE_EXACT, TRACE_HUTCH, TRACE_NONE = 0, 1, 2          # CFM_TRACE_*
+
+
+def _mask_of(names):
+    return sum(bit for n, bit in AUG_REG_BITS if n in names)
+
+
+def _reg_integrands(mask, v, jac):
+    """The regulariser integrands of ``mask`` at a velocity v [B, d] (jac [B, d, d]: dv/dx, read with bit 1 only), in
+    the reference's order: L1Reg, L2Reg, SquaredL2Reg, JacobianFrobeniusReg of augmentation.py:21-73."""
+    d = v.shape[1]
+    out = []
+    if mask & 4:
+        out.append(v.abs().mean(1))
+    if mask & 8:
+        out.append(torch.norm(v, p=2, dim=1) / d ** 0.5)
+    if mask & 1:
+        out.append((v * v).sum(1))
+    if mask & 2:
+        out.append(torch.norm(jac.reshape(jac.shape[0], -1), p=2, dim=1) / d)
+    return out
+
+
+class AugmentationModule(torch.nn.Module):
+    """The reference's ``AugmentationModule`` (runner/src/models/components/augmentation.py:137-210): which path
+    integrals a solve carries in front of the state, in which order, and with which coefficients.  ``names`` /
+    ``coeffs`` / ``aug_dims`` and both return shapes of ``forward`` are the reference's.  ``cnf_estimator``: None or
+    ``"exact"``.  ``integrands(f, t, x)`` evaluates the columns' time derivatives for any callable field with autograd
+    (what ``AugmentedVectorField`` does, :266-303); ``FlowSolver.odeint`` integrates them, in one HIP launch where it can."""
+
+    def __init__(self, cnf_estimator=None, l1_reg=0., l2_reg=0., squared_l2_reg=0., jacobian_frobenius_reg=0.,
+                 jacobian_diag_frobenius_reg=0., jacobian_off_diag_frobenius_reg=0.):
+        super().__init__()
+        if cnf_estimator not in (None, "exact"):
+            raise ValueError(f"cnf_estimator {cnf_estimator!r}: None or 'exact' (the reference's AugmentationModule builds "
+                             "the exact trace for 'exact' and none for anything else)")
+        if jacobian_diag_frobenius_reg > 0. or jacobian_off_diag_frobenius_reg > 0.:
+            raise NotImplementedError(
+                "jacobian_diag_frobenius_reg / jacobian_off_diag_frobenius_reg are not built: the reference takes the "
+                "diagonal as jac.view(N, -1)[:, ::d], which for d > 1 is the first output's gradient and not the "
+                "diagonal (that would be a stride of d + 1), and no config of the reference sets either coefficient")
+        self.cnf_estimator = cnf_estimator
+        given = {"L1": l1_reg, "L2": l2_reg, "squared_L2": squared_l2_reg, "jacobian_frobenius": jacobian_frobenius_reg}
+        self.names = (["log_prob"] if cnf_estimator == "exact" else []) + [n for n, _ in AUG_REG_BITS if given[n] > 0.]
+        self.coeffs = torch.tensor(([1] if cnf_estimator == "exact" else []) + [given[n] for n, _ in AUG_REG_BITS if given[n] > 0.])
+        self.aug_dims = len(self.names)
+        self.reg_mask = _mask_of(self.names)
+
+    def forward(self, x):
+        """``(reg, x)`` without a trace, ``(delta_logprob, reg, x)`` with one: the regulariser columns times their
+        coefficients (``zeros(1)`` when there is none)."""
+        if self.cnf_estimator is None:
+            if self.aug_dims == 0:
+                return torch.zeros(1).type_as(x), x
+            aug, x = x[:, :self.aug_dims], x[:, self.aug_dims:]
+            return aug * self.coeffs.to(aug), x
+        delta_logprob, aug, x = x[:, :1], x[:, 1:self.aug_dims], x[:, self.aug_dims:]
+        reg = aug * self.coeffs[1:].to(aug)
+        if self.aug_dims == 1:
+            reg = torch.zeros(1).type_as(x)
+        return delta_logprob, reg, x
+
+    def integrands(self, f, t, x):
+        """``(augs [B, aug_dims], dx [B, d])`` of the field ``f(t, x)`` at x [B, d]: the Jacobian, where a column needs
+        it (log_prob, jacobian_frobenius), by one autograd.grad per output column."""
+        need_jac = self.cnf_estimator == "exact" or bool(self.reg_mask & 2)
+        with torch.enable_grad() if need_jac else contextlib.nullcontext():
+            xin = x.detach().requires_grad_(True) if need_jac else x
+            dx = f(t, xin)
+            dx = dx.reshape(dx.shape[0], -1)
+            jac = None
+            if need_jac:
+                rows = [torch.autograd.grad(dx[:, j].sum(), xin, retain_graph=True)[0] for j in range(dx.shape[1])]
+                jac = torch.stack(rows, 1)                       # jac[b, j, i] = d dx_j / d x_i
+        dx = dx.detach() if need_jac else dx
+        cols = [-torch.diagonal(jac, dim1=1, dim2=2).sum(1)] if self.cnf_estimator == "exact" else []
+        cols += _reg_integrands(self.reg_mask, dx, jac)
+        augs = torch.stack(cols, 1) if cols else dx.new_zeros((dx.shape[0], 0))
+        return augs, dx
+
+
+def augmented_euler_hip(m, x0, t_span, mode, mask):
+    """``(traj [n_t, B, a + d], nfe)`` of one launch of ``cfm_ode_euler_cnf_reg_mlp_f32`` on the MLP ``m`` from
+    ``[0, .., 0, x0]`` (exact trace or none: no probe), or None where the entry declines (CFM_EINVAL inside the envelope:
+    the fused path is switched off, or the grid has more than 3 B (a + d) points)."""
+    lib = _lib.load()
+    dev = x0.device
+    Wp, bp, dims, keep = m.hip_params(dev)
+    a = (mode != TRACE_NONE) + bin(mask).count("1")
+    B, d = x0.shape
+    state = torch.cat([torch.zeros((B, a), dtype=torch.float32, device=dev), _lib.to_dev_f32(x0, dev)], 1)
+    ts, tsp, n_t = _lib.t_span_f32(t_span)
+    traj = torch.empty((n_t, B, a + d), dtype=torch.float32, device=dev)
+    jsq = torch.empty((max(n_t - 1, 1), B), dtype=torch.float32, device=dev) if mask & 2 else None
+    ws = _lib.workspace(_lib.OP_ODE, B, max(dims[1:4]), a + d, dev)
+    nfe = ctypes.c_int(0)
+    rc = lib.cfm_ode_euler_cnf_reg_mlp_f32(Wp, bp, dims, 4, ptr(state), B, tsp, n_t, mode, None, mask, ptr(traj), ptr(jsq),
+                                           ctypes.byref(nfe), ptr(ws), stream_ptr())
+    if rc == -1:
+        return None
+    _lib.check(rc, "cfm_ode_euler_cnf_reg_mlp_f32")
+    return traj, nfe.value
 
 
 class _CNFRegEulerFunction(torch.autograd.Function):
@@ -332,24 +444,28 @@ class RegularizedCNF(DifferentiableCNF):
     ``AugmentationModule`` builds (runner/src/models/components/augmentation.py:137-210) under ``AugmentedVectorField``
     (:266-303), integrated and differentiated as ``CNFLitModule.step`` does (runner/src/models/cfm_module.py:1412-1454).
 
-    The state is ``[l, (e), (f), y]`` of width 1 + r + d.  A column is carried only if its coefficient is > 0, in the
-    reference's order (``names``): ``log_prob``; ``squared_L2`` (e += h |v|^2, ``SquaredL2Reg``); ``jacobian_frobenius``
-    (f += h ||dv/dx||_F / d, ``JacobianFrobeniusReg``).  With both coefficients 0 this is the parent class.
+    The state is ``[l, (L1), (L2), (e), (f), y]`` of width 1 + r + d.  A column is carried only if its coefficient is > 0,
+    in the reference's order (``names``): ``log_prob``; ``L1`` (+= h mean_j |v_j|, ``L1Reg``); ``L2`` (+= h |v| / sqrt(d),
+    ``L2Reg``); ``squared_L2`` (e += h |v|^2, ``SquaredL2Reg``); ``jacobian_frobenius`` (f += h ||dv/dx||_F / d,
+    ``JacobianFrobeniusReg``).  With every coefficient 0 this is the parent class.
 
     ``solve`` runs on the HIP kernels (``last_path == "hip"``: ``cfm_ode_euler_cnf_reg_mlp_f32`` forward, one launch of
     ``cfm_cnf_reg_euler_grad_f32`` backward; columns l and y are bit-equal to the parent's solve) under the parent's
-    conditions, for the exact trace with either or both penalties and for a Hutchinson estimator with ``squared_L2``
-    alone.  Everything else runs the same recurrence in differentiable torch ops (``"generic"``): CPU, float64, other
+    conditions, for the exact trace with any of the penalties and for a Hutchinson estimator without
+    ``jacobian_frobenius``.  Everything else runs the same recurrence in differentiable torch ops (``"generic"``): CPU, float64, other
     fields, ``jacobian_frobenius`` with a Hutchinson estimator, the fused path switched off, a grid of more than
     3 B (1 + r + d) points."""
 
-    def __init__(self, model, squared_l2_reg=0.0, jacobian_frobenius_reg=0.0, estimator="exact", noise=None):
+    def __init__(self, model, squared_l2_reg=0.0, jacobian_frobenius_reg=0.0, estimator="exact", noise=None, l1_reg=0.0,
+                 l2_reg=0.0):
         super().__init__(model, estimator=estimator, noise=noise)
-        if squared_l2_reg < 0.0 or jacobian_frobenius_reg < 0.0:
+        given = {"L1": l1_reg, "L2": l2_reg, "squared_L2": squared_l2_reg, "jacobian_frobenius": jacobian_frobenius_reg}
+        if min(given.values()) < 0.0:
             raise ValueError("a regularisation coefficient is >= 0 (0: the column is not carried)")
-        self.reg_mask = (1 if squared_l2_reg > 0.0 else 0) | (2 if jacobian_frobenius_reg > 0.0 else 0)
-        self.names = ["log_prob"] + [n for k, n in enumerate(REG_NAMES) if self.reg_mask >> k & 1]
-        self.coeffs = torch.tensor([1.0] + [float(c) for c in (squared_l2_reg, jacobian_frobenius_reg) if c > 0.0])
+        carried = [n for n, _ in AUG_REG_BITS if given[n] > 0.0]
+        self.reg_mask = _mask_of(carried)
+        self.names = ["log_prob"] + carried
+        self.coeffs = torch.tensor([1.0] + [float(given[n]) for n in carried])
         self.aug_dims = len(self.names)
 
     def solve(self, x_aug, t_span):
@@ -358,7 +474,7 @@ class RegularizedCNF(DifferentiableCNF):
         a = self.aug_dims
         if x_aug.dim() != 2 or x_aug.shape[1] < a + 1:
             raise ValueError(f"the state is [B, {a} + d] ({', '.join(self.names)}, x); got {tuple(x_aug.shape)}")
-        return self._solve(x_aug, t_span, a, _CNFRegEulerFunction, self.estimator == "exact" or self.reg_mask == 1,
+        return self._solve(x_aug, t_span, a, _CNFRegEulerFunction, self.estimator == "exact" or not self.reg_mask & 2,
                            (self.reg_mask,))
 
     def _solve_generic(self, x_aug, ts, eps):
@@ -397,12 +513,8 @@ class RegularizedCNF(DifferentiableCNF):
                 v, jv = torch.func.vmap(lambda yy, ee: torch.func.jvp(f, (yy,), (ee,)))(y, eps)
                 div = (eps * jv).sum(-1)
             cols[0] = cols[0] - h * div
-            k = 1
-            if self.reg_mask & 1:
-                cols[k] = cols[k] + h * (v * v).sum(1)
-                k += 1
-            if self.reg_mask & 2:
-                cols[k] = cols[k] + h * torch.norm(jac.reshape(jac.shape[0], -1), p=2, dim=1) / d
+            for k, g in enumerate(_reg_integrands(self.reg_mask, v, jac), 1):
+                cols[k] = cols[k] + h * g
             y = y + h * v
         return torch.cat([torch.stack(cols, 1), y], 1)
 

@@ -32,6 +32,13 @@
 //          J e_k, one cg_gemm_t and one cg_outer on a sixth tile buffer JB; S is read from the forward's side buffer
 //          jsq [n_t - 1, B].  Below Tb_3 the sweep is the one above.
 // REG = 0 is the kernel as it was: every REG branch is an `if constexpr`.
+//
+// NV (reg_mask bits 2 and 3): the state is [l, (L1), (L2), (e), (f), y], L1 += h (sum_j |v_j|) / d,
+// L2 += h |v| / sqrt(d).  With c1, c2 their upstream columns g_n gains c1 (sum_j |v_j|) / d + c2 |v| / sqrt(d), so the primal
+// output cotangent is h (a + 2 ce v + c1 sign(v) / d + c2 v / (sqrt(d) |v|)), sign(0) = 0 and no c2 term where |v| = 0
+// (torch.abs's and torch.norm's backward).  |v|^2 per row is one sm_rowsum over v (a scratch region behind the tile
+// buffers); nothing else changes.  As in the forward, the Jacobian bit stays compile-time (REG is 0 or 2) and which of
+// e, L1, L2 are carried is read from `mask` at run time: a column that is absent has cotangent 0.
 #pragma once
 
 static_assert(SM_MB == 1, "the gradient kernel is written for one 16-row block per tile");
@@ -113,17 +120,23 @@ static_assert(cg_lds_bytes == 127488, "the gradient kernel");
 // the sixth tile buffer (JB) of the jacobian_frobenius sweep: above 128 KB, inside the CU's 160 KB
 constexpr size_t cg_lds_bytes_jac = cg_lds_bytes + sizeof(float) * SM_ROWS * SM_LD;
 static_assert(cg_lds_bytes_jac == 131840 && cg_lds_bytes_jac <= 160 * 1024, "the gradient kernel with the Jacobian penalty");
+// NV: sm_rowsum's scratch behind the last tile buffer
+constexpr size_t cg_lds_bytes_red = sizeof(float) * 4 * SM_ROWS;
+static_assert(cg_lds_bytes + cg_lds_bytes_red <= 128 * 1024 && cg_lds_bytes_jac + cg_lds_bytes_red <= 160 * 1024, "the |v| row sum");
 
-// traj [n_t, B, D]: the forward solve (y_n is read), D = 1 + cg_reg_cols(REG) + d; G [B, D]; g0 [B, D] or null;
+// traj [n_t, B, D]: the forward solve (y_n is read), D = 1 + cg_reg_cols(REG) + d (NV: cg_aug_cols(0, mask) + d);
+// G [B, D]; g0 [B, D] or null;
 // part [gridDim.x][P]: the workgroup's partial gradient in the order W0, b0, W1, b1, W2, b2, W3, b3 (each as the caller's
-// tensor is laid out); jsq [n_t - 1, B]: S per (step, row) as the forward wrote it (read with REG bit 1 only)
-template <int MODE, int REG = 0>
+// tensor is laid out); jsq [n_t - 1, B]: S per (step, row) as the forward wrote it (read with REG bit 1 only); mask:
+// reg_mask, read by the NV kernels only
+template <int MODE, int REG = 0, bool NV = false>
 __global__ __launch_bounds__(256) void ode_small_euler_grad(SmArgs A, int B, int d, const float* __restrict__ tspan, int n_t,
                                                          const float* __restrict__ traj, const float* __restrict__ eps,
                                                          const float* __restrict__ G, float* __restrict__ g0,
                                                          float* __restrict__ part, int P,
-                                                         const float* __restrict__ jsq) {
+                                                         const float* __restrict__ jsq, int mask) {
     static_assert(REG >= 0 && REG <= 3 && (MODE == AUG_EXACT || !(REG & 2)), "the Jacobian penalty needs the exact directions");
+    static_assert(!NV || !(REG & 1), "NV: bit 0 is read from mask");
     extern __shared__ __attribute__((aligned(16))) float small_lds[];
     constexpr int TS = SM_ROWS * SM_LD, WS = SM_W * SM_LD;
     float* Wl = small_lds;
@@ -136,10 +149,15 @@ __global__ __launch_bounds__(256) void ode_small_euler_grad(SmArgs A, int B, int
     float* X3 = X2 + TS;
     float* Y3 = X3 + TS;
     float* JB = Y3 + TS;                      // REG bit 1 only (cg_lds_bytes_jac)
+    float* red = (REG & 2) ? JB + TS : JB;    // NV only (cg_lds_bytes_red)
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     sm_stage_weights(A, d, Wl, bl, wt, tid);
     cg_stage_transposed(A, WT, tid);
-    constexpr int c0 = 1 + cg_reg_cols(REG);  // the column of y_0 in a state row
+    // the columns of L1, L2, e, f and y_0 in a state row [l, (L1), (L2), (e), (f), y]
+    const bool h1 = NV && (mask & 4), h2 = NV && (mask & 8), he = NV ? (mask & 1) != 0 : (REG & 1) != 0;
+    const int k1 = 1, k2 = k1 + (h1 ? 1 : 0);
+    const int ke = NV ? k2 + (h2 ? 1 : 0) : 1, kf = NV ? ke + (he ? 1 : 0) : 1 + (REG & 1);
+    const int c0 = NV ? kf + ((REG >> 1) & 1) : 1 + cg_reg_cols(REG);
     const int D = d + c0;
     const size_t n = (size_t)B * D;
     const int col = wv * 16 + (lane & 15);
@@ -159,7 +177,7 @@ __global__ __launch_bounds__(256) void ode_small_euler_grad(SmArgs A, int B, int
 
     for (int row0 = blockIdx.x * SM_ROWS; row0 < B; row0 += gridDim.x * SM_ROWS) {
         const int nrows = B - row0;
-        SmTile a, cv, ep, yn, ce, cf;
+        SmTile a, cv, ep, yn, ce, cf, cl1, cl2;
 #pragma unroll
         for (int i = 0; i < SM_V; ++i) {
             const int gr = row0 + sm_row(i, lane);
@@ -167,7 +185,12 @@ __global__ __launch_bounds__(256) void ode_small_euler_grad(SmArgs A, int B, int
             a.v[i] = ok ? G[(size_t)gr * D + c0 + col] : 0.f;
             cv.v[i] = gr < B ? G[(size_t)gr * D] : 0.f;
             if constexpr (REG & 1) ce.v[i] = gr < B ? G[(size_t)gr * D + 1] : 0.f;
-            if constexpr (REG & 2) cf.v[i] = gr < B ? G[(size_t)gr * D + 1 + (REG & 1)] : 0.f;
+            if constexpr (REG & 2) cf.v[i] = gr < B ? G[(size_t)gr * D + kf] : 0.f;
+            if constexpr (NV) {
+                ce.v[i] = (he && gr < B) ? G[(size_t)gr * D + ke] : 0.f;
+                cl1.v[i] = (h1 && gr < B) ? G[(size_t)gr * D + k1] : 0.f;
+                cl2.v[i] = (h2 && gr < B) ? G[(size_t)gr * D + k2] : 0.f;
+            }
             ep.v[i] = (MODE == AUG_HUTCH && ok) ? eps[(size_t)gr * d + col] : 0.f;
             yn.v[i] = (ok && n_t >= 2) ? traj[(size_t)(n_t - 2) * n + (size_t)gr * D + c0 + col] : 0.f;
         }
@@ -232,6 +255,27 @@ __global__ __launch_bounds__(256) void ode_small_euler_grad(SmArgs A, int B, int
                     for (int i = 0; i < SM_V; ++i) {
                         const float v = (col < d) ? c[0][i] + bv : 0.f;
                         ap.v[i] = h * (a.v[i] + 2.f * ce.v[i] * v);
+                    }
+                }
+                if constexpr (NV) {                       // the same v; the seed gains the L1 and L2 terms
+                    cg_put(dst, hh[2], lane, col);
+                    sm_lds_barrier();
+                    sm_gemm(dst, W3, wv, lane, c);
+                    const float bv = (col < d) ? bl[3 * SM_W + col] : 0.f;
+                    SmTile vv, p;
+#pragma unroll
+                    for (int i = 0; i < SM_V; ++i) {
+                        vv.v[i] = (col < d) ? c[0][i] + bv : 0.f;
+                        p.v[i] = vv.v[i] * vv.v[i];
+                    }
+                    const SmTile vs = sm_rowsum(p, red, wv, lane);         // |v|^2 per row
+                    const float rd = 1.f / (float)d, rsd = 1.f / sqrtf((float)d);
+#pragma unroll
+                    for (int i = 0; i < SM_V; ++i) {
+                        const float v = vv.v[i];
+                        const float sg = v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f);
+                        const float rn = vs.v[i] > 0.f ? rsd / sqrtf(vs.v[i]) : 0.f;
+                        ap.v[i] = h * (((a.v[i] + 2.f * ce.v[i] * v) + cl1.v[i] * sg * rd) + cl2.v[i] * v * rn);
                     }
                 }
             }
@@ -381,7 +425,12 @@ __global__ __launch_bounds__(256) void ode_small_euler_grad(SmArgs A, int B, int
                 if (gr < B && col < d) g0[(size_t)gr * D + c0 + col] = a.v[i];
                 if (gr < B && lw) g0[(size_t)gr * D] = cv.v[i];
                 if constexpr (REG & 1) { if (gr < B && lw) g0[(size_t)gr * D + 1] = ce.v[i]; }
-                if constexpr (REG & 2) { if (gr < B && lw) g0[(size_t)gr * D + 1 + (REG & 1)] = cf.v[i]; }
+                if constexpr (REG & 2) { if (gr < B && lw) g0[(size_t)gr * D + kf] = cf.v[i]; }
+                if constexpr (NV) {
+                    if (gr < B && lw && he) g0[(size_t)gr * D + ke] = ce.v[i];
+                    if (gr < B && lw && h1) g0[(size_t)gr * D + k1] = cl1.v[i];
+                    if (gr < B && lw && h2) g0[(size_t)gr * D + k2] = cl2.v[i];
+                }
             }
         }
     }
@@ -389,13 +438,13 @@ __global__ __launch_bounds__(256) void ode_small_euler_grad(SmArgs A, int B, int
     cg_store_partial(A, d, part + (size_t)blockIdx.x * P, dWa, dba, dwt, lane, col);
 }
 
-template <int MODE, int REG = 0>
+template <int MODE, int REG = 0, bool NV = false>
 static int cnf_grad_launch(const SmArgs& A, int B, int d, const float* tspan_dev, int n_t, const float* traj,
                            const float* eps, const float* G, float* g0, float* part, int P, const CgOut& O, hipStream_t s,
-                           const float* jsq = nullptr) {
-    return cg_launch<ode_small_euler_grad<MODE, REG>, ((REG & 2) ? 160 : 128) * 1024>(
-        (REG & 2) ? cg_lds_bytes_jac : cg_lds_bytes, s, B, part, P, A, O, 1.f, nullptr, A, B, d, tspan_dev, n_t, traj, eps, G, g0,
-        part, P, jsq);
+                           const float* jsq = nullptr, int mask = 0) {
+    return cg_launch<ode_small_euler_grad<MODE, REG, NV>, ((REG & 2) ? 160 : 128) * 1024>(
+        ((REG & 2) ? cg_lds_bytes_jac : cg_lds_bytes) + (NV ? cg_lds_bytes_red : 0), s, B, part, P, A, O, 1.f, nullptr, A, B, d,
+        tspan_dev, n_t, traj, eps, G, g0, part, P, jsq, mask);
 }
 
 extern "C" int cfm_cnf_euler_grad_f32(const float* const* W, const float* const* b, const int* dims, int n_layers,
@@ -418,7 +467,8 @@ extern "C" int cfm_cnf_euler_grad_f32(const float* const* W, const float* const*
 }
 
 // the gradient of the regularised solve (cfm_ode_euler_cnf_reg_mlp_f32, cnf_reg.h): traj, g_final, g_initial [., B, D] with
-// D = 1 + cg_reg_cols(reg_mask) + d; jac_sq: the forward's side buffer (reg_mask bit 1)
+// D = cg_aug_cols(mode, reg_mask) + d; jac_sq: the forward's side buffer (reg_mask bit 1); mode 2 (no trace) has no gradient:
+// cnf_check refuses it
 extern "C" int cfm_cnf_reg_euler_grad_f32(const float* const* W, const float* const* b, const int* dims, int n_layers,
                                           const float* traj, int B, const float* t_span, int n_t, int mode, const float* eps,
                                           int reg_mask, const float* jac_sq, const float* g_final, float* const* dW,
@@ -434,6 +484,11 @@ extern "C" int cfm_cnf_reg_euler_grad_f32(const float* const* W, const float* co
     const CgWs w = cg_carve(ws, n_t);
     rc = cfm_hip(hipMemcpyAsync(w.tspan, t_span, sizeof(float) * n_t, hipMemcpyHostToDevice, s));
     if (rc) return rc;
+    if (reg_mask & 12) {        // three NV instantiations: bits 0, 2 and 3 at run time
+        if (mode == 1) return cnf_grad_launch<AUG_HUTCH, 0, true>(A, B, d, w.tspan, n_t, traj, eps, g_final, g_initial, w.part, P, O, s, jac_sq, reg_mask);
+        if (reg_mask & 2) return cnf_grad_launch<AUG_EXACT, 2, true>(A, B, d, w.tspan, n_t, traj, eps, g_final, g_initial, w.part, P, O, s, jac_sq, reg_mask);
+        return cnf_grad_launch<AUG_EXACT, 0, true>(A, B, d, w.tspan, n_t, traj, eps, g_final, g_initial, w.part, P, O, s, jac_sq, reg_mask);
+    }
     if (mode == 1) return cnf_grad_launch<AUG_HUTCH, 1>(A, B, d, w.tspan, n_t, traj, eps, g_final, g_initial, w.part, P, O, s, jac_sq);
     if (reg_mask == 1) return cnf_grad_launch<AUG_EXACT, 1>(A, B, d, w.tspan, n_t, traj, eps, g_final, g_initial, w.part, P, O, s, jac_sq);
     if (reg_mask == 2) return cnf_grad_launch<AUG_EXACT, 2>(A, B, d, w.tspan, n_t, traj, eps, g_final, g_initial, w.part, P, O, s, jac_sq);

@@ -5,7 +5,7 @@
 // with its kernel ode_small_euler_grad<MODE, REG> in cnf_grad.h (small_grad.hip).
 #pragma once
 
-// cnf_reg.hip: the solve, one launch (mode 0 exact / 1 Hutchinson; reg_mask checked by the caller)
+// cnf_reg.hip: the solve, one launch (mode 0 exact / 1 Hutchinson / 2 no trace; reg_mask checked by the caller)
 extern "C" int cfm_cnf_reg_solve_internal(const SmArgs* A, int B, int d, const float* t_span, int n_t, float* traj,
                                           float* tspan_dev, const float* eps, float* jsq, int mode, int reg_mask,
                                           hipStream_t s);
@@ -16,11 +16,11 @@ extern "C" int cfm_ode_euler_cnf_reg_mlp_f32(const float* const* W, const float*
                                              void* stream) {
     int d; SmArgs A;
     if (!x0 || !t_span || !traj || !ws || n_t < 1 || cnf_reg_check(mode, reg_mask, jac_sq)) return CFM_EINVAL;
-    int rc = cnf_check(W, b, dims, n_layers, B, mode, eps, &d, &A);
+    int rc = cnf_check(W, b, dims, n_layers, B, mode, eps, &d, &A, CFM_TRACE_NONE);
     if (rc) return rc;
     if (!fx_monotone(t_span, n_t)) return CFM_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    const int D = d + 1 + cg_reg_cols(reg_mask);
+    const int D = d + cg_aug_cols(mode, reg_mask);              // [(l), (L1), (L2), (e), (f), y]
     OdeWs w = ode_carve(ws, B, maxwidth(dims, n_layers), D);       // workspace of CFM_OP_ODE at D
     const size_t n = (size_t)B * D;
     if ((size_t)n_t > 3 * n) return CFM_EINVAL;                    // t_span copy: w.x .. w.xt

@@ -14,18 +14,30 @@
 // The three row sums use three scratch regions, so none is overwritten while another wave still reads it.  S_n is written
 // per (step, row) to the caller's side buffer jsq [n_t - 1, B]: the backward divides by sqrt(S) and reads the forward's
 // bits there in place of a second pass over the directions.
+//
+// NV: the sampler's path diagnostics, AugmentationModule's L1 and L2 columns, and the "no trace" mode.
+// State [(l), (L1), (L2), (e), (f), y] in the reference's order; per step, at (y_n, t_n):
+//   L1 += h (sum_j |v_j|) / d        L2 += h sqrt(sum_j v_j^2) / sqrt(d)
+// L2 and e share the row sum |v|^2; L1 takes one more sm_rowsum in a fourth scratch region.  The trace mode and the
+// Jacobian bit change the sweep and are template parameters; which of L1, L2 and e are carried only changes which
+// columns are stepped and stored, so an NV kernel reads that from `mask` at run time (REG is 0 or 2 there).  NV = false
+// is the kernel as it was: every NV branch is an `if constexpr`.  MODE == AUG_NONE has no l column and no direction
+// sweep: sm_field and two row sums, the y columns those of ode_small_fixed<CFM_ODE_EULER, AUG_NONE>.
 #include "small_field.h"
 
 constexpr int cg_reg_cols(int REG) { return (REG & 1) + ((REG >> 1) & 1); }
 
 // sm_field_aug<MODE> with the penalties' integrands: vsq = |v|^2 (REG bit 0) and jsq = S (REG bit 1, exact trace only),
-// per row in every lane holding the row.  Ab2: the third tile buffer; red: 3 x [4][SM_ROWS].
-template <int MODE, int REG>
+// per row in every lane holding the row.  Ab2: the third tile buffer; red: 3 x [4][SM_ROWS].  NV: vsq always, and
+// l1 = sum_j |v_j| through a fourth region of red.
+template <int MODE, int REG, bool NV = false>
 __device__ __forceinline__ SmTile sm_field_reg(const SmTile& y, float t, const SmArgs& A, int d, float* Abuf0, float* Abuf1,
                                                float* Abuf2, const float* Wl, const float* bl, const float* wt,
                                                const SmTile& eps, int nrows, float* red, int wv, int lane, SmTile& div,
-                                               SmTile& vsq, SmTile& jsq) {
-    static_assert(REG >= 1 && REG <= 3 && (MODE == AUG_EXACT || (MODE == AUG_HUTCH && REG == 1)), "exact x {e, f, e + f}; Hutchinson x {e}");
+                                               SmTile& vsq, SmTile& jsq, SmTile& l1) {
+    static_assert(NV ? (REG == 0 || (REG == 2 && MODE == AUG_EXACT))
+                     : (REG >= 1 && REG <= 3 && (MODE == AUG_EXACT || (MODE == AUG_HUTCH && REG == 1))),
+                  "exact x {e, f, e + f}; Hutchinson x {e}; NV: the Jacobian bit alone is compile-time");
     const int col = wv * 16 + (lane & 15);
 #pragma unroll
     for (int i = 0; i < SM_V; ++i) Abuf0[sm_row(i, lane) * SM_LD + col] = (col < d) ? y.v[i] : 0.f;
@@ -120,24 +132,38 @@ __device__ __forceinline__ SmTile sm_field_reg(const SmTile& y, float t, const S
         }
     }
     div = sm_rowsum(q, red, wv, lane);
-    if constexpr (REG & 1) {
+    if constexpr ((REG & 1) || NV) {
         SmTile p;
 #pragma unroll
         for (int i = 0; i < SM_V; ++i) p.v[i] = acc.v[i] * acc.v[i];
         vsq = sm_rowsum(p, red + 4 * SM_ROWS, wv, lane);
     }
     if constexpr (REG & 2) jsq = sm_rowsum(sq, red + 8 * SM_ROWS, wv, lane);
+    if constexpr (NV) {
+        SmTile p;
+#pragma unroll
+        for (int i = 0; i < SM_V; ++i) p.v[i] = fabsf(acc.v[i]);
+        l1 = sm_rowsum(p, red + 12 * SM_ROWS, wv, lane);
+    }
     return acc;
 }
 
 constexpr size_t cr_lds_bytes = small_lds_bytes(1, 3, true) + sizeof(float) * 8 * SM_ROWS;
 static_assert(cr_lds_bytes == 84736, "the regularised solve");
+// NV: a fourth row-sum region; without a trace two tile buffers and two regions (vsq, l1): two workgroups fit a CU
+constexpr size_t cr_lds_bytes_nv = cr_lds_bytes + sizeof(float) * 4 * SM_ROWS;
+constexpr size_t cr_lds_bytes_notrace = small_lds_bytes(1, 2, true) + sizeof(float) * 4 * SM_ROWS;
+static_assert(cr_lds_bytes_nv == 84992 && cr_lds_bytes_notrace == 80128 && 2 * cr_lds_bytes_notrace <= 160 * 1024,
+              "the regularised solve with the |v| integrals");
 
-// traj [n_t, B, D], slice 0 = the initial state; jsq [n_t - 1, B] (written with REG bit 1 only)
-template <int MODE, int REG>
+// traj [n_t, B, D], slice 0 = the initial state; jsq [n_t - 1, B] (written with REG bit 1 only); mask: reg_mask, read by
+// the NV kernels only (bits 0, 2, 3: which of e, L1, L2 the state carries)
+template <int MODE, int REG, bool NV = false>
 __global__ __launch_bounds__(256) void ode_small_euler_reg(SmArgs A, int B, int d, const float* __restrict__ tspan, int n_t,
                                                         float* __restrict__ traj, const float* __restrict__ eps,
-                                                        float* __restrict__ jsq) {
+                                                        float* __restrict__ jsq, int mask) {
+    static_assert(MODE != AUG_NONE || (NV && REG == 0), "no trace: an NV kernel without the Jacobian bit");
+    constexpr bool TRACE = MODE != AUG_NONE;
     extern __shared__ __attribute__((aligned(16))) float small_lds[];
     float* Wl = small_lds;
     float* bl = Wl + 4 * SM_W * SM_LD;
@@ -145,30 +171,50 @@ __global__ __launch_bounds__(256) void ode_small_euler_reg(SmArgs A, int B, int 
     float* Ab0 = wt + SM_W;
     float* Ab1 = Ab0 + SM_ROWS * SM_LD;
     float* Ab2 = Ab1 + SM_ROWS * SM_LD;
-    float* red = Ab2 + SM_ROWS * SM_LD;
+    float* red = TRACE ? Ab2 + SM_ROWS * SM_LD : Ab2;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     sm_stage_weights(A, d, Wl, bl, wt, tid);
-    constexpr int ce = 1, cf = 1 + (REG & 1), c0 = 1 + cg_reg_cols(REG);     // the columns of e, f and y_0
+    // the columns of L1, L2, e, f and y_0: [(l), (L1), (L2), (e), (f), y]
+    const bool h1 = NV && (mask & 4), h2 = NV && (mask & 8), he = NV ? (mask & 1) != 0 : (REG & 1) != 0;
+    const int c1 = TRACE ? 1 : 0, c2 = c1 + (h1 ? 1 : 0);
+    const int ce = NV ? c2 + (h2 ? 1 : 0) : 1, cf = NV ? ce + (he ? 1 : 0) : 1 + (REG & 1);
+    const int c0 = NV ? cf + ((REG >> 1) & 1) : 1 + cg_reg_cols(REG);
     const int D = d + c0;
     const size_t n = (size_t)B * D;
     const int col = wv * 16 + (lane & 15);
     const bool lw = wv == 0 && (lane & 15) == 0;
     for (int row0 = blockIdx.x * SM_ROWS; row0 < B; row0 += gridDim.x * SM_ROWS) {
-        SmTile x, xl, xe, xf, ep;
+        SmTile x, xl, xe, xf, ep, x1, x2;
 #pragma unroll
         for (int i = 0; i < SM_V; ++i) {
             const int gr = row0 + sm_row(i, lane);
             x.v[i] = (gr < B && col < d) ? traj[(size_t)gr * D + c0 + col] : 0.f;
-            xl.v[i] = gr < B ? traj[(size_t)gr * D] : 0.f;
-            xe.v[i] = ((REG & 1) && gr < B) ? traj[(size_t)gr * D + ce] : 0.f;
+            xl.v[i] = (TRACE && gr < B) ? traj[(size_t)gr * D] : 0.f;
+            xe.v[i] = (he && gr < B) ? traj[(size_t)gr * D + ce] : 0.f;
             xf.v[i] = ((REG & 2) && gr < B) ? traj[(size_t)gr * D + cf] : 0.f;
             ep.v[i] = (MODE == AUG_HUTCH && gr < B && col < d) ? eps[(size_t)gr * d + col] : 0.f;
+            if constexpr (NV) {
+                x1.v[i] = (h1 && gr < B) ? traj[(size_t)gr * D + c1] : 0.f;
+                x2.v[i] = (h2 && gr < B) ? traj[(size_t)gr * D + c2] : 0.f;
+            }
         }
         __syncthreads();
         for (int k = 0; k + 1 < n_t; ++k) {
             const float t = tspan[k], dt = tspan[k + 1] - tspan[k];
-            SmTile dv, vs, js;
-            const SmTile f = sm_field_reg<MODE, REG>(x, t, A, d, Ab0, Ab1, Ab2, Wl, bl, wt, ep, B - row0, red, wv, lane, dv, vs, js);
+            SmTile dv, vs, js, ls;
+            SmTile f;
+            if constexpr (TRACE) {
+                f = sm_field_reg<MODE, REG, NV>(x, t, A, d, Ab0, Ab1, Ab2, Wl, bl, wt, ep, B - row0, red, wv, lane, dv, vs, js, ls);
+            } else {
+                f = sm_field(x, t, A, d, Ab0, Ab1, Wl, bl, wt, wv, lane);
+                SmTile p;
+#pragma unroll
+                for (int i = 0; i < SM_V; ++i) p.v[i] = f.v[i] * f.v[i];
+                vs = sm_rowsum(p, red, wv, lane);
+#pragma unroll
+                for (int i = 0; i < SM_V; ++i) p.v[i] = fabsf(f.v[i]);
+                ls = sm_rowsum(p, red + 4 * SM_ROWS, wv, lane);
+            }
 #pragma unroll
             for (int i = 0; i < SM_V; ++i) {
                 const float acc = 1.f * f.v[i];                                   // fx_b<CFM_ODE_EULER>(0)
@@ -176,11 +222,20 @@ __global__ __launch_bounds__(256) void ode_small_euler_reg(SmArgs A, int B, int 
                 const int gr = row0 + sm_row(i, lane);
                 const size_t at = (size_t)(k + 1) * n + (size_t)gr * D;
                 if (gr < B && col < d) traj[at + c0 + col] = x.v[i];
-                const float lf = -dv.v[i];
-                const float lacc = 1.f * lf;
-                xl.v[i] = fmaf(dt, lacc, xl.v[i]);
-                if (gr < B && lw) traj[at] = xl.v[i];
-                if constexpr (REG & 1) {
+                if constexpr (TRACE) {
+                    const float lf = -dv.v[i];
+                    const float lacc = 1.f * lf;
+                    xl.v[i] = fmaf(dt, lacc, xl.v[i]);
+                    if (gr < B && lw) traj[at] = xl.v[i];
+                }
+                if constexpr (NV) {
+                    x1.v[i] = fmaf(dt, ls.v[i] / (float)d, x1.v[i]);
+                    x2.v[i] = fmaf(dt, sqrtf(vs.v[i]) / sqrtf((float)d), x2.v[i]);
+                    if (gr < B && lw && h1) traj[at + c1] = x1.v[i];
+                    if (gr < B && lw && h2) traj[at + c2] = x2.v[i];
+                    xe.v[i] = fmaf(dt, vs.v[i], xe.v[i]);
+                    if (gr < B && lw && he) traj[at + ce] = xe.v[i];
+                } else if constexpr (REG & 1) {
                     xe.v[i] = fmaf(dt, vs.v[i], xe.v[i]);
                     if (gr < B && lw) traj[at + ce] = xe.v[i];
                 }
@@ -196,22 +251,32 @@ __global__ __launch_bounds__(256) void ode_small_euler_reg(SmArgs A, int B, int 
     }
 }
 
-template <int MODE, int REG>
+template <int MODE, int REG, bool NV = false>
 static int cnf_reg_solve(const SmArgs& A, int B, int d, const float* t_span, int n_t, float* traj, float* tspan_dev,
-                         const float* eps, float* jsq, hipStream_t s) {
-    const int grid = small_grid<ode_small_euler_reg<MODE, REG>, 128 * 1024>(B);
+                         const float* eps, float* jsq, int mask, hipStream_t s) {
+    const int grid = small_grid<ode_small_euler_reg<MODE, REG, NV>, 128 * 1024>(B);
     if (grid < 0) return CFM_EINVAL;
     int rc = cfm_hip(hipMemcpyAsync(tspan_dev, t_span, sizeof(float) * n_t, hipMemcpyHostToDevice, s));
     if (rc) return rc;
-    hipLaunchKernelGGL((ode_small_euler_reg<MODE, REG>), dim3(grid), dim3(256), cr_lds_bytes, s, A, B, d, tspan_dev, n_t, traj, eps, jsq);
+    const size_t lds = !NV ? cr_lds_bytes : MODE == AUG_NONE ? cr_lds_bytes_notrace : cr_lds_bytes_nv;
+    hipLaunchKernelGGL((ode_small_euler_reg<MODE, REG, NV>), dim3(grid), dim3(256), lds, s, A, B, d, tspan_dev, n_t, traj, eps,
+                       jsq, mask);
     return cfm_status();
 }
 
+// Eight instantiations: the four of masks 1 to 3 as they were, and four NV ones (no trace; exact with and without the
+// Jacobian bit; Hutchinson) that take bits 0, 2 and 3 at run time.  Masks 1 to 3 with a trace never reach an NV kernel.
 extern "C" int cfm_cnf_reg_solve_internal(const SmArgs* A, int B, int d, const float* t_span, int n_t, float* traj,
                                           float* tspan_dev, const float* eps, float* jsq, int mode, int reg_mask,
                                           hipStream_t s) {
-    if (mode == 1) return cnf_reg_solve<AUG_HUTCH, 1>(*A, B, d, t_span, n_t, traj, tspan_dev, eps, jsq, s);
-    if (reg_mask == 1) return cnf_reg_solve<AUG_EXACT, 1>(*A, B, d, t_span, n_t, traj, tspan_dev, eps, jsq, s);
-    if (reg_mask == 2) return cnf_reg_solve<AUG_EXACT, 2>(*A, B, d, t_span, n_t, traj, tspan_dev, eps, jsq, s);
-    return cnf_reg_solve<AUG_EXACT, 3>(*A, B, d, t_span, n_t, traj, tspan_dev, eps, jsq, s);
+    if (mode == 2) return cnf_reg_solve<AUG_NONE, 0, true>(*A, B, d, t_span, n_t, traj, tspan_dev, eps, jsq, reg_mask, s);
+    if (reg_mask & 12) {
+        if (mode == 1) return cnf_reg_solve<AUG_HUTCH, 0, true>(*A, B, d, t_span, n_t, traj, tspan_dev, eps, jsq, reg_mask, s);
+        if (reg_mask & 2) return cnf_reg_solve<AUG_EXACT, 2, true>(*A, B, d, t_span, n_t, traj, tspan_dev, eps, jsq, reg_mask, s);
+        return cnf_reg_solve<AUG_EXACT, 0, true>(*A, B, d, t_span, n_t, traj, tspan_dev, eps, jsq, reg_mask, s);
+    }
+    if (mode == 1) return cnf_reg_solve<AUG_HUTCH, 1>(*A, B, d, t_span, n_t, traj, tspan_dev, eps, jsq, reg_mask, s);
+    if (reg_mask == 1) return cnf_reg_solve<AUG_EXACT, 1>(*A, B, d, t_span, n_t, traj, tspan_dev, eps, jsq, reg_mask, s);
+    if (reg_mask == 2) return cnf_reg_solve<AUG_EXACT, 2>(*A, B, d, t_span, n_t, traj, tspan_dev, eps, jsq, reg_mask, s);
+    return cnf_reg_solve<AUG_EXACT, 3>(*A, B, d, t_span, n_t, traj, tspan_dev, eps, jsq, reg_mask, s);
 }

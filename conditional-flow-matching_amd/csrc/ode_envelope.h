@@ -14,11 +14,11 @@ struct OdeStepRec { float t, dt, t_k1; int out; };
 static_assert(sizeof(OdeStepRec) == 16, "the step log's record");
 
 // the envelope of the CNF entries: the small-field kernels (small_envelope, every width >= 1, d + 1 <= SM_W), fused path
-// on, mode 0 (exact trace) or 1 (Hutchinson, eps given)
+// on, mode 0 (exact trace) or 1 (Hutchinson, eps given); max_mode 2 lets the regularised solve's "no trace" through
 static inline int cnf_check(const float* const* W, const float* const* b, const int* dims, int n_layers, int B, int mode,
-                            const float* eps, int* d_out, SmArgs* A) {
+                            const float* eps, int* d_out, SmArgs* A, int max_mode = 1) {
     int d;
-    if (!W || !b || B <= 0 || (mode != 0 && mode != 1) || (mode == 1 && !eps)) return CFM_EINVAL;
+    if (!W || !b || B <= 0 || mode < 0 || mode > max_mode || (mode == 1 && !eps)) return CFM_EINVAL;
     if (small_envelope(dims, n_layers, &d)) return CFM_EINVAL;
     for (int l = 1; l <= 3; ++l) if (dims[l] < 1) return CFM_EINVAL;
     if (d < 1 || d + 1 > SM_W || !cfm_ode_fused_internal()) return CFM_EINVAL;
@@ -27,11 +27,15 @@ static inline int cnf_check(const float* const* W, const float* const* b, const 
     return 0;
 }
 
-// the regularised CNF state [l, (e), (f), y]: reg_mask bit 0 squared_L2, bit 1 jacobian_frobenius; at
-// least one; the Jacobian penalty with the exact trace only (mode 0) and with its side buffer
+// the regularised CNF state [(l), (L1), (L2), (e), (f), y], the reference's order, not bit order:
+// reg_mask bit 0 squared_L2, bit 1 jacobian_frobenius, bit 2 L1, bit 3 L2; at least one; the Jacobian penalty with the
+// exact trace only (mode 0) and with its side buffer; mode 2 (no trace) carries no l column
 constexpr int cg_reg_cols(int REG) { return (REG & 1) + ((REG >> 1) & 1); }
+constexpr int cg_aug_cols(int mode, int reg_mask) {
+    return (mode != 2) + (reg_mask & 1) + ((reg_mask >> 1) & 1) + ((reg_mask >> 2) & 1) + ((reg_mask >> 3) & 1);
+}
 static inline int cnf_reg_check(int mode, int reg_mask, const float* jac_sq) {
-    if (reg_mask < 1 || reg_mask > 3) return CFM_EINVAL;
+    if (mode < 0 || mode > 2 || reg_mask < 1 || reg_mask > 15) return CFM_EINVAL;
     if ((reg_mask & 2) && (mode != 0 || !jac_sq)) return CFM_EINVAL;
     return 0;
 }

@@ -393,12 +393,13 @@ class FlowSolver(torch.nn.Module):
     schedule ``sigma``; ``last_path`` says ``"hip"`` or ``"eager"`` after a call."""
 
     def __init__(self, vector_field, dim, score_field=None, sigma=None, ode_solver="euler", sde_solver="euler",
-                 dt=0.01, atol=1e-5, rtol=1e-5, **kwargs):
+                 dt=0.01, atol=1e-5, rtol=1e-5, augmentations=None, **kwargs):
         super().__init__()
         self.net, self.dim, self.score_net = vector_field, dim, score_field
         self.separate_score = score_field is not None
         self.sigma, self.ode_solver, self.sde_solver = sigma, ode_solver, sde_solver
         self.dt, self.atol, self.rtol, self.nfe = dt, atol, rtol, 0
+        self.augmentations = augmentations          # a cnf.AugmentationModule or None; may be assigned later (solver.py:201)
         self.last_path = None
 
     def forward_flow_and_score(self, t, x, only_flow=False):       # solver.py:103-121
@@ -427,11 +428,57 @@ class FlowSolver(torch.nn.Module):
         return self.forward_flow_and_score(t, x, only_flow=True)
 
     def odeint(self, x0, t_span):
+        """The ODE trajectory [n_t, B, d]; with ``augmentations`` set, ``(traj, aug [n_t, B, aug_dims])`` as solver.py:201-216:
+        the path integrals of the ``AugmentationModule`` from zero initial columns.  ``ode_solver="euler"`` on an fp32 CUDA
+        state of a small-envelope time-varying ``cfm_amd.MLP`` flow net runs one launch of ``cfm_ode_euler_cnf_reg_mlp_f32``
+        (``last_path == "hip"``, ``nfe == n_t - 1``); everything else steps the augmented field in torch ops
+        (``"eager"``)."""
         from .ode import NeuralODE
         self.nfe = 0
-        node = NeuralODE(self.forward_ode_drift, solver=self.ode_solver, atol=self.atol, rtol=self.rtol,
-                         return_t_eval=False)
-        return node(x0, t_span)
+        if self.augmentations is None:
+            node = NeuralODE(self.forward_ode_drift, solver=self.ode_solver, atol=self.atol, rtol=self.rtol,
+                             return_t_eval=False)
+            return node(x0, t_span)
+        return self._odeint_augmented(x0, t_span, self._hip_flow(x0))
+
+    def _hip_flow(self, x0):
+        """The flow MLP when the augmented Euler kernel takes ``forward_ode_drift`` on x0 (cnf._small_envelope), else None."""
+        from .cnf import _small_envelope
+        m = time_mlp(self.net, bare=True)
+        if (m is None or self.ode_solver != "euler" or x0.dim() != 2 or not x0.is_cuda or x0.dtype != torch.float32
+                or not _small_envelope(m, x0.shape[1])):
+            return None
+        ok = all(p.dtype == torch.float32 and p.device == x0.device for p in m.parameters())
+        return m if ok else None
+
+    def _odeint_augmented(self, x0, t_span, m):
+        """``(traj, aug)`` under ``self.augmentations``: one HIP launch on the MLP ``m`` where there is one and the entry
+        takes the call, else the augmented field ``[augs, dx]`` stepped by ``NeuralODE``'s generic path."""
+        from .cnf import TRACE_EXACT, TRACE_NONE, augmented_euler_hip
+        from .ode import NeuralODE, _check_t_span
+        am = self.augmentations
+        a = am.aug_dims
+        if a == 0:
+            node = NeuralODE(self.forward_ode_drift, solver=self.ode_solver, atol=self.atol, rtol=self.rtol,
+                             return_t_eval=False)
+            traj = node(x0, t_span)
+            return traj, traj.new_zeros((*traj.shape[:2], 0))
+        if m is not None and am.reg_mask:
+            _check_t_span(torch.as_tensor(t_span, dtype=torch.float32).cpu())
+            with torch.no_grad():
+                got = augmented_euler_hip(m, x0, t_span, TRACE_EXACT if am.cnf_estimator == "exact" else TRACE_NONE, am.reg_mask)
+            if got is not None:
+                self.last_path, self.nfe = "hip", got[1]
+                return got[0][:, :, a:], got[0][:, :, :a]
+        self.last_path = "eager"
+
+        def field(t, state):
+            augs, dx = am.integrands(self.forward_ode_drift, t, state[:, a:])
+            return torch.cat([augs, dx], 1)
+        node = NeuralODE(field, solver=self.ode_solver, atol=self.atol, rtol=self.rtol, return_t_eval=False)
+        x = x0.reshape(x0.shape[0], -1)
+        sol = node(torch.cat([x.new_zeros((x.shape[0], a)), x], 1), t_span)
+        return sol[:, :, a:], sol[:, :, :a]
 
     def _hip_fields(self):
         """(flow MLP, score MLP) when sdeint's HIP paths can take the pair (the rule of NeuralODE._hip_mlp), else None."""
@@ -468,7 +515,9 @@ class DSBMFlowSolver(FlowSolver):
     ``midpoint`` or ``rk4`` run ``cfm_ode_fixed_pair_mlp_f32`` (one launch for 4 layers of widths <= 64;
     ``fused=False`` forces its launch-per-stage form: two forward passes, the halved difference, the stage combine —
     the same bits); ``dopri5`` / ``tsit5`` and every other field run ``NeuralODE``'s generic path on the combined
-    callable.  ``nfe`` counts one evaluation of the pair per stage.  ``last_path``: ``"hip"`` or ``"eager"``."""
+    callable.  ``nfe`` counts one evaluation of the pair per stage.  ``last_path``: ``"hip"`` or ``"eager"``.  With
+    ``augmentations`` set, ``odeint`` returns ``(traj, aug)`` from the generic path alone (the pair kernel has no augmented
+    form)."""
 
     def __init__(self, vector_field, dim, score_field=None, sigma=None, ode_solver="euler", sde_solver="euler", dt=0.01,
                  **kwargs):
@@ -516,6 +565,8 @@ class DSBMFlowSolver(FlowSolver):
     def odeint(self, x0, t_span, fused=None):
         from .ode import NeuralODE, _check_t_span
         self.nfe = 0
+        if self.augmentations is not None:      # the pair kernel has no augmented form: the combined callable, stepped in torch ops
+            return self._odeint_augmented(x0, t_span, None)
         pair = self._hip_pair()
         if (pair is not None and self.ode_solver in _lib.ODE_SCHEME and x0.dim() == 2 and x0.dtype == torch.float32
                 and torch.cuda.is_available()):

@@ -613,15 +613,28 @@ int cfm_cnf_euler_grad_f32(const float* const* W, const float* const* b, const i
                            const float* eps, const float* g_final, float* const* dW, float* const* db,
                            float* g_initial, void* ws, void* stream);
 
-/* Regularised CNF training (RNODE / TrajectoryNet): the Euler solve of the state that AugmentationModule builds
- * (runner/src/models/components/augmentation.py:137-210) under AugmentedVectorField (:266-303), and its gradient: what
- * CNFLitModule.step (runner/src/models/cfm_module.py:1412-1454) integrates and differentiates.
- * reg_mask: bit 0 = squared_L2 (SquaredL2Reg, augmentation.py:31-34: |v|^2), bit 1 = jacobian_frobenius
- * (JacobianFrobeniusReg, :64-73: ||dv/dx||_F / d); at least one bit (mask 0 is cfm_ode_fixed_cnf_mlp_f32 /
- * cfm_cnf_euler_grad_f32).  State rows [l, (e), (f), x], D = 1 + popcount(reg_mask) + d, columns in the reference's order
- * (:158-177); per step y += h v, l -= h div, e += h |v|^2, f += h ||J||_F / d, everything at (y_n, t_n); columns l and x
- * are the bit patterns of cfm_ode_fixed_cnf_mlp_f32 at CFM_ODE_EULER.  mode / eps as cfm_mlp_divergence_f32; bit 1 needs
- * mode 0 (the Jacobian's columns are the exact trace's directions), mode 1 takes reg_mask 1 only: CFM_EINVAL otherwise.
+/* trace modes of the regularised solve (modes 0 and 1 are the `mode` of cfm_mlp_divergence_f32) and its reg_mask bits */
+#define CFM_TRACE_EXACT      0   /* l -= h tr(dv/dx), d exact directions */
+#define CFM_TRACE_HUTCH      1   /* l -= h eps^T (dv/dx) eps, one probe per row, fixed for the solve */
+#define CFM_TRACE_NONE       2   /* AugmentationModule(cnf_estimator=None): no l column, no divergence; eps is ignored */
+#define CFM_REG_SQUARED_L2          1   /* SquaredL2Reg         (augmentation.py:31-34): |v|^2 */
+#define CFM_REG_JACOBIAN_FROBENIUS  2   /* JacobianFrobeniusReg (:64-73): ||dv/dx||_F / d */
+#define CFM_REG_L1                  4   /* L1Reg                (:21-23): (sum_j |v_j|) / d */
+#define CFM_REG_L2                  8   /* L2Reg                (:26-28, :10-12): sqrt(sum_j v_j^2) / sqrt(d) */
+
+/* The Euler solve of the state that AugmentationModule builds (runner/src/models/components/augmentation.py:137-210)
+ * under AugmentedVectorField (:266-303), and its gradient.  With a trace it is regularised CNF training (RNODE /
+ * TrajectoryNet): what CNFLitModule.step (runner/src/models/cfm_module.py:1412-1454) integrates and differentiates.
+ * Without one (CFM_TRACE_NONE) it is the sampler with path diagnostics: FlowSolver.odeint under val_augmentations
+ * (runner/src/models/components/solver.py:201-216, cfm_module.py:441-505).
+ * mode: CFM_TRACE_*; reg_mask: CFM_REG_* bits, 1 <= reg_mask <= 15 (mask 0 with a trace is cfm_ode_fixed_cnf_mlp_f32 /
+ * cfm_cnf_euler_grad_f32, without one cfm_ode_fixed_mlp_f32).  State rows [(l), (L1), (L2), (e), (f), x] in the
+ * reference's order (:158-177), which is not bit order; D = (mode != 2) + popcount(reg_mask) + d.  Per step y += h v,
+ * l -= h div, L1 += h (sum_j |v_j|) / d, L2 += h |v| / sqrt(d), e += h |v|^2, f += h ||J||_F / d, everything at (y_n, t_n).
+ * Columns l and x are the bit patterns of cfm_ode_fixed_cnf_mlp_f32 at CFM_ODE_EULER (CFM_TRACE_NONE: x those of
+ * cfm_ode_fixed_mlp_f32 at CFM_ODE_EULER), and l, e, f, x do not depend on bits 2 and 3.  eps as cfm_mlp_divergence_f32
+ * (read with CFM_TRACE_HUTCH only).  CFM_REG_JACOBIAN_FROBENIUS needs CFM_TRACE_EXACT (the Jacobian's columns are the
+ * exact trace's directions) and jac_sq: CFM_EINVAL otherwise, and for a mode outside 0..2 or a mask outside 1..15.
  * Forward: x0 device [B,D], traj device [n_t,B,D]; jac_sq device [n_t-1,B], written with bit 1 (||J||_F^2 per step and row,
  * which the gradient reads back), NULL allowed without it; t_span host float[n_t], strictly monotone either way;
  * ws: cfm_workspace_bytes(CFM_OP_ODE, B, max width, D), CFM_EINVAL when n_t > 3 B D.
@@ -634,8 +647,10 @@ int cfm_ode_euler_cnf_reg_mlp_f32(const float* const* W, const float* const* b, 
  * of cfm_module.py:1443, which in autograd differentiates JacobianFrobeniusReg's d rows of
  * autograd.grad(..., create_graph=True) (augmentation.py:37-61) a second time.  traj, t_span, mode, eps, reg_mask, jac_sq:
  * as given to / written by the forward; g_final device [B,D] = dL/d(final state); outputs as cfm_cnf_euler_grad_f32, with
- * g_initial device [B,D] or NULL (the columns of l, e and f pass through: each enters the recurrence linearly).  Where
- * ||J||_F = 0 its term has gradient 0, as torch.norm's backward has it.
+ * g_initial device [B,D] or NULL (the augmented columns pass through: each enters the recurrence linearly).  Where
+ * ||J||_F = 0 its term has gradient 0, as torch.norm's backward has it; so has L2's where |v| = 0, and L1's where
+ * v_j = 0 (torch.abs's backward: sign(0) = 0).  mode: CFM_TRACE_EXACT or CFM_TRACE_HUTCH; CFM_TRACE_NONE is CFM_EINVAL
+ * (no training loop differentiates the sampler's diagnostics).
  * ws: cfm_workspace_bytes(CFM_OP_CNF_GRAD, B, n_t, 0).  The result is the same bit pattern run to run. */
 int cfm_cnf_reg_euler_grad_f32(const float* const* W, const float* const* b, const int* dims, int n_layers,
                                const float* traj, int B, const float* t_span, int n_t, int mode,
