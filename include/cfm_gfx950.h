@@ -24,6 +24,15 @@
  *     (tests/test_gpu_stream_contract.py overwrites each behind a busy stream, at up to 640 KB);
  *   - no entry point allocates or frees device memory: scratch comes from the
  *     caller through `ws` (size from cfm_workspace_bytes);
+ *   - the contents of `ws` and of every output buffer on entry are ARBITRARY (stale bytes of another solve, zeros, NaN
+ *     patterns): an entry initialises every word it waits on, sums into or indexes by, on `stream`, and writes its
+ *     outputs whole.  Nothing outside the output buffers and the first cfm_workspace_bytes bytes of `ws` (for the
+ *     entries that state their own size: those bytes) is written, and inputs are not modified, except by the entries
+ *     documented as in place (cfm_scale_inv_f32, cfm_sqrt_inplace_f32, cfm_adam_step_f32, cfm_sde_em_step_f32).  The
+ *     one precondition on an output is stated where it holds: `out` of cfm_rbf_mix_sum_f32 is zeroed by the caller.
+ *     Where an entry declines a shape (CFM_EINVAL for a t_span that does not fit its scratch, for a solve outside
+ *     the one-launch kernel's envelope), the declining call has written nothing.
+ *     (tests/test_gpu_memory_contract.py: every entry on 0x00-, 0xFF- and stale-filled buffers between guard zones);
  *   - return value: 0 = ok, <0 = invalid argument (CFM_E*), >0 = hipError_t;
  *   - no exceptions cross the boundary; no global state except a lazily
  *     initialised per-device properties cache, per HOST THREAD the captured launch

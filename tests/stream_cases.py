@@ -24,6 +24,9 @@ relative tolerance named in the case — the RBF sum at the 1e-6 of its own test
 (the bound tests/test_gpu_unbalanced.py puts on a plan's mass; 2^-52 per addition leaves room for 4000 of them), the fp32
 marginal error at 1e-5 — and everything else bit for bit.  The assignment cases compare the permutation only.
 
+The factories take shape parameters whose defaults are the table's shapes, and the ops read their sizes from the inputs:
+tests/test_gpu_memory_contract.py builds its edge shapes (FOOTPRINT_EXTRA) from them; the table's cases and ids do not move.
+
 Importing this module needs neither a device nor the library (the host test reads the table's keys)."""
 import ctypes
 import math
@@ -202,8 +205,8 @@ SK_ITERS = 20              # stop_thr = 0: a fixed iteration count, far above th
 ERR_RTOL = 1e-5            # last_err: fp32 partial sums added with atomics
 
 
-def _mk_cost(seed, dev):
-    return _to(dev, {"M": _cost(_g(seed, 3), B0, B1)})
+def _mk_cost(seed, dev, b0=B0, b1=B1):
+    return _to(dev, {"M": _cost(_g(seed, 3), b0, b1)})
 
 
 def _op_sinkhorn(inp):
@@ -222,19 +225,19 @@ case("cfm_sinkhorn_log_f32")(_mk_cost, _op_sinkhorn)
 case("cfm_sinkhorn_log_points_f32")(_mk_clouds(B0, B1, 2), _op_sinkhorn_points)
 
 
-def _mk_solved(with_u=0, rows=False):
+def _mk_solved(with_u=0, rows=False, b0=B0, b1=B1):
     """M and the Sinkhorn workspace of a finished solve on it (default stream, synchronised); u01 / rows for the samplers."""
     def make(seed, dev):
         from cfm_amd import optimal_transport as ot
         g = _g(seed, 4)
-        M = _cost(g, B0, B1).to(dev)
+        M = _cost(g, b0, b1).to(dev)
         r = ot.sinkhorn_log(M, REG, max_iter=SK_ITERS, stop_thr=0.0)
         torch.cuda.synchronize()
         inp = {"M": M, "ws": r.ws}
         if with_u:
             inp["u01"] = torch.rand(with_u, generator=g, dtype=torch.float64).to(dev)
         if rows:
-            inp["rows"] = torch.randint(0, B0, (with_u,), generator=g, dtype=torch.int64).to(dev)
+            inp["rows"] = torch.randint(0, b0, (with_u,), generator=g, dtype=torch.int64).to(dev)
         return inp
     return make
 
@@ -249,8 +252,9 @@ def _result(inp):
 def _op_potentials(inp):
     L = _lib()
     dev = inp["M"].device
-    u, v = torch.empty(B0, dtype=torch.float64, device=dev), torch.empty(B1, dtype=torch.float64, device=dev)
-    rc = L.load().cfm_sinkhorn_potentials_f64(L.ptr(inp["ws"]), B0, B1, L.ptr(u), L.ptr(v), L.stream_ptr())
+    b0, b1 = inp["M"].shape
+    u, v = torch.empty(b0, dtype=torch.float64, device=dev), torch.empty(b1, dtype=torch.float64, device=dev)
+    rc = L.load().cfm_sinkhorn_potentials_f64(L.ptr(inp["ws"]), b0, b1, L.ptr(u), L.ptr(v), L.stream_ptr())
     return [("u", u, None), ("v", v, None)], (rc,)
 
 
@@ -262,7 +266,8 @@ def _op_plan(inp):
 def _op_sk_cost(inp):
     L = _lib()
     out = torch.zeros(1, dtype=torch.float64, device=inp["M"].device)
-    rc = L.load().cfm_sinkhorn_cost_f64(L.ptr(inp["M"]), B0, B1, REG, L.ptr(inp["ws"]), L.ptr(out), L.stream_ptr())
+    b0, b1 = inp["M"].shape
+    rc = L.load().cfm_sinkhorn_cost_f64(L.ptr(inp["M"]), b0, b1, REG, L.ptr(inp["ws"]), L.ptr(out), L.stream_ptr())
     return [("cost", out, 1e-12)], (rc,)
 
 
@@ -285,10 +290,13 @@ case("cfm_partial_entropic_f64", note="plan at 1e-12: the mass normalisation is 
 
 
 # ------------------------------------------------------------------------------------------------ exact solvers
-def _mk_square(nb=1):
+def _mk_square(nb=1, n=NA):
+    """n = 1: _cost normalises by a maximum that is zero there; a constant 1 x 1 matrix instead."""
     def make(seed, dev):
         g = _g(seed, 5)
-        return _to(dev, {f"M{k}": _cost(g, NA, NA) for k in range(nb)})
+        if n == 1:
+            return _to(dev, {f"M{k}": torch.full((1, 1), 0.5 + 0.25 * seed + k) for k in range(nb)})
+        return _to(dev, {f"M{k}": _cost(g, n, n) for k in range(nb)})
     return make
 
 
@@ -299,7 +307,7 @@ def _op_assign(inp):
 
 def _op_assign_batch(inp):
     from cfm_amd import optimal_transport as ot
-    return [("perm", ot.assign_exact_batch([inp["M0"], inp["M1"]]), None)], ()
+    return [("perm", ot.assign_exact_batch([inp[k] for k in sorted(inp) if k[0] == "M"]), None)], ()
 
 
 case("cfm_assign_exact_f32")(_mk_square(1), _op_assign)
@@ -310,11 +318,12 @@ def _op_transport(inp):
     L = _lib()
     M = inp["M"]
     dev = M.device
-    plan = torch.empty((B0, B1), dtype=torch.float64, device=dev)
+    b0, b1 = M.shape
+    plan = torch.empty((b0, b1), dtype=torch.float64, device=dev)
     tot = torch.empty(1, dtype=torch.float64, device=dev)
     info = torch.empty(8, dtype=torch.int32, device=dev)
-    ws = _ws(L.OP_TRANSPORT, B0, B1, 0, dev)
-    rc = L.load().cfm_transport_exact_f32(L.ptr(M), B0, B1, None, L.ptr(plan), L.ptr(tot), L.ptr(info), L.ptr(ws), L.stream_ptr())
+    ws = _ws(L.OP_TRANSPORT, b0, b1, 0, dev)
+    rc = L.load().cfm_transport_exact_f32(L.ptr(M), b0, b1, None, L.ptr(plan), L.ptr(tot), L.ptr(info), L.ptr(ws), L.stream_ptr())
     return [("plan", plan, None), ("total", tot, 1e-12), ("status", info[:1], None)], (rc,)
 
 
@@ -378,15 +387,15 @@ case("cfm_plan_sample_rows_pi_f64")(_mk_pi(True), _op_rows_pi)
 XB, XD = 1000, 5
 
 
-def _mk_xt(kind):
+def _mk_xt(kind, B=XB, d=XD):
     def make(seed, dev):
         g = _g(seed, 8)
-        inp = {"x0": _randn(g, XB, XD), "x1": _randn(g, XB, XD) + 0.25, "eps": _randn(g, XB, XD),
-               "i": torch.randperm(XB, generator=g), "j": torch.randperm(XB, generator=g)}
+        inp = {"x0": _randn(g, B, d), "x1": _randn(g, B, d) + 0.25, "eps": _randn(g, B, d),
+               "i": torch.randperm(B, generator=g), "j": torch.randperm(B, generator=g)}
         if kind == "icfm":
-            inp["t"] = _rand(g, XB)
+            inp["t"] = _rand(g, B)
         else:
-            inp["coef"] = _rand(g, XB, 4) * 0.9 + 0.05
+            inp["coef"] = _rand(g, B, 4) * 0.9 + 0.05
         return _to(dev, inp)
     return make
 
@@ -396,7 +405,7 @@ def _op_xt(inp):
     xt, ut, x0g, x1g = (torch.empty_like(inp["eps"]) for _ in range(4))
     p = L.ptr
     rc = L.load().cfm_sample_xt_ut_f32(L.VARIANT_ICFM, p(inp["x0"]), p(inp["x1"]), p(inp["i"]), p(inp["j"]), p(inp["t"]),
-                                       p(inp["eps"]), 0.1, None, None, None, XB, XD, p(xt), p(ut), p(x0g), p(x1g), L.stream_ptr())
+                                       p(inp["eps"]), 0.1, None, None, None, *inp["eps"].shape, p(xt), p(ut), p(x0g), p(x1g), L.stream_ptr())
     return [("xt", xt, None), ("ut", ut, None), ("x0g", x0g, None), ("x1g", x1g, None)], (rc,)
 
 
@@ -405,7 +414,7 @@ def _op_xt_sched(inp):
     xt, ut = torch.empty_like(inp["eps"]), torch.empty_like(inp["eps"])
     p = L.ptr
     rc = L.load().cfm_sample_xt_ut_sched_f32(p(inp["x0"]), p(inp["x1"]), p(inp["i"]), p(inp["j"]), p(inp["coef"]), p(inp["eps"]),
-                                             None, XB, XD, p(xt), p(ut), L.stream_ptr())
+                                             None, *inp["eps"].shape, p(xt), p(ut), L.stream_ptr())
     return [("xt", xt, None), ("ut", ut, None)], (rc,)
 
 
@@ -414,7 +423,7 @@ def _op_dsbm_sample(inp):
     xt, ft, bt = (torch.empty_like(inp["eps"]) for _ in range(3))
     p = L.ptr
     rc = L.load().cfm_sample_dsbm_f32(p(inp["x0"]), p(inp["x1"]), p(inp["i"]), p(inp["j"]), p(inp["coef"]), p(inp["eps"]),
-                                      XB, XD, p(xt), p(ft), p(bt), L.stream_ptr())
+                                      *inp["eps"].shape, p(xt), p(ft), p(bt), L.stream_ptr())
     return [("xt", xt, None), ("ft", ft, None), ("bt", bt, None)], (rc,)
 
 
@@ -431,10 +440,10 @@ case("cfm_gather_rows")(_mk_xt("icfm"), _op_gather)
 TT = 5
 
 
-def _mk_traj(seed, dev):
+def _mk_traj(seed, dev, B=XB, d=XD):
     g = _g(seed, 9)
-    return _to(dev, {"X": _randn(g, XB, TT, XD), "t_select": torch.randint(0, TT - 1, (XB,), generator=g, dtype=torch.int64),
-                     "t": _rand(g, XB) * 0.99, "eps": _randn(g, XB, XD)})
+    return _to(dev, {"X": _randn(g, B, TT, d), "t_select": torch.randint(0, TT - 1, (B,), generator=g, dtype=torch.int64),
+                     "t": _rand(g, B) * 0.99, "eps": _randn(g, B, d)})
 
 
 def _op_traj(inp):
@@ -442,7 +451,8 @@ def _op_traj(inp):
     p = L.ptr
     xt, ut = torch.empty_like(inp["eps"]), torch.empty_like(inp["eps"])
     tn = torch.empty_like(inp["t"])
-    rc = L.load().cfm_traj_xt_ut_f32(0, L.VARIANT_ICFM, p(inp["X"]), XB, TT, XD, None, p(inp["t_select"]), p(inp["t"]),
+    B, d = inp["eps"].shape
+    rc = L.load().cfm_traj_xt_ut_f32(0, L.VARIANT_ICFM, p(inp["X"]), B, TT, d, None, p(inp["t_select"]), p(inp["t"]),
                                      p(inp["eps"]), 0.1, None, 0, None, p(xt), p(ut), p(tn), L.stream_ptr())
     return [("xt", xt, None), ("ut", ut, None), ("t_net", tn, None)], (rc,)
 
@@ -488,29 +498,30 @@ def _train_ws(dims, B, dev, nets=1):
     return torch.empty(one * nets, dtype=torch.uint8, device=dev)
 
 
-def _mk_fwd_train(seed, dev):
+def _mk_fwd_train(seed, dev, B=BS):
     g = _g(seed, 11)
-    return _to(dev, {**_net(g, TD), "x": _randn(g, BS, TD[0])})
+    return _to(dev, {**_net(g, TD), "x": _randn(g, B, TD[0])})
 
 
 def _op_fwd_train(inp):
     L = _lib()
     Wp, bp, cd, dims, n = _tables(inp)
     dev = inp["x"].device
-    hid, pre = _train_bufs(dims, BS, dev)
-    out = torch.empty((BS, dims[n]), dtype=torch.float32, device=dev)
-    rc = L.load().cfm_mlp_forward_train_f32(L.ptr(inp["x"]), Wp, bp, cd, n, BS, _ptrs(hid), _ptrs(pre), L.ptr(out), L.stream_ptr())
+    B = inp["x"].shape[0]
+    hid, pre = _train_bufs(dims, B, dev)
+    out = torch.empty((B, dims[n]), dtype=torch.float32, device=dev)
+    rc = L.load().cfm_mlp_forward_train_f32(L.ptr(inp["x"]), Wp, bp, cd, n, B, _ptrs(hid), _ptrs(pre), L.ptr(out), L.stream_ptr())
     return [("out", out, None)] + [(f"hidden{l}", h, None) for l, h in enumerate(hid)] + [(f"preact{l}", z, None) for l, z in enumerate(pre)], (rc,)
 
 
 case("cfm_mlp_forward_train_f32")(_mk_fwd_train, _op_fwd_train)
 
 
-def _mk_backward(seed, dev):
+def _mk_backward(seed, dev, B=BS):
     g = _g(seed, 12)
-    inp = {**_net(g, TD), "a0": _randn(g, BS, TD[0]), "dout": _randn(g, BS, TD[-1])}
+    inp = {**_net(g, TD), "a0": _randn(g, B, TD[0]), "dout": _randn(g, B, TD[-1])}
     for l in range(1, 4):
-        inp[f"z{l}"] = _randn(g, BS, TD[l])
+        inp[f"z{l}"] = _randn(g, B, TD[l])
         inp[f"a{l}"] = torch.nn.functional.selu(inp[f"z{l}"])
     return _to(dev, inp)
 
@@ -534,23 +545,24 @@ def _op_backward(inp):
     dev = inp["dout"].device
     dW, db = _grads(inp)
     dx = torch.empty_like(inp["a0"])
-    ws = _train_ws(dims, BS, dev)
+    B = inp["a0"].shape[0]
+    ws = _train_ws(dims, B, dev)
     rc = L.load().cfm_mlp_backward_f32(_ptrs([inp[f"a{l}"] for l in range(n)]), _ptrs([None] + [inp[f"z{l}"] for l in range(1, n)]),
-                                       Wp, cd, n, BS, L.ptr(inp["dout"]), _ptrs(dW), _ptrs(db), L.ptr(dx), L.ptr(ws), L.stream_ptr())
+                                       Wp, cd, n, B, L.ptr(inp["dout"]), _ptrs(dW), _ptrs(db), L.ptr(dx), L.ptr(ws), L.stream_ptr())
     return _grad_outs(dW, db) + [("dx", dx, None)], (rc,)
 
 
 case("cfm_mlp_backward_f32")(_mk_backward, _op_backward)
 
 
-def _mk_step(kind):
+def _mk_step(kind, B=BS):
     def make(seed, dev):
         g = _g(seed, 13)
         d, o = TD[0] - 1, TD[-1]
-        inp = {**_net(g, TD, "f"), "xt": _randn(g, BS, d), "t": _rand(g, BS), "ut": _randn(g, BS, o)}
+        inp = {**_net(g, TD, "f"), "xt": _randn(g, B, d), "t": _rand(g, B), "ut": _randn(g, B, o)}
         if kind != "reg":
             inp.update(_net(g, TD, "s"))
-            inp.update({"eps": _randn(g, BS, o), "lam": _rand(g, BS) + 0.5, "wb": _rand(g, BS) + 0.5})
+            inp.update({"eps": _randn(g, B, o), "lam": _rand(g, B) + 0.5, "wb": _rand(g, B) + 0.5})
         return _to(dev, inp)
     return make
 
@@ -560,12 +572,13 @@ def _op_regression(inp):
     p = L.ptr
     Wp, bp, cd, dims, n = _tables(inp, "f")
     dev = inp["xt"].device
-    hid, pre = _train_bufs(dims, BS, dev)
+    B = inp["xt"].shape[0]
+    hid, pre = _train_bufs(dims, B, dev)
     dW, db = _grads(inp, "f")
-    g = torch.empty((BS, dims[n]), dtype=torch.float32, device=dev)
+    g = torch.empty((B, dims[n]), dtype=torch.float32, device=dev)
     loss = torch.empty(1, dtype=torch.float32, device=dev)
-    ws = _train_ws(dims, BS, dev)
-    rc = L.load().cfm_mlp_regression_step_f32(p(inp["xt"]), p(inp["t"]), p(inp["ut"]), Wp, bp, cd, n, BS, _ptrs(hid), _ptrs(pre),
+    ws = _train_ws(dims, B, dev)
+    rc = L.load().cfm_mlp_regression_step_f32(p(inp["xt"]), p(inp["t"]), p(inp["ut"]), Wp, bp, cd, n, B, _ptrs(hid), _ptrs(pre),
                                               p(g), _ptrs(dW), _ptrs(db), p(loss), None, p(ws), L.stream_ptr())
     return _grad_outs(dW, db) + [("g", g, None), ("loss", loss, None)], (rc,)
 
@@ -584,13 +597,14 @@ def _op_sf2m(inp):
     p = L.ptr
     Wp, bp, cd, dims, n, dW, db = _two_net(inp)
     dev = inp["xt"].device
-    hid, pre = _train_bufs(dims, BS, dev, nets=2)
-    gf = torch.empty((BS, dims[n]), dtype=torch.float32, device=dev)
+    B = inp["xt"].shape[0]
+    hid, pre = _train_bufs(dims, B, dev, nets=2)
+    gf = torch.empty((B, dims[n]), dtype=torch.float32, device=dev)
     gs = torch.empty_like(gf)
     losses = torch.empty(2, dtype=torch.float32, device=dev)
-    ws = _train_ws(dims, BS, dev, nets=2)
+    ws = _train_ws(dims, B, dev, nets=2)
     rc = L.load().cfm_mlp_sf2m_step_f32(p(inp["xt"]), p(inp["t"]), p(inp["ut"]), p(inp["eps"]), p(inp["lam"]), Wp, bp, _ptrs(hid),
-                                        _ptrs(pre), _ptrs(dW), _ptrs(db), cd, n, BS, p(gf), p(gs), p(losses), 0.5, p(ws), L.stream_ptr())
+                                        _ptrs(pre), _ptrs(dW), _ptrs(db), cd, n, B, p(gf), p(gs), p(losses), 0.5, p(ws), L.stream_ptr())
     return _grad_outs(dW, db) + [("g_flow", gf, None), ("g_score", gs, None), ("losses", losses, None)], (rc,)
 
 
@@ -599,13 +613,14 @@ def _op_dsbm_step(inp):
     p = L.ptr
     Wp, bp, cd, dims, n, dW, db = _two_net(inp)
     dev = inp["xt"].device
-    hid, pre = _train_bufs(dims, BS, dev, nets=2)
-    gf = torch.empty((BS, dims[n]), dtype=torch.float32, device=dev)
+    B = inp["xt"].shape[0]
+    hid, pre = _train_bufs(dims, B, dev, nets=2)
+    gf = torch.empty((B, dims[n]), dtype=torch.float32, device=dev)
     gb = torch.empty_like(gf)
     losses = torch.empty(2, dtype=torch.float32, device=dev)
-    ws = _train_ws(dims, BS, dev, nets=2)
+    ws = _train_ws(dims, B, dev, nets=2)
     rc = L.load().cfm_mlp_dsbm_step_f32(p(inp["xt"]), p(inp["t"]), p(inp["ut"]), p(inp["eps"]), p(inp["lam"]), p(inp["wb"]), Wp, bp,
-                                        _ptrs(hid), _ptrs(pre), _ptrs(dW), _ptrs(db), cd, n, BS, p(gf), p(gb), p(losses), p(ws), L.stream_ptr())
+                                        _ptrs(hid), _ptrs(pre), _ptrs(dW), _ptrs(db), cd, n, B, p(gf), p(gb), p(losses), p(ws), L.stream_ptr())
     return _grad_outs(dW, db) + [("g_fwd", gf, None), ("g_bwd", gb, None), ("losses", losses, None)], (rc,)
 
 
@@ -616,23 +631,31 @@ case("cfm_mlp_dsbm_step_f32")(_mk_step("two"), _op_dsbm_step)
 ADAM_NUMELS = [257, 1, 65537]
 
 
-def _mk_adam(seed, dev):
+def _mk_adam(seed, dev, numels=tuple(ADAM_NUMELS)):
     g = _g(seed, 14)
     inp = {}
-    for k, n in enumerate(ADAM_NUMELS):
+    for k, n in enumerate(numels):
         inp.update({f"p{k}": _randn(g, n), f"g{k}": _randn(g, n), f"m{k}": _randn(g, n) * 0.1, f"v{k}": _rand(g, n) * 0.01})
     return _to(dev, inp)
 
 
+def _adam_numels(inp):
+    out = []
+    while f"p{len(out)}" in inp:
+        out.append(inp[f"p{len(out)}"].numel())
+    return out
+
+
 def _prep_adam(inp):
-    rec = [[inp[f"{c}{k}"].data_ptr() for c in "pgmv"] + [n] for k, n in enumerate(ADAM_NUMELS)]
+    rec = [[inp[f"{c}{k}"].data_ptr() for c in "pgmv"] + [n] for k, n in enumerate(_adam_numels(inp))]
     inp["_table"] = torch.tensor(rec, dtype=torch.int64).to(inp["p0"].device)
 
 
 def _op_adam(inp):
     L = _lib()
-    rc = L.load().cfm_adam_step_f32(L.ptr(inp["_table"]), len(ADAM_NUMELS), 1e-3, 0.9, 0.999, 1e-8, 0.01, 3, 0.5, L.stream_ptr())
-    return [(f"{c}{k}", inp[f"{c}{k}"], None) for k in range(len(ADAM_NUMELS)) for c in "pgmv"], (rc,)
+    nt = len(_adam_numels(inp))
+    rc = L.load().cfm_adam_step_f32(L.ptr(inp["_table"]), nt, 1e-3, 0.9, 0.999, 1e-8, 0.01, 3, 0.5, L.stream_ptr())
+    return [(f"{c}{k}", inp[f"{c}{k}"], None) for k in range(nt) for c in "pgmv"], (rc,)
 
 
 case("cfm_adam_step_f32", prep=_prep_adam)(_mk_adam, _op_adam)
@@ -701,17 +724,18 @@ def _sde_records(seed, srk, n=SDE_STEPS):
     return np.frombuffer(b"".join(recs), dtype=np.uint8).copy()
 
 
-def _mk_sde(srk, n_steps=SDE_STEPS):
+def _mk_sde(srk, n_steps=SDE_STEPS, B=BS, d=2):
     def make(seed, dev):
         g = _g(seed, 17)
-        dims = [3, 64, 64, 64, 2]
-        inp = _to(dev, {**_net(g, dims, "f"), **_net(g, dims, "s"), "y0": _randn(g, BS, 2)})
+        dims = [d + 1, 64, 64, 64, d]
+        inp = _to(dev, {**_net(g, dims, "f"), **_net(g, dims, "s"), "y0": _randn(g, B, d)})
         inp["steps"] = _sde_records(seed, srk, n_steps)
         return inp
     return make
 
 
-def _op_sde(srk, n_steps=SDE_STEPS):
+def _op_sde(srk, n_steps=SDE_STEPS, slack=256):
+    """slack: bytes of workspace beyond the sizeof(record) * n_steps the header asks for."""
     def op(inp):
         L = _lib()
         Wf, bf, cd, dims, n = _tables(inp, "f")
@@ -720,7 +744,7 @@ def _op_sde(srk, n_steps=SDE_STEPS):
         B, d = y0.shape
         rec = 32 if srk else 16
         out = torch.empty((SDE_OUT, B, d), dtype=torch.float32, device=y0.device)
-        ws = torch.empty(rec * n_steps + 256, dtype=torch.uint8, device=y0.device)
+        ws = torch.empty(rec * n_steps + slack, dtype=torch.uint8, device=y0.device)
         fn = getattr(L.load(), "cfm_sde_srk_mlp_f32" if srk else "cfm_sde_em_mlp_f32")
         rc = fn(Wf, bf, Wsn, bsn, cd, n, L.ptr(y0), B, _hp(inp["steps"]), n_steps, 0, None, 1234, L.ptr(out), L.ptr(ws), L.stream_ptr())
         return [("traj", out, None)], (rc,)
@@ -855,10 +879,10 @@ case("cfm_ode_dopri5_cnf_mlp_f32", "exact")(_mk_ode(B=300, aug=1), _op_cnf_adapt
 case("cfm_ode_adaptive_cnf_mlp_f32", "hutch-tsit5")(_mk_ode(B=300, aug=1, eps=True), _op_cnf_adaptive("cfm_ode_adaptive_cnf_mlp_f32", 1, 1))
 
 
-def _mk_eval(out_dim=None):
+def _mk_eval(out_dim=None, B=BS, d=OD):
     def make(seed, dev):
         g = _g(seed, 19)
-        return _to(dev, {**_net(g, [OD + 1, OW, OW, OW, OD if out_dim is None else out_dim]), "x": _randn(g, BS, OD)})
+        return _to(dev, {**_net(g, [d + 1, OW, OW, OW, d if out_dim is None else out_dim]), "x": _randn(g, B, d)})
     return make
 
 
@@ -866,8 +890,9 @@ def _op_divergence(inp):
     L = _lib()
     Wp, bp, cd, dims, n = _tables(inp)
     x = inp["x"]
-    v, div = torch.empty_like(x), torch.empty(BS, dtype=torch.float32, device=x.device)
-    rc = L.load().cfm_mlp_divergence_f32(Wp, bp, cd, n, L.ptr(x), BS, 0.3, 0, None, L.ptr(v), L.ptr(div), None, L.stream_ptr())
+    B = x.shape[0]
+    v, div = torch.empty_like(x), torch.empty(B, dtype=torch.float32, device=x.device)
+    rc = L.load().cfm_mlp_divergence_f32(Wp, bp, cd, n, L.ptr(x), B, 0.3, 0, None, L.ptr(v), L.ptr(div), None, L.stream_ptr())
     return [("v", v, None), ("div", div, None)], (rc,)
 
 
@@ -875,8 +900,9 @@ def _op_grad_field(inp):
     L = _lib()
     Wp, bp, cd, dims, n = _tables(inp)
     x = inp["x"]
-    v, lap = torch.empty_like(x), torch.empty(BS, dtype=torch.float32, device=x.device)
-    rc = L.load().cfm_mlp_grad_field_f32(Wp, bp, cd, n, L.ptr(x), OD, BS, 0.3, L.ptr(v), L.ptr(lap), None, L.stream_ptr())
+    B, d = x.shape
+    v, lap = torch.empty_like(x), torch.empty(B, dtype=torch.float32, device=x.device)
+    rc = L.load().cfm_mlp_grad_field_f32(Wp, bp, cd, n, L.ptr(x), d, B, 0.3, L.ptr(v), L.ptr(lap), None, L.stream_ptr())
     return [("v", v, None), ("lap", lap, None)], (rc,)
 
 
@@ -889,7 +915,7 @@ REG_MASK = 3               # both penalties: rows [l, e, f, x]
 def _op_cnf_reg(inp):
     L, Wp, bp, cd, n, x0, B, ts, traj, ws = _ode_common(inp)
     nfe = ci(-1)
-    jsq = torch.empty((len(ts) - 1, B), dtype=torch.float32, device=x0.device)
+    jsq = torch.empty((max(len(ts) - 1, 1), B), dtype=torch.float32, device=x0.device)
     rc = L.load().cfm_ode_euler_cnf_reg_mlp_f32(Wp, bp, cd, n, L.ptr(x0), B, _hp(ts), len(ts), 0, None, REG_MASK, L.ptr(traj), L.ptr(jsq),
                                                 ctypes.byref(nfe), L.ptr(ws), L.stream_ptr())
     return [("traj", traj, None), ("jac_sq", jsq, None)], (rc, nfe.value)
@@ -899,17 +925,17 @@ case("cfm_ode_euler_cnf_reg_mlp_f32")(_mk_ode(aug=3), _op_cnf_reg)
 
 
 # ------------------------------------------------------------------------------------------------ gradients of the solves
-def _mk_grad(aug, jac=False):
+def _mk_grad(aug, jac=False, B=BS, d=OD, n_t=ONT):
     """The checkpoints a gradient entry reads are inputs like any other: finite states, not necessarily a solve's."""
     def make(seed, dev):
         g = _g(seed, 20)
-        D = aug + OD
-        inp = {**_net(g, [OD + 1, OW, OW, OW, OD]), "traj": _randn(g, ONT, BS, D),
-               "g": _randn(g, ONT, BS, D) if aug == 0 else _randn(g, BS, D)}
+        D = aug + d
+        inp = {**_net(g, [d + 1, OW, OW, OW, d]), "traj": _randn(g, n_t, B, D),
+               "g": _randn(g, n_t, B, D) if aug == 0 else _randn(g, B, D)}
         if jac:
-            inp["jac_sq"] = _rand(g, ONT - 1, BS) + 0.5
+            inp["jac_sq"] = _rand(g, max(n_t - 1, 1), B) + 0.5
         inp = _to(dev, inp)
-        inp["t_span"] = _grid(seed, ONT)
+        inp["t_span"] = _grid(seed, n_t) if n_t > 1 else np.array([0.25 * seed], dtype=np.float32)
         return inp
     return make
 
@@ -921,6 +947,7 @@ def _op_solve_grad(entry):
         Wp, bp, cd, dims, n = _tables(inp)
         traj, ts = inp["traj"], inp["t_span"]
         dev = traj.device
+        ONT, BS = traj.shape[0], traj.shape[1]           # (this case's own n_t and B)
         dW, db = _grads(inp)
         gi = torch.empty_like(traj[0])
         fn = getattr(L.load(), entry)
@@ -946,6 +973,7 @@ MAX_STEPS = 64             # step log of the recording solve; zero-filled, so a 
 
 
 def _rec_call(inp, log, ysteps, tol=TOL):
+    MAX_STEPS = ysteps.shape[0]
     L, Wp, bp, cd, n, x0, B, ts, traj, ws = _ode_common(inp)
     nfe, steps, nacc = ci(-1), ci(-1), ci(-1)
     rc = L.load().cfm_ode_adaptive_rec_mlp_f32(Wp, bp, cd, n, L.ptr(x0), B, _hp(ts), len(ts), 1, tol, tol, L.ptr(traj), ctypes.byref(steps),
@@ -956,8 +984,9 @@ def _rec_call(inp, log, ysteps, tol=TOL):
 
 def _op_rec(inp, tol=TOL):
     x0 = inp["x0"]
-    log = torch.zeros(MAX_STEPS * 4, dtype=torch.int32, device=x0.device)
-    ysteps = torch.zeros((MAX_STEPS,) + tuple(x0.shape), dtype=torch.float32, device=x0.device)
+    max_steps = inp.get("_max_steps", MAX_STEPS)
+    log = torch.zeros(max_steps * 4, dtype=torch.int32, device=x0.device)
+    ysteps = torch.zeros((max_steps,) + tuple(x0.shape), dtype=torch.float32, device=x0.device)
     traj, host = _rec_call(inp, log, ysteps, tol)
     return [("traj", traj, None), ("log", log, None), ("ysteps", ysteps, None)], host
 
