@@ -27,6 +27,7 @@ from .schedule import (  # noqa: F401
 from .cnf import CNF, AugmentationModule, DifferentiableCNF, RegularizedCNF, log_likelihood  # noqa: F401
 from .ode import AdaptiveDifferentiableNeuralODE, DifferentiableNeuralODE  # noqa: F401
 from .action_matching import action_matching_loss  # noqa: F401
+from .icnn import ICNN, icnn_f_loss, icnn_g_loss, icnn_w2  # noqa: F401
 from .optim import FusedAdam  # noqa: F401
 from .train import DSBMStep, RegressionStep, SF2MStep  # noqa: F401
 from .sde import DSBMFlowSolver, FlowSolver  # noqa: F401

@@ -27,6 +27,7 @@ OP_SINKHORN, OP_ASSIGN, OP_SAMPLE_DENSE, OP_MLP, OP_ODE, OP_UNBALANCED, OP_COST,
 OP_CNF_GRAD = 10
 OP_ACTION_GRAD = 11
 OP_ODE_GRAD = 12
+OP_ICNN = 13
 VARIANT_ICFM, VARIANT_SB, VARIANT_TARGET, VARIANT_VP = 0, 1, 2, 3
 VARIANT_SCHED = 4      # the scheduled bridge: cfm_sample_xt_ut_sched_f32 and cfm_traj_xt_ut_f32 mode 0
 
@@ -118,7 +119,25 @@ SIGNATURES = {
                                          _vp, _vp]),
     "cfm_ode_adaptive_grad_f32": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cfm_ode_adaptive_grad_available": (_i, [_vp, _i]),
+    "cfm_icnn_f32": (_i, [_vp]),
 }
+# ops of cfm_icnn_f32 and its descriptor (include/cfm_gfx950.h: cfm_icnn_net, cfm_icnn_call; tests/test_icnn_host.py
+# compares the field lists with the header's text)
+ICNN_TRANSPORT, ICNN_W2, ICNN_F_STEP, ICNN_G_STEP = 0, 1, 2, 3
+ICNN_MAX_DIM = 64
+
+
+class IcnnNet(ctypes.Structure):
+    _fields_ = [("Wz", _vp * 5), ("bz0", _vp), ("Wx", _vp * 4), ("bx", _vp * 3),
+                ("dWz", _vp * 5), ("dbz0", _vp), ("dWx", _vp * 4), ("dbx", _vp * 3)]
+
+
+class IcnnCall(ctypes.Structure):
+    _fields_ = [("size", _sz), ("op", _i), ("d", _i), ("dimh", _i), ("L", _i), ("B", _i), ("reg", _f),
+                ("f", IcnnNet), ("g", IcnnNet), ("x", _vp), ("y", _vp), ("p", _vp), ("w", _vp), ("losses", _vp),
+                ("ws", _vp), ("stream", _vp)]
+
+
 # solver selectors of the cfm_ode_adaptive_* / cfm_ode_fixed_* entries (include/cfm_gfx950.h)
 ODE_TABLEAU = {"dopri5": 0, "tsit5": 1}
 ODE_SCHEME = {"euler": 0, "midpoint": 1, "rk4": 2}

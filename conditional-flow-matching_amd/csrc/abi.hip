@@ -10,6 +10,7 @@ extern "C" size_t cfm_ode_ws_bytes_internal(int B, int width, int d);
 extern "C" size_t cfm_cnf_grad_ws_bytes_internal(int B, int n_t);
 extern "C" size_t cfm_action_grad_ws_bytes_internal(int B);
 extern "C" size_t cfm_ode_grad_ws_bytes_internal(int B, int n_t);
+extern "C" size_t cfm_icnn_ws_bytes_internal(int B);
 extern "C" size_t cfm_ub_ws_bytes_internal(int B0, int B1);
 extern "C" size_t cfm_cost_ws_bytes_internal(int B0, int B1, int d);
 extern "C" size_t cfm_mlp_train_ws_bytes_internal(int B, int maxw, int max_params);
@@ -34,6 +35,7 @@ extern "C" size_t cfm_workspace_bytes(int op, int B0, int B1, int d) {
         case CFM_OP_CNF_GRAD: return cfm_align_up(cfm_cnf_grad_ws_bytes_internal(B0, B1), 256);
         case CFM_OP_ACTION_GRAD: return cfm_align_up(cfm_action_grad_ws_bytes_internal(B0), 256);
         case CFM_OP_ODE_GRAD: return cfm_align_up(cfm_ode_grad_ws_bytes_internal(B0, B1), 256);
+        case CFM_OP_ICNN: return cfm_align_up(cfm_icnn_ws_bytes_internal(B0), 256);
         default: return 0;
     }
 }

@@ -1,6 +1,6 @@
 // action_grad.h — the action-matching loss and its parameter gradient in one launch (included by small_grad.hip after
-// cnf_grad.h; SmTile, sm_gemm, cg_gemm_t, selu_f, selu_slope come from small_field.h, cg_put, cg_outer, cg_sum4 from
-// cnf_grad.h, the host tail and the reduce launch from small_grad.hip, grad_check from ode_envelope.h).
+// cnf_grad.h; SmTile, sm_gemm, cg_gemm_t, cg_put, cg_outer, cg_sum4, selu_f, selu_slope come from small_field.h,
+// the host tail and the reduce launch from small_grad.hip, grad_check from ode_envelope.h).
 //
 // Counterpart of ActionMatchingLitModule.step (runner/src/models/cfm_module.py:670-694) and the loss.backward() that
 // follows it: per row  l = s(x0, 0) - s(x1, 1) + 1/2 |grad_x s(xt, t)|^2 + d/dt s(xt, t),  loss = mean l, for the action net

@@ -7,7 +7,7 @@ HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -fvisibility=hidden -ffp-contract=off -Wno-unused-result $CFM_EXTRA_FLAGS"
 mkdir -p "$HERE/obj"
 objs=""; pids=""
-for f in abi cost sinkhorn sinkhorn_pts assign transport sample elem traj mlp mlp_train ode small_grad cnf_reg unbalanced; do
+for f in abi cost sinkhorn sinkhorn_pts assign transport sample elem traj mlp mlp_train ode small_grad icnn cnf_reg unbalanced; do
   src="$HERE/$f.hip"; obj="$HERE/obj/$f.o"
   stale=0
   if [ ! -f "$obj" ] || [ "$src" -nt "$obj" ]; then stale=1; fi

@@ -41,35 +41,6 @@
 // e, L1, L2 are carried is read from `mask` at run time: a column that is absent has cotangent 0.
 #pragma once
 
-static_assert(SM_MB == 1, "the gradient kernel is written for one 16-row block per tile");
-__device__ __forceinline__ void cg_put(float* __restrict__ buf, const SmTile& v, int lane, int col) {
-#pragma unroll
-    for (int i = 0; i < SM_V; ++i) buf[sm_row(i, lane) * SM_LD + col] = v.v[i];
-}
-
-// acc[mb](C layout of block mb) += Z^T H over the 16 rows of the tile: element i of lane -> dW[16 mb + 4 (lane >> 4) + i]
-// [16 wave + (lane & 15)], dW[n][k] = sum_r Z[r][n] H[r][k]
-__device__ __forceinline__ void cg_outer(const float* __restrict__ Zbuf, const float* __restrict__ Hbuf, int wv, int lane,
-                                         f32x4 (&acc)[4]) {
-    const int fr = lane & 15, fk = lane >> 4;
-    const float* zp = Zbuf + fk * SM_LD + fr;
-    const float* hp = Hbuf + fk * SM_LD + wv * 16 + fr;
-    float a[4][SM_ROWS / 4], b[SM_ROWS / 4];
-#pragma unroll
-    for (int j = 0; j < SM_ROWS / 4; ++j) {
-        b[j] = hp[4 * j * SM_LD];
-#pragma unroll
-        for (int mb = 0; mb < 4; ++mb) a[mb][j] = zp[4 * j * SM_LD + 16 * mb];
-    }
-#pragma unroll
-    for (int j = 0; j < SM_ROWS / 4; ++j) {
-#pragma unroll
-        for (int mb = 0; mb < 4; ++mb) acc[mb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[mb][j], b[j], acc[mb], 0, 0, 0);
-    }
-}
-
-__device__ __forceinline__ float cg_sum4(const SmTile& v) { return (v.v[0] + v.v[1]) + (v.v[2] + v.v[3]); }
-
 // W1^T, W2^T -> LDS, zero padded to [2][64][SM_LD]: WT[l - 1][k][r] = W_l[r][k]
 __device__ __forceinline__ void cg_stage_transposed(const SmArgs& A, float* WT, int tid) {
 #pragma unroll

@@ -1,7 +1,7 @@
 // ode_grad.h — gradient of the fixed-step solves of ode_small_fixed<SCHEME, AUG_NONE> (euler, midpoint, rk4) with respect
-// to the field's parameters and the initial state (included by small_grad.hip after cnf_grad.h, whose cg_put, cg_outer,
-// cg_sum4, cg_stage_transposed and cg_store_partial it runs on; the host tail is small_grad.hip's, the tile engine
-// small_field.h's, the reverse step ode_reverse.h's: one text for this kernel and ode_small_adaptive_grad).
+// to the field's parameters and the initial state (included by small_grad.hip after cnf_grad.h, whose
+// cg_stage_transposed and cg_store_partial it runs on; the host tail is small_grad.hip's, the tile engine with cg_put,
+// cg_outer and cg_sum4 small_field.h's, the reverse step ode_reverse.h's: one text for this kernel and ode_small_adaptive_grad).
 //
 // Forward, per step n with h = tspan[n + 1] - tspan[n]:  Y_1 = y_n,  Y_s = fmaf(h, sum_{q<s} a_sq k_q, y_n),
 // k_s = f(t_n + c_s h, Y_s),  y_{n+1} = fmaf(h, sum_s b_s k_s, y_n).  Given G = dL/d traj [n_t, B, d]:  lam_N = G[N], and for

@@ -5,7 +5,7 @@
 //   T::a(s, q)   stage s + 2 is Y = fmaf(h, sum_{q <= s} a(s, q) k_{q+1}, y_n)     (fp64; every use casts to float)
 //   T::b(s)      y_{n+1} = fmaf(h, sum_s b(s) k_{s+1}, y_n)
 // The caller supplies y_n, lam_{n+1}, the signed step h, the stage times tsg (the field's arguments) and the accumulators.
-// Runs on cg_put, cg_outer, cg_sum4, cg_stage_transposed of cnf_grad.h and on the tile engine of small_field.h.
+// Runs on cg_stage_transposed of cnf_grad.h and on the tile engine of small_field.h (cg_put, cg_outer, cg_sum4 among it).
 #pragma once
 
 // one staged net, the transposed copies of its two 64 x 64 layers, four tile buffers

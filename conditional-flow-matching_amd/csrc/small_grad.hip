@@ -15,7 +15,6 @@
 #include "ode_tableau.h"
 #include "ode_envelope.h"
 
-#define CG_MAXGRID 256                                 // workgroups (= partial gradients) at most
 #define CG_PMAX (4 * SM_W * SM_W + 4 * SM_W)           // floats of one partial gradient at most
 
 struct CgOut { float* dW[4]; float* db[4]; };

@@ -759,6 +759,67 @@ int cfm_action_matching_grad_f32(const float* const* W, const float* const* b, c
                                  const float* x0, const float* x1, const float* xt, const float* t, int B,
                                  float* loss, float* const* dW, float* const* db, void* ws, void* stream);
 
+/* K14 — input-convex networks for optimal transport (Makkuva et al. 2020): the runner's ICNN
+ * (runner/src/models/components/icnn_model.py) and the minimax objective of ICNNLitModule.training_step / compute_w2
+ * (runner/src/models/icnn_module.py:98-135, 229-245), whose every step is three autograd.grad(create_graph=True) graphs.
+ * A net of L = num_hidden_layers, width dimh, input d:  a_1 = Wz[0] x + bz0,  h_l = softplus(a_l) (beta 1, threshold 20),
+ * a_{l+1} = Wz[l] h_l + Wx[l-1] x + bx[l-1] (l = 1 .. L-1),  out = Wz[L] h_L + Wx[L-1] x.  Wz[0], Wx[0 .. L-2]: [dimh, d];
+ * Wz[1 .. L-1]: [dimh, dimh]; Wz[L]: [1, dimh]; Wx[L-1]: [1, d]; bz0, bx[.]: [dimh].  Entries of the tables beyond the net's
+ * L are not read.  The gradient tables mirror the weight tables.
+ * Envelope: f and g of one shape, 2 <= L <= 4, 1 <= dimh <= 64, 1 <= d <= CFM_ICNN_MAX_DIM, B >= 1, reg >= 0, the fused
+ * small-field path on (cfm_ode_set_fused).  Outside it, for a wrong `size`, an unknown op or a missing operand the entry
+ * returns CFM_EINVAL before any HIP call.
+ *   CFM_ICNN_TRANSPORT  p [B,d] = grad_x f(x): the transport map of the net in slot f.  Reads f, x.  1 launch.
+ *   CFM_ICNN_W2         p = grad g(y); losses = (w2, f_loss, g_loss) of compute_w2, no penalty.  Reads f, g, x, y.  3 launches.
+ *   CFM_ICNN_F_STEP     p = grad g(y); losses = (loss_f, its data term mean(f(x) - f(p)), its penalty
+ *                       reg sum_{W in f.Wz} |relu(-W)|^2 / 2); f's gradient tables = d loss_f / d theta_f.  3 launches.
+ *   CFM_ICNN_G_STEP     p = grad g(y); w [B,d] = grad f(p) - y; losses = (loss_g, mean(f(p) - y.p), the penalty on g.Wz);
+ *                       g's gradient tables = d loss_g / d theta_g with f held constant (a double backward in autograd).
+ *                       4 launches.
+ * x, y: device [B,d].  Outputs are overwritten whole: p by every op, w by G_STEP, losses[3] by every op but TRANSPORT, the
+ * gradient tables of the net that is trained.  ws: cfm_workspace_bytes(CFM_OP_ICNN, B, 0, 0), unused by TRANSPORT.
+ * The result is the same bit pattern run to run (per-workgroup partials, added in a fixed order by the last launch).
+ * The operands travel in a descriptor: the caller writes sizeof(cfm_icnn_call) into `size`.  The stream is a field of
+ * it, and every convention at the top of this header holds for this entry unchanged (all work on `stream`, no allocation,
+ * ws and outputs arbitrary on entry, nothing else written, a declining call writes nothing, the descriptor may be
+ * freed on return).  tests/test_gpu_icnn_contract.py asserts them; the case tables of tests/stream_cases.py find their
+ * entries by a `void* stream` PARAMETER, so this entry's cases are to be folded into that table by hand. */
+#define CFM_OP_ICNN        13   /* cfm_icnn_f32 (B, 0, 0): per-workgroup partial gradients + loss terms */
+#define CFM_ICNN_MAX_DIM   64
+#define CFM_ICNN_TRANSPORT  0
+#define CFM_ICNN_W2         1
+#define CFM_ICNN_F_STEP     2
+#define CFM_ICNN_G_STEP     3
+typedef struct cfm_icnn_net {
+    const float* Wz[5];
+    const float* bz0;
+    const float* Wx[4];
+    const float* bx[3];
+    float* dWz[5];
+    float* dbz0;
+    float* dWx[4];
+    float* dbx[3];
+} cfm_icnn_net;
+typedef struct cfm_icnn_call {
+    size_t size;
+    int op;
+    int d;
+    int dimh;
+    int L;
+    int B;
+    float reg;
+    cfm_icnn_net f;
+    cfm_icnn_net g;
+    const float* x;
+    const float* y;
+    float* p;
+    float* w;
+    float* losses;
+    void* ws;
+    void* stream;
+} cfm_icnn_call;
+int cfm_icnn_f32(const cfm_icnn_call* call);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
