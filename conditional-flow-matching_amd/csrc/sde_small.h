@@ -42,10 +42,39 @@ __device__ __forceinline__ void philox_normal4(unsigned long long seed, unsigned
 
 struct EmStep { float te, h, gs; int is_out; };      // per step: field time, step, g sqrt|h|, trajectory point after it
 
+// ---- LOGQP: the path KL beside the state (torchsde's sdeint(..., logqp=True) with h = 0) ----
+// One more drift-only component, lr' = 1/2 sum_j (f_j / g)^2, integrated by the scheme that runs the state and written
+// per OUTPUT INTERVAL (logratio [n_out, B]: the increase since the previous trajectory point, not a running sum).  The
+// step's drift tile is squared where the step forms it, reduced per row (sm_rowsum: 16 lanes, then the four waves
+// through `red`, the 4 x SM_ROWS floats behind the tile buffers) and accumulated as lr = fma(qw_k, rowsum, lr) with
+// ONE host-computed float per step (Euler-Maruyama: qw_k = h_k / (2 g_k^2); srk: h / (12 sigma^2), the sum being
+// (k1^2 + k2^2) + 4 k3^2).  Columns >= d of a drift tile are zero; rows >= B are summed and never stored.  sm_rowsum
+// runs once per step: its next write to `red` comes a whole field evaluation (several barriers) after its reads.
+// The state update is the plain kernel's, statement for statement: the trajectory keeps its bits.
+enum { SDE_REVERSE = 1, SDE_LOGQP = 2 };              // the entries' flag word
+static_assert(small_lds_bytes(2, 2, true) == 150784 && small_lds_bytes(2, 2, true) <= 160 * 1024,
+              "the two-net SDE kernels with the row-sum scratch of LOGQP");
+
+// wave 0's lanes that lead a row group hand the interval's log-ratio out; every lane starts the next interval at zero
+__device__ __forceinline__ void sde_logqp_out(SmTile& lr, float* __restrict__ logratio, int oidx, int row0, int B, int wv,
+                                              int lane) {
+    if (wv == 0 && (lane & 15) == 0) {
+#pragma unroll
+        for (int i = 0; i < SM_V; ++i) {
+            const int gr = row0 + sm_row(i, lane);
+            if (gr < B) logratio[(size_t)oidx * B + gr] = lr.v[i];
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < SM_V; ++i) lr.v[i] = 0.f;
+}
+
+template <bool LOGQP>
 __global__ __launch_bounds__(256) void ode_small_em(SmArgs F, SmArgs S, int has_s, int B, int d,
-                                                    const EmStep* __restrict__ steps, int n_steps, int reverse,
+                                                    const EmStep* __restrict__ steps, int n_steps, int flags,
                                                     const float* __restrict__ xi, unsigned long long seed,
-                                                    const float* __restrict__ y0, float* __restrict__ out) {
+                                                    const float* __restrict__ y0, float* __restrict__ out,
+                                                    const float* __restrict__ qw, float* __restrict__ logratio) {
     extern __shared__ __attribute__((aligned(16))) float small_lds[];
     float* WlF = small_lds;
     float* blF = WlF + 4 * SM_W * SM_LD;
@@ -55,7 +84,9 @@ __global__ __launch_bounds__(256) void ode_small_em(SmArgs F, SmArgs S, int has_
     float* wtS = blS + 4 * SM_W;
     float* Ab0 = wtS + SM_W;
     float* Ab1 = Ab0 + SM_ROWS * SM_LD;
+    float* red = Ab1 + SM_ROWS * SM_LD;               // (LOGQP alone carves and touches it)
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const bool reverse = (flags & SDE_REVERSE) != 0;
     sm_stage_weights(F, d, WlF, blF, wtF, tid);
     if (has_s) sm_stage_weights(S, d, WlS, blS, wtS, tid);
     const size_t n = (size_t)B * d;
@@ -69,6 +100,9 @@ __global__ __launch_bounds__(256) void ode_small_em(SmArgs F, SmArgs S, int has_
         }
         __syncthreads();
         int oidx = 0;
+        SmTile lr, q;
+#pragma unroll
+        for (int i = 0; i < SM_V; ++i) lr.v[i] = q.v[i] = 0.f;
         for (int k = 0; k < n_steps; ++k) {
             const EmStep st = steps[k];
             const SmTile v = sm_field(x, st.te, F, d, Ab0, Ab1, WlF, blF, wtF, wv, lane);
@@ -84,11 +118,19 @@ __global__ __launch_bounds__(256) void ode_small_em(SmArgs F, SmArgs S, int has_
                 const bool ok = gr < B && col < d;
                 float f = reverse ? -v.v[i] : v.v[i];
                 if (has_s) f = fmaf(1.0f, sc.v[i], f);
+                if constexpr (LOGQP) q.v[i] = f * f;
                 float r = fmaf(st.h, f, x.v[i]);
                 const float noise = xi ? (ok ? xi[(size_t)k * n + (size_t)gr * d + col] : 0.f) : z[i & 3];
                 r = fmaf(st.gs, noise, r);
                 x.v[i] = ok ? r : 0.f;
                 if (st.is_out && ok) out[(size_t)oidx * n + (size_t)gr * d + col] = r;
+            }
+            if constexpr (LOGQP) {
+                const float w = qw[k];
+                const SmTile rs = sm_rowsum(q, red, wv, lane);
+#pragma unroll
+                for (int i = 0; i < SM_V; ++i) lr.v[i] = fmaf(w, rs.v[i], lr.v[i]);
+                if (st.is_out) sde_logqp_out(lr, logratio, oidx, row0, B, wv, lane);
             }
             oidx += st.is_out ? 1 : 0;
         }
@@ -104,10 +146,12 @@ __global__ __launch_bounds__(256) void ode_small_em(SmArgs F, SmArgs S, int has_
 // scheme); x, k1, k2 stay in registers for the whole trajectory of the tile.  Layout, LDS use and the xi == NULL
 // Philox mode are ode_small_em's; xi != NULL is [n_steps, 2, B, d] (plane 0: xi1, plane 1: xi2) and the trajectory
 // is then bit-equal to the launch-per-step scheme (three forward passes per field + cfm_sde_srk_step_f32).
+template <bool LOGQP>
 __global__ __launch_bounds__(256) void ode_small_srk(SmArgs F, SmArgs S, int has_s, int B, int d,
-                                                     const SrkStep* __restrict__ steps, int n_steps, int reverse,
+                                                     const SrkStep* __restrict__ steps, int n_steps, int flags,
                                                      const float* __restrict__ xi, unsigned long long seed,
-                                                     const float* __restrict__ y0, float* __restrict__ out) {
+                                                     const float* __restrict__ y0, float* __restrict__ out,
+                                                     const float* __restrict__ qw, float* __restrict__ logratio) {
     extern __shared__ __attribute__((aligned(16))) float small_lds[];
     float* WlF = small_lds;
     float* blF = WlF + 4 * SM_W * SM_LD;
@@ -117,7 +161,9 @@ __global__ __launch_bounds__(256) void ode_small_srk(SmArgs F, SmArgs S, int has
     float* wtS = blS + 4 * SM_W;
     float* Ab0 = wtS + SM_W;
     float* Ab1 = Ab0 + SM_ROWS * SM_LD;
+    float* red = Ab1 + SM_ROWS * SM_LD;               // (LOGQP alone carves and touches it)
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const bool reverse = (flags & SDE_REVERSE) != 0;
     sm_stage_weights(F, d, WlF, blF, wtF, tid);
     if (has_s) sm_stage_weights(S, d, WlS, blS, wtS, tid);
     const size_t n = (size_t)B * d;
@@ -140,6 +186,9 @@ __global__ __launch_bounds__(256) void ode_small_srk(SmArgs F, SmArgs S, int has
         }
         __syncthreads();
         int oidx = 0;
+        SmTile lr;
+#pragma unroll
+        for (int i = 0; i < SM_V; ++i) lr.v[i] = 0.f;
         for (int k = 0; k < n_steps; ++k) {
             const SrkStep st = steps[k];
             static_assert(SM_V == 4, "ode_small_srk draws TWO Philox blocks of 4 normals per lane and step (xi1, xi2): with "
@@ -176,6 +225,17 @@ __global__ __launch_bounds__(256) void ode_small_srk(SmArgs F, SmArgs S, int has
                 x.v[i] = ok ? r : 0.f;
                 if (st.is_out && ok) out[(size_t)oidx * n + (size_t)gr * d + col] = r;
             }
+            if constexpr (LOGQP) {
+                // the three stage drifts combined elementwise first: ONE row reduction per step
+                SmTile q;
+#pragma unroll
+                for (int i = 0; i < SM_V; ++i) q.v[i] = fmaf(4.0f, k3.v[i] * k3.v[i], k1.v[i] * k1.v[i] + k2.v[i] * k2.v[i]);
+                const float w = qw[k];
+                const SmTile rs = sm_rowsum(q, red, wv, lane);
+#pragma unroll
+                for (int i = 0; i < SM_V; ++i) lr.v[i] = fmaf(w, rs.v[i], lr.v[i]);
+                if (st.is_out) sde_logqp_out(lr, logratio, oidx, row0, B, wv, lane);
+            }
             oidx += st.is_out ? 1 : 0;
         }
         __syncthreads();
@@ -185,41 +245,57 @@ __global__ __launch_bounds__(256) void ode_small_srk(SmArgs F, SmArgs S, int has
 // ---- entry points.  steps_host: n_steps Step records (host; EmStep: {te, h, g sqrt|h|, is_out}); ws: device scratch
 // of >= sizeof(Step) n_steps bytes.  Ws == NULL: no score field.  Returns CFM_EINVAL for anything but two 4-layer fields
 // of widths <= 64 with a time column (the caller then steps launch by launch).
-template <auto KERNEL, class Step>
+// flags: SDE_REVERSE | SDE_LOGQP, any other bit CFM_EINVAL.  With SDE_LOGQP the n_steps records are followed by n_steps
+// floats qw (one copy moves both into ws: (sizeof(Step) + 4) n_steps bytes) and out [n_out, B, d] by logratio [n_out, B],
+// n_out counted from the records; without it every byte read and written is what it was before the flag existed.
+template <auto KERNEL, auto KERNEL_LOGQP, class Step>
 static int sde_small(const float* const* Wf, const float* const* bf, const float* const* Ws, const float* const* bs,
                      const int* dims, int n_layers, const float* y0, int B, const void* steps_host, int n_steps,
-                     int reverse, const float* xi, unsigned long long seed, float* out, void* ws, void* stream) {
+                     int flags, const float* xi, unsigned long long seed, float* out, void* ws, void* stream) {
     int d;
     if (!Wf || !bf || !y0 || !out || !steps_host || !ws || B < 0 || n_steps < 0) return CFM_EINVAL;
+    if (flags & ~(SDE_REVERSE | SDE_LOGQP)) return CFM_EINVAL;
     if (small_envelope(dims, n_layers, &d)) return CFM_EINVAL;
     for (int l = 1; l <= 3; ++l) if (dims[l] < 1) return CFM_EINVAL;
     if (B == 0 || n_steps == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
+    const bool logqp = (flags & SDE_LOGQP) != 0;
     const SmArgs F = small_args(Wf, bf, dims), S = small_args(Ws ? Ws : Wf, bs ? bs : bf, dims);
-    const int grid = small_grid<KERNEL, 160 * 1024>(B);
+    const int grid = logqp ? small_grid<KERNEL_LOGQP, 160 * 1024>(B) : small_grid<KERNEL, 160 * 1024>(B);
     if (grid < 0) return CFM_EINVAL;
-    int rc = cfm_hip(hipMemcpyAsync(ws, steps_host, sizeof(Step) * (size_t)n_steps, hipMemcpyHostToDevice, s));
+    const size_t rec_bytes = sizeof(Step) * (size_t)n_steps;
+    int rc = cfm_hip(hipMemcpyAsync(ws, steps_host, rec_bytes + (logqp ? sizeof(float) * (size_t)n_steps : 0),
+                                    hipMemcpyHostToDevice, s));
     if (rc) return rc;
-    hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(256), small_lds_bytes(2, 2, false), s, F, S, (Ws && bs) ? 1 : 0, B, d,
-                       (const Step*)ws, n_steps, reverse, xi, seed, y0, out);
+    const int has_s = (Ws && bs) ? 1 : 0;
+    if (logqp) {
+        size_t n_out = 0;
+        for (int k = 0; k < n_steps; ++k) n_out += ((const Step*)steps_host)[k].is_out ? 1 : 0;
+        hipLaunchKernelGGL(KERNEL_LOGQP, dim3(grid), dim3(256), small_lds_bytes(2, 2, true), s, F, S, has_s, B, d,
+                           (const Step*)ws, n_steps, flags, xi, seed, y0, out, (const float*)((const char*)ws + rec_bytes),
+                           out + n_out * (size_t)B * d);
+    } else {
+        hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(256), small_lds_bytes(2, 2, false), s, F, S, has_s, B, d,
+                           (const Step*)ws, n_steps, flags, xi, seed, y0, out, (const float*)nullptr, (float*)nullptr);
+    }
     return cfm_status();
 }
 
 extern "C" int cfm_sde_em_mlp_f32(const float* const* Wf, const float* const* bf, const float* const* Ws,
                                   const float* const* bs, const int* dims, int n_layers, const float* y0, int B,
-                                  const void* steps_host, int n_steps, int reverse, const float* xi,
+                                  const void* steps_host, int n_steps, int flags, const float* xi,
                                   unsigned long long seed, float* out, void* ws, void* stream) {
-    return sde_small<ode_small_em, EmStep>(Wf, bf, Ws, bs, dims, n_layers, y0, B, steps_host, n_steps, reverse, xi, seed, out,
-                                           ws, stream);
+    return sde_small<ode_small_em<false>, ode_small_em<true>, EmStep>(Wf, bf, Ws, bs, dims, n_layers, y0, B, steps_host, n_steps,
+                                                                      flags, xi, seed, out, ws, stream);
 }
 
 // as cfm_sde_em_mlp_f32, on SrkStep records; d >= 1 (the Euler-Maruyama entry accepts an empty state)
 extern "C" int cfm_sde_srk_mlp_f32(const float* const* Wf, const float* const* bf, const float* const* Ws,
                                    const float* const* bs, const int* dims, int n_layers, const float* y0, int B,
-                                   const void* steps_host, int n_steps, int reverse, const float* xi,
+                                   const void* steps_host, int n_steps, int flags, const float* xi,
                                    unsigned long long seed, float* out, void* ws, void* stream) {
     static_assert(sizeof(SrkStep) == 32, "the host packs 32-byte records");
     if (dims && n_layers == 4 && dims[4] < 1) return CFM_EINVAL;
-    return sde_small<ode_small_srk, SrkStep>(Wf, bf, Ws, bs, dims, n_layers, y0, B, steps_host, n_steps, reverse, xi, seed,
-                                             out, ws, stream);
+    return sde_small<ode_small_srk<false>, ode_small_srk<true>, SrkStep>(Wf, bf, Ws, bs, dims, n_layers, y0, B, steps_host,
+                                                                         n_steps, flags, xi, seed, out, ws, stream);
 }

@@ -18,6 +18,19 @@ also for ``reverse=True`` (what the reference's SDE classes and the eager scheme
 the way back passes ``lambda t: schedule(1 - t)``.  ``srk`` with a schedule is not built.
 The Brownian increments come from ``torch.randn`` on the state's device (torchsde's BrownianInterval
 stream is not reproducible without torchsde: the noise stream is NOT bit-compatible, the scheme is).
+
+``logqp=True`` (``sdeint``, ``FlowSolver.sdeint``, ``DSBMFlowSolver.sdeint``: the validation loop of the runner's SF2M and
+DSBM modules, cfm_module.py:911-983) returns ``(ys, log_ratio_increments)`` as ``torchsde.sdeint`` does.  Recalled, not read
+(torchsde is not installed here): its ``SDELogqp`` for diagonal noise adds one state column with drift
+``0.5 * (u ** 2).sum(1)``, ``u = stable_division(f - h, g)`` (every ``|g| <= 1e-7`` replaced by ``1e-7 * sign(g)``), zero
+diffusion and zero start, and ``sdeint`` returns the column's INCREASE over each interval of ``ts`` (``[len(ts) - 1, B]``,
+not cumulative) next to the state without it.  Here the column is one more drift-only component of the scheme that runs
+the state, on the refined grid: ``euler`` adds ``h_k * q(t_k, y_k)`` with f and g of the state update of step k; ``srk``
+adds ``(h / 6) ((q1 + q2) + 4 q3)`` on the three stage drifts (the column's own stage values enter nothing).  The
+Brownian increments keep their shapes (torchsde would draw one more column, which multiplies zero).  The one-launch
+kernels accumulate it from the drift tile they hold (``h = 0``: csrc/sde_small.h, LOGQP), the launch-per-step path in a
+few torch ops per step, the eager path from ``sde.h`` where the object has one; the trajectory is the same bits with
+and without it.
 """
 import math
 
@@ -59,6 +72,10 @@ class FlowScoreSDE(torch.nn.Module):
         s = self.sigma(t) if callable(self.sigma) else self.sigma
         return torch.ones_like(y) * s
 
+    def h(self, t, y):
+        """The prior drift of ``sdeint(..., logqp=True)``: zero (runner/src/models/components/solver.py:43-44)."""
+        return torch.zeros_like(y)
+
 
 class DriftSDE(torch.nn.Module):
     """dy = drift([y, t]) dt + sigma dW — ONE drift net, as DSBM trains them (runner/src/models/components/solver.py:249-257
@@ -77,6 +94,7 @@ class DriftSDE(torch.nn.Module):
 
     _cat = FlowScoreSDE._cat
     g = FlowScoreSDE.g
+    h = FlowScoreSDE.h
 
     def f(self, t, y):
         return self.drift(self._cat(1 - t if self.reverse else t, y))
@@ -161,9 +179,49 @@ def _srk_records(steps, sigma, reverse):
     return b"".join(recs)
 
 
+_LOGQP_EPS = 1e-7        # torchsde's stable_division
+
+
+def _stable_division(a, b, eps=_LOGQP_EPS):
+    """torchsde's ``misc.stable_division``: every ``b`` with ``|b| <= eps`` becomes ``eps * sign(b)`` (so 0 stays 0)."""
+    b = torch.where(b.abs() > eps, b, torch.full_like(b, eps) * b.sign())
+    return a / b
+
+
+def _logqp_weights(steps, g, srk):
+    """qw_k of the HIP paths under ``logqp``, as float32 values: the per-step factor of the row sum of squared drifts,
+    ``h_k / (2 g_k^2)`` for ``euler`` and ``h / (12 sigma^2)`` for ``srk`` (whose sum is (k1^2 + k2^2) + 4 k3^2), formed
+    in float64 and rounded once.  ``0 < |g_k| <= 1e-7`` enters as ``1e-7 sign(g_k)`` (stable_division; for qw alone);
+    ``g_k == 0`` raises."""
+    import struct
+    qw = []
+    for (t, h, _), gk in zip(steps, g):
+        if gk == 0.0:
+            raise ValueError(f"sdeint(logqp=True): g = 0 at t = {t}: the log-ratio integrand (f / g)^2 is infinite there "
+                             "(torchsde would return inf or nan)")
+        if abs(gk) <= _LOGQP_EPS:
+            gk = math.copysign(_LOGQP_EPS, gk)
+        qw.append(0.5 * h / ((6.0 if srk else 1.0) * gk * gk))
+    return list(struct.unpack(f"<{len(qw)}f", struct.pack(f"<{len(qw)}f", *qw)))
+
+
+def _packed_steps(steps, g_steps, srk, reverse, qw=None):
+    """(blob, workspace bytes) of a one-launch call: the step records (``_srk_records`` / ``_em_records``), and with ``qw``
+    (``_logqp_weights``) the records followed by the n_steps float32 weights, for a workspace of (record + 4) n_steps
+    bytes (include/cfm_gfx950.h, the entries' flag bit 1)."""
+    import struct
+    if srk:
+        blob = _srk_records(steps, g_steps[0] if steps else 0.0, reverse)          # (srk: sigma is constant)
+    else:
+        blob = _em_records(steps, g_steps, reverse)
+    if qw is not None:
+        blob += struct.pack(f"<{len(qw)}f", *qw)
+    return blob, len(blob)
+
+
 def _kernel_reverse_flag(sde):
-    """The ``reverse`` argument of the one-launch kernels: it NEGATES the first field, which is FlowScoreSDE's way back;
-    a DriftSDE's reverse lives in the records' te = 1 - t alone (flag 0 in both directions)."""
+    """The ``reverse`` bit (bit 0 of the flag word) of the one-launch kernels: it NEGATES the first field, which is
+    FlowScoreSDE's way back; a DriftSDE's reverse lives in the records' te = 1 - t alone (0 in both directions)."""
     return 1 if (sde.reverse and sde.negate_reverse) else 0
 
 
@@ -187,20 +245,18 @@ def _noise_arg(noise, method, n_steps, y0):
     return noise
 
 
-def _run_one_launch(sde, fields, y0, y, steps, g_steps, srk, given, noise, generator):
+def _run_one_launch(sde, fields, y0, y, steps, g_steps, srk, given, noise, generator, qw=None):
     """The whole trajectory in one launch of cfm_sde_em_mlp_f32 / cfm_sde_srk_mlp_f32.  fields: ``_fused_fields(sde)``; y:
-    the fp32 device copy of y0; given: the caller's normals on the device, or None for ``noise`` "torch" / "philox"."""
+    the fp32 device copy of y0; given: the caller's normals on the device, or None for ``noise`` "torch" / "philox".
+    qw (``_logqp_weights``): the call's logqp form, ``(trajectory, log-ratio increments [n_out, B])``."""
     import ctypes
     lib = _lib.load()
     dev = y.device
     f, s, dims = fields
     B, d = y.shape
     n_out = sum(1 for st in steps if st[2])
-    if srk:
-        blob, rec = _srk_records(steps, g_steps[0] if steps else 0.0, sde.reverse), 32          # (srk: sigma is constant)
-    else:
-        blob, rec = _em_records(steps, g_steps, sde.reverse), 16
-    host = (ctypes.c_char * (rec * len(steps))).from_buffer_copy(blob)
+    blob, ws_bytes = _packed_steps(steps, g_steps, srk, sde.reverse, qw)
+    host = (ctypes.c_char * ws_bytes).from_buffer_copy(blob)
     xi = given
     seed = 0
     if xi is None and noise == "torch":
@@ -211,23 +267,34 @@ def _run_one_launch(sde, fields, y0, y, steps, g_steps, srk, given, noise, gener
     Wf, bf, _, keep_f = f.hip_params(dev)
     Ws, bs, _, keep_s = s.hip_params(dev) if s is not None else (None, None, None, None)      # one field: Ws = bs = NULL
     cd = (ctypes.c_int * 5)(*dims)
-    traj = torch.empty((n_out, B, d), dtype=torch.float32, device=dev)
-    ws = torch.empty(rec * len(steps) + 256, dtype=torch.uint8, device=dev)
+    flags = _kernel_reverse_flag(sde)
+    if qw is None:
+        traj = out = torch.empty((n_out, B, d), dtype=torch.float32, device=dev)
+    else:
+        # one buffer: the trajectory followed by the log-ratio increments
+        flags |= 2
+        out = torch.empty(n_out * B * d + n_out * B, dtype=torch.float32, device=dev)
+        traj, lr = out[:n_out * B * d].view(n_out, B, d), out[n_out * B * d:].view(n_out, B)
+    ws = torch.empty(ws_bytes + 256, dtype=torch.uint8, device=dev)
     name = "cfm_sde_srk_mlp_f32" if srk else "cfm_sde_em_mlp_f32"
-    check(getattr(lib, name)(Wf, bf, Ws, bs, cd, 4, ptr(y), B, host, len(steps), _kernel_reverse_flag(sde),
-                             ptr(xi), seed, ptr(traj), ptr(ws), stream_ptr()), name)
+    check(getattr(lib, name)(Wf, bf, Ws, bs, cd, 4, ptr(y), B, host, len(steps), flags,
+                             ptr(xi), seed, ptr(out), ptr(ws), stream_ptr()), name)
     # (no synchronisation: a host array may be dropped as soon as the call returns, include/cfm_gfx950.h)
-    return torch.cat([y0.to(torch.float32)[None].to(y0.device), traj.to(y0.device)])
+    traj = torch.cat([y0.to(torch.float32)[None].to(y0.device), traj.to(y0.device)])
+    return traj if qw is None else (traj, lr.to(y0.device))
 
 
-def _run_stepped(sde, y0, y, steps, g_steps, srk, given, generator):
+def _run_stepped(sde, y0, y, steps, g_steps, srk, given, generator, qw=None):
     """A launch per step: the fields through ``MLP.forward_hip``, the state update in cfm_sde_em_step_f32 (``euler``) or
     one cfm_sde_srk_step_f32 per stage (``srk``).  y: the fp32 device copy of y0, updated in place; the increments are
-    drawn inside the loop unless ``given``."""
+    drawn inside the loop unless ``given``.  qw (``_logqp_weights``): the log-ratio column too, a few torch ops per step on
+    the field values the step kernel gets (no kernel of its own: the runner's nets take the one-launch path)."""
     lib = _lib.load()
     dev = y.device
     out = [y0]
     sign = 1.0
+    lr = torch.zeros(y.shape[0], dtype=torch.float32, device=dev) if qw is not None else None
+    lrs = []
     if srk:
         sigma = g_steps[0] if steps else 0.0          # (srk: constant)
 
@@ -251,6 +318,9 @@ def _run_stepped(sde, y0, y, steps, g_steps, srk, given, generator):
                     v2, s2 = pair(ys, t + h)
                 elif stage == 2:
                     v3, s3 = pair(ys, t + 0.5 * h)
+            if lr is not None:
+                k1, k2, k3 = v1 + s1, v2 + s2, v3 + s3
+                lr = lr + qw[k] * ((k1 * k1 + k2 * k2) + 4.0 * (k3 * k3)).sum(1)
         else:
             te = (1.0 - t) if sde.reverse else t
             v = sde.drift.forward_hip(y, te)
@@ -258,19 +328,37 @@ def _run_stepped(sde, y0, y, steps, g_steps, srk, given, generator):
             if sde.reverse and sde.negate_reverse:
                 v = -v
             xi = given[k] if given is not None else torch.randn(y.shape, device=dev, dtype=torch.float32, generator=generator)
+            if lr is not None:
+                f = v + s if s is not None else v
+                lr = lr + qw[k] * (f * f).sum(1)
             check(lib.cfm_sde_em_step_f32(ptr(y), ptr(v), ptr(s), ptr(xi), float(h), g_steps[k], sign,
                                           y.numel(), stream_ptr()), "cfm_sde_em_step_f32")
         if is_out:
             out.append(y.clone().to(y0.device))
-    return torch.stack([o.to(torch.float32) for o in out])
+            if lr is not None:
+                lrs.append(lr.to(y0.device))
+                lr = torch.zeros_like(lr)
+    traj = torch.stack([o.to(torch.float32) for o in out])
+    if qw is None:
+        return traj
+    return traj, (torch.stack(lrs) if lrs else torch.zeros((0, y.shape[0]), dtype=torch.float32, device=y0.device))
 
 
-def _run_eager(sde, y0, steps, srk, given, generator):
-    """The same schemes in eager torch ops on ``sde.f`` / ``sde.g``, in the caller's dtype and on its device."""
+def _run_eager(sde, y0, steps, srk, given, generator, logqp=False):
+    """The same schemes in eager torch ops on ``sde.f`` / ``sde.g``, in the caller's dtype and on its device.  logqp: also
+    the log-ratio column lr' = 1/2 sum_j u_j^2, u = stable_division(f - h, g), as one more drift-only component of the
+    scheme (``sde.h(t, y)`` when the object has one, else 0), returned as its increase over every interval of ``ts``."""
     out = [y0]
     y = y0
     if given is not None:
         given = given.to(device=y.device, dtype=y.dtype)
+    prior = getattr(sde, "h", None)
+
+    def q(tt, yy, f, g):
+        u = _stable_division(f - prior(tt, yy) if prior is not None else f, g)
+        return 0.5 * (u * u).flatten(1).sum(1)
+    lr = torch.zeros(y.shape[0], dtype=y.dtype, device=y.device) if logqp else None
+    lrs = []
     for k, (t, h, is_out) in enumerate(steps):
         tt = torch.as_tensor(t, dtype=y.dtype, device=y.device)
         if srk:
@@ -279,19 +367,32 @@ def _run_eager(sde, y0, steps, srk, given, generator):
                                                                 generator=generator)
             gs = float(sde.sigma) * math.sqrt(abs(h))
             k1 = sde.f(tt, y)
-            k2 = sde.f(tt + h, y + h * k1)
-            k3 = sde.f(tt + 0.5 * h, y + (0.25 * h) * (k1 + k2) + (0.75 * gs) * (xi[0] + xi[1] / math.sqrt(3.0)))
+            y2 = y + h * k1
+            k2 = sde.f(tt + h, y2)
+            y3 = y + (0.25 * h) * (k1 + k2) + (0.75 * gs) * (xi[0] + xi[1] / math.sqrt(3.0))
+            k3 = sde.f(tt + 0.5 * h, y3)
+            if logqp:
+                g = torch.full_like(y, float(sde.sigma))
+                lr = lr + (h / 6.0) * ((q(tt, y, k1, g) + q(tt + h, y2, k2, g)) + 4.0 * q(tt + 0.5 * h, y3, k3, g))
             y = y + (h / 6.0) * ((k1 + k2) + 4.0 * k3) + gs * xi[0]
         else:
             xi = given[k] if given is not None else torch.randn(y.shape, device=y.device, dtype=y.dtype, generator=generator)
-            y = y + h * sde.f(tt, y) + sde.g(tt, y) * math.sqrt(abs(h)) * xi
+            f, g = sde.f(tt, y), sde.g(tt, y)
+            if logqp:
+                lr = lr + h * q(tt, y, f, g)
+            y = y + h * f + g * math.sqrt(abs(h)) * xi
         if is_out:
             out.append(y)
-    return torch.stack(out)
+            if logqp:
+                lrs.append(lr)
+                lr = torch.zeros_like(lr)
+    if not logqp:
+        return torch.stack(out)
+    return torch.stack(out), (torch.stack(lrs) if lrs else y.new_zeros((0, y.shape[0])))
 
 
 @torch.no_grad()
-def sdeint(sde, y0, ts, method="euler", dt=1e-3, generator=None, noise="philox", fused=None, **unused):
+def sdeint(sde, y0, ts, method="euler", dt=1e-3, generator=None, noise="philox", fused=None, logqp=False, **unused):
     """Trajectory [len(ts), B, d] of ``sde`` (an object with f(t, y), g(t, y)) from y0 on the ``ts`` grid refined to
     steps of at most ``dt``.  ``method="euler"`` (default): Euler-Maruyama.  ``method="srk"``: torchsde's default
     scheme for diagonal Ito noise (SRI2W1, strong order 1.5), built for ``FlowScoreSDE`` with a constant ``sigma`` and
@@ -308,7 +409,15 @@ def sdeint(sde, y0, ts, method="euler", dt=1e-3, generator=None, noise="philox",
     caller's standard normals, ``[n_steps, B, d]`` for ``euler`` and ``[n_steps, 2, B, d]`` for ``srk`` with
     ``n_steps`` the length of the refined grid.  ``fused=False`` forces the launch-per-step scheme (measurement /
     test switch).  A callable ``sde.sigma`` with a scalar value (a noise schedule) runs on the same ``euler`` kernels,
-    evaluated per refined step at the solver's time t_k (module docstring); a non-scalar value keeps the eager scheme."""
+    evaluated per refined step at the solver's time t_k (module docstring); a non-scalar value keeps the eager scheme.
+
+    ``logqp=True`` (torchsde's keyword): returns ``(ys, log_ratio_increments)``, the second ``[len(ts) - 1, B]``: the
+    increase over each interval of ``ts`` (not cumulative) of the column with drift ``0.5 * (u ** 2).sum(1)``,
+    ``u = stable_division(f - h, g)``, zero diffusion and zero start, integrated by the scheme that runs the state
+    (module docstring).  The trajectory is the one ``logqp=False`` gives on the same noise, bit for bit, on every path:
+    the one-launch kernels reduce the drift tile they hold (``h = 0``), the launch-per-step path adds a few torch ops
+    per step, the eager path evaluates ``sde.h`` when the object has one.  On the HIP paths a step with ``g == 0``
+    raises ``ValueError`` before any launch."""
     if method not in ("euler", "srk"):
         raise NotImplementedError(f"sdeint method {method!r}: 'euler' (Euler-Maruyama) and 'srk' (SRI2W1) are built")
     srk = method == "srk"
@@ -333,10 +442,14 @@ def sdeint(sde, y0, ts, method="euler", dt=1e-3, generator=None, noise="philox",
                 raise ValueError("sdeint(fused=True): sigma(t) must be a scalar (a noise schedule); state-dependent noise "
                                  "is stepped in eager torch")
             fast = False
+    qw = None
+    if fast and logqp:
+        # (before any launch and before last_path: g = 0 raises here)
+        qw = _logqp_weights(steps, g_steps if g_steps is not None else [float(sde.sigma)] * len(steps), srk)
     if known:
         sde.last_path = "hip" if fast else "eager"
     if not fast:
-        return _run_eager(sde, y0, steps, srk, given, generator)
+        return _run_eager(sde, y0, steps, srk, given, generator, logqp)
     _lib.load()
     dev = _lib.require_gpu()
     y = _lib.to_dev_f32(y0, dev).clone()
@@ -355,8 +468,8 @@ def sdeint(sde, y0, ts, method="euler", dt=1e-3, generator=None, noise="philox",
     if g_steps is None:
         g_steps = [float(sde.sigma)] * len(steps)
     if fields is not None:
-        return _run_one_launch(sde, fields, y0, y, steps, g_steps, srk, given, noise, generator)
-    return _run_stepped(sde, y0, y, steps, g_steps, srk, given, generator)
+        return _run_one_launch(sde, fields, y0, y, steps, g_steps, srk, given, noise, generator, qw)
+    return _run_stepped(sde, y0, y, steps, g_steps, srk, given, generator, qw)
 
 
 def _mlp_pair(first, second):
@@ -368,6 +481,13 @@ def _mlp_pair(first, second):
 def _refuse_srk(who):
     raise NotImplementedError(f"{who}(sde_solver='srk'): sigma is a schedule sigma(t) here, and 'srk' is built "
                               "for constant diagonal noise only (the full SRI2W1 tableau is not built)")
+
+
+def _refuse_adaptive(adaptive):
+    if adaptive:
+        raise NotImplementedError("sdeint(adaptive=True): the samplers here step the refined t_span grid with fixed steps "
+                                  "(Euler-Maruyama, srk); torchsde's adaptive step-size control with its Brownian-interval "
+                                  "queries is not built")
 
 
 class _SolverSDE:
@@ -382,6 +502,9 @@ class _SolverSDE:
 
     def g(self, t, y):
         return self.solver.sigma(t) * torch.ones_like(y)
+
+    def h(self, t, y):
+        return torch.zeros_like(y)
 
 
 class FlowSolver(torch.nn.Module):
@@ -486,19 +609,23 @@ class FlowSolver(torch.nn.Module):
             return None
         return _mlp_pair(self.net, self.score_net)
 
-    def sdeint(self, x0, t_span, reverse=False, generator=None):
+    def sdeint(self, x0, t_span, reverse=False, generator=None, *, logqp=False, adaptive=False):
+        """solver.py:157-182.  ``logqp=True``: ``(traj, kldiv)`` as ``sde.sdeint`` returns them, ``kldiv [n_t - 1, B]`` per
+        interval of ``t_span`` (cfm_module.py:911-983 logs ``mean(kldiv[-1])``).  ``adaptive=True`` is not built."""
+        _refuse_adaptive(adaptive)
         if self.sde_solver == "srk":
             _refuse_srk("FlowSolver")
         self.nfe = 0
         fields = self._hip_fields()
         if fields is not None:
             sde = FlowScoreSDE(fields[0], fields[1], sigma=self.sigma, reverse=reverse)
-            out = sdeint(sde, x0, t_span, method="euler", dt=self.dt, generator=generator)
+            out = sdeint(sde, x0, t_span, method="euler", dt=self.dt, generator=generator, logqp=logqp)
             self.last_path = sde.last_path
             self.nfe = len(_grid(t_span, float(self.dt)))          # one evaluation of the field pair per refined step
             return out
         self.last_path = "eager"
-        return sdeint(_SolverSDE(self, reverse), x0, t_span, method=self.sde_solver, dt=self.dt, generator=generator)
+        return sdeint(_SolverSDE(self, reverse), x0, t_span, method=self.sde_solver, dt=self.dt, generator=generator,
+                      logqp=logqp)
 
 
 class DSBMFlowSolver(FlowSolver):
@@ -545,7 +672,8 @@ class DSBMFlowSolver(FlowSolver):
         """(forward MLP, backward MLP) when the HIP paths can take them (the rule of NeuralODE._hip_mlp), else None."""
         return _mlp_pair(self.net, self.score_net)
 
-    def sdeint(self, x0, t_span, reverse=False, generator=None, noise="philox", fused=None):
+    def sdeint(self, x0, t_span, reverse=False, generator=None, noise="philox", fused=None, *, logqp=False, adaptive=False):
+        _refuse_adaptive(adaptive)
         if self.sde_solver == "srk":
             _refuse_srk("DSBMFlowSolver")
         if self.sigma is None:
@@ -554,12 +682,14 @@ class DSBMFlowSolver(FlowSolver):
         pair = self._hip_pair()
         if pair is not None:
             sde = DriftSDE(pair[1] if reverse else pair[0], sigma=self.sigma, reverse=reverse)
-            out = sdeint(sde, x0, t_span, method="euler", dt=self.dt, generator=generator, noise=noise, fused=fused)
+            out = sdeint(sde, x0, t_span, method="euler", dt=self.dt, generator=generator, noise=noise, fused=fused,
+                         logqp=logqp)
             self.last_path = sde.last_path
             self.nfe = len(_grid(t_span, float(self.dt)))          # one drift evaluation per refined step
             return out
         self.last_path = "eager"
-        return sdeint(_SolverSDE(self, reverse), x0, t_span, method="euler", dt=self.dt, generator=generator, noise=noise)
+        return sdeint(_SolverSDE(self, reverse), x0, t_span, method="euler", dt=self.dt, generator=generator, noise=noise,
+                      logqp=logqp)
 
     @torch.no_grad()
     def odeint(self, x0, t_span, fused=None):

@@ -493,10 +493,18 @@ int cfm_sde_em_step_f32(float* y, const float* v, const float* s, const float* x
  * int is_out} on the HOST (copied into ws: >= 16 n_steps bytes of device scratch); out [n_out, B, d] receives the
  * state after every step with is_out != 0.  xi: caller's N(0,1) noise [n_steps, B, d] (then the trajectory is
  * bit-equal to stepping with cfm_mlp_forward_f32 + cfm_sde_em_step_f32), or NULL: Philox4x32-10 noise from `seed`
- * in the kernel.  CFM_EINVAL for other field shapes (step launch by launch instead). */
+ * in the kernel.  CFM_EINVAL for other field shapes (step launch by launch instead).
+ * flags: bit 0 = reverse (as above), bit 1 = logqp, any higher bit: CFM_EINVAL before any work.  With bit 1 clear every
+ * byte read and written is as described above.  logqp (torchsde's sdeint(..., logqp=True) with prior drift h = 0) also
+ * integrates 1/2 sum_j (f_j / g)^2 with the same Euler steps, f being the drift of the state update:
+ *   steps_host: the n_steps records followed by n_steps floats qw_k = h_k / (2 g_k^2) (the host divides, in double, and
+ *               rounds once; g_k = 0 is the caller's to refuse);  ws: >= (16 + 4) n_steps bytes;
+ *   out:        the trajectory [n_out, B, d] followed by logratio [n_out, B], n_out the records with is_out != 0:
+ *               logratio[o][b] is the INCREASE over the steps since trajectory point o - 1 (since y0 for o = 0), not a
+ *               running sum.  The trajectory is bit-equal to the one without the bit. */
 int cfm_sde_em_mlp_f32(const float* const* Wf, const float* const* bf, const float* const* Ws,
                        const float* const* bs, const int* dims, int n_layers, const float* y0, int B,
-                       const void* steps_host, int n_steps, int reverse, const float* xi,
+                       const void* steps_host, int n_steps, int flags, const float* xi,
                        unsigned long long seed, float* out, void* ws, void* stream);
 /* SF2M sampling — one stage of an `srk` step: Roessler's SRI2W1 (strong order 1.5) for CONSTANT diagonal noise
  * g = sigma, the scheme torchsde.sdeint runs when no method is given (noise_type "diagonal", sde_type "ito").
@@ -519,10 +527,15 @@ int cfm_sde_srk_step_f32(int stage, float* y, float* ys, const float* v1, const 
  * te2, te3 (field times of the stages at t, t + h, t + h/2; reverse: 1 - them), h, g sqrt|h|, 0.75 g sqrt|h|; int
  * is_out, pad} on the HOST (copied into ws: >= 32 n_steps bytes of device scratch).  xi: caller's N(0,1) noise
  * [n_steps, 2, B, d] (plane 0: xi1, plane 1: xi2; then the trajectory is bit-equal to stepping with
- * cfm_mlp_forward_f32 + cfm_sde_srk_step_f32), or NULL: two Philox4x32-10 streams from `seed` in the kernel. */
+ * cfm_mlp_forward_f32 + cfm_sde_srk_step_f32), or NULL: two Philox4x32-10 streams from `seed` in the kernel.
+ * flags: bit 0 = reverse, bit 1 = logqp, any higher bit: CFM_EINVAL, as for cfm_sde_em_mlp_f32.  logqp integrates
+ * 1/2 sum_j (f_j / g)^2 as one more drift-only component of the scheme: per step (h/6)((q1 + q2) + 4 q3) with
+ * q_i = 1/2 sum_j (k_i,j / g)^2 on the three stage drifts.  steps_host: the n_steps records followed by n_steps floats
+ * qw_k = h / (12 g^2); ws: >= (32 + 4) n_steps bytes; out: the trajectory [n_out, B, d] followed by logratio [n_out, B],
+ * per-interval increases as for cfm_sde_em_mlp_f32.  With bit 1 clear nothing differs from the description above. */
 int cfm_sde_srk_mlp_f32(const float* const* Wf, const float* const* bf, const float* const* Ws,
                         const float* const* bs, const int* dims, int n_layers, const float* y0, int B,
-                        const void* steps_host, int n_steps, int reverse, const float* xi,
+                        const void* steps_host, int n_steps, int flags, const float* xi,
                         unsigned long long seed, float* out, void* ws, void* stream);
 /* Mixture-RBF kernel sum  out[0] += sum_e sum_q exp(-gammas[q] * D[e])  over a squared-distance matrix D
  * (n elements, device fp32; gammas device fp32[n_gamma]; out device double, zeroed by the caller).
