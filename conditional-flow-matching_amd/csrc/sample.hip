@@ -13,10 +13,9 @@
 //    ulp of a step, probability < 1e-12 per draw).
 //  * dense plan (Sinkhorn): never materialised.  fp64 row sums of
 //    exp(u_i + v_j - M_ij/reg) (one wave per row), block scan over rows, then one
-//    wave per draw: binary search of the row, segmented in-row scan, walk.
-#include "cfm_common.h"
-
-extern "C" size_t cfm_sk_ws_bytes_internal(int B0, int B1);
+//    wave per draw: binary search of the row, segmented in-row scan, walk (sd_row_scan, sd_row_walk: shared with the
+//    per-row draws of sample_trajectory).  The potentials come out of a Sinkhorn workspace (sinkhorn_state.h).
+#include "sinkhorn_state.h"
 
 __global__ __launch_bounds__(256) void sample_perm_kernel(const int* __restrict__ perm,
                                                           const double* __restrict__ u01, int B,
@@ -98,6 +97,56 @@ __global__ __launch_bounds__(1024) void sd_rowscan(double* __restrict__ rs, int 
     }
 }
 
+// One wave on plan row i.  Segmented scan: lane owns columns [jb, je) = [lane*L, lane*L + L); seg is their sum, inc the
+// inclusive scan of seg over the lanes (inc of lane 63: the row total, as the scan sees it).
+struct SdRowScan { int jb, je; double seg, inc; };
+template <class P>
+__device__ __forceinline__ SdRowScan sd_row_scan(const P& plan, int i, int B1, int lane) {
+    SdRowScan sc;
+    const int L = (B1 + 63) / 64;
+    sc.jb = lane * L; sc.je = min(B1, sc.jb + L);
+    sc.seg = 0.0;
+    for (int j = sc.jb; j < sc.je; ++j) sc.seg += plan(i, j);
+    sc.inc = sc.seg;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        double t = __shfl_up(sc.inc, o, 64);
+        if (lane >= o) sc.inc += t;
+    }
+    return sc;
+}
+// The first column of row i whose running sum, counted from `base` (the mass of the rows in front; 0.0 for a draw
+// within the row), exceeds target: the first lane whose scan does walks its columns.  Uniform across the wave.
+template <class P>
+__device__ __forceinline__ int sd_row_walk(const P& plan, int i, int B1, int lane, const SdRowScan& sc, double base,
+                                           double target) {
+    const bool hit = (base + sc.inc) > target;
+    const unsigned long long mask = __ballot(hit);
+    int jout = B1 - 1;
+    if (mask != 0ull) {
+        const int src = __ffsll((long long)mask) - 1;
+        if (lane == src) {
+            double run = base + (sc.inc - sc.seg);
+            int jj = sc.je - 1;
+            for (int j = sc.jb; j < sc.je; ++j) {
+                run += plan(i, j);
+                if (run > target) { jj = j; break; }
+            }
+            jout = jj;
+        }
+        jout = __shfl(jout, src, 64);
+    } else {
+        // rounding put the target past this row's mass (or the row has none, or its total is NaN: numpy raises there):
+        // last column carrying mass
+        int jl = -1;
+        for (int j = sc.je - 1; j >= sc.jb; --j) if (plan(i, j) > 0.0) { jl = j; break; }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) jl = max(jl, __shfl_xor(jl, o, 64));
+        jout = jl >= 0 ? jl : B1 - 1;
+    }
+    return jout;
+}
+
 template <class P>
 __global__ __launch_bounds__(256) void sd_sample(P plan, int B0, int B1,
                                                  const double* __restrict__ rinc,
@@ -117,40 +166,8 @@ __global__ __launch_bounds__(256) void sd_sample(P plan, int B0, int B1,
     }
     const int i = lo;
     const double base = (i > 0) ? rinc[i - 1] : 0.0;
-    // segmented scan: lane owns columns [lane*L, lane*L + L)
-    const int L = (B1 + 63) / 64;
-    const int jb = lane * L, je = min(B1, jb + L);
-    double seg = 0.0;
-    for (int j = jb; j < je; ++j) seg += plan(i, j);
-    double inc = seg;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        double t = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += t;
-    }
-    const bool hit = (base + inc) > target;
-    const unsigned long long mask = __ballot(hit);
-    int jout = B1 - 1;
-    if (mask != 0ull) {
-        const int src = __ffsll((long long)mask) - 1;
-        if (lane == src) {
-            double run = base + (inc - seg);
-            int jj = je - 1;
-            for (int j = jb; j < je; ++j) {
-                run += plan(i, j);
-                if (run > target) { jj = j; break; }
-            }
-            jout = jj;
-        }
-        jout = __shfl(jout, src, 64);
-    } else {
-        // rounding put the target past this row's mass: last column carrying mass
-        int jl = -1;
-        for (int j = je - 1; j >= jb; --j) if (plan(i, j) > 0.0) { jl = j; break; }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) jl = max(jl, __shfl_xor(jl, o, 64));
-        jout = jl >= 0 ? jl : B1 - 1;
-    }
+    const SdRowScan sc = sd_row_scan(plan, i, B1, lane);
+    const int jout = sd_row_walk(plan, i, B1, lane, sc, base, target);
     if (lane == 0) { oi[k] = i; oj[k] = jout; }
 }
 
@@ -169,13 +186,20 @@ static int sd_run(P plan, int B0, int B1, const double* u01, int n, int64_t* i, 
     return cfm_status();
 }
 
-// layout of the Sinkhorn workspace (must match sinkhorn.hip)
-struct SkStateView { int done, iters_done, vfinal, precise; double err2[2]; double last_err; };
-
-__global__ void sd_pick_v(const SkStateView* st, const double* v0, const double* v1, int B1,
+__global__ void sd_pick_v(const SkState* st, const double* v0, const double* v1, int B1,
                           double* vout) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j < B1) vout[j] = st->vfinal ? v1[j] : v0[j];
+}
+
+// The plan of a solved Sinkhorn workspace; ws (CFM_OP_SAMPLE_DENSE): [row sums B0 + 8][v copy B1], the final v is
+// copied into it here.
+static PlanFromPotentials sd_plan_of(const float* M, int B0, int B1, double reg, const void* sk_ws, void* ws,
+                                     hipStream_t s) {
+    const SkWs w = sk_carve((void*)sk_ws, B0, B1);
+    double* vsel = (double*)ws + ((size_t)B0 + 8);
+    hipLaunchKernelGGL(sd_pick_v, dim3((B1 + 255) / 256), dim3(256), 0, s, w.st, w.v[0], w.v[1], B1, vsel);
+    return PlanFromPotentials{M, w.u, vsel, 1.0 / reg, B1};
 }
 
 extern "C" int cfm_plan_sample_dense(const float* M, int B0, int B1, double reg, const void* sk_ws,
@@ -184,17 +208,7 @@ extern "C" int cfm_plan_sample_dense(const float* M, int B0, int B1, double reg,
     if (!M || !sk_ws || !ws || B0 <= 0 || B1 <= 0 || n < 0 || !(reg > 0.0)) return CFM_EINVAL;
     if (n > 0 && (!u01 || !i || !j)) return CFM_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    // ws: [row sums B0][v copy B1]
-    double* rs = (double*)ws;
-    double* vsel = rs + ((size_t)B0 + 8);
-    const char* q = (const char*)sk_ws;
-    const SkStateView* st = (const SkStateView*)q;
-    const double* u = (const double*)(q + 256);
-    const double* v0 = u + B0;
-    const double* v1 = v0 + B1;
-    hipLaunchKernelGGL(sd_pick_v, dim3((B1 + 255) / 256), dim3(256), 0, s, st, v0, v1, B1, vsel);
-    PlanFromPotentials plan{M, u, vsel, 1.0 / reg, B1};
-    return sd_run(plan, B0, B1, u01, n, i, j, ws, s);
+    return sd_run(sd_plan_of(M, B0, B1, reg, sk_ws, ws, s), B0, B1, u01, n, i, j, ws, s);
 }
 
 extern "C" int cfm_plan_sample_pi_f64(const double* pi, int B0, int B1, const double* u01, int n,
@@ -223,41 +237,9 @@ __global__ __launch_bounds__(256) void sd_sample_rows(P plan, int B0, int B1, co
     if (r < 0) r = 0;
     if (r > B0 - 1) r = B0 - 1;
     const int i = (int)r;
-    const int L = (B1 + 63) / 64;
-    const int jb = lane * L, je = min(B1, jb + L);
-    double seg = 0.0;
-    for (int j = jb; j < je; ++j) seg += plan(i, j);
-    double inc = seg;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        double t = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += t;
-    }
-    const double T = __shfl(inc, 63, 64);                 // the row total, as the scan sees it
-    const double target = u01[k] * T;
-    const bool hit = inc > target;
-    const unsigned long long mask = __ballot(hit);
-    int jout = B1 - 1;
-    if (mask != 0ull) {
-        const int src = __ffsll((long long)mask) - 1;
-        if (lane == src) {
-            double run = inc - seg;
-            int jj = je - 1;
-            for (int j = jb; j < je; ++j) {
-                run += plan(i, j);
-                if (run > target) { jj = j; break; }
-            }
-            jout = jj;
-        }
-        jout = __shfl(jout, src, 64);
-    } else {
-        // (a row without mass, or a NaN total: numpy raises there; return the last column carrying mass)
-        int jl = -1;
-        for (int j = je - 1; j >= jb; --j) if (plan(i, j) > 0.0) { jl = j; break; }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) jl = max(jl, __shfl_xor(jl, o, 64));
-        jout = jl >= 0 ? jl : B1 - 1;
-    }
+    const SdRowScan sc = sd_row_scan(plan, i, B1, lane);
+    const double T = __shfl(sc.inc, 63, 64);              // the row total, as the scan sees it
+    const int jout = sd_row_walk(plan, i, B1, lane, sc, 0.0, u01[k] * T);
     if (lane == 0) oj[k] = jout;
 }
 
@@ -268,14 +250,7 @@ extern "C" int cfm_plan_sample_rows_dense(const float* M, int B0, int B1, double
     if (n == 0) return 0;
     if (!rows || !u01 || !j) return CFM_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    double* vsel = (double*)ws + ((size_t)B0 + 8);        // same carving as cfm_plan_sample_dense
-    const char* q = (const char*)sk_ws;
-    const SkStateView* st = (const SkStateView*)q;
-    const double* u = (const double*)(q + 256);
-    const double* v0 = u + B0;
-    const double* v1 = v0 + B1;
-    hipLaunchKernelGGL(sd_pick_v, dim3((B1 + 255) / 256), dim3(256), 0, s, st, v0, v1, B1, vsel);
-    PlanFromPotentials plan{M, u, vsel, 1.0 / reg, B1};
+    const PlanFromPotentials plan = sd_plan_of(M, B0, B1, reg, sk_ws, ws, s);
     hipLaunchKernelGGL(sd_sample_rows<PlanFromPotentials>, dim3((n + 3) / 4), dim3(256), 0, s, plan, B0, B1, rows, u01, n, j);
     return cfm_status();
 }

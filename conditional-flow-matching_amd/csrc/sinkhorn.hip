@@ -23,58 +23,12 @@
 //
 // Convergence is decided on the device (no host sync): every kernel of the
 // pre-enqueued sequence reads the state block and exits if `done` is set.
-#include "cfm_common.h"
+// The state block, the workspace carving, the decision itself (sk_decide) and the iteration schedule (sk_solve) are
+// sinkhorn_state.h's, shared with sinkhorn_pts.hip; the init / finish kernels of both solvers are defined here.
+#include "sinkhorn_state.h"
 #include <mutex>
 #include <stdlib.h>
 #include <type_traits>
-
-#define SK_NEG (-1.0e300)
-#define SK_NCHUNK_MAX 64
-
-struct SkState {
-    int done;        // set once converged
-    int iters_done;  // POT's ii+1 at break, or max_iter
-    int vfinal;      // which v buffer holds the final v
-    int precise;     // 1: fp64 exp/accumulate (near convergence)
-    double err2[2];  // sum of squared marginal violations (ping-pong)
-    double last_err;
-};
-
-struct SkWs {
-    SkState* st;
-    double* u;
-    double* v[2];
-    double* pm;  // [nchunk][B1]
-    double* ps;  // [nchunk][B1]
-};
-
-static inline int sk_nchunk(int B0, int B1) {
-    int tiles = (B1 + 255) / 256;
-    int n = (1024 + tiles - 1) / tiles;  // aim for ~1024 workgroups
-    if (n > SK_NCHUNK_MAX) n = SK_NCHUNK_MAX;
-    int maxn = (B0 + 31) / 32;           // at least 32 rows per strip
-    if (n > maxn) n = maxn;
-    if (n < 1) n = 1;
-    return n;
-}
-
-static inline size_t sk_ws_bytes(int B0, int B1) {
-    size_t nchunk = sk_nchunk(B0, B1);
-    return 256 + sizeof(double) * ((size_t)B0 + 2 * (size_t)B1 + 2 * nchunk * (size_t)B1) + 64;
-}
-
-static inline SkWs sk_carve(void* ws, int B0, int B1) {
-    SkWs w;
-    char* p = (char*)ws;
-    w.st = (SkState*)p; p += 256;
-    w.u = (double*)p; p += sizeof(double) * (size_t)B0;
-    w.v[0] = (double*)p; p += sizeof(double) * (size_t)B1;
-    w.v[1] = (double*)p; p += sizeof(double) * (size_t)B1;
-    size_t nchunk = sk_nchunk(B0, B1);
-    w.pm = (double*)p; p += sizeof(double) * nchunk * (size_t)B1;
-    w.ps = (double*)p;
-    return w;
-}
 
 extern "C" size_t cfm_sk_ws_bytes_internal(int B0, int B1) { return sk_ws_bytes(B0, B1); }
 
@@ -87,6 +41,10 @@ __global__ void sk_init(SkState* st, double* u, double* v0, double* v1, int B0, 
         st->done = 0; st->iters_done = max_iter; st->vfinal = (max_iter - 1) & 1; st->precise = 0;
         st->err2[0] = 0.0; st->err2[1] = 0.0; st->last_err = 1.0;
     }
+}
+void sk_launch_init(const SkWs& w, int B0, int B1, int max_iter, hipStream_t s) {
+    const int n = B0 > B1 ? B0 : B1;
+    hipLaunchKernelGGL(sk_init, dim3((n + 255) / 256), dim3(256), 0, s, w.st, w.u, w.v[0], w.v[1], B0, B1, max_iter);
 }
 
 __device__ __forceinline__ float4 sk_load4(const float* __restrict__ row, int j, int B1, bool vec) {
@@ -392,28 +350,8 @@ __global__ __launch_bounds__(FAST ? SK_ROW_THREADS : 256, FAST ? SK_ROW_OCC : 4)
                                                       double* __restrict__ u, int rows_per_wg,
                                                       int check, int slot, double stop_thr, int ii,
                                                       int vec, int v_in_lds, double precise_below) {
-    if (st->done) return;
-    if (check) {
-        const double err = sqrt(st->err2[slot]);
-        if (err < stop_thr) {
-            if (blockIdx.x == 0 && threadIdx.x == 0) {
-                st->last_err = err;
-                st->iters_done = ii;          // iterations 0..ii-1 ran; POT broke at ii-1
-                st->vfinal = (ii - 1) & 1;
-                __threadfence();
-                st->done = 1;
-            }
-            return;
-        }
-        if (blockIdx.x == 0 && threadIdx.x == 0) {
-            st->last_err = err;
-            // fp32 exp leaves ~1e-7 relative noise per column sum -> ~1e-7/sqrt(B1) in the L2
-            // violation; go precise well above that floor when the caller asks for less.
-            if (!st->precise && err < precise_below && stop_thr < precise_below) st->precise = 1;
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) st->err2[slot ^ 1] = 0.0;  // next accumulation slot
-    const int precise = st->precise;
+    int precise;
+    if (!sk_decide(st, check, slot, stop_thr, ii, precise_below, precise)) return;
 
     extern __shared__ __attribute__((aligned(16))) double vs[];
     if (FAST) {
@@ -574,39 +512,13 @@ __global__ __launch_bounds__(SK_STREAM_THREADS, SK_STREAM_OCC) void sk_row_strea
 #pragma unroll
         for (int k = 0; k < NF4; ++k) c[k] = *reinterpret_cast<const float4*>(row + 256 * k);
     }
-    if (st->done) return;
-    if (check) {
-        const double err = sqrt(st->err2[slot]);
-        if (err < stop_thr) {
-            if (blockIdx.x == 0 && threadIdx.x == 0) {
-                st->last_err = err;
-                st->iters_done = ii;
-                st->vfinal = (ii - 1) & 1;
-                __threadfence();
-                st->done = 1;
-            }
-            return;
-        }
-        if (blockIdx.x == 0 && threadIdx.x == 0) {
-            st->last_err = err;
-            if (!st->precise && err < precise_below && stop_thr < precise_below) st->precise = 1;
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) st->err2[slot ^ 1] = 0.0;
-    const int precise = st->precise;
+    int precise;
+    if (!sk_decide(st, check, slot, stop_thr, ii, precise_below, precise)) return;
     for (int j = threadIdx.x * 2; j < B1; j += 2 * SK_STREAM_THREADS)
         *reinterpret_cast<double2*>(vs + j) = *reinterpret_cast<const double2*>(v + j);
     __syncthreads();
     if (precise) sk_stream_rows<true, NF4>(M, B0, B1, inv_reg, loga, vs, u, c, r0, r_stride);
     else         sk_stream_rows<false, NF4>(M, B0, B1, inv_reg, loga, vs, u, c, r0, r_stride);
-}
-
-template <int NF4>
-static void sk_launch_stream(int grid, size_t lds, hipStream_t s, const float* M, int B0, int B1, double inv_reg,
-                             double loga, SkState* st, const double* v, double* u, int check, int slot,
-                             double stop_thr, int ii, double precise_below) {
-    hipLaunchKernelGGL(sk_row_stream<NF4>, dim3(grid), dim3(SK_STREAM_THREADS), lds, s, M, B0, B1, inv_reg, loga,
-                       st, v, u, check, slot, stop_thr, ii, precise_below);
 }
 
 __global__ void sk_finish(SkState* st, const double* u, const double* v0, const double* v1,
@@ -622,6 +534,12 @@ __global__ void sk_finish(SkState* st, const double* u, const double* v0, const 
         if (iters_done) *iters_done = st->iters_done;
         if (last_err) *last_err = (float)le;
     }
+}
+void sk_launch_finish(const SkWs& w, int B0, int B1, double reg, float* f, float* g, int* iters_done, float* last_err,
+                      int pending, int slot, hipStream_t s) {
+    const int n = B0 > B1 ? B0 : B1;
+    hipLaunchKernelGGL(sk_finish, dim3((n + 255) / 256), dim3(256), 0, s, w.st, w.u, w.v[0], w.v[1],
+                       B0, B1, reg, f, g, iters_done, last_err, pending, slot);
 }
 
 // The shape arithmetic of cfm_sinkhorn_log_f32, in one place: which kernels a B0 x B1 problem takes and on what
@@ -649,9 +567,9 @@ static inline SkShape sk_shape(int B0, int B1, bool m_aligned16) {
     sh.lds_bytes = sh.v_in_lds ? (size_t)B1 * 8 : 0;
     sh.stream_nf4 = 0; sh.stream_want = 0;
     if (sh.row_fast) {
-        // units of 256 * nf4 columns: the largest of 4, 8, 12, 16 float4 per lane that divides the row
-        for (int q = 4; q <= SK_STREAM_UNIT; q += 4)
-            if ((B1 / 256) % q == 0) sh.stream_nf4 = q;
+        // units of 256 * SK_STREAM_UNIT = 1024 columns: a fast row is a whole number of them
+        static_assert(SK_STREAM_UNIT == 4, "row_fast promises whole 1024-column units");
+        sh.stream_nf4 = SK_STREAM_UNIT;
         sh.stream_want = (B0 + SK_STREAM_WAVES - 1) / SK_STREAM_WAVES;
     }
     return sh;
@@ -699,70 +617,40 @@ extern "C" int cfm_sinkhorn_log_f32(const float* M, int B0, int B1, double reg, 
     }
     const size_t lds = v_in_lds ? (size_t)B1 * 8 : 0;
     // streaming row pass: a persistent grid of SK_STREAM_WAVES-wave workgroups
-    int stream_grid = 0, stream_nf4 = 0;
+    int stream_grid = 0;
     if (row_fast && v_in_lds) {
         const int cus = cfm_device_cus();
         const int per_cu = cfm_once_per_device([] {
             const char* e = getenv("CFM_SK_STREAM");       // workgroups per CU; 0 = one-shot row pass
             int pc = e ? atoi(e) : 1;
-            const void* fns[4] = {(const void*)sk_row_stream<4>, (const void*)sk_row_stream<8>,
-                                  (const void*)sk_row_stream<12>, (const void*)sk_row_stream<16>};
-            for (int q = 0; q < 4; ++q)
-                if (hipFuncSetAttribute(fns[q], hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess) pc = 0;
+            if (hipFuncSetAttribute((const void*)sk_row_stream<SK_STREAM_UNIT>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    128 * 1024) != hipSuccess) pc = 0;
             return pc < 0 ? 0 : pc;
         });
-        stream_nf4 = sh.stream_nf4;
         const int want = sh.stream_want;
-        stream_grid = (per_cu > 0 && stream_nf4 > 0) ? (want < cus * per_cu ? want : cus * per_cu) : 0;
+        stream_grid = (per_cu > 0 && sh.stream_nf4 > 0) ? (want < cus * per_cu ? want : cus * per_cu) : 0;
     }
 
-    int n = B0 > B1 ? B0 : B1;
-    hipLaunchKernelGGL(sk_init, dim3((n + 255) / 256), dim3(256), 0, s, w.st, w.u, w.v[0], w.v[1],
-                       B0, B1, max_iter);
-    // iteration ii: v^(ii) -> v[ii&1];  error of iteration ii-1 is measured by
-    // the column pass of iteration ii and decided at the start of its row pass.
-    // Short runs are enqueued in one go (no host sync); for very long caps
-    // (wasserstein() passes numItermax=1e7) the host polls `done` every 512
-    // iterations so the queue stays bounded.
-    const bool poll = max_iter > 4096;
-    int host_done = 0;
-    for (int ii = 0; ii <= max_iter; ++ii) {
-        const int check = (ii >= 1) && (((ii - 1) % check_every) == 0);
-        const int slot = ii & 1;
-        const bool trailing = (ii == max_iter);
-        if (trailing && !check) break;  // nothing left to measure
-        hipLaunchKernelGGL(sk_col_pass, dim3(col_tiles, nchunk), dim3(256), 0, s, M, B0, B1, inv_reg,
-                           w.st, w.u, w.pm, w.ps, rows_per_chunk, vec);
-        hipLaunchKernelGGL(sk_col_finalize, dim3((B1 + 63) / 64), dim3(256), 0, s, B1, nchunk, logb, b,
-                           w.st, w.pm, w.ps, w.v[(ii + 1) & 1], w.v[ii & 1], check, slot);
-        if (trailing) break;
-        if (row_fast && v_in_lds && stream_grid > 0)
-            switch (stream_nf4) {
-            case 4:  sk_launch_stream<4>(stream_grid, lds, s, M, B0, B1, inv_reg, loga, w.st, w.v[ii & 1], w.u, check, slot, stop_thr, ii, precise_below); break;
-            case 8:  sk_launch_stream<8>(stream_grid, lds, s, M, B0, B1, inv_reg, loga, w.st, w.v[ii & 1], w.u, check, slot, stop_thr, ii, precise_below); break;
-            case 12: sk_launch_stream<12>(stream_grid, lds, s, M, B0, B1, inv_reg, loga, w.st, w.v[ii & 1], w.u, check, slot, stop_thr, ii, precise_below); break;
-            default: sk_launch_stream<16>(stream_grid, lds, s, M, B0, B1, inv_reg, loga, w.st, w.v[ii & 1], w.u, check, slot, stop_thr, ii, precise_below); break;
-            }
-        else if (row_fast && v_in_lds)
-            hipLaunchKernelGGL(sk_row_pass<true>, dim3(row_wgs), dim3(SK_ROW_THREADS), lds, s, M, B0, B1, inv_reg, loga,
-                               w.st, w.v[ii & 1], w.u, rows_per_wg, check, slot, stop_thr, ii,
-                               vec, v_in_lds, precise_below);
-        else
-            hipLaunchKernelGGL(sk_row_pass<false>, dim3(row_wgs), dim3(256), lds, s, M, B0, B1, inv_reg, loga,
-                               w.st, w.v[ii & 1], w.u, rows_per_wg, check, slot, stop_thr, ii,
-                               vec, v_in_lds, precise_below);
-        if (poll && (ii & 511) == 511) {
-            int rc = cfm_hip(hipMemcpyAsync(&host_done, &w.st->done, sizeof(int), hipMemcpyDeviceToHost, s));
-            if (rc) return rc;
-            rc = cfm_hip(hipStreamSynchronize(s));
-            if (rc) return rc;
-            if (host_done) break;
-        }
-    }
-    const int pending = (max_iter >= 1) && (((max_iter - 1) % check_every) == 0);
-    hipLaunchKernelGGL(sk_finish, dim3((n + 255) / 256), dim3(256), 0, s, w.st, w.u, w.v[0], w.v[1],
-                       B0, B1, reg, f, g, iters_done, last_err, pending, max_iter & 1);
-    return cfm_status();
+    return sk_solve(w, B0, B1, reg, max_iter, check_every, f, g, iters_done, last_err, s,
+        [&](int ii, int check, int slot) {
+            hipLaunchKernelGGL(sk_col_pass, dim3(col_tiles, nchunk), dim3(256), 0, s, M, B0, B1, inv_reg,
+                               w.st, w.u, w.pm, w.ps, rows_per_chunk, vec);
+            hipLaunchKernelGGL(sk_col_finalize, dim3((B1 + 63) / 64), dim3(256), 0, s, B1, nchunk, logb, b,
+                               w.st, w.pm, w.ps, w.v[(ii + 1) & 1], w.v[ii & 1], check, slot);
+        },
+        [&](int ii, int check, int slot) {
+            if (row_fast && v_in_lds && stream_grid > 0)
+                hipLaunchKernelGGL(sk_row_stream<SK_STREAM_UNIT>, dim3(stream_grid), dim3(SK_STREAM_THREADS), lds, s, M, B0, B1,
+                                   inv_reg, loga, w.st, w.v[ii & 1], w.u, check, slot, stop_thr, ii, precise_below);
+            else if (row_fast && v_in_lds)
+                hipLaunchKernelGGL(sk_row_pass<true>, dim3(row_wgs), dim3(SK_ROW_THREADS), lds, s, M, B0, B1, inv_reg, loga,
+                                   w.st, w.v[ii & 1], w.u, rows_per_wg, check, slot, stop_thr, ii,
+                                   vec, v_in_lds, precise_below);
+            else
+                hipLaunchKernelGGL(sk_row_pass<false>, dim3(row_wgs), dim3(256), lds, s, M, B0, B1, inv_reg, loga,
+                                   w.st, w.v[ii & 1], w.u, rows_per_wg, check, slot, stop_thr, ii,
+                                   vec, v_in_lds, precise_below);
+        });
 }
 
 __global__ void sk_copy_potentials(const SkState* st, const double* u, const double* v0,

@@ -17,19 +17,10 @@
 // with fp32 exp per lane (fp64 exp near convergence, as in sinkhorn.hip), two lane exchanges across the
 // sub-groups, an LDS merge across the waves, and the 16 new potentials written by wave 0 — together
 // with their share of the marginal violation on check iterations.
-#include "cfm_common.h"
+// State block, workspace, convergence decision, iteration schedule and the init / finish launches: sinkhorn_state.h.
+#include "sinkhorn_state.h"
 #include <type_traits>
 #include <mutex>
-
-#define SK_NEG (-1.0e300)
-
-// (identical to sinkhorn.hip: the two files share the workspace)
-struct SkState {
-    int done; int iters_done; int vfinal; int precise;
-    double err2[2];
-    double last_err;
-};
-extern "C" size_t cfm_sk_ws_bytes_internal(int B0, int B1);
 
 #define PTS_T 1024
 #define PTS_NW (PTS_T / 64)
@@ -129,27 +120,13 @@ __global__ __launch_bounds__(PTS_T) void sk_pts_pass(const float* __restrict__ o
         for (int q = 0; q < D; ++q) pre_pts[k][q] = ok ? other_pts[(size_t)t * D + q] : 0.f;
     }
     const double pold = (!row_update && check && o < n_own) ? pot_old[o] : 0.0;
-    if (st->done) return;
-    if (row_update) {
-        // the convergence decision for the previous iteration: every workgroup derives it from the same data
-        if (check) {
-            const double err = sqrt(st->err2[slot]);
-            if (err < stop_thr) {
-                if (blockIdx.x == 0 && threadIdx.x == 0) {
-                    st->last_err = err; st->iters_done = ii; st->vfinal = (ii - 1) & 1;
-                    __threadfence();
-                    st->done = 1;
-                }
-                return;
-            }
-            if (blockIdx.x == 0 && threadIdx.x == 0) {
-                st->last_err = err;
-                if (!st->precise && err < precise_below && stop_thr < precise_below) st->precise = 1;
-            }
-        }
-        if (blockIdx.x == 0 && threadIdx.x == 0) st->err2[slot ^ 1] = 0.0;
+    int precise;
+    if (row_update) {       // the convergence decision for the previous iteration
+        if (!sk_decide(st, check, slot, stop_thr, ii, precise_below, precise)) return;
+    } else {
+        if (st->done) return;
+        precise = st->precise;
     }
-    const int precise = st->precise;
     double m = SK_NEG, s_acc = 0.0;
     for (int c0 = 0; c0 < n_other; c0 += stage_cap) {
         const int n_stage = (n_other - c0 < stage_cap) ? n_other - c0 : stage_cap;
@@ -212,32 +189,6 @@ __global__ __launch_bounds__(PTS_T) void sk_pts_pass(const float* __restrict__ o
     }
 }
 
-// (kernels of sinkhorn.hip, reused through their C entry points would need a header; the three small ones
-//  are restated here as they touch only the shared state layout)
-__global__ void sk_pts_init(SkState* st, double* u, double* v0, double* v1, int B0, int B1, int max_iter) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < B0) u[i] = 0.0;
-    if (i < B1) { v0[i] = 0.0; v1[i] = 0.0; }
-    if (i == 0) {
-        st->done = 0; st->iters_done = max_iter; st->vfinal = (max_iter - 1) & 1; st->precise = 0;
-        st->err2[0] = 0.0; st->err2[1] = 0.0; st->last_err = 1.0;
-    }
-}
-__global__ void sk_pts_finish(SkState* st, const double* u, const double* v0, const double* v1, int B0, int B1,
-                              double reg, float* f, float* g, int* iters_done, float* last_err, int pending_check,
-                              int slot) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const double* v = st->vfinal ? v1 : v0;
-    if (i < B0 && f) f[i] = (float)(reg * u[i]);
-    if (i < B1 && g) g[i] = (float)(reg * v[i]);
-    if (i == 0) {
-        double le = st->last_err;
-        if (!st->done && pending_check) { le = sqrt(st->err2[slot]); st->last_err = le; }
-        if (iters_done) *iters_done = st->iters_done;
-        if (last_err) *last_err = (float)le;
-    }
-}
-
 template <int D>
 static void pts_launch(int grid, size_t lds, hipStream_t s, const float* own, const float* other, int n_own, int n_other,
                        double inv_reg, double logw, double wgt, SkState* st, const double* pot_other,
@@ -294,16 +245,11 @@ extern "C" int cfm_sinkhorn_log_points_f32(const float* x0, const float* x1, int
         return CFM_EINVAL;
     if (((uintptr_t)ws & 15) != 0) return CFM_EALIGN;
     hipStream_t s = (hipStream_t)stream;
-    // workspace layout of sinkhorn.hip: state (256 B) | u [B0] | v[0] [B1] | v[1] [B1] | strip partials (unused here)
-    char* p = (char*)ws;
-    SkState* st = (SkState*)p; p += 256;
-    double* u = (double*)p; p += sizeof(double) * (size_t)B0;
-    double* v[2]; v[0] = (double*)p; p += sizeof(double) * (size_t)B1; v[1] = (double*)p;
+    const SkWs w = sk_carve(ws, B0, B1);        // (the strip partials stay unused here)
     const double inv_reg = 1.0 / reg;
     const double a = 1.0 / B0, b = 1.0 / B1;
     const double precise_below = 1e-4 / sqrt((double)B1);
     const double loga = log(a), logb = log(b);
-    const int n_max = B0 > B1 ? B0 : B1;
     const PtsShape sh = pts_shape(B0, B1, d);
     const int stage_cap = sh.stage_cap;
     const size_t lds = sh.lds_bytes;
@@ -314,33 +260,14 @@ extern "C" int cfm_sinkhorn_log_points_f32(const float* x0, const float* x1, int
         for (int q = 0; q < 8; ++q) (void)hipFuncSetAttribute(fns[q], hipFuncAttributeMaxDynamicSharedMemorySize, 136 * 1024);
         return 0;
     });
-    const int n = n_max;
-    hipLaunchKernelGGL(sk_pts_init, dim3((n + 255) / 256), dim3(256), 0, s, st, u, v[0], v[1], B0, B1, max_iter);
     const int col_grid = sh.col_grid, row_grid = sh.row_grid;
-    const bool poll = max_iter > 4096;
-    int host_done = 0;
-    for (int ii = 0; ii <= max_iter; ++ii) {
-        const int check = (ii >= 1) && (((ii - 1) % check_every) == 0);
-        const int slot = ii & 1;
-        const bool trailing = (ii == max_iter);
-        if (trailing && !check) break;
-        // column update: own = x1 (v), other = x0 with u
-        PTS_DISPATCH(d, col_grid, lds, s, x1, x0, B1, B0, inv_reg, logb, b, st, u, v[(ii + 1) & 1], v[ii & 1], 0, check, slot,
-                     stop_thr, ii, precise_below, stage_cap);
-        if (trailing) break;
-        // row update: own = x0 (u), other = x1 with the new v
-        PTS_DISPATCH(d, row_grid, lds, s, x0, x1, B0, B1, inv_reg, loga, a, st, v[ii & 1], u, u, 1, check, slot,
-                     stop_thr, ii, precise_below, stage_cap);
-        if (poll && (ii & 511) == 511) {
-            int rc = cfm_hip(hipMemcpyAsync(&host_done, &st->done, sizeof(int), hipMemcpyDeviceToHost, s));
-            if (rc) return rc;
-            rc = cfm_hip(hipStreamSynchronize(s));
-            if (rc) return rc;
-            if (host_done) break;
-        }
-    }
-    const int pending = (max_iter >= 1) && (((max_iter - 1) % check_every) == 0);
-    hipLaunchKernelGGL(sk_pts_finish, dim3((n + 255) / 256), dim3(256), 0, s, st, u, v[0], v[1], B0, B1, reg, f, g,
-                       iters_done, last_err, pending, max_iter & 1);
-    return cfm_status();
+    return sk_solve(w, B0, B1, reg, max_iter, check_every, f, g, iters_done, last_err, s,
+        [&](int ii, int check, int slot) {      // column update: own = x1 (v), other = x0 with u
+            PTS_DISPATCH(d, col_grid, lds, s, x1, x0, B1, B0, inv_reg, logb, b, w.st, w.u, w.v[(ii + 1) & 1], w.v[ii & 1], 0,
+                         check, slot, stop_thr, ii, precise_below, stage_cap);
+        },
+        [&](int ii, int check, int slot) {      // row update: own = x0 (u), other = x1 with the new v
+            PTS_DISPATCH(d, row_grid, lds, s, x0, x1, B0, B1, inv_reg, loga, a, w.st, w.v[ii & 1], w.u, w.u, 1, check, slot,
+                         stop_thr, ii, precise_below, stage_cap);
+        });
 }

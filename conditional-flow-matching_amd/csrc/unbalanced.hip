@@ -20,9 +20,10 @@
 // Partial is POT's Dykstra loop; its three B0 x B1 correction matrices q1, q2, q3 are constant
 // along rows / columns / everywhere (q1 <- q1 * Kprev / K1 = 1 / r_i, ...), so the iteration is
 // carried on two scaling vectors and a scalar: K = diag(alpha) K0 diag(beta).
-#include "cfm_common.h"
+// The row strips of coldot follow the rule of the Sinkhorn column pass (sk_nchunk, sinkhorn_state.h).
+#include "sinkhorn_state.h"
 
-#define UB_NCHUNK_MAX 64
+#define UB_NCHUNK_MAX SK_NCHUNK_MAX
 
 struct UbState {
     int done, iters, status, final_idx;   // status: 0 ok, 1 numerical error (previous iterate returned)
@@ -51,17 +52,8 @@ struct UbWs {
     double* part;     // [nchunk][B1]
 };
 
-static inline int ub_nchunk(int B0, int B1) {
-    int tiles = (B1 + 255) / 256;
-    int n = (1024 + tiles - 1) / tiles;
-    if (n > UB_NCHUNK_MAX) n = UB_NCHUNK_MAX;
-    int maxn = (B0 + 31) / 32;
-    if (n > maxn) n = maxn;
-    return n < 1 ? 1 : n;
-}
-
 static inline size_t ub_ws_bytes(int B0, int B1) {
-    size_t nchunk = ub_nchunk(B0, B1);
+    size_t nchunk = sk_nchunk(B0, B1);
     return 512 + sizeof(double) * (4 * (size_t)B0 + 5 * (size_t)B1 + nchunk * (size_t)B1) + 256;
 }
 
@@ -117,7 +109,6 @@ __global__ void ub_state_init(UbState* st) {
     }
 }
 
-
 // partial column sums over a strip of rows: part[chunk][j] = sum_{i in strip} w_i K_ij
 __global__ __launch_bounds__(256) void ub_coldot(const double* __restrict__ K, int B0, int B1,
                                                  const UbState* __restrict__ st,
@@ -146,9 +137,6 @@ __device__ __forceinline__ void ub_atomic_max_abs(unsigned long long* slot, doub
     // |v| >= 0: the bit pattern orders like the value; NaN never wins (flagged separately)
     atomicMax(slot, (unsigned long long)__double_as_longlong(fabs(v)));
 }
-
-
-
 
 // plan = u_i K_ij v_j  (in place)
 __global__ __launch_bounds__(256) void ub_plan(double* __restrict__ K, int B0, int B1,
@@ -241,7 +229,7 @@ __global__ __launch_bounds__(256) void ub_row_fused(const double* __restrict__ K
         //  two arrays: one device-scope atomic per ROW — 4096 waves, one lane each, on one address — cost 11 ns apiece
         //  at the memory side, 135 us per check launch; the launch-per-step kernel issued them 64 lanes at a time)
     } else {
-        // alpha arrives with its scalar factor still pending (fold[p]: one multiplication, exactly the one pt_fold did)
+        // alpha arrives with its scalar factor still pending (fold[p]: one multiplication)
         const double al = up * fo, a1 = al * rh;
         const double rowsum = a1 * kv;
         const double rr = fmin(a / rowsum, 1.0);
@@ -385,7 +373,7 @@ extern "C" int cfm_unbalanced_sinkhorn_f64(const float* M, int B0, int B1, doubl
     hipStream_t s = (hipStream_t)stream;
     UbWs w = ub_carve(ws, B0, B1);
     const size_t n = (size_t)B0 * B1;
-    const int nchunk = ub_nchunk(B0, B1);
+    const int nchunk = sk_nchunk(B0, B1);
     const int rows_per_chunk = (B0 + nchunk - 1) / nchunk;
     const double a = 1.0 / B0, b = 1.0 / B1, fi = reg_m / (reg_m + reg);
     hipLaunchKernelGGL(ub_state_init, dim3(1), dim3(64), 0, s, w.st);
@@ -415,21 +403,18 @@ __global__ __launch_bounds__(256) void pt_scale(double* __restrict__ K, size_t n
     for (size_t k = (size_t)blockIdx.x * 256 + threadIdx.x; k < n; k += (size_t)gridDim.x * 256) K[k] *= f;
 }
 
-
-
 // || diag(alpha) K0 diag(beta) - diag(alpha2) K0 diag(beta2) ||_F^2 (alpha2 already carries sigma * s)
 __global__ __launch_bounds__(256) void pt_err(const double* __restrict__ K, int B0, int B1, UbState* st,
                                               const double* __restrict__ alpha, const double* __restrict__ beta,
                                               const double* __restrict__ alpha2, const double* __restrict__ beta2, int p) {
     if (st->done) return;
     const size_t n = (size_t)B0 * B1;
-    // fused loop: the scalar factors are still pending on alpha = U[p] and alpha2 = U[p ^ 1] (one multiplication each,
-    // the one pt_fold did before the value was stored); launch-per-step loop (p < 0): already applied
-    const double fa = p >= 0 ? st->fold[p] : 1.0, fb = p >= 0 ? st->fold[p ^ 1] : 1.0;
+    // the scalar factors are still pending on alpha = U[p] and alpha2 = U[p ^ 1]: one multiplication each
+    const double fa = st->fold[p], fb = st->fold[p ^ 1];
     double acc = 0.0;
     for (size_t k = (size_t)blockIdx.x * 256 + threadIdx.x; k < n; k += (size_t)gridDim.x * 256) {
         const int i = (int)(k / B1), j = (int)(k - (size_t)i * B1);
-        const double al = p >= 0 ? alpha[i] * fa : alpha[i], al2 = p >= 0 ? alpha2[i] * fb : alpha2[i];
+        const double al = alpha[i] * fa, al2 = alpha2[i] * fb;
         const double d = K[k] * (al * beta[j] - al2 * beta2[j]);
         acc += d * d;
     }
@@ -439,16 +424,6 @@ __global__ __launch_bounds__(256) void pt_err(const double* __restrict__ K, int 
     __syncthreads();
     if (threadIdx.x == 0) atomicAdd(&st->err2, sd[0] + sd[1] + sd[2] + sd[3]);
 }
-
-
-__global__ void pt_fold(int B0, const UbState* st, double* __restrict__ alpha2) {
-    if (st->done) return;
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < B0) {
-        alpha2[i] *= st->fold[0];
-    }
-}
-
 
 // loop control (POT entropic_partial_wasserstein): nan / inf in K -> warning, break (K kept);
 // cpt % 10 == 0: err = ||Kprev - K||_F; `while err > stopThr and cpt < numItermax`.
@@ -472,7 +447,7 @@ extern "C" int cfm_partial_entropic_f64(const float* M, int B0, int B1, double r
     hipStream_t s = (hipStream_t)stream;
     UbWs w = ub_carve(ws, B0, B1);
     const size_t n = (size_t)B0 * B1;
-    const int nchunk = ub_nchunk(B0, B1);
+    const int nchunk = sk_nchunk(B0, B1);
     const int rows_per_chunk = (B0 + nchunk - 1) / nchunk;
     const double a = 1.0 / B0, b = 1.0 / B1;
     const int nmax = B0 > B1 ? B0 : B1;

@@ -235,12 +235,8 @@ class SinkhornResult:
     __slots__ = ("f", "g", "iters", "err", "ws", "reg", "M")
 
 
-def sinkhorn_log(M, reg, max_iter=_SINKHORN_MAX_ITER, stop_thr=_SINKHORN_STOP_THR,
-                 check_every=_SINKHORN_CHECK_EVERY):
-    """Log-domain Sinkhorn on the GPU; potentials stay resident (fp64) in the workspace."""
-    lib = _lib.load()
-    B0, B1 = M.shape
-    dev = M.device
+def _sinkhorn_result(lib, B0, B1, reg, M, dev):
+    """The outputs and the workspace of one Sinkhorn solve of either entry point, allocated."""
     r = SinkhornResult()
     r.f = torch.empty(B0, dtype=torch.float32, device=dev)
     r.g = torch.empty(B1, dtype=torch.float32, device=dev)
@@ -251,6 +247,15 @@ def sinkhorn_log(M, reg, max_iter=_SINKHORN_MAX_ITER, stop_thr=_SINKHORN_STOP_TH
     # next same-shape solve on this stream while earlier results are still alive.
     r.ws = torch.empty(lib.cfm_workspace_bytes(_lib.OP_SINKHORN, B0, B1, 0), dtype=torch.uint8, device=dev)
     r.reg, r.M = float(reg), M
+    return r
+
+
+def sinkhorn_log(M, reg, max_iter=_SINKHORN_MAX_ITER, stop_thr=_SINKHORN_STOP_THR,
+                 check_every=_SINKHORN_CHECK_EVERY):
+    """Log-domain Sinkhorn on the GPU; potentials stay resident (fp64) in the workspace."""
+    lib = _lib.load()
+    B0, B1 = M.shape
+    r = _sinkhorn_result(lib, B0, B1, reg, M, M.device)
     check(lib.cfm_sinkhorn_log_f32(ptr(M), B0, B1, float(reg), int(max_iter), float(stop_thr),
                                    int(check_every), ptr(r.f), ptr(r.g), ptr(r.iters), ptr(r.err),
                                    ptr(r.ws), stream_ptr()), "cfm_sinkhorn_log_f32")
@@ -273,14 +278,7 @@ def sinkhorn_log_points(x0, x1, M, reg, max_iter=_SINKHORN_MAX_ITER, stop_thr=_S
     lib = _lib.load()
     B0, d = x0.shape
     B1 = x1.shape[0]
-    dev = x0.device
-    r = SinkhornResult()
-    r.f = torch.empty(B0, dtype=torch.float32, device=dev)
-    r.g = torch.empty(B1, dtype=torch.float32, device=dev)
-    r.iters = torch.zeros(1, dtype=torch.int32, device=dev)
-    r.err = torch.zeros(1, dtype=torch.float32, device=dev)
-    r.ws = torch.empty(lib.cfm_workspace_bytes(_lib.OP_SINKHORN, B0, B1, 0), dtype=torch.uint8, device=dev)
-    r.reg, r.M = float(reg), M
+    r = _sinkhorn_result(lib, B0, B1, reg, M, x0.device)
     check(lib.cfm_sinkhorn_log_points_f32(ptr(x0), ptr(x1), B0, B1, d, float(reg), int(max_iter), float(stop_thr),
                                           int(check_every), ptr(r.f), ptr(r.g), ptr(r.iters), ptr(r.err),
                                           ptr(r.ws), stream_ptr()), "cfm_sinkhorn_log_points_f32")

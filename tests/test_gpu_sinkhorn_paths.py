@@ -601,7 +601,7 @@ def test_points_variant_sentinel(dev, B0, B1, d):
 # ------------------------------------------------------------------------------------------- (i) unbalanced / partial
 @pytest.mark.parametrize("B0,B1", [(33, 1027), (5, 300), (2055, 70), (1, 7), (7, 1)])
 def test_unbalanced_and_partial_strips(dev, B0, B1):
-    """The same strip logic (ub_nchunk) at two strips, one strip, 64 strips with an empty last one, one row / column."""
+    """The same strip logic (sk_nchunk) at two strips, one strip, 64 strips with an empty last one, one row / column."""
     ot = _ot()
     Mnp = _cloud_cost(B0, B1)
     M = _to_dev(Mnp, dev)
