@@ -18,6 +18,11 @@ also for ``reverse=True`` (what the reference's SDE classes and the eager scheme
 the way back passes ``lambda t: schedule(1 - t)``.  ``srk`` with a schedule is not built.
 The Brownian increments come from ``torch.randn`` on the state's device (torchsde's BrownianInterval
 stream is not reproducible without torchsde: the noise stream is NOT bit-compatible, the scheme is).
+Under ``noise="philox"`` the one-launch kernels draw them themselves: Philox4x32-10 keyed by one ``torch.randint(0, 2**62)``
+draw of the generator per ``sdeint`` call, counter (element, refined step, stream), 24-bit uniforms and Box-Muller
+(include/cfm_gfx950.h has the layout) — a stream of its own, pinned element by element to the host restatement
+``tests/philox_ref.py`` (``tests/test_gpu_sde_philox.py``), in which a row's noise depends on its position in the batch
+and the seed, not on the batch size.
 
 ``logqp=True`` (``sdeint``, ``FlowSolver.sdeint``, ``DSBMFlowSolver.sdeint``: the validation loop of the runner's SF2M and
 DSBM modules, cfm_module.py:911-983) returns ``(ys, log_ratio_increments)`` as ``torchsde.sdeint`` does.  Recalled, not read

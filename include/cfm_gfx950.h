@@ -501,7 +501,20 @@ int cfm_sde_em_step_f32(float* y, const float* v, const float* s, const float* x
  *               rounds once; g_k = 0 is the caller's to refuse);  ws: >= (16 + 4) n_steps bytes;
  *   out:        the trajectory [n_out, B, d] followed by logratio [n_out, B], n_out the records with is_out != 0:
  *               logratio[o][b] is the INCREASE over the steps since trajectory point o - 1 (since y0 for o = 0), not a
- *               running sum.  The trajectory is bit-equal to the one without the bit. */
+ *               running sum.  The trajectory is bit-equal to the one without the bit.
+ * The stream of xi == NULL (pinned by tests/test_philox_host.py and tests/test_gpu_sde_philox.py against the host
+ * restatement tests/philox_ref.py; it is not torchsde's stream):
+ *   block:    Philox4x32-10 (Salmon et al., SC'11) on counter {elem lo, elem hi, step, stream} under key {seed lo,
+ *             seed hi}; step = k, the index of the record in steps_host (the refined grid, non-output steps included);
+ *             stream = 0x5f2d.  A step with g_sqrt_h == 0 draws nothing.
+ *   uniforms: the top 24 bits of each word: u0 = ((c0 >> 8) + 1) / 2^24, u1 = (c1 >> 8) / 2^24, u2, u3 likewise from c2, c3;
+ *   normals:  Box-Muller in float32: r0 = sqrt(-2 ln u0), r1 = sqrt(-2 ln u2),
+ *             z = (r0 cos 2 pi u1, r0 sin 2 pi u1, r1 cos 2 pi u3, r1 sin 2 pi u3);  |z| <= sqrt(48 ln 2).
+ *   elements: batch row `row`, state column `col` takes z[row % 4] of the block at
+ *             elem = 256 (row / 16) + 64 (col / 16) + 16 ((row % 16) / 4) + col % 16
+ *             (256 lanes per 16-row tile: the lane that holds the element in the kernel).
+ * So a row's noise depends on its position in the batch, the step and the seed — not on B, d, the flags or the number of
+ * fields: the first rows of a larger batch reproduce a smaller one bit for bit. */
 int cfm_sde_em_mlp_f32(const float* const* Wf, const float* const* bf, const float* const* Ws,
                        const float* const* bs, const int* dims, int n_layers, const float* y0, int B,
                        const void* steps_host, int n_steps, int flags, const float* xi,
@@ -532,7 +545,11 @@ int cfm_sde_srk_step_f32(int stage, float* y, float* ys, const float* v1, const 
  * 1/2 sum_j (f_j / g)^2 as one more drift-only component of the scheme: per step (h/6)((q1 + q2) + 4 q3) with
  * q_i = 1/2 sum_j (k_i,j / g)^2 on the three stage drifts.  steps_host: the n_steps records followed by n_steps floats
  * qw_k = h / (12 g^2); ws: >= (32 + 4) n_steps bytes; out: the trajectory [n_out, B, d] followed by logratio [n_out, B],
- * per-interval increases as for cfm_sde_em_mlp_f32.  With bit 1 clear nothing differs from the description above. */
+ * per-interval increases as for cfm_sde_em_mlp_f32.  With bit 1 clear nothing differs from the description above.
+ * The streams of xi == NULL are cfm_sde_em_mlp_f32's (same key, counter, uniforms, Box-Muller and element map, step =
+ * the record's index): xi1 at stream word 0x5f2d — the very normals the Euler-Maruyama entry draws from that seed —
+ * and xi2 at stream word 0x5f2e on the same counters.  A row's noise depends on its position, the step and the seed,
+ * not on B. */
 int cfm_sde_srk_mlp_f32(const float* const* Wf, const float* const* bf, const float* const* Ws,
                         const float* const* bs, const int* dims, int n_layers, const float* y0, int B,
                         const void* steps_host, int n_steps, int flags, const float* xi,

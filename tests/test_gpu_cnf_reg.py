@@ -248,3 +248,42 @@ def test_jacobian_penalty_with_a_hutchinson_estimator_goes_generic():
     cnf = cfm_amd.RegularizedCNF(m, jacobian_frobenius_reg=0.5, estimator="hutch_rademacher")
     out = cnf.solve(torch.zeros(5, 4, device=dev), torch.tensor([1.0, 0.5, 0.0]))
     assert cnf.last_path == "generic" and out.shape == (5, 4)
+
+
+# the forward's own stride: cfm_ode_euler_cnf_reg_mlp_f32 is launched on at most 4096 workgroups (the gradient's 256 above)
+FWD_BIG = 16 * 4096 + 5
+FWD_ROWS = (slice(0, 16), slice(16 * 2051, 16 * 2052), slice(FWD_BIG - 21, FWD_BIG))
+
+
+def test_second_grid_pass_of_the_forward_solve():
+    """B = 16 * 4096 + 5, d = 2, hidden widths (33, 16, 24), both penalties, exact trace, three output times on a non-uniform
+    grid (an Euler solve steps exactly its t_span): workgroup 0 of ode_small_euler_reg runs tile 4096 after tile 0, on the
+    three tile buffers and the row-sum scratch of its first pass.  Rows of a tile do not interact (the row sums run over
+    columns and directions), so the first tile, a middle one and the last full tile with the 5-row tail are bit-equal —
+    every column [l, e, f, y] at every output time — to the same rows solved alone; the tail is within 1e-5 max|column| of
+    the float64 restatement at every output time."""
+    from cfm_amd.cnf import TRACE_EXACT, augmented_euler_hip
+    dev = torch.device("cuda")
+    d, mask = 2, 3
+    Ws, bs = cr.mlp_params(d, (33, 16, 24), 1)
+    m = cr.make_mlp(Ws, bs, device=dev)
+    x = torch.randn(FWD_BIG, d, generator=torch.Generator().manual_seed(2)).to(dev)
+    ts = np.array([0.0, 0.25, 0.5, 1.0], dtype=np.float32)
+    with torch.no_grad():
+        big, nfe = augmented_euler_hip(m, x, torch.tensor(ts), TRACE_EXACT, mask)
+        big = big.cpu()
+        assert big.shape == (4, FWD_BIG, 3 + d) and nfe == 3 and bool(torch.isfinite(big).all())
+        for rows in FWD_ROWS:
+            alone = augmented_euler_hip(m, x[rows].contiguous(), torch.tensor(ts), TRACE_EXACT, mask)[0].cpu()
+            assert torch.equal(big[:, rows], alone), (rows, float((big[:, rows] - alone).abs().max()))
+    tail = FWD_ROWS[-1]
+    xa = torch.cat([torch.zeros((21, 3), dtype=torch.float64), x[tail].double().cpu()], 1)
+    params = tr.as_params(Ws, bs, requires_grad=False)
+    for k in range(1, 4):
+        with torch.no_grad():
+            want = rr.euler_solve(params, xa, ts[:k + 1], mask).numpy()
+        got = big[k, tail].double().numpy()
+        for c in range(3 + d):
+            err = float(np.abs(got[:, c] - want[:, c]).max() / np.abs(want[:, c]).max())
+            print(f"forward B={FWD_BIG} t={ts[k]} column {c}: {err:.2e}")
+            assert err <= BOUND, (k, c, err)

@@ -482,3 +482,30 @@ def test_all_three_routes_run_on_hip_and_resample_pairs_is_their_composition(dev
     assert torch.equal(pairs[:32, 0], x0[:32]) and torch.equal(pairs[32:, 1], x1[32:])
     with pytest.raises(NotImplementedError, match="srk"):
         _solver(fwd, bwd, 1.0, sde_solver="srk").sdeint(x0, ts)
+
+
+# ------------------------------------------------------------------------------------------- the second grid pass ----
+BIG = 16 * 4096 + 5
+PASS2_ROWS = (slice(0, 16), slice(16 * 2051, 16 * 2052), slice(BIG - 21, BIG))
+
+
+def test_second_grid_pass_of_the_pair_ode_kernel(dev):
+    """B = 16 * 4096 + 5, d = 2, hidden widths (33, 16, 24), rk4 over three output times on a non-uniform grid (a fixed-step
+    solve steps exactly its t_span): ode_small_fixed_pair runs on at most 4096 workgroups, so workgroup 0 takes tile 4096
+    after tile 0.  Rows of a tile do not interact: the first tile, a middle one and the last full tile with the 5-row tail
+    are bit-equal to the same rows solved alone, and the tail is within 1e-5 of the float64 restatement."""
+    import cnf_restate as R
+    fwd, bwd = R.make_mlp(*R.mlp_params(2, (33, 16, 24), 80), dev), R.make_mlp(*R.mlp_params(2, (33, 16, 24), 81), dev)
+    s = _solver(fwd, bwd, 1.0, ode_solver="rk4")
+    x0 = torch.randn(BIG, 2, generator=torch.Generator().manual_seed(82)).to(dev)
+    ts = torch.tensor([0.0, 0.25, 0.5, 1.0])
+    big = s.odeint(x0, ts)
+    assert s.last_path == "hip" and big.shape == (4, BIG, 2) and s.nfe == 12 and bool(torch.isfinite(big).all())
+    for rows in PASS2_ROWS:
+        alone = s.odeint(x0[rows].contiguous(), ts)
+        assert s.last_path == "hip"
+        assert torch.equal(big[:, rows], alone), (rows, float((big[:, rows] - alone).abs().max()))
+    tail = PASS2_ROWS[-1]
+    dev_ = _rel(big[:, tail].double().cpu(), _pair_f64(fwd, bwd, x0[tail], ts, "rk4"))
+    print(f"pair ode rk4 B={BIG}: tail tile vs float64 {dev_:.2e}")
+    assert dev_ <= 1e-5

@@ -392,3 +392,33 @@ def test_abi_old_entries_are_the_new_ones_at_dopri5_and_euler(dev):
                                          ptr(ws), stream_ptr()) == 0
     torch.cuda.synchronize()
     assert torch.equal(a, b) and na.value == nb.value == len(ts) - 1
+
+
+# ---------------------------------------------------------------------------------------- the second grid pass
+BIG = 16 * 4096 + 5
+PASS2_ROWS = (slice(0, 16), slice(16 * 2051, 16 * 2052), slice(BIG - 21, BIG))
+
+
+@pytest.mark.parametrize("solver", ["euler", "midpoint", "rk4"])
+def test_second_grid_pass_of_the_fused_fixed_step_sampler(dev, solver):
+    """B = 16 * 4096 + 5, d = 2, hidden widths (33, 16, 24), three output times on a non-uniform grid (a fixed-step solve
+    steps exactly its t_span: there is no refined step): ode_small_fixed<*, AUG_NONE, FIELD_MLP> is launched on at most
+    4096 workgroups, so workgroup 0 runs tile 4096 after tile 0 on the same LDS tile buffers.  Rows of a tile do not
+    interact: the first tile, a middle one and the last full tile with the 5-row tail are bit-equal to the same rows
+    solved alone, and the tail is within this file's 1e-5 of the float64 restatement."""
+    from cfm_amd import _lib
+    _lib.load().cfm_ode_set_fused(1)
+    Ws, bs = R.mlp_params(2, (33, 16, 24), seed=21)
+    x = torch.randn(BIG, 2, generator=torch.Generator().manual_seed(22))
+    ts = torch.tensor([0.0, 0.25, 0.5, 1.0])
+    node = _node(Ws, bs, solver, 1e-4, dev)
+    big = node.trajectory(x, ts).cpu()
+    assert node.last_path == "hip" and big.shape == (4, BIG, 2) and (node.n_steps, node.nfe) == (3, 3 * STAGES[solver])
+    assert bool(torch.isfinite(big).all())
+    for rows in PASS2_ROWS:
+        alone = node.trajectory(x[rows].contiguous(), ts).cpu()
+        assert node.last_path == "hip"
+        assert torch.equal(big[:, rows], alone), (solver, rows, float((big[:, rows] - alone).abs().max()))
+    tail = PASS2_ROWS[-1]
+    ref = rk.fixed_trajectory(R.mlp_field_np(Ws, bs), x[tail].numpy(), ts.numpy(), solver)
+    _close(big[:, tail].numpy(), ref, f"{solver} B={BIG} tail tile")

@@ -366,3 +366,47 @@ def test_zero_g_is_refused_before_any_launch(dev):
     assert torch.is_tensor(sdeint(sde, x0, torch.tensor(TS), dt=DT))           # without logqp sigma = 0 is an ODE
     with pytest.raises(ValueError, match="g = 0"):
         sdeint(sde, x0, torch.tensor(TS), dt=DT, logqp=True)
+
+
+# ------------------------------------------------------------------------------------------------ 8. second grid pass
+BIG = 16 * 4096 + 5
+PASS2_TS = [0.0, 0.25, 0.5, 1.0]                           # at DT = 1/8: 2 + 2 + 4 steps, three output intervals
+PASS2_ROWS = (slice(0, 16), slice(16 * 2051, 16 * 2052), slice(BIG - 21, BIG))
+PASS2_MODES = [m for m in MODES if m[2] == 0.5]             # euler and srk at a constant sigma, forward and reverse
+
+
+@pytest.mark.parametrize("name, method, sig, rev", PASS2_MODES, ids=[m[0] for m in PASS2_MODES])
+def test_second_grid_pass_keeps_the_rows_and_the_log_ratio(dev, reference, name, method, sig, rev):
+    """B = 16 * 4096 + 5, d = 2, hidden widths (33, 16, 24): more than the 4096 workgroups of a launch, so workgroup 0 runs
+    tile 4096 after tile 0 — on the `red` scratch of sm_rowsum, the wave-0 store of `logratio` and the output index of its
+    first pass.  Rows of a tile do not interact (the row sum runs over columns), so the first tile, a middle one and the
+    last full tile with the 5-row tail are bit-equal, state and log-ratio, to the same rows run alone on the same noise
+    rows; the state is the bits of the run without logqp; and the tail's log-ratio is held to the bound of the restatement
+    test (8 E32) against the float64 eager scheme."""
+    import cnf_restate as R
+    from cfm_amd.sde import FlowScoreSDE, sdeint
+    d = 2
+    v, s = R.make_mlp(*R.mlp_params(d, (33, 16, 24), 70)), R.make_mlp(*R.mlp_params(d, (33, 16, 24), 71))
+    _, e32 = reference
+    g = torch.Generator().manual_seed(72)
+    x0 = torch.randn((BIG, d), generator=g)
+    xi = torch.randn((N_STEPS, 2, BIG, d) if method == "srk" else (N_STEPS, BIG, d), generator=g)
+    sde = FlowScoreSDE(copy.deepcopy(v).to(dev), copy.deepcopy(s).to(dev), sigma=_sigma(sig), reverse=rev)
+    ts = torch.tensor(PASS2_TS)
+
+    def run(x, z, logqp=True):
+        out = sdeint(sde, x.to(dev), ts, method=method, dt=DT, noise=z.contiguous().to(dev), fused=True, logqp=logqp)
+        return (out[0].cpu(), out[1].cpu()) if logqp else out.cpu()
+    ys, lr = run(x0, xi)
+    assert sde.last_path == "hip" and ys.shape == (4, BIG, d) and lr.shape == (3, BIG)
+    assert bool(torch.isfinite(lr).all()) and bool((lr > 0).all())
+    assert torch.equal(ys, run(x0, xi, logqp=False))
+    for rows in PASS2_ROWS:
+        ya, la = run(x0[rows], xi[..., rows, :])
+        assert torch.equal(ys[:, rows], ya), rows
+        assert torch.equal(lr[:, rows], la), (rows, float((lr[:, rows] - la).abs().max()))
+    tail = PASS2_ROWS[-1]
+    ys64, lr64 = _eager(v, s, _sigma(sig), rev, method, x0[tail], xi[..., tail, :], torch.float64, ts=PASS2_TS)
+    err = _err(lr[:, tail], lr64)
+    print(f"[sde logqp] B={BIG} {name}: tail tile {err:.3e} (bound {8 * e32:.3e}; state {_err(ys[:, tail], ys64):.3e})")
+    assert err <= 8 * e32, (name, err, 8 * e32)

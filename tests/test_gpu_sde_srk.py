@@ -316,3 +316,41 @@ def test_c_entry_rejects_what_the_kernel_is_not_built_for(dev):
         assert call(**kw) == EINVAL, kw
     assert call(B=0) == 0 and call(n_steps=0) == 0
     torch.cuda.synchronize()
+
+
+# ---- the second grid pass: more than 4096 tiles, so workgroup 0 runs tile 4096 after tile 0 ----
+BIG = 16 * 4096 + 5
+PASS2_TS, PASS2_DT = [0.0, 0.25, 0.5, 1.0], 0.25          # 1 + 1 + 2 steps: the last output is reached through a refined step
+# the first tile, a middle one, and the last full tile with the 5-row tail behind it (workgroups 4095 and 0 again)
+PASS2_ROWS = (slice(0, 16), slice(16 * 2051, 16 * 2052), slice(BIG - 21, BIG))
+
+
+@pytest.mark.parametrize("reverse", [False, True], ids=["forward", "reverse"])
+@pytest.mark.parametrize("method", ["euler", "srk"])
+def test_second_grid_pass_on_a_given_noise_tensor(dev, method, reverse):
+    """B = 16 * 4096 + 5, d = 2, hidden widths (33, 16, 24): small_grid caps the launch at 4096 workgroups, so the row loop of
+    ode_small_em / ode_small_srk takes a second pass, on the LDS tile buffers and the output index of the first.  Rows of
+    a tile do not interact in these kernels, so the rows of PASS2_ROWS are bit-equal to the same rows run alone as a
+    small batch on the same noise rows; and the tail tile is held to this file's bound against the float64 restatement."""
+    from cfm_amd.sde import FlowScoreSDE, sdeint
+    d, srk = 2, method == "srk"
+    v, s = _two_mixed_fields(dev, d, (33, 16, 24), seed=60)
+    g = torch.Generator().manual_seed(61)
+    x0 = torch.randn((BIG, d), generator=g)
+    n = _n_steps(PASS2_TS, PASS2_DT)
+    assert n == 4
+    xi = torch.randn((n, 2, BIG, d) if srk else (n, BIG, d), generator=g)
+    sde = FlowScoreSDE(v, s, sigma=0.7, reverse=reverse)
+    run = lambda x, z: sdeint(sde, x.to(dev), torch.tensor(PASS2_TS), method=method, dt=PASS2_DT, noise=z.contiguous().to(dev),
+                              fused=True).cpu()
+    big = run(x0, xi)
+    assert sde.last_path == "hip" and big.shape == (4, BIG, d) and bool(torch.isfinite(big).all())
+    for rows in PASS2_ROWS:
+        alone = run(x0[rows], xi[..., rows, :])
+        assert torch.equal(big[:, rows], alone), (rows, float((big[:, rows] - alone).abs().max()))
+    tail = PASS2_ROWS[-1]
+    ref = (_restatement if srk else _em_restatement)(v, s, x0[tail].numpy(), PASS2_TS, PASS2_DT, 0.7, xi[..., tail, :].numpy(),
+                                                     reverse=reverse)
+    err = np.abs(big[:, tail].numpy() - ref).max() / np.abs(ref).max()
+    print(f"{method} reverse={reverse} B={BIG}: tail tile {err:.3e} of max|ref|")
+    assert err <= 2e-5, err
