@@ -1,5 +1,6 @@
 // cnf_reg.h — the C entry of the regularised CNF solve (RNODE / TrajectoryNet) (included by ode.hip: the CFM_OP_ODE
-// workspace lives there; the envelope checks cnf_check and cnf_reg_check come from ode_envelope.h).  The forward kernel is a
+// workspace and the prelude of the one-launch fixed-step entries, ode_fixed_onelaunch, live there; the envelope checks
+// cnf_check and cnf_reg_check come from ode_envelope.h).  The forward kernel is a
 // translation unit of its own, cnf_reg.hip, which says what the solve computes: the small-field kernels of ode.hip are
 // compiled exactly as they were before it existed.  The gradient entry cfm_cnf_reg_euler_grad_f32 sits
 // with its kernel ode_small_euler_grad<MODE, REG> in cnf_grad.h (small_grad.hip).
@@ -14,19 +15,12 @@ extern "C" int cfm_ode_euler_cnf_reg_mlp_f32(const float* const* W, const float*
                                              const float* x0, int B, const float* t_span, int n_t, int mode,
                                              const float* eps, int reg_mask, float* traj, float* jac_sq, int* nfe, void* ws,
                                              void* stream) {
-    int d; SmArgs A;
-    if (!x0 || !t_span || !traj || !ws || n_t < 1 || cnf_reg_check(mode, reg_mask, jac_sq)) return CFM_EINVAL;
-    int rc = cnf_check(W, b, dims, n_layers, B, mode, eps, &d, &A, CFM_TRACE_NONE);
-    if (rc) return rc;
-    if (!fx_monotone(t_span, n_t)) return CFM_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    const int D = d + cg_aug_cols(mode, reg_mask);              // [(l), (L1), (L2), (e), (f), y]
-    OdeWs w = ode_carve(ws, B, maxwidth(dims, n_layers), D);       // workspace of CFM_OP_ODE at D
-    const size_t n = (size_t)B * D;
-    if ((size_t)n_t > 3 * n) return CFM_EINVAL;                    // t_span copy: w.x .. w.xt
-    rc = cfm_hip(hipMemcpyAsync(traj, x0, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (rc) return rc;
-    if (nfe) *nfe = n_t - 1;
-    if (n_t < 2) return 0;
-    return cfm_cnf_reg_solve_internal(&A, B, d, t_span, n_t, traj, w.x, eps, jac_sq, mode, reg_mask, s);
+    SmArgs A;
+    if (cnf_reg_check(mode, reg_mask, jac_sq)) return CFM_EINVAL;
+    // Euler: one evaluation per step; the state is [(l), (L1), (L2), (e), (f), y]
+    return ode_fixed_onelaunch(x0, B, t_span, n_t, traj, nfe, 1, cg_aug_cols(mode, reg_mask), dims, n_layers, ws, stream,
+        [&](int* d) { return cnf_check(W, b, dims, n_layers, B, mode, eps, d, &A, CFM_TRACE_NONE); },
+        [&](int d, float* tspan_dev, hipStream_t s) {
+            return cfm_cnf_reg_solve_internal(&A, B, d, t_span, n_t, traj, tspan_dev, eps, jac_sq, mode, reg_mask, s);
+        });
 }

@@ -14,6 +14,9 @@
 //           end.  Stage combinations and the scaled error norm are fused
 //           elementwise kernels; the scalar step controller runs on the host in
 //           fp32 (one 8-byte read-back per step attempt).
+//
+// In dependency order, nothing declared ahead of its definition: elementwise kernels and the workspace, the tile
+// kernels, their launch helpers, the host drivers, the C entries.
 #include "cfm_common.h"
 #include "small_field.h"
 #include "grad_field.h"
@@ -22,6 +25,7 @@
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
+#include <atomic>
 #include <mutex>
 
 int cfm_mlp_forward_impl(const float* x, const float* t, float tval, int has_t, int t_per_row,
@@ -106,6 +110,11 @@ __global__ void ode_controller(const double* __restrict__ e2, double n, float* _
     out[1] = ode_step_factor(ratio);
 }
 
+// k <- 0.5f * (k - kb): the stage derivative of the pair from the two nets' outputs (layer driver)
+__global__ __launch_bounds__(256) void ode_half_diff(size_t n, float* __restrict__ k, const float* __restrict__ kb) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) k[i] = 0.5f * (k[i] - kb[i]);
+}
+
 static inline int ode_blocks(size_t n) {
     size_t b = (n + 255) / 256;
     return (int)(b < 2048 ? (b ? b : 1) : 2048);
@@ -153,313 +162,23 @@ static int check_mlp(const int* dims, int n_layers, int* d_out) {
     return 0;
 }
 
-static int g_ode_fused = -1;     // -1: from the environment (CFM_ODE_FUSED=0 disables), else 0 / 1
-extern "C" void cfm_ode_set_fused(int on) { g_ode_fused = on ? 1 : 0; }
+// The fused-path switch.  -1: not read yet (CFM_ODE_FUSED=0 in the environment disables), else 0 / 1.  Entries run on
+// several host threads at once: relaxed accesses, and the first readers all derive the same value from the environment.
+static std::atomic<int> g_ode_fused{-1};
+extern "C" void cfm_ode_set_fused(int on) { g_ode_fused.store(on ? 1 : 0, std::memory_order_relaxed); }
 extern "C" int cfm_ode_fused_internal() {       // not exported: small_grad.hip's entries read the switch through it
-    if (g_ode_fused < 0) { const char* e = getenv("CFM_ODE_FUSED"); g_ode_fused = (e && e[0] == '0') ? 0 : 1; }
-    return g_ode_fused;
-}
-
-static int ode_fixed_small(int scheme, const float* const* W, const float* const* b, const int* dims, int B, int d,
-                           const float* t_span, int n_t, float* traj, float* tspan_dev, hipStream_t s);
-
-extern "C" int cfm_ode_fixed_mlp_f32(const float* const* W, const float* const* b, const int* dims,
-                                     int n_layers, const float* x0, int B, const float* t_span,
-                                     int n_t, int scheme, float* traj, int* nfe, void* ws, void* stream) {
-    int d;
-    if (!W || !b || !x0 || !t_span || !traj || !ws || B <= 0 || n_t < 1 || !fx_known(scheme)) return CFM_EINVAL;
-    int rc = check_mlp(dims, n_layers, &d);
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    const int width = maxwidth(dims, n_layers);
-    OdeWs w = ode_carve(ws, B, width, d);
-    const size_t n = (size_t)B * d;
-    const int ns = fx_stages_host(scheme);
-    rc = cfm_hip(hipMemcpyAsync(traj, x0, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (rc) return rc;
-    // small vector fields: rows are independent and the steps are fixed, so ONE launch integrates the
-    // whole t_span (a workgroup walks its 64-row tile through every step, weights resident in LDS)
-    if (cfm_ode_fused_internal() && small_envelope(dims, n_layers, nullptr) == 0 && d + 1 <= SM_W && n >= (size_t)n_t && n_t >= 2) {
-        rc = ode_fixed_small(scheme, W, b, dims, B, d, t_span, n_t, traj, w.xt, s);
-        if (nfe) *nfe = ns * (n_t - 1);
-        return rc;
+    int v = g_ode_fused.load(std::memory_order_relaxed);
+    if (v < 0) {
+        const char* e = getenv("CFM_ODE_FUSED");
+        const int env = (e && e[0] == '0') ? 0 : 1;
+        if (g_ode_fused.compare_exchange_strong(v, env, std::memory_order_relaxed)) v = env;   // (else v: what a setter stored)
     }
-    int evals = 0;
-    for (int k = 0; k + 1 < n_t; ++k) {
-        const float t = t_span[k], dt = t_span[k + 1] - t_span[k];
-        const float* xk = traj + (size_t)k * n;
-        for (int sg = 0; sg < ns; ++sg) {
-            const float* yin = xk;
-            float tsg = t;
-            if (sg > 0) {
-                Stages st{}; st.n = sg;
-                for (int q = 0; q < 7; ++q) { st.k[q] = w.k[q < sg ? q : 0]; st.c[q] = q < sg ? (float)fx_a_host(scheme, sg - 1, q) : 0.f; }
-                hipLaunchKernelGGL(ode_combine, dim3(ode_blocks(n)), dim3(256), 0, s, n, xk, dt, st, w.xt, (float*)nullptr);
-                yin = w.xt;
-                tsg = t + (float)fx_c_host(scheme, sg - 1) * dt;
-            }
-            rc = cfm_mlp_forward_impl(yin, nullptr, tsg, 1, 0, W, b, dims, n_layers, B, w.k[sg], w.act, s);
-            if (rc) return rc;
-            ++evals;
-        }
-        Stages st{}; st.n = ns;
-        for (int q = 0; q < 7; ++q) { st.k[q] = w.k[q < ns ? q : 0]; st.c[q] = q < ns ? (float)fx_b_host(scheme, q) : 0.f; }
-        hipLaunchKernelGGL(ode_combine, dim3(ode_blocks(n)), dim3(256), 0, s, n, xk, dt, st,
-                           traj + (size_t)(k + 1) * n, (float*)nullptr);
-    }
-    if (nfe) *nfe = evals;
-    return cfm_status();
+    return v;
 }
 
-extern "C" int cfm_ode_euler_mlp_f32(const float* const* W, const float* const* b, const int* dims,
-                                     int n_layers, const float* x0, int B, const float* t_span,
-                                     int n_t, float* traj, int* nfe, void* ws, void* stream) {
-    return cfm_ode_fixed_mlp_f32(W, b, dims, n_layers, x0, B, t_span, n_t, CFM_ODE_EULER, traj, nfe, ws, stream);
-}
-
-// Read-back buffer of the adaptive host drivers (pinned host memory, 64 bytes): one per HOST THREAD, as the assignment
-// driver's poll buffer (assign_driver.h, AsgThread) — two threads in adaptive solves on their own streams read their own
-// norms and controller words, never each other's.  Allocated by the thread's first read and kept for its lifetime.
-static thread_local double* g_ode_pinned = nullptr;
-
-static int read_red(hipStream_t s, const double* dev, int count, double* host) {
-    if (count < 1 || count > 8) return CFM_EINVAL;
-    double* pinned = g_ode_pinned;
-    if (!pinned) {
-        int rc = cfm_hip(hipHostMalloc((void**)&pinned, 64, hipHostMallocDefault));
-        if (rc) return rc;
-        g_ode_pinned = pinned;
-    }
-    int rc = cfm_hip(hipMemcpyAsync(pinned, dev, sizeof(double) * count, hipMemcpyDeviceToHost, s));
-    if (rc) return rc;
-    rc = cfm_hip(hipStreamSynchronize(s));
-    if (rc) return rc;
-    for (int i = 0; i < count; ++i) host[i] = pinned[i];
-    return 0;
-}
-
+// ---- tile kernels: a whole solve (adaptive, fixed-step, pair) or one evaluation of [v, div] in one launch ------------
 // OdeStepRec (ode_envelope.h): the record of an accepted step that the recording solve keeps
 struct OdeRec { OdeStepRec* log; float* ysteps; int max_steps; };   // log [max_steps], ysteps [max_steps, B, d]: device
-
-template <int TAB, int MODE, int FIELD, bool REC = false>
-static int ode_dopri5_small(const float* const* W, const float* const* b, const int* dims, int B, int d,
-                            const float* t_span, int n_t, float tsign, const float* eps, float atol, float rtol,
-                            float* traj, int* n_steps, int* nfe, float* xbuf, float* kbuf, float* tspan_dev,
-                            void* state_dev, char* sync_dev, float t0, float dt0, int evals0, hipStream_t s,
-                            OdeRec rec = OdeRec{nullptr, nullptr, 0}, int* n_accepted = nullptr);
-
-// the tableau selector (validated by the entry points) picks the instantiation
-template <int MODE, int FIELD = FIELD_MLP, class... Args>
-static int ode_adaptive_small(int tab, Args... args) {
-    return tab == CFM_ODE_TSIT5 ? ode_dopri5_small<CFM_ODE_TSIT5, MODE, FIELD>(args...)
-                                : ode_dopri5_small<CFM_ODE_DOPRI5, MODE, FIELD>(args...);
-}
-// the recording variant: the plain MLP field only
-template <class... Args>
-static int ode_adaptive_small_rec(int tab, Args... args) {
-    return tab == CFM_ODE_TSIT5 ? ode_dopri5_small<CFM_ODE_TSIT5, AUG_NONE, FIELD_MLP, true>(args...)
-                                : ode_dopri5_small<CFM_ODE_DOPRI5, AUG_NONE, FIELD_MLP, true>(args...);
-}
-
-// Time direction of a t_span (torchdyn's rule, SURVEY.md A.4): a strictly decreasing grid is integrated as
-// g(s, y) = -f(-s, y) on s = -t_span.  ts receives the (increasing) grid the solver steps on; the returned sign
-// goes into the field's time argument (f is evaluated at sign * s) and into every stage / init-step coefficient
-// (y = x + (sign * dt) * sum a k), so the field arithmetic never changes and the solve is, bit for bit, the
-// forward solve of the field whose time column and last layer are negated.  0: not strictly monotone.
-static float ode_direction(const float* t_span, int n_t, float* ts) {
-    int up = 1, down = 1;
-    for (int k = 0; k + 1 < n_t; ++k) {
-        if (!(t_span[k + 1] > t_span[k])) up = 0;
-        if (!(t_span[k + 1] < t_span[k])) down = 0;
-    }
-    if (!up && !down) return 0.f;
-    const float sg = up ? 1.f : -1.f;
-    for (int k = 0; k < n_t; ++k) ts[k] = sg * t_span[k];
-    return sg;
-}
-
-// Hairer II.4 initial step of the host drivers (d0, d1, d2 as RMS norms over n elements).  f(t, x, k) evaluates
-// the field at solver time t (s-space: the caller applies the time sign); hsign = the time sign.
-template <class F>
-static int ode_init_step(F&& f, size_t n, float t, float hsign, float atol, float rtol, const OdeWs& w,
-                         hipStream_t s, float* dt_out) {
-    const int nb = ode_blocks(n);
-    const float order = 5.f;
-    auto rms = [&](double sumsq) -> float { return (float)sqrt(sumsq / (double)n); };
-    int rc = cfm_hip(hipMemsetAsync(w.red, 0, 64, s));
-    if (rc) return rc;
-    hipLaunchKernelGGL(ode_sqnorm, dim3(nb), dim3(256), 0, s, n, w.x, (const float*)nullptr, w.x, atol, rtol, w.red + 0);
-    hipLaunchKernelGGL(ode_sqnorm, dim3(nb), dim3(256), 0, s, n, w.k[0], (const float*)nullptr, w.x, atol, rtol, w.red + 1);
-    double r2[3];
-    rc = read_red(s, w.red, 2, r2);
-    if (rc) return rc;
-    const float d0 = rms(r2[0]), d1 = rms(r2[1]);
-    const float h0 = (d0 < 1e-5f || d1 < 1e-5f) ? 1e-6f : 0.01f * d0 / d1;
-    Stages st{}; st.n = 1; st.c[0] = 1.f;
-    for (int q = 0; q < 7; ++q) st.k[q] = w.k[0];
-    hipLaunchKernelGGL(ode_combine, dim3(nb), dim3(256), 0, s, n, w.x, hsign * h0, st, w.xt, (float*)nullptr);
-    rc = f(t + h0, w.xt, w.k[1]);
-    if (rc) return rc;
-    hipLaunchKernelGGL(ode_sqnorm, dim3(nb), dim3(256), 0, s, n, w.k[1], w.k[0], w.x, atol, rtol, w.red + 2);
-    rc = read_red(s, w.red + 2, 1, r2);
-    if (rc) return rc;
-    const float d2 = rms(r2[0]) / h0;
-    float h1;
-    if (d1 <= 1e-15f && d2 <= 1e-15f) h1 = fmaxf(1e-6f, h0 * 1e-3f);
-    else h1 = powf(0.01f / fmaxf(d1, d2), 1.0f / (order + 1.f));
-    *dt_out = fminf(100.f * h0, h1);
-    return 0;
-}
-
-static int ode_dopri5_layers(int tab, const float* const* W, const float* const* b, const int* dims, int n_layers, int d,
-                             const float* x0, int B, const float* t_span, int n_t, float tsign, float atol,
-                             float rtol, float* traj, int* n_steps, int* nfe, void* ws, void* stream,
-                             const OdeRec* rec = nullptr, int* n_accepted = nullptr);
-
-extern "C" int cfm_ode_adaptive_mlp_f32(const float* const* W, const float* const* b, const int* dims,
-                                        int n_layers, const float* x0, int B, const float* t_span,
-                                        int n_t, int tableau, float atol, float rtol, float* traj, int* n_steps,
-                                        int* nfe, void* ws, void* stream) {
-    int d;
-    if (!W || !b || !x0 || !t_span || !traj || !ws || B <= 0 || n_t < 2 || !rk_adaptive_known(tableau)) return CFM_EINVAL;
-    int rc = check_mlp(dims, n_layers, &d);
-    if (rc) return rc;
-    float* ts = (float*)malloc(sizeof(float) * (size_t)n_t);   // the grid in solver time (s = sign * t)
-    if (!ts) return CFM_EINVAL;
-    const float tsign = ode_direction(t_span, n_t, ts);
-    if (tsign == 0.f) { free(ts); return CFM_EINVAL; }          // strictly monotone t_span only
-    rc = ode_dopri5_layers(tableau, W, b, dims, n_layers, d, x0, B, ts, n_t, tsign, atol, rtol, traj, n_steps, nfe, ws, stream);
-    free(ts);
-    return rc;
-}
-
-extern "C" int cfm_ode_dopri5_mlp_f32(const float* const* W, const float* const* b, const int* dims,
-                                      int n_layers, const float* x0, int B, const float* t_span,
-                                      int n_t, float atol, float rtol, float* traj, int* n_steps,
-                                      int* nfe, void* ws, void* stream) {
-    return cfm_ode_adaptive_mlp_f32(W, b, dims, n_layers, x0, B, t_span, n_t, CFM_ODE_DOPRI5, atol, rtol, traj, n_steps, nfe, ws, stream);
-}
-
-// cfm_ode_adaptive_mlp_f32 on the recording instantiation of the one-launch kernel: the same arithmetic (traj, n_steps and
-// nfe are its bits), plus the starting state and the record of every accepted step.  CFM_EINVAL wherever the plain entry
-// would leave that kernel; CFM_ENOCONV when the log filled up before the end of the grid.
-extern "C" int cfm_ode_adaptive_rec_mlp_f32(const float* const* W, const float* const* b, const int* dims,
-                                            int n_layers, const float* x0, int B, const float* t_span,
-                                            int n_t, int tableau, float atol, float rtol, float* traj, int* n_steps,
-                                            int* nfe, int max_steps, void* log, float* ysteps, int* n_accepted, void* ws,
-                                            void* stream) {
-    int d;
-    if (!W || !b || !x0 || !t_span || !traj || !ws || B <= 0 || n_t < 2 || !rk_adaptive_known(tableau)) return CFM_EINVAL;
-    if (max_steps < 1 || !log || !ysteps || !n_accepted) return CFM_EINVAL;
-    int rc = check_mlp(dims, n_layers, &d);
-    if (rc) return rc;
-    float* ts = (float*)malloc(sizeof(float) * (size_t)n_t);
-    if (!ts) return CFM_EINVAL;
-    const float tsign = ode_direction(t_span, n_t, ts);
-    if (tsign == 0.f) { free(ts); return CFM_EINVAL; }
-    const OdeRec rec{(OdeStepRec*)log, ysteps, max_steps};
-    *n_accepted = 0;
-    rc = ode_dopri5_layers(tableau, W, b, dims, n_layers, d, x0, B, ts, n_t, tsign, atol, rtol, traj, n_steps, nfe, ws, stream,
-                           &rec, n_accepted);
-    free(ts);
-    return rc;
-}
-
-static int ode_dopri5_layers(int tab, const float* const* W, const float* const* b, const int* dims, int n_layers, int d,
-                             const float* x0, int B, const float* t_span, int n_t, float tsign, float atol,
-                             float rtol, float* traj, int* n_steps, int* nfe, void* ws, void* stream,
-                             const OdeRec* rec, int* n_accepted) {
-    int rc;
-    hipStream_t s = (hipStream_t)stream;
-    const int width = maxwidth(dims, n_layers);
-    OdeWs w = ode_carve(ws, B, width, d);
-    const size_t n = (size_t)B * d;
-    // small vector fields: the whole step attempt in one kernel, controller on the device
-    const bool small = cfm_ode_fused_internal() && small_envelope(dims, n_layers, nullptr) == 0 && d + 1 <= SM_W && n >= (size_t)n_t;
-    if (rec && !small) return CFM_EINVAL;              // only the one-launch kernel records its steps
-    const int nb = ode_blocks(n);
-    int evals = 0, steps = 0;
-
-    auto f = [&](float t, const float* xin, float* kout) -> int {
-        ++evals;
-        return cfm_mlp_forward_impl(xin, nullptr, tsign * t, 1, 0, W, b, dims, n_layers, B, kout, w.act, s);
-    };
-
-    rc = cfm_hip(hipMemcpyAsync(w.x, x0, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (rc) return rc;
-    rc = cfm_hip(hipMemcpyAsync(traj, x0, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (rc) return rc;
-
-    float t = t_span[0];
-    const float T = t_span[n_t - 1];
-    rc = f(t, w.x, w.k[0]);
-    if (rc) return rc;
-
-    // ---- init_step (Hairer II.4) ----
-    float dt;
-    rc = ode_init_step(f, n, t, tsign, atol, rtol, w, s, &dt);
-    if (rc) return rc;
-
-    if (small && rec)
-        return ode_adaptive_small_rec(tab, W, b, dims, B, d, t_span, n_t, tsign, nullptr, atol, rtol, traj, n_steps, nfe, w.x,
-                                      w.k[0], w.xt, (void*)(w.red + 16), w.sync, t, dt, evals, s, *rec, n_accepted);
-    if (small)
-        return ode_adaptive_small<0>(tab, W, b, dims, B, d, t_span, n_t, tsign, nullptr, atol, rtol, traj, n_steps, nfe, w.x,
-                                   w.k[0], w.xt, (void*)(w.red + 16), w.sync, t, dt, evals, s);
-
-    int ckpt = 1;  // next t_span index to land on
-    const int max_attempts = 1000000;
-    while (t < T && steps < max_attempts) {
-        if (t + dt > T) dt = T - t;
-        float dt_old = dt; bool flag = false;
-        if (ckpt < n_t && t + dt > t_span[ckpt]) { dt_old = dt; flag = true; dt = t_span[ckpt] - t; }
-        const bool lands = (ckpt < n_t) && (flag || t + dt == t_span[ckpt]);
-        // stages k2..k6, then x_new and k7 (FSAL)
-        for (int sIdx = 0; sIdx < 6; ++sIdx) {
-            Stages st{}; st.n = sIdx + 1;
-            for (int q = 0; q < 7; ++q) { st.k[q] = w.k[q < 7 ? q : 0]; st.c[q] = q <= sIdx ? (float)rk_a_host(tab, sIdx, q) : 0.f; }
-            float* dst = (sIdx == 5) ? w.xn : w.xt;
-            hipLaunchKernelGGL(ode_combine, dim3(nb), dim3(256), 0, s, n, w.x, tsign * dt, st, dst, (float*)nullptr);
-            rc = f(t + rk_c_host(tab, sIdx) * dt, dst, w.k[sIdx + 1]);
-            if (rc) return rc;
-        }
-        {
-            Stages st{}; st.n = 7;
-            for (int q = 0; q < 7; ++q) { st.k[q] = w.k[q]; st.c[q] = (float)rk_e_host(tab, q); }
-            rc = cfm_hip(hipMemsetAsync(w.red + 4, 0, 8, s));
-            if (rc) return rc;
-            hipLaunchKernelGGL(ode_error, dim3(nb), dim3(256), 0, s, n, w.x, w.xn, dt, st, atol, rtol, w.red + 4);
-        }
-        hipLaunchKernelGGL(ode_controller, dim3(1), dim3(1), 0, s, w.red + 4, (double)n, (float*)(w.red + 6));
-        double ctl;
-        rc = read_red(s, w.red + 6, 1, &ctl);
-        if (rc) return rc;
-        ++steps;
-        float ratio, factor;
-        memcpy(&ratio, (const char*)&ctl, 4); memcpy(&factor, (const char*)&ctl + 4, 4);
-        const bool accept = ratio <= 1.f;
-        if (accept) {
-            if (lands) {
-                t = t_span[ckpt];
-                rc = cfm_hip(hipMemcpyAsync(traj + (size_t)ckpt * n, w.xn, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-                if (rc) return rc;
-                ++ckpt;
-            } else {
-                t = t + dt;
-            }
-            float* tmp = w.x; w.x = w.xn; w.xn = tmp;          // x <- x_new
-            tmp = w.k[0]; w.k[0] = w.k[6]; w.k[6] = tmp;        // k1 <- k7 (FSAL)
-        }
-        if (flag) dt = dt_old - dt;
-        dt = dt * factor;                  // (ode_step_factor on the device, see ode_controller)
-        if (!(dt > 1e-12f)) dt = 1e-12f;   // guard (documented deviation)
-    }
-    if (n_steps) *n_steps = steps;
-    if (nfe) *nfe = evals;
-    rc = cfm_hip(hipStreamSynchronize(s));
-    if (rc) return rc;
-    return (t < T) ? CFM_ENOCONV : 0;
-}
 
 struct SmState { float t, dt; int ckpt, steps, evals, par, done, pad; };
 // One persistent solve at a time per process, whatever its augmentation mode (see ode_dopri5_small)
@@ -766,90 +485,6 @@ __global__ __launch_bounds__(256) void ode_small_dopri(SmArgs A, int B, int d, S
     }
 }
 
-// Workgroups of ode_small_dopri<TAB, ., MODE, FIELD, REC> that can be resident at once (the grid rendezvous needs grid <= this);
-// -1: the query failed.  One result per device and instantiation: the grid is sized from the occupancy of the kernel launched.
-template <int TAB, int MODE, int FIELD, bool REC>
-static int ode_dopri_resident() {
-    constexpr size_t lds = small_lds_bytes(1, 2, MODE != AUG_NONE);
-    return cfm_once_per_device([] {
-        hipError_t e = hipFuncSetAttribute((const void*)ode_small_dopri<TAB, true, MODE, FIELD, REC>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-        hipError_t e2 = hipFuncSetAttribute((const void*)ode_small_dopri<TAB, false, MODE, FIELD, REC>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-        int pa = 0, pb = 0;
-        if (e == hipSuccess && e2 == hipSuccess &&
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&pa, (const void*)ode_small_dopri<TAB, true, MODE, FIELD, REC>, 256, lds) == hipSuccess &&
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&pb, (const void*)ode_small_dopri<TAB, false, MODE, FIELD, REC>, 256, lds) == hipSuccess &&
-            pa > 0 && pb > 0)
-            return cfm_device_cus() * (pa < pb ? pa : pb);
-        return -1;
-    });
-}
-
-// Rows up to which the recording solve keeps its state in registers (one 16-row tile per resident workgroup); above, x and
-// k_1 travel through the parity buffers.  For tests and measurements that must sit on either side of that limit; < 0: the
-// occupancy query failed or the tableau is unknown.
-extern "C" int cfm_ode_rec_resident_rows(int tableau) {
-    if (!rk_adaptive_known(tableau)) return CFM_EINVAL;
-    int g = tableau == CFM_ODE_TSIT5 ? ode_dopri_resident<CFM_ODE_TSIT5, AUG_NONE, FIELD_MLP, true>()
-                                     : ode_dopri_resident<CFM_ODE_DOPRI5, AUG_NONE, FIELD_MLP, true>();
-    if (g < 0) return CFM_EINVAL;
-    return SM_ROWS * (g < SM_MAXGRID ? g : SM_MAXGRID);
-}
-
-template <int TAB, int MODE, int FIELD, bool REC>
-static int ode_dopri5_small(const float* const* W, const float* const* b, const int* dims, int B, int d,
-                            const float* t_span, int n_t, float tsign, const float* eps, float atol, float rtol,
-                            float* traj, int* n_steps, int* nfe, float* xbuf, float* kbuf, float* tspan_dev,
-                            void* state_dev, char* sync_dev, float t0, float dt0, int evals0, hipStream_t s,
-                            OdeRec rec, int* n_accepted) {
-    const SmArgs A = small_args(W, b, dims);
-    constexpr size_t lds = small_lds_bytes(1, 2, MODE != AUG_NONE);
-    const int resident = ode_dopri_resident<TAB, MODE, FIELD, REC>();
-    // (the recording entry answers CFM_EINVAL only before any GPU work, as a decline its caller may act on: a query that
-    // fails here, after the first evaluations, is an error of its own)
-    if (resident < 0) return REC ? (int)hipErrorInvalidDeviceFunction : CFM_EINVAL;
-    int rc = cfm_hip(hipMemcpyAsync(tspan_dev, t_span, sizeof(float) * n_t, hipMemcpyHostToDevice, s));
-    if (rc) return rc;
-    SmState h[2];
-    memset(h, 0, sizeof(h));
-    h[0].t = t0; h[0].dt = dt0; h[0].ckpt = 1; h[0].steps = 0; h[0].evals = evals0; h[0].par = 0; h[0].done = 0;
-    rc = cfm_hip(hipMemcpyAsync(state_dev, h, sizeof(h), hipMemcpyHostToDevice, s));
-    if (rc) return rc;
-    double* partial = (double*)sync_dev;
-    unsigned long long* lines = (unsigned long long*)(sync_dev + 3 * SM_MAXGRID * 8);
-    rc = cfm_hip(hipMemsetAsync(partial, 0xFF, 3 * SM_MAXGRID * 8, s));   // every slot: negative NaN = not arrived
-    if (rc) return rc;
-    SmState* st = (SmState*)state_dev;
-    const int tiles = (B + SM_ROWS - 1) / SM_ROWS;
-    int grid = tiles < resident ? tiles : resident;
-    if (grid > SM_MAXGRID) grid = SM_MAXGRID;
-    // One persistent solve at a time per process: two of them launched from two streams could each get only part
-    // of their workgroups resident and wait for the rest forever (the bounded wait would turn that into
-    // CFM_ETIMEOUT after 4 s).  The call is synchronous anyway: the lock is held until the solve has finished.
-    std::lock_guard<std::mutex> persistent_lock(g_persistent_mu);
-    if (tiles <= grid)
-        hipLaunchKernelGGL((ode_small_dopri<TAB, true, MODE, FIELD, REC>), dim3(grid), dim3(256), lds, s, A, B, d, st, xbuf, kbuf, tspan_dev, n_t,
-                           atol, rtol, traj, partial, lines, 1000000, tsign, eps, rec);
-    else
-        hipLaunchKernelGGL((ode_small_dopri<TAB, false, MODE, FIELD, REC>), dim3(grid), dim3(256), lds, s, A, B, d, st, xbuf, kbuf, tspan_dev, n_t,
-                           atol, rtol, traj, partial, lines, 1000000, tsign, eps, rec);
-    rc = cfm_status();
-    if (rc) return rc;
-    SmState cur, cnt;
-    rc = cfm_hip(hipMemcpyAsync(&cur, st + 1, sizeof(SmState), hipMemcpyDeviceToHost, s));
-    if (rc) return rc;
-    if (REC) {
-        rc = cfm_hip(hipMemcpyAsync(&cnt, st + 2, sizeof(SmState), hipMemcpyDeviceToHost, s));
-        if (rc) return rc;
-    }
-    rc = cfm_hip(hipStreamSynchronize(s));
-    if (rc) return rc;
-    if (REC && n_accepted) *n_accepted = cnt.steps;
-    if (n_steps) *n_steps = cur.steps;
-    if (nfe) *nfe = cur.evals;
-    if (cur.pad == 2) return CFM_ETIMEOUT;
-    return cur.done && cur.pad == 0 ? 0 : CFM_ENOCONV;     // (pad 1: max_attempts, pad 3: the step log is full)
-}
-
 #include "sde_small.h"
 
 // Fixed-step explicit Runge-Kutta (euler / midpoint / rk4: fx_stages<SCHEME>() = 1, 2 or 4 stages) for the same small
@@ -945,33 +580,6 @@ __global__ __launch_bounds__(256) void ode_small_fixed(SmArgs A, int B, int d, c
     }
 }
 
-template <int SCHEME, int MODE, int FIELD>
-static int ode_fixed_small_t(const float* const* W, const float* const* b, const int* dims, int B, int d,
-                             const float* t_span, int n_t, float* traj, float* tspan_dev, const float* eps,
-                             hipStream_t s) {
-    const int grid = small_grid<ode_small_fixed<SCHEME, MODE, FIELD>, 128 * 1024>(B);
-    if (grid < 0) return CFM_EINVAL;
-    int rc = cfm_hip(hipMemcpyAsync(tspan_dev, t_span, sizeof(float) * n_t, hipMemcpyHostToDevice, s));
-    if (rc) return rc;
-    hipLaunchKernelGGL((ode_small_fixed<SCHEME, MODE, FIELD>), dim3(grid), dim3(256), small_lds_bytes(1, 2, MODE != AUG_NONE), s,
-                       small_args(W, b, dims), B, d, tspan_dev, n_t, traj, eps);
-    return cfm_status();
-}
-
-// the scheme selector (validated by the entry points) picks the instantiation
-template <int MODE, int FIELD = FIELD_MLP>
-static int ode_fixed_small_m(int scheme, const float* const* W, const float* const* b, const int* dims, int B, int d,
-                             const float* t_span, int n_t, float* traj, float* tspan_dev, const float* eps, hipStream_t s) {
-    if (scheme == CFM_ODE_RK4) return ode_fixed_small_t<CFM_ODE_RK4, MODE, FIELD>(W, b, dims, B, d, t_span, n_t, traj, tspan_dev, eps, s);
-    if (scheme == CFM_ODE_MIDPOINT) return ode_fixed_small_t<CFM_ODE_MIDPOINT, MODE, FIELD>(W, b, dims, B, d, t_span, n_t, traj, tspan_dev, eps, s);
-    return ode_fixed_small_t<CFM_ODE_EULER, MODE, FIELD>(W, b, dims, B, d, t_span, n_t, traj, tspan_dev, eps, s);
-}
-
-static int ode_fixed_small(int scheme, const float* const* W, const float* const* b, const int* dims, int B, int d,
-                           const float* t_span, int n_t, float* traj, float* tspan_dev, hipStream_t s) {
-    return ode_fixed_small_m<AUG_NONE>(scheme, W, b, dims, B, d, t_span, n_t, traj, tspan_dev, nullptr, s);
-}
-
 // ---- DSBM: the probability-flow ODE of a forward and a backward drift net, dx/dt = (f(t, x) - b(t, x)) / 2 ----------
 // runner/src/models/components/solver.py:259-263 (DSBMFlowSolver.forward_ode_drift).  ode_small_fixed with two fields: both
 // nets' weights in LDS in the layout of the SDE kernels (sde_small.h: small_lds_bytes(2, 2, false)), every stage derivative
@@ -1041,77 +649,6 @@ __global__ __launch_bounds__(256) void ode_small_fixed_pair(SmArgs F, SmArgs S, 
     }
 }
 
-template <int SCHEME>
-static int ode_fixed_pair_small_t(const SmArgs& F, const SmArgs& S, int B, int d, const float* t_span, int n_t, float* traj,
-                                  float* tspan_dev, hipStream_t s) {
-    const int grid = small_grid<ode_small_fixed_pair<SCHEME>, 160 * 1024>(B);
-    if (grid < 0) return CFM_EINVAL;
-    int rc = cfm_hip(hipMemcpyAsync(tspan_dev, t_span, sizeof(float) * n_t, hipMemcpyHostToDevice, s));
-    if (rc) return rc;
-    hipLaunchKernelGGL((ode_small_fixed_pair<SCHEME>), dim3(grid), dim3(256), small_lds_bytes(2, 2, false), s, F, S, B, d,
-                       tspan_dev, n_t, traj);
-    return cfm_status();
-}
-
-// k <- 0.5f * (k - kb): the stage derivative of the pair from the two nets' outputs (layer driver)
-__global__ __launch_bounds__(256) void ode_half_diff(size_t n, float* __restrict__ k, const float* __restrict__ kb) {
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) k[i] = 0.5f * (k[i] - kb[i]);
-}
-
-extern "C" int cfm_ode_fixed_pair_mlp_f32(const float* const* Wf, const float* const* bf, const float* const* Wb,
-                                          const float* const* bb, const int* dims, int n_layers, const float* x0, int B,
-                                          const float* t_span, int n_t, int scheme, float* traj, int* nfe, void* ws,
-                                          void* stream) {
-    int d;
-    if (!Wf || !bf || !Wb || !bb || !x0 || !t_span || !traj || !ws || B <= 0 || n_t < 1 || !fx_known(scheme)) return CFM_EINVAL;
-    int rc = check_mlp(dims, n_layers, &d);
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    const int width = maxwidth(dims, n_layers);
-    OdeWs w = ode_carve(ws, B, width, d);
-    const size_t n = (size_t)B * d;
-    const int ns = fx_stages_host(scheme);
-    rc = cfm_hip(hipMemcpyAsync(traj, x0, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (rc) return rc;
-    if (cfm_ode_fused_internal() && small_envelope(dims, n_layers, nullptr) == 0 && d + 1 <= SM_W && n >= (size_t)n_t && n_t >= 2) {
-        const SmArgs F = small_args(Wf, bf, dims), S = small_args(Wb, bb, dims);
-        if (scheme == CFM_ODE_RK4) rc = ode_fixed_pair_small_t<CFM_ODE_RK4>(F, S, B, d, t_span, n_t, traj, w.xt, s);
-        else if (scheme == CFM_ODE_MIDPOINT) rc = ode_fixed_pair_small_t<CFM_ODE_MIDPOINT>(F, S, B, d, t_span, n_t, traj, w.xt, s);
-        else rc = ode_fixed_pair_small_t<CFM_ODE_EULER>(F, S, B, d, t_span, n_t, traj, w.xt, s);
-        if (nfe) *nfe = ns * (n_t - 1);
-        return rc;
-    }
-    // the layer driver of cfm_ode_fixed_mlp_f32 with two forward passes and the halved difference per stage
-    int evals = 0;
-    for (int k = 0; k + 1 < n_t; ++k) {
-        const float t = t_span[k], dt = t_span[k + 1] - t_span[k];
-        const float* xk = traj + (size_t)k * n;
-        for (int sg = 0; sg < ns; ++sg) {
-            const float* yin = xk;
-            float tsg = t;
-            if (sg > 0) {
-                Stages st{}; st.n = sg;
-                for (int q = 0; q < 7; ++q) { st.k[q] = w.k[q < sg ? q : 0]; st.c[q] = q < sg ? (float)fx_a_host(scheme, sg - 1, q) : 0.f; }
-                hipLaunchKernelGGL(ode_combine, dim3(ode_blocks(n)), dim3(256), 0, s, n, xk, dt, st, w.xt, (float*)nullptr);
-                yin = w.xt;
-                tsg = t + (float)fx_c_host(scheme, sg - 1) * dt;
-            }
-            rc = cfm_mlp_forward_impl(yin, nullptr, tsg, 1, 0, Wf, bf, dims, n_layers, B, w.k[sg], w.act, s);
-            if (rc) return rc;
-            rc = cfm_mlp_forward_impl(yin, nullptr, tsg, 1, 0, Wb, bb, dims, n_layers, B, w.x, w.act, s);
-            if (rc) return rc;
-            hipLaunchKernelGGL(ode_half_diff, dim3(ode_blocks(n)), dim3(256), 0, s, n, w.k[sg], w.x);
-            ++evals;
-        }
-        Stages st{}; st.n = ns;
-        for (int q = 0; q < 7; ++q) { st.k[q] = w.k[q < ns ? q : 0]; st.c[q] = q < ns ? (float)fx_b_host(scheme, q) : 0.f; }
-        hipLaunchKernelGGL(ode_combine, dim3(ode_blocks(n)), dim3(256), 0, s, n, xk, dt, st,
-                           traj + (size_t)(k + 1) * n, (float*)nullptr);
-    }
-    if (nfe) *nfe = evals;
-    return cfm_status();
-}
-
 // ---- CNF: one evaluation of [v, div] (the tile kernel of the augmented solves, once) --------------------------
 // x: rows of stride ldx (d values each); v: rows of stride ldv; div[row * lddiv] = dsign * div.
 // FIELD_GRAD: v = grad_x s and div = its Laplacian (AUG_EXACT), or v alone (AUG_NONE: div is not touched).
@@ -1153,6 +690,126 @@ __global__ __launch_bounds__(256) void ode_small_div(SmArgs A, int B, int d, con
     }
 }
 
+// ---- launch helpers of the tile kernels ---------------------------------------------------------------------------
+// Workgroups of ode_small_dopri<TAB, ., MODE, FIELD, REC> that can be resident at once (the grid rendezvous needs grid <= this);
+// -1: the query failed.  One result per device and instantiation: the grid is sized from the occupancy of the kernel launched.
+template <int TAB, int MODE, int FIELD, bool REC>
+static int ode_dopri_resident() {
+    constexpr size_t lds = small_lds_bytes(1, 2, MODE != AUG_NONE);
+    return cfm_once_per_device([] {
+        hipError_t e = hipFuncSetAttribute((const void*)ode_small_dopri<TAB, true, MODE, FIELD, REC>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+        hipError_t e2 = hipFuncSetAttribute((const void*)ode_small_dopri<TAB, false, MODE, FIELD, REC>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+        int pa = 0, pb = 0;
+        if (e == hipSuccess && e2 == hipSuccess &&
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&pa, (const void*)ode_small_dopri<TAB, true, MODE, FIELD, REC>, 256, lds) == hipSuccess &&
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&pb, (const void*)ode_small_dopri<TAB, false, MODE, FIELD, REC>, 256, lds) == hipSuccess &&
+            pa > 0 && pb > 0)
+            return cfm_device_cus() * (pa < pb ? pa : pb);
+        return -1;
+    });
+}
+
+template <int TAB, int MODE, int FIELD, bool REC = false>
+static int ode_dopri5_small(const float* const* W, const float* const* b, const int* dims, int B, int d,
+                            const float* t_span, int n_t, float tsign, const float* eps, float atol, float rtol,
+                            float* traj, int* n_steps, int* nfe, float* xbuf, float* kbuf, float* tspan_dev,
+                            void* state_dev, char* sync_dev, float t0, float dt0, int evals0, hipStream_t s,
+                            OdeRec rec = OdeRec{nullptr, nullptr, 0}, int* n_accepted = nullptr) {
+    const SmArgs A = small_args(W, b, dims);
+    constexpr size_t lds = small_lds_bytes(1, 2, MODE != AUG_NONE);
+    const int resident = ode_dopri_resident<TAB, MODE, FIELD, REC>();
+    // (the recording entry answers CFM_EINVAL only before any GPU work, as a decline its caller may act on: a query that
+    // fails here, after the first evaluations, is an error of its own)
+    if (resident < 0) return REC ? (int)hipErrorInvalidDeviceFunction : CFM_EINVAL;
+    int rc = cfm_hip(hipMemcpyAsync(tspan_dev, t_span, sizeof(float) * n_t, hipMemcpyHostToDevice, s));
+    if (rc) return rc;
+    SmState h[2];
+    memset(h, 0, sizeof(h));
+    h[0].t = t0; h[0].dt = dt0; h[0].ckpt = 1; h[0].steps = 0; h[0].evals = evals0; h[0].par = 0; h[0].done = 0;
+    rc = cfm_hip(hipMemcpyAsync(state_dev, h, sizeof(h), hipMemcpyHostToDevice, s));
+    if (rc) return rc;
+    double* partial = (double*)sync_dev;
+    unsigned long long* lines = (unsigned long long*)(sync_dev + 3 * SM_MAXGRID * 8);
+    rc = cfm_hip(hipMemsetAsync(partial, 0xFF, 3 * SM_MAXGRID * 8, s));   // every slot: negative NaN = not arrived
+    if (rc) return rc;
+    SmState* st = (SmState*)state_dev;
+    const int tiles = (B + SM_ROWS - 1) / SM_ROWS;
+    int grid = tiles < resident ? tiles : resident;
+    if (grid > SM_MAXGRID) grid = SM_MAXGRID;
+    // One persistent solve at a time per process: two of them launched from two streams could each get only part
+    // of their workgroups resident and wait for the rest forever (the bounded wait would turn that into
+    // CFM_ETIMEOUT after 4 s).  The call is synchronous anyway: the lock is held until the solve has finished.
+    std::lock_guard<std::mutex> persistent_lock(g_persistent_mu);
+    if (tiles <= grid)
+        hipLaunchKernelGGL((ode_small_dopri<TAB, true, MODE, FIELD, REC>), dim3(grid), dim3(256), lds, s, A, B, d, st, xbuf, kbuf, tspan_dev, n_t,
+                           atol, rtol, traj, partial, lines, 1000000, tsign, eps, rec);
+    else
+        hipLaunchKernelGGL((ode_small_dopri<TAB, false, MODE, FIELD, REC>), dim3(grid), dim3(256), lds, s, A, B, d, st, xbuf, kbuf, tspan_dev, n_t,
+                           atol, rtol, traj, partial, lines, 1000000, tsign, eps, rec);
+    rc = cfm_status();
+    if (rc) return rc;
+    SmState cur, cnt;
+    rc = cfm_hip(hipMemcpyAsync(&cur, st + 1, sizeof(SmState), hipMemcpyDeviceToHost, s));
+    if (rc) return rc;
+    if (REC) {
+        rc = cfm_hip(hipMemcpyAsync(&cnt, st + 2, sizeof(SmState), hipMemcpyDeviceToHost, s));
+        if (rc) return rc;
+    }
+    rc = cfm_hip(hipStreamSynchronize(s));
+    if (rc) return rc;
+    if (REC && n_accepted) *n_accepted = cnt.steps;
+    if (n_steps) *n_steps = cur.steps;
+    if (nfe) *nfe = cur.evals;
+    if (cur.pad == 2) return CFM_ETIMEOUT;
+    return cur.done && cur.pad == 0 ? 0 : CFM_ENOCONV;     // (pad 1: max_attempts, pad 3: the step log is full)
+}
+
+// the tableau selector (validated by the entry points) picks the instantiation (REC: the plain MLP field only)
+template <int MODE, int FIELD = FIELD_MLP, bool REC = false, class... Args>
+static int ode_adaptive_small(int tab, Args... args) {
+    return tab == CFM_ODE_TSIT5 ? ode_dopri5_small<CFM_ODE_TSIT5, MODE, FIELD, REC>(args...)
+                                : ode_dopri5_small<CFM_ODE_DOPRI5, MODE, FIELD, REC>(args...);
+}
+
+template <int SCHEME, int MODE, int FIELD>
+static int ode_fixed_small_t(const float* const* W, const float* const* b, const int* dims, int B, int d,
+                             const float* t_span, int n_t, float* traj, float* tspan_dev, const float* eps,
+                             hipStream_t s) {
+    const int grid = small_grid<ode_small_fixed<SCHEME, MODE, FIELD>, 128 * 1024>(B);
+    if (grid < 0) return CFM_EINVAL;
+    int rc = cfm_hip(hipMemcpyAsync(tspan_dev, t_span, sizeof(float) * n_t, hipMemcpyHostToDevice, s));
+    if (rc) return rc;
+    hipLaunchKernelGGL((ode_small_fixed<SCHEME, MODE, FIELD>), dim3(grid), dim3(256), small_lds_bytes(1, 2, MODE != AUG_NONE), s,
+                       small_args(W, b, dims), B, d, tspan_dev, n_t, traj, eps);
+    return cfm_status();
+}
+
+// the scheme selector (validated by the entry points) picks the instantiation
+template <int MODE, int FIELD = FIELD_MLP>
+static int ode_fixed_small_m(int scheme, const float* const* W, const float* const* b, const int* dims, int B, int d,
+                             const float* t_span, int n_t, float* traj, float* tspan_dev, const float* eps, hipStream_t s) {
+    if (scheme == CFM_ODE_RK4) return ode_fixed_small_t<CFM_ODE_RK4, MODE, FIELD>(W, b, dims, B, d, t_span, n_t, traj, tspan_dev, eps, s);
+    if (scheme == CFM_ODE_MIDPOINT) return ode_fixed_small_t<CFM_ODE_MIDPOINT, MODE, FIELD>(W, b, dims, B, d, t_span, n_t, traj, tspan_dev, eps, s);
+    return ode_fixed_small_t<CFM_ODE_EULER, MODE, FIELD>(W, b, dims, B, d, t_span, n_t, traj, tspan_dev, eps, s);
+}
+
+static int ode_fixed_small(int scheme, const float* const* W, const float* const* b, const int* dims, int B, int d,
+                           const float* t_span, int n_t, float* traj, float* tspan_dev, hipStream_t s) {
+    return ode_fixed_small_m<AUG_NONE>(scheme, W, b, dims, B, d, t_span, n_t, traj, tspan_dev, nullptr, s);
+}
+
+template <int SCHEME>
+static int ode_fixed_pair_small_t(const SmArgs& F, const SmArgs& S, int B, int d, const float* t_span, int n_t, float* traj,
+                                  float* tspan_dev, hipStream_t s) {
+    const int grid = small_grid<ode_small_fixed_pair<SCHEME>, 160 * 1024>(B);
+    if (grid < 0) return CFM_EINVAL;
+    int rc = cfm_hip(hipMemcpyAsync(tspan_dev, t_span, sizeof(float) * n_t, hipMemcpyHostToDevice, s));
+    if (rc) return rc;
+    hipLaunchKernelGGL((ode_small_fixed_pair<SCHEME>), dim3(grid), dim3(256), small_lds_bytes(2, 2, false), s, F, S, B, d,
+                       tspan_dev, n_t, traj);
+    return cfm_status();
+}
+
 template <int MODE, int FIELD = FIELD_MLP>
 static int cnf_eval(const SmArgs& A, int B, int d, const float* x, int ldx, float t, const float* eps, float* v, int ldv,
                     float* div, int lddiv, float dsign, hipStream_t s) {
@@ -1161,6 +818,254 @@ static int cnf_eval(const SmArgs& A, int B, int d, const float* x, int ldx, floa
     hipLaunchKernelGGL((ode_small_div<MODE, FIELD>), dim3(grid), dim3(256), small_lds_bytes(1, 2, true), s, A, B, d, x, ldx, t, eps, v, ldv,
                        div, lddiv, dsign);
     return cfm_status();
+}
+
+// ---- host drivers: what the entries below share, each written once ------------------------------------------------
+// Read-back buffer of the adaptive host drivers (pinned host memory, 64 bytes): one per HOST THREAD, as the assignment
+// driver's poll buffer (assign_driver.h, AsgThread) — two threads in adaptive solves on their own streams read their own
+// norms and controller words, never each other's.  Allocated by the thread's first read and kept for its lifetime.
+static thread_local double* g_ode_pinned = nullptr;
+
+static int read_red(hipStream_t s, const double* dev, int count, double* host) {
+    if (count < 1 || count > 8) return CFM_EINVAL;
+    double* pinned = g_ode_pinned;
+    if (!pinned) {
+        int rc = cfm_hip(hipHostMalloc((void**)&pinned, 64, hipHostMallocDefault));
+        if (rc) return rc;
+        g_ode_pinned = pinned;
+    }
+    int rc = cfm_hip(hipMemcpyAsync(pinned, dev, sizeof(double) * count, hipMemcpyDeviceToHost, s));
+    if (rc) return rc;
+    rc = cfm_hip(hipStreamSynchronize(s));
+    if (rc) return rc;
+    for (int i = 0; i < count; ++i) host[i] = pinned[i];
+    return 0;
+}
+
+// The argument of ode_combine / ode_error: k[q] and coef(q) for q < n; the kernels read nothing beyond n, where the
+// struct holds k[0] and 0.
+template <class C>
+static Stages ode_stages(float* const* k, int n, C&& coef) {
+    Stages st{}; st.n = n;
+    for (int q = 0; q < 7; ++q) { st.k[q] = k[q < n ? q : 0]; st.c[q] = q < n ? (float)coef(q) : 0.f; }
+    return st;
+}
+
+// Whether the one-launch kernels take a solve of the plain MLP field: fused path on, the field inside the tile engine's
+// envelope, and room for the t_span copy in w.xt (n = B d >= n_t).  fixed_step: the fixed-step entries also want a step
+// to take (n_t >= 2); the adaptive entries have refused n_t < 2 before they ask.
+static bool ode_small_path(const int* dims, int n_layers, int d, size_t n, int n_t, bool fixed_step) {
+    return cfm_ode_fused_internal() && small_envelope(dims, n_layers, nullptr) == 0 && d + 1 <= SM_W && n >= (size_t)n_t &&
+           (!fixed_step || n_t >= 2);
+}
+
+// The fixed-step layer-per-kernel driver: explicit RK steps on t_span, one ode_combine per stage state and per step end,
+// traj[0] = x0 already in place.  f(t, xin, kout) evaluates a stage derivative.  Any grid is taken as it comes, on purpose
+// (the one-launch kernels of these entries do the same): a repeated or non-monotone point is a step of dt <= 0.
+template <class F>
+static int ode_fixed_layers(F&& f, int scheme, size_t n, const float* t_span, int n_t, float* traj, const OdeWs& w, int* nfe,
+                            hipStream_t s) {
+    const int ns = fx_stages_host(scheme), nb = ode_blocks(n);
+    int evals = 0;
+    for (int k = 0; k + 1 < n_t; ++k) {
+        const float t = t_span[k], dt = t_span[k + 1] - t_span[k];
+        const float* xk = traj + (size_t)k * n;
+        for (int sg = 0; sg < ns; ++sg) {
+            const float* yin = xk;
+            float tsg = t;
+            if (sg > 0) {
+                hipLaunchKernelGGL(ode_combine, dim3(nb), dim3(256), 0, s, n, xk, dt,
+                                   ode_stages(w.k, sg, [&](int q) { return fx_a_host(scheme, sg - 1, q); }), w.xt, (float*)nullptr);
+                yin = w.xt;
+                tsg = t + (float)fx_c_host(scheme, sg - 1) * dt;
+            }
+            const int rc = f(tsg, yin, w.k[sg]);
+            if (rc) return rc;
+            ++evals;
+        }
+        hipLaunchKernelGGL(ode_combine, dim3(nb), dim3(256), 0, s, n, xk, dt,
+                           ode_stages(w.k, ns, [&](int q) { return fx_b_host(scheme, q); }), traj + (size_t)(k + 1) * n, (float*)nullptr);
+    }
+    if (nfe) *nfe = evals;
+    return cfm_status();
+}
+
+// Time direction of a t_span (torchdyn's rule, SURVEY.md A.4): a strictly decreasing grid is integrated as
+// g(s, y) = -f(-s, y) on s = -t_span.  ts receives the (increasing) grid the solver steps on; the returned sign
+// goes into the field's time argument (f is evaluated at sign * s) and into every stage / init-step coefficient
+// (y = x + (sign * dt) * sum a k), so the field arithmetic never changes and the solve is, bit for bit, the
+// forward solve of the field whose time column and last layer are negated.  0: not strictly monotone.
+static float ode_direction(const float* t_span, int n_t, float* ts) {
+    int up = 1, down = 1;
+    for (int k = 0; k + 1 < n_t; ++k) {
+        if (!(t_span[k + 1] > t_span[k])) up = 0;
+        if (!(t_span[k + 1] < t_span[k])) down = 0;
+    }
+    if (!up && !down) return 0.f;
+    const float sg = up ? 1.f : -1.f;
+    for (int k = 0; k < n_t; ++k) ts[k] = sg * t_span[k];
+    return sg;
+}
+
+// The solver-time grid of an adaptive entry, for the length of the call.  sign == 0: no memory, or a t_span that is not
+// strictly monotone; the entries answer CFM_EINVAL to both.  (malloc, not new: nothing here throws across the C boundary.)
+struct OdeGrid {
+    float* ts;
+    float sign;
+    OdeGrid(const float* t_span, int n_t) : ts((float*)malloc(sizeof(float) * (size_t)n_t)), sign(ts ? ode_direction(t_span, n_t, ts) : 0.f) {}
+    ~OdeGrid() { free(ts); }
+    OdeGrid(const OdeGrid&) = delete;
+    OdeGrid& operator=(const OdeGrid&) = delete;
+};
+
+// Hairer II.4 initial step of the host drivers (d0, d1, d2 as RMS norms over n elements).  f(t, x, k) evaluates
+// the field at solver time t (s-space: the caller applies the time sign); hsign = the time sign.
+template <class F>
+static int ode_init_step(F&& f, size_t n, float t, float hsign, float atol, float rtol, const OdeWs& w,
+                         hipStream_t s, float* dt_out) {
+    const int nb = ode_blocks(n);
+    const float order = 5.f;
+    auto rms = [&](double sumsq) -> float { return (float)sqrt(sumsq / (double)n); };
+    int rc = cfm_hip(hipMemsetAsync(w.red, 0, 64, s));
+    if (rc) return rc;
+    hipLaunchKernelGGL(ode_sqnorm, dim3(nb), dim3(256), 0, s, n, w.x, (const float*)nullptr, w.x, atol, rtol, w.red + 0);
+    hipLaunchKernelGGL(ode_sqnorm, dim3(nb), dim3(256), 0, s, n, w.k[0], (const float*)nullptr, w.x, atol, rtol, w.red + 1);
+    double r2[3];
+    rc = read_red(s, w.red, 2, r2);
+    if (rc) return rc;
+    const float d0 = rms(r2[0]), d1 = rms(r2[1]);
+    const float h0 = (d0 < 1e-5f || d1 < 1e-5f) ? 1e-6f : 0.01f * d0 / d1;
+    hipLaunchKernelGGL(ode_combine, dim3(nb), dim3(256), 0, s, n, w.x, hsign * h0, ode_stages(w.k, 1, [](int) { return 1.f; }), w.xt,
+                       (float*)nullptr);
+    rc = f(t + h0, w.xt, w.k[1]);
+    if (rc) return rc;
+    hipLaunchKernelGGL(ode_sqnorm, dim3(nb), dim3(256), 0, s, n, w.k[1], w.k[0], w.x, atol, rtol, w.red + 2);
+    rc = read_red(s, w.red + 2, 1, r2);
+    if (rc) return rc;
+    const float d2 = rms(r2[0]) / h0;
+    float h1;
+    if (d1 <= 1e-15f && d2 <= 1e-15f) h1 = fmaxf(1e-6f, h0 * 1e-3f);
+    else h1 = powf(0.01f / fmaxf(d1, d2), 1.0f / (order + 1.f));
+    *dt_out = fminf(100.f * h0, h1);
+    return 0;
+}
+
+// The start of an adaptive solve on the host: x0 into w.x and traj[0], k_1 = f(t0, x0) into w.k[0], the initial step.
+template <class F>
+static int ode_adaptive_start(F&& f, const float* x0, size_t n, float t0, float tsign, float atol, float rtol, const OdeWs& w,
+                              float* traj, hipStream_t s, float* dt_out) {
+    int rc = cfm_hip(hipMemcpyAsync(w.x, x0, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (rc) return rc;
+    rc = cfm_hip(hipMemcpyAsync(traj, x0, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (rc) return rc;
+    rc = f(t0, w.x, w.k[0]);
+    if (rc) return rc;
+    return ode_init_step(f, n, t0, tsign, atol, rtol, w, s, dt_out);
+}
+
+static int ode_dopri5_layers(int tab, const float* const* W, const float* const* b, const int* dims, int n_layers, int d,
+                             const float* x0, int B, const float* t_span, int n_t, float tsign, float atol,
+                             float rtol, float* traj, int* n_steps, int* nfe, void* ws, void* stream,
+                             const OdeRec* rec = nullptr, int* n_accepted = nullptr) {
+    hipStream_t s = (hipStream_t)stream;
+    OdeWs w = ode_carve(ws, B, maxwidth(dims, n_layers), d);
+    const size_t n = (size_t)B * d;
+    // small vector fields: the whole step attempt in one kernel, controller on the device
+    const bool small = ode_small_path(dims, n_layers, d, n, n_t, false);
+    if (rec && !small) return CFM_EINVAL;              // only the one-launch kernel records its steps: declined before any GPU work
+    const int nb = ode_blocks(n);
+    int evals = 0, steps = 0;
+
+    auto f = [&](float t, const float* xin, float* kout) -> int {
+        ++evals;
+        return cfm_mlp_forward_impl(xin, nullptr, tsign * t, 1, 0, W, b, dims, n_layers, B, kout, w.act, s);
+    };
+    float t = t_span[0], dt;
+    const float T = t_span[n_t - 1];
+    int rc = ode_adaptive_start(f, x0, n, t, tsign, atol, rtol, w, traj, s, &dt);
+    if (rc) return rc;
+
+    if (small && rec)
+        return ode_adaptive_small<AUG_NONE, FIELD_MLP, true>(tab, W, b, dims, B, d, t_span, n_t, tsign, nullptr, atol, rtol, traj, n_steps,
+                                                             nfe, w.x, w.k[0], w.xt, (void*)(w.red + 16), w.sync, t, dt, evals, s, *rec,
+                                                             n_accepted);
+    if (small)
+        return ode_adaptive_small<0>(tab, W, b, dims, B, d, t_span, n_t, tsign, nullptr, atol, rtol, traj, n_steps, nfe, w.x,
+                                   w.k[0], w.xt, (void*)(w.red + 16), w.sync, t, dt, evals, s);
+
+    int ckpt = 1;  // next t_span index to land on
+    const int max_attempts = 1000000;
+    while (t < T && steps < max_attempts) {
+        if (t + dt > T) dt = T - t;
+        float dt_old = dt; bool flag = false;
+        if (ckpt < n_t && t + dt > t_span[ckpt]) { dt_old = dt; flag = true; dt = t_span[ckpt] - t; }
+        const bool lands = (ckpt < n_t) && (flag || t + dt == t_span[ckpt]);
+        // stages k2..k6, then x_new and k7 (FSAL)
+        for (int sIdx = 0; sIdx < 6; ++sIdx) {
+            float* dst = (sIdx == 5) ? w.xn : w.xt;
+            hipLaunchKernelGGL(ode_combine, dim3(nb), dim3(256), 0, s, n, w.x, tsign * dt,
+                               ode_stages(w.k, sIdx + 1, [&](int q) { return rk_a_host(tab, sIdx, q); }), dst, (float*)nullptr);
+            rc = f(t + rk_c_host(tab, sIdx) * dt, dst, w.k[sIdx + 1]);
+            if (rc) return rc;
+        }
+        rc = cfm_hip(hipMemsetAsync(w.red + 4, 0, 8, s));
+        if (rc) return rc;
+        hipLaunchKernelGGL(ode_error, dim3(nb), dim3(256), 0, s, n, w.x, w.xn, dt, ode_stages(w.k, 7, [&](int q) { return rk_e_host(tab, q); }),
+                           atol, rtol, w.red + 4);
+        hipLaunchKernelGGL(ode_controller, dim3(1), dim3(1), 0, s, w.red + 4, (double)n, (float*)(w.red + 6));
+        double ctl;
+        rc = read_red(s, w.red + 6, 1, &ctl);
+        if (rc) return rc;
+        ++steps;
+        float ratio, factor;
+        memcpy(&ratio, (const char*)&ctl, 4); memcpy(&factor, (const char*)&ctl + 4, 4);
+        const bool accept = ratio <= 1.f;
+        if (accept) {
+            if (lands) {
+                t = t_span[ckpt];
+                rc = cfm_hip(hipMemcpyAsync(traj + (size_t)ckpt * n, w.xn, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+                if (rc) return rc;
+                ++ckpt;
+            } else {
+                t = t + dt;
+            }
+            float* tmp = w.x; w.x = w.xn; w.xn = tmp;          // x <- x_new
+            tmp = w.k[0]; w.k[0] = w.k[6]; w.k[6] = tmp;        // k1 <- k7 (FSAL)
+        }
+        if (flag) dt = dt_old - dt;
+        dt = dt * factor;                  // (ode_step_factor on the device, see ode_controller)
+        if (!(dt > 1e-12f)) dt = 1e-12f;   // guard (documented deviation)
+    }
+    if (n_steps) *n_steps = steps;
+    if (nfe) *nfe = evals;
+    rc = cfm_hip(hipStreamSynchronize(s));
+    if (rc) return rc;
+    return (t < T) ? CFM_ENOCONV : 0;
+}
+
+// Adaptive solve of a small field whose first evaluations and initial step come from the one-evaluation kernel:
+// the augmented MLP field (state [B, 1 + d]) and the plain gradient field (state [B, d]).
+template <int MODE, int FIELD = FIELD_MLP>
+static int cnf_dopri5(int tab, const SmArgs& A, const float* const* W, const float* const* b, const int* dims, int d,
+                      const float* x0, int B, const float* ts, int n_t, float tsign, const float* eps, float atol,
+                      float rtol, float* traj, int* n_steps, int* nfe, void* ws, hipStream_t s) {
+    const int D = MODE != AUG_NONE ? d + 1 : d;
+    OdeWs w = ode_carve(ws, B, maxwidth(dims, 4), D);  // workspace of CFM_OP_ODE at D: every buffer is [B, D] (4: both envelopes)
+    const size_t n = (size_t)B * D;
+    if (n < (size_t)n_t) return CFM_EINVAL;            // t_span copy: w.xt (the kernel's x / k buffers are w.x and w.k[0]); deliberate
+    int evals = 0;
+    // the field in solver time, at tsign * t (the sign of g = -f(-s, .) rides on the coefficients); augmented: k = [-div, v]
+    auto f = [&](float t, const float* xin, float* kout) -> int {
+        ++evals;
+        if constexpr (MODE == AUG_NONE) return cnf_eval<MODE, FIELD>(A, B, d, xin, D, tsign * t, eps, kout, D, nullptr, 0, 0.f, s);
+        else return cnf_eval<MODE, FIELD>(A, B, d, xin + 1, D, tsign * t, eps, kout + 1, D, kout, D, -1.f, s);
+    };
+    const float t = ts[0];
+    float dt;
+    const int rc = ode_adaptive_start(f, x0, n, t, tsign, atol, rtol, w, traj, s, &dt);   // d0, d1, d2 over all B D elements
+    if (rc) return rc;
+    return ode_adaptive_small<MODE, FIELD>(tab, W, b, dims, B, d, ts, n_t, tsign, eps, atol, rtol, traj, n_steps, nfe, w.x, w.k[0],
+                                         w.xt, (void*)(w.red + 16), w.sync, t, dt, evals, s);
 }
 
 // a fixed-step grid: strictly monotone, either way
@@ -1172,6 +1077,146 @@ static int fx_monotone(const float* t_span, int n_t) {
         for (int k = 1; k + 1 < n_t; ++k) if ((t_span[k + 1] > t_span[k]) != up) return 0;
     }
     return 1;
+}
+
+// The fixed-step entries that have the one launch only (CNF, gradient field, regularised CNF), up to the launch.
+// envelope(&d) is the entry's own check; the state of x0 / traj and the CFM_OP_ODE workspace are [B, D], D = d + aug_cols.
+// Deliberately unlike the plain and pair entries: the grid must be strictly monotone (fx_monotone), and the t_span copy
+// lives in w.x .. w.xt, so only n_t > 3 B D is refused, before any GPU work.  traj[0] = x0 and *nfe are written before
+// the launch (nfe stands even when the launch fails); n_t = 1 ends there.  launch(d, tspan_dev, s) does the rest.
+template <class Envelope, class Launch>
+static int ode_fixed_onelaunch(const float* x0, int B, const float* t_span, int n_t, float* traj, int* nfe, int stages,
+                               int aug_cols, const int* dims, int n_layers, void* ws, void* stream, Envelope&& envelope,
+                               Launch&& launch) {
+    int d;
+    if (!x0 || !t_span || !traj || !ws || n_t < 1) return CFM_EINVAL;
+    int rc = envelope(&d);
+    if (rc) return rc;
+    if (!fx_monotone(t_span, n_t)) return CFM_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    OdeWs w = ode_carve(ws, B, maxwidth(dims, n_layers), d + aug_cols);
+    const size_t n = (size_t)B * (d + aug_cols);
+    if ((size_t)n_t > 3 * n) return CFM_EINVAL;
+    rc = cfm_hip(hipMemcpyAsync(traj, x0, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (rc) return rc;
+    if (nfe) *nfe = stages * (n_t - 1);
+    if (n_t < 2) return 0;
+    return launch(d, w.x, s);
+}
+
+// ---- the C entries ------------------------------------------------------------------------------------------------
+extern "C" int cfm_ode_fixed_mlp_f32(const float* const* W, const float* const* b, const int* dims,
+                                     int n_layers, const float* x0, int B, const float* t_span,
+                                     int n_t, int scheme, float* traj, int* nfe, void* ws, void* stream) {
+    int d;
+    if (!W || !b || !x0 || !t_span || !traj || !ws || B <= 0 || n_t < 1 || !fx_known(scheme)) return CFM_EINVAL;
+    int rc = check_mlp(dims, n_layers, &d);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    OdeWs w = ode_carve(ws, B, maxwidth(dims, n_layers), d);
+    const size_t n = (size_t)B * d;
+    rc = cfm_hip(hipMemcpyAsync(traj, x0, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (rc) return rc;
+    // small vector fields: rows are independent and the steps are fixed, so ONE launch integrates the
+    // whole t_span (a workgroup walks its 64-row tile through every step, weights resident in LDS)
+    if (ode_small_path(dims, n_layers, d, n, n_t, true)) {
+        rc = ode_fixed_small(scheme, W, b, dims, B, d, t_span, n_t, traj, w.xt, s);
+        if (nfe) *nfe = fx_stages_host(scheme) * (n_t - 1);        // (written even when the launch failed)
+        return rc;
+    }
+    return ode_fixed_layers([&](float t, const float* xin, float* kout) {
+        return cfm_mlp_forward_impl(xin, nullptr, t, 1, 0, W, b, dims, n_layers, B, kout, w.act, s);
+    }, scheme, n, t_span, n_t, traj, w, nfe, s);
+}
+
+extern "C" int cfm_ode_euler_mlp_f32(const float* const* W, const float* const* b, const int* dims,
+                                     int n_layers, const float* x0, int B, const float* t_span,
+                                     int n_t, float* traj, int* nfe, void* ws, void* stream) {
+    return cfm_ode_fixed_mlp_f32(W, b, dims, n_layers, x0, B, t_span, n_t, CFM_ODE_EULER, traj, nfe, ws, stream);
+}
+
+extern "C" int cfm_ode_fixed_pair_mlp_f32(const float* const* Wf, const float* const* bf, const float* const* Wb,
+                                          const float* const* bb, const int* dims, int n_layers, const float* x0, int B,
+                                          const float* t_span, int n_t, int scheme, float* traj, int* nfe, void* ws,
+                                          void* stream) {
+    int d;
+    if (!Wf || !bf || !Wb || !bb || !x0 || !t_span || !traj || !ws || B <= 0 || n_t < 1 || !fx_known(scheme)) return CFM_EINVAL;
+    int rc = check_mlp(dims, n_layers, &d);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    OdeWs w = ode_carve(ws, B, maxwidth(dims, n_layers), d);
+    const size_t n = (size_t)B * d;
+    rc = cfm_hip(hipMemcpyAsync(traj, x0, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (rc) return rc;
+    if (ode_small_path(dims, n_layers, d, n, n_t, true)) {
+        const SmArgs F = small_args(Wf, bf, dims), S = small_args(Wb, bb, dims);
+        if (scheme == CFM_ODE_RK4) rc = ode_fixed_pair_small_t<CFM_ODE_RK4>(F, S, B, d, t_span, n_t, traj, w.xt, s);
+        else if (scheme == CFM_ODE_MIDPOINT) rc = ode_fixed_pair_small_t<CFM_ODE_MIDPOINT>(F, S, B, d, t_span, n_t, traj, w.xt, s);
+        else rc = ode_fixed_pair_small_t<CFM_ODE_EULER>(F, S, B, d, t_span, n_t, traj, w.xt, s);
+        if (nfe) *nfe = fx_stages_host(scheme) * (n_t - 1);        // (written even when the launch failed)
+        return rc;
+    }
+    // the stage derivative of the layer driver: two forward passes (the second net's output in w.x) and the halved difference
+    return ode_fixed_layers([&](float t, const float* xin, float* kout) {
+        int rc = cfm_mlp_forward_impl(xin, nullptr, t, 1, 0, Wf, bf, dims, n_layers, B, kout, w.act, s);
+        if (rc) return rc;
+        rc = cfm_mlp_forward_impl(xin, nullptr, t, 1, 0, Wb, bb, dims, n_layers, B, w.x, w.act, s);
+        if (rc) return rc;
+        hipLaunchKernelGGL(ode_half_diff, dim3(ode_blocks(n)), dim3(256), 0, s, n, kout, w.x);
+        return 0;
+    }, scheme, n, t_span, n_t, traj, w, nfe, s);
+}
+
+extern "C" int cfm_ode_adaptive_mlp_f32(const float* const* W, const float* const* b, const int* dims,
+                                        int n_layers, const float* x0, int B, const float* t_span,
+                                        int n_t, int tableau, float atol, float rtol, float* traj, int* n_steps,
+                                        int* nfe, void* ws, void* stream) {
+    int d;
+    if (!W || !b || !x0 || !t_span || !traj || !ws || B <= 0 || n_t < 2 || !rk_adaptive_known(tableau)) return CFM_EINVAL;
+    int rc = check_mlp(dims, n_layers, &d);
+    if (rc) return rc;
+    const OdeGrid g(t_span, n_t);
+    if (g.sign == 0.f) return CFM_EINVAL;
+    return ode_dopri5_layers(tableau, W, b, dims, n_layers, d, x0, B, g.ts, n_t, g.sign, atol, rtol, traj, n_steps, nfe, ws, stream);
+}
+
+extern "C" int cfm_ode_dopri5_mlp_f32(const float* const* W, const float* const* b, const int* dims,
+                                      int n_layers, const float* x0, int B, const float* t_span,
+                                      int n_t, float atol, float rtol, float* traj, int* n_steps,
+                                      int* nfe, void* ws, void* stream) {
+    return cfm_ode_adaptive_mlp_f32(W, b, dims, n_layers, x0, B, t_span, n_t, CFM_ODE_DOPRI5, atol, rtol, traj, n_steps, nfe, ws, stream);
+}
+
+// cfm_ode_adaptive_mlp_f32 on the recording instantiation of the one-launch kernel: the same arithmetic (traj, n_steps and
+// nfe are its bits), plus the starting state and the record of every accepted step.  CFM_EINVAL wherever the plain entry
+// would leave that kernel; CFM_ENOCONV when the log filled up before the end of the grid.
+extern "C" int cfm_ode_adaptive_rec_mlp_f32(const float* const* W, const float* const* b, const int* dims,
+                                            int n_layers, const float* x0, int B, const float* t_span,
+                                            int n_t, int tableau, float atol, float rtol, float* traj, int* n_steps,
+                                            int* nfe, int max_steps, void* log, float* ysteps, int* n_accepted, void* ws,
+                                            void* stream) {
+    int d;
+    if (!W || !b || !x0 || !t_span || !traj || !ws || B <= 0 || n_t < 2 || !rk_adaptive_known(tableau)) return CFM_EINVAL;
+    if (max_steps < 1 || !log || !ysteps || !n_accepted) return CFM_EINVAL;
+    int rc = check_mlp(dims, n_layers, &d);
+    if (rc) return rc;
+    const OdeGrid g(t_span, n_t);
+    if (g.sign == 0.f) return CFM_EINVAL;
+    const OdeRec rec{(OdeStepRec*)log, ysteps, max_steps};
+    *n_accepted = 0;                // (a decline off the one-launch path, below, already reads 0)
+    return ode_dopri5_layers(tableau, W, b, dims, n_layers, d, x0, B, g.ts, n_t, g.sign, atol, rtol, traj, n_steps, nfe, ws, stream,
+                             &rec, n_accepted);
+}
+
+// Rows up to which the recording solve keeps its state in registers (one 16-row tile per resident workgroup); above, x and
+// k_1 travel through the parity buffers.  For tests and measurements that must sit on either side of that limit; < 0: the
+// occupancy query failed or the tableau is unknown.
+extern "C" int cfm_ode_rec_resident_rows(int tableau) {
+    if (!rk_adaptive_known(tableau)) return CFM_EINVAL;
+    int g = tableau == CFM_ODE_TSIT5 ? ode_dopri_resident<CFM_ODE_TSIT5, AUG_NONE, FIELD_MLP, true>()
+                                     : ode_dopri_resident<CFM_ODE_DOPRI5, AUG_NONE, FIELD_MLP, true>();
+    if (g < 0) return CFM_EINVAL;
+    return SM_ROWS * (g < SM_MAXGRID ? g : SM_MAXGRID);
 }
 
 extern "C" int cfm_mlp_divergence_f32(const float* const* W, const float* const* b, const int* dims, int n_layers,
@@ -1190,59 +1235,20 @@ extern "C" int cfm_mlp_divergence_f32(const float* const* W, const float* const*
 extern "C" int cfm_ode_fixed_cnf_mlp_f32(const float* const* W, const float* const* b, const int* dims, int n_layers,
                                          const float* x0, int B, const float* t_span, int n_t, int mode,
                                          const float* eps, int scheme, float* traj, int* nfe, void* ws, void* stream) {
-    int d; SmArgs A;
-    if (!x0 || !t_span || !traj || !ws || n_t < 1 || !fx_known(scheme)) return CFM_EINVAL;
-    int rc = cnf_check(W, b, dims, n_layers, B, mode, eps, &d, &A);
-    if (rc) return rc;
-    if (!fx_monotone(t_span, n_t)) return CFM_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    const int width = maxwidth(dims, n_layers);
-    OdeWs w = ode_carve(ws, B, width, d + 1);          // workspace of CFM_OP_ODE at d + 1
-    const size_t n = (size_t)B * (d + 1);
-    if ((size_t)n_t > 3 * n) return CFM_EINVAL;        // t_span copy: w.x .. w.xt
-    rc = cfm_hip(hipMemcpyAsync(traj, x0, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (rc) return rc;
-    if (nfe) *nfe = fx_stages_host(scheme) * (n_t - 1);
-    if (n_t < 2) return 0;
-    return mode == 0 ? ode_fixed_small_m<AUG_EXACT>(scheme, W, b, dims, B, d, t_span, n_t, traj, w.x, eps, s)
-                     : ode_fixed_small_m<AUG_HUTCH>(scheme, W, b, dims, B, d, t_span, n_t, traj, w.x, eps, s);
+    SmArgs A;
+    if (!fx_known(scheme)) return CFM_EINVAL;
+    return ode_fixed_onelaunch(x0, B, t_span, n_t, traj, nfe, fx_stages_host(scheme), 1, dims, n_layers, ws, stream,
+        [&](int* d) { return cnf_check(W, b, dims, n_layers, B, mode, eps, d, &A); },
+        [&](int d, float* tspan_dev, hipStream_t s) {
+            return mode == 0 ? ode_fixed_small_m<AUG_EXACT>(scheme, W, b, dims, B, d, t_span, n_t, traj, tspan_dev, eps, s)
+                             : ode_fixed_small_m<AUG_HUTCH>(scheme, W, b, dims, B, d, t_span, n_t, traj, tspan_dev, eps, s);
+        });
 }
 
 extern "C" int cfm_ode_euler_cnf_mlp_f32(const float* const* W, const float* const* b, const int* dims, int n_layers,
                                          const float* x0, int B, const float* t_span, int n_t, int mode,
                                          const float* eps, float* traj, int* nfe, void* ws, void* stream) {
     return cfm_ode_fixed_cnf_mlp_f32(W, b, dims, n_layers, x0, B, t_span, n_t, mode, eps, CFM_ODE_EULER, traj, nfe, ws, stream);
-}
-
-// Adaptive solve of a small field whose first evaluations and initial step come from the one-evaluation kernel:
-// the augmented MLP field (state [B, 1 + d]) and the plain gradient field (state [B, d]).
-template <int MODE, int FIELD = FIELD_MLP>
-static int cnf_dopri5(int tab, const SmArgs& A, const float* const* W, const float* const* b, const int* dims, int d,
-                      const float* x0, int B, const float* ts, int n_t, float tsign, const float* eps, float atol,
-                      float rtol, float* traj, int* n_steps, int* nfe, void* ws, hipStream_t s) {
-    const int D = MODE != AUG_NONE ? d + 1 : d;
-    OdeWs w = ode_carve(ws, B, maxwidth(dims, 4), D);  // workspace of CFM_OP_ODE at D: every buffer is [B, D]
-    const size_t n = (size_t)B * D;
-    if (n < (size_t)n_t) return CFM_EINVAL;            // t_span copy: w.xt
-    int evals = 0;
-    // the field in solver time, at tsign * t (the sign of g = -f(-s, .) rides on the coefficients); augmented: k = [-div, v]
-    auto f = [&](float t, const float* xin, float* kout) -> int {
-        ++evals;
-        if constexpr (MODE == AUG_NONE) return cnf_eval<MODE, FIELD>(A, B, d, xin, D, tsign * t, eps, kout, D, nullptr, 0, 0.f, s);
-        else return cnf_eval<MODE, FIELD>(A, B, d, xin + 1, D, tsign * t, eps, kout + 1, D, kout, D, -1.f, s);
-    };
-    int rc = cfm_hip(hipMemcpyAsync(w.x, x0, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (rc) return rc;
-    rc = cfm_hip(hipMemcpyAsync(traj, x0, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (rc) return rc;
-    const float t = ts[0];
-    rc = f(t, w.x, w.k[0]);
-    if (rc) return rc;
-    float dt;
-    rc = ode_init_step(f, n, t, tsign, atol, rtol, w, s, &dt);   // d0, d1, d2 over all B (1 + d) elements
-    if (rc) return rc;
-    return ode_adaptive_small<MODE, FIELD>(tab, W, b, dims, B, d, ts, n_t, tsign, eps, atol, rtol, traj, n_steps, nfe, w.x, w.k[0],
-                                         w.xt, (void*)(w.red + 16), w.sync, t, dt, evals, s);
 }
 
 extern "C" int cfm_ode_adaptive_cnf_mlp_f32(const float* const* W, const float* const* b, const int* dims, int n_layers,
@@ -1253,18 +1259,12 @@ extern "C" int cfm_ode_adaptive_cnf_mlp_f32(const float* const* W, const float* 
     if (!x0 || !t_span || !traj || !ws || n_t < 2 || !rk_adaptive_known(tableau)) return CFM_EINVAL;
     int rc = cnf_check(W, b, dims, n_layers, B, mode, eps, &d, &A);
     if (rc) return rc;
-    float* ts = (float*)malloc(sizeof(float) * (size_t)n_t);
-    if (!ts) return CFM_EINVAL;
-    const float tsign = ode_direction(t_span, n_t, ts);
-    if (tsign == 0.f) rc = CFM_EINVAL;
-    else if (mode == 0)
-        rc = cnf_dopri5<AUG_EXACT>(tableau, A, W, b, dims, d, x0, B, ts, n_t, tsign, eps, atol, rtol, traj, n_steps, nfe, ws,
-                                   (hipStream_t)stream);
-    else
-        rc = cnf_dopri5<AUG_HUTCH>(tableau, A, W, b, dims, d, x0, B, ts, n_t, tsign, eps, atol, rtol, traj, n_steps, nfe, ws,
-                                   (hipStream_t)stream);
-    free(ts);
-    return rc;
+    const OdeGrid g(t_span, n_t);
+    if (g.sign == 0.f) return CFM_EINVAL;
+    return mode == 0 ? cnf_dopri5<AUG_EXACT>(tableau, A, W, b, dims, d, x0, B, g.ts, n_t, g.sign, eps, atol, rtol, traj, n_steps, nfe, ws,
+                                             (hipStream_t)stream)
+                     : cnf_dopri5<AUG_HUTCH>(tableau, A, W, b, dims, d, x0, B, g.ts, n_t, g.sign, eps, atol, rtol, traj, n_steps, nfe, ws,
+                                             (hipStream_t)stream);
 }
 
 extern "C" int cfm_ode_dopri5_cnf_mlp_f32(const float* const* W, const float* const* b, const int* dims, int n_layers,
@@ -1295,21 +1295,13 @@ extern "C" int cfm_mlp_grad_field_f32(const float* const* W, const float* const*
 template <int MODE>
 static int grad_fixed(const float* const* W, const float* const* b, const int* dims, int n_layers, const float* x0, int B,
                       const float* t_span, int n_t, int scheme, float* traj, int* nfe, void* ws, void* stream) {
-    int d; SmArgs A;
-    if (!x0 || !t_span || !traj || !ws || n_t < 1 || !fx_known(scheme)) return CFM_EINVAL;
-    int rc = grad_check(W, b, dims, n_layers, B, &d, &A);
-    if (rc) return rc;
-    if (!fx_monotone(t_span, n_t)) return CFM_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    const int D = MODE != AUG_NONE ? d + 1 : d;
-    OdeWs w = ode_carve(ws, B, maxwidth(dims, n_layers), D);
-    const size_t n = (size_t)B * D;
-    if ((size_t)n_t > 3 * n) return CFM_EINVAL;        // t_span copy: w.x .. w.xt
-    rc = cfm_hip(hipMemcpyAsync(traj, x0, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (rc) return rc;
-    if (nfe) *nfe = fx_stages_host(scheme) * (n_t - 1);
-    if (n_t < 2) return 0;
-    return ode_fixed_small_m<MODE, FIELD_GRAD>(scheme, W, b, dims, B, d, t_span, n_t, traj, w.x, nullptr, s);
+    SmArgs A;
+    if (!fx_known(scheme)) return CFM_EINVAL;
+    return ode_fixed_onelaunch(x0, B, t_span, n_t, traj, nfe, fx_stages_host(scheme), MODE != AUG_NONE, dims, n_layers, ws, stream,
+        [&](int* d) { return grad_check(W, b, dims, n_layers, B, d, &A); },
+        [&](int d, float* tspan_dev, hipStream_t s) {
+            return ode_fixed_small_m<MODE, FIELD_GRAD>(scheme, W, b, dims, B, d, t_span, n_t, traj, tspan_dev, nullptr, s);
+        });
 }
 
 extern "C" int cfm_ode_fixed_gradmlp_f32(const float* const* W, const float* const* b, const int* dims, int n_layers,
@@ -1333,14 +1325,10 @@ extern "C" int cfm_ode_adaptive_gradmlp_f32(const float* const* W, const float* 
     if (!x0 || !t_span || !traj || !ws || n_t < 2 || !rk_adaptive_known(tableau)) return CFM_EINVAL;
     int rc = grad_check(W, b, dims, n_layers, B, &d, &A);
     if (rc) return rc;
-    float* ts = (float*)malloc(sizeof(float) * (size_t)n_t);
-    if (!ts) return CFM_EINVAL;
-    const float tsign = ode_direction(t_span, n_t, ts);
-    rc = tsign == 0.f ? CFM_EINVAL
-                      : cnf_dopri5<AUG_NONE, FIELD_GRAD>(tableau, A, W, b, dims, d, x0, B, ts, n_t, tsign, nullptr, atol, rtol,
-                                                         traj, n_steps, nfe, ws, (hipStream_t)stream);
-    free(ts);
-    return rc;
+    const OdeGrid g(t_span, n_t);
+    if (g.sign == 0.f) return CFM_EINVAL;
+    return cnf_dopri5<AUG_NONE, FIELD_GRAD>(tableau, A, W, b, dims, d, x0, B, g.ts, n_t, g.sign, nullptr, atol, rtol, traj, n_steps, nfe,
+                                            ws, (hipStream_t)stream);
 }
 
 // ---- regularised CNF training: the Euler solve with the kinetic / Jacobian path integrals (ode_small_euler_reg of
@@ -1348,4 +1336,7 @@ extern "C" int cfm_ode_adaptive_gradmlp_f32(const float* const* W, const float* 
 #include "cnf_reg.h"
 
 // The gradients of these solves (CNF, regularised CNF, fixed-step, adaptive, action matching) are a translation unit of
-// their own, small_grad.hip: folding or moving their code cannot perturb the kernels above.
+// their own, small_grad.hip: folding or moving their code cannot perturb the kernels above.  Host code of this file can
+// be folded and moved freely, as long as the device text of every kernel stays what it was (profiles/ode_host_fold.txt:
+// all 51 kernels compared before and after); the device-side folds that were measured and lost are in
+// profiles/ode_unit_fold.txt and profiles/grad_unit_split.txt.

@@ -355,6 +355,158 @@ def test_abi_unknown_selector_is_einval(dev):
     assert float(traj.abs().max()) == 0.0                       # refused before anything was written
 
 
+EDGE_SENTINEL = 7.5
+EDGE_WIDTH = {"plain": 2, "pair": 2, "cnf": 3, "gradmlp": 2, "cnf_gradmlp": 3, "reg": 4}     # state columns at d = 2
+EDGE_GRID = np.array([0.0, 0.3, 0.55, 1.0], np.float32)
+NON_MONOTONE = (np.array([0.0, 0.5, 0.25, 1.0], np.float32), np.array([0.0, 0.5, 0.5, 1.0], np.float32))
+
+
+@pytest.mark.parametrize("edge,B", [("one_point", 1), ("one_point", 17), ("non_monotone", 1), ("non_monotone", 17),
+                                    ("few_elements", 1), ("recording_off_path", 1), ("recording_off_path", 17)])
+def test_abi_entry_edges(dev, edge, B):
+    """What the solver entries answer at the edges of their arguments (include/cfm_gfx950.h), d = 2, hidden width 64.
+    one_point: n_t = 1 is a solve without a step: traj[0] = x0, nfe = 0, nothing else written.
+    non_monotone: the plain and the pair fixed-step entries step any grid (dt <= 0 included) on both paths, within this
+    file's float64 bound; the fixed-step entries that have the one launch only and every adaptive entry refuse it.
+    few_elements: B d = 2 < n_t = 4 sends the plain entries down the layer path (same bound); the adaptive CNF entry
+    refuses B (d + 1) < n_t and the fixed one n_t > 3 B (d + 1), both before anything is written.
+    recording_off_path: the recording entry declines off the one-launch kernel with n_accepted = 0 and traj untouched."""
+    import cfm_amd
+    from cfm_amd import _lib
+    from cfm_amd._lib import ptr, stream_ptr
+    lib = _lib.load()
+    d, w, tol = 2, 64, 1e-4
+    Ws, bs = R.mlp_params(d, w, seed=31)
+    Wb, bb = R.mlp_params(d, w, seed=32)
+    Wp, bp, dims, keep = R.make_mlp(Ws, bs, dev).hip_params(dev)
+    Wq, bq, _, keep_b = R.make_mlp(Wb, bb, dev).hip_params(dev)
+    torch.manual_seed(33)
+    Wa, ba, adims, keep_a = cfm_amd.MLP(dim=d, out_dim=1, time_varying=True, w=w).to(dev).hip_params(dev)
+    ws = _lib.workspace(_lib.OP_ODE, B, w, d + 2, dev)
+    f, fb = R.mlp_field_np(Ws, bs), R.mlp_field_np(Wb, bb)
+    field = {"plain": f, "pair": lambda t, y: 0.5 * (f(t, y) - fb(t, y))}
+    x0 = {k: torch.randn(B, D, generator=torch.Generator().manual_seed(34)).to(dev) for k, D in EDGE_WIDTH.items()}
+    max_steps = 64
+    log, ysteps = torch.zeros((max_steps, 4), device=dev), torch.zeros((max_steps, B, d), device=dev)
+
+    def fixed(name, scheme, ts, traj, nfe, ws=ws):
+        head = (ptr(x0[name]), B, ts.ctypes.data_as(ctypes.c_void_p), len(ts))
+        tail = (ptr(traj), ctypes.byref(nfe), ptr(ws), stream_ptr())
+        if name == "plain":
+            return lib.cfm_ode_fixed_mlp_f32(Wp, bp, dims, 4, *head, scheme, *tail)
+        if name == "pair":
+            return lib.cfm_ode_fixed_pair_mlp_f32(Wp, bp, Wq, bq, dims, 4, *head, scheme, *tail)
+        if name == "cnf":
+            return lib.cfm_ode_fixed_cnf_mlp_f32(Wp, bp, dims, 4, *head, 0, None, scheme, *tail)
+        if name == "gradmlp":
+            return lib.cfm_ode_fixed_gradmlp_f32(Wa, ba, adims, 4, *head, scheme, *tail)
+        if name == "cnf_gradmlp":
+            return lib.cfm_ode_fixed_cnf_gradmlp_f32(Wa, ba, adims, 4, *head, 0, None, scheme, *tail)
+        assert name == "reg" and scheme == 0                    # Euler, exact trace, the squared_L2 column
+        return lib.cfm_ode_euler_cnf_reg_mlp_f32(Wp, bp, dims, 4, *head, 0, None, 1, ptr(traj), None, ctypes.byref(nfe), ptr(ws),
+                                                 stream_ptr())
+
+    def adaptive(name, tab, ts, traj, nfe, steps, nacc=None, net=(Wp, bp, dims), ws=ws):
+        head = (4, ptr(x0["cnf" if name == "cnf" else "plain"]), B, ts.ctypes.data_as(ctypes.c_void_p), len(ts))
+        tail = (tol, tol, ptr(traj), ctypes.byref(steps), ctypes.byref(nfe))
+        if name == "plain":
+            return lib.cfm_ode_adaptive_mlp_f32(*net, *head, tab, *tail, ptr(ws), stream_ptr())
+        if name == "rec":
+            return lib.cfm_ode_adaptive_rec_mlp_f32(*net, *head, tab, *tail, max_steps, ptr(log), ptr(ysteps), ctypes.byref(nacc),
+                                                    ptr(ws), stream_ptr())
+        if name == "cnf":
+            return lib.cfm_ode_adaptive_cnf_mlp_f32(*net, *head, 0, None, tab, *tail, ptr(ws), stream_ptr())
+        assert name == "gradmlp"
+        return lib.cfm_ode_adaptive_gradmlp_f32(Wa, ba, adims, *head, tab, *tail, ptr(ws), stream_ptr())
+
+    schemes = lambda name: (0,) if name == "reg" else (0, 1, 2)     # noqa: E731
+    solver_of = {v: k for k, v in _lib.ODE_SCHEME.items()}
+    nfe, steps, nacc = ctypes.c_int(-7), ctypes.c_int(-7), ctypes.c_int(-5)
+
+    if edge == "one_point":
+        for name, D in EDGE_WIDTH.items():
+            for scheme in schemes(name):
+                traj = torch.full((2, B, D), EDGE_SENTINEL, device=dev)
+                nfe.value = -7
+                assert fixed(name, scheme, np.array([0.3], np.float32), traj, nfe) == 0, (name, scheme)
+                torch.cuda.synchronize()
+                assert nfe.value == 0, (name, scheme, nfe.value)
+                assert torch.equal(traj[0], x0[name]) and bool((traj[1] == EDGE_SENTINEL).all()), (name, scheme)
+
+    elif edge == "non_monotone":
+        zeros = torch.zeros((4, B, d + 2), device=dev)
+        for ts in NON_MONOTONE:
+            for name in ("cnf", "gradmlp", "cnf_gradmlp", "reg"):
+                for scheme in schemes(name):
+                    assert fixed(name, scheme, ts, zeros, nfe) == -1, (name, scheme, ts)
+            for name in ("plain", "rec", "cnf", "gradmlp"):
+                for tab in (0, 1):
+                    assert adaptive(name, tab, ts, zeros, nfe, steps, nacc) == -1, (name, tab, ts)
+            ref = {(name, s): rk.fixed_trajectory(field[name], x0[name].cpu().numpy(), ts, solver_of[s])
+                   for name in ("plain", "pair") for s in (0, 1, 2)}
+            try:
+                for fused in (1, 0):
+                    lib.cfm_ode_set_fused(fused)
+                    for (name, scheme), want in ref.items():
+                        traj = torch.zeros((4, B, d), device=dev)
+                        assert fixed(name, scheme, ts, traj, nfe) == 0, (name, scheme, ts, fused)
+                        torch.cuda.synchronize()
+                        assert nfe.value == 3 * STAGES[solver_of[scheme]]
+                        _close(traj.cpu().numpy(), want, f"{name} {solver_of[scheme]} on {ts} fused={fused}")
+            finally:
+                lib.cfm_ode_set_fused(1)
+        torch.cuda.synchronize()
+        assert float(zeros.abs().max()) == 0.0                  # refused before anything was written
+
+    elif edge == "few_elements":
+        assert B * d < len(EDGE_GRID)
+        x = x0["plain"].cpu().numpy()
+        for scheme in (0, 1, 2):
+            traj = torch.zeros((4, B, d), device=dev)
+            assert fixed("plain", scheme, EDGE_GRID, traj, nfe) == 0
+            torch.cuda.synchronize()
+            assert nfe.value == 3 * STAGES[solver_of[scheme]]
+            _close(traj.cpu().numpy(), rk.fixed_trajectory(f, x, EDGE_GRID, solver_of[scheme]), f"B d < n_t {solver_of[scheme]}")
+        for solver, tab in _lib.ODE_TABLEAU.items():
+            want, info = rk.adaptive_trajectory(f, x, EDGE_GRID, tol, tol, solver, return_log=True)
+            assert rk.ratios_clear_of_one(info["log"]) and all(l[3] and l[2] < 0.06 for l in info["log"]), info["log"]
+            traj = torch.zeros((4, B, d), device=dev)
+            assert adaptive("plain", tab, EDGE_GRID, traj, nfe, steps) == 0
+            torch.cuda.synchronize()
+            assert (steps.value, nfe.value) == (info["steps"], info["nfe"]), (solver, steps.value, nfe.value, info)
+            _close(traj.cpu().numpy(), want, f"B d < n_t {solver}")
+        kept = torch.full((10, B, d + 1), EDGE_SENTINEL, device=dev)
+        for tab in (0, 1):
+            assert B * (d + 1) < len(EDGE_GRID) and adaptive("cnf", tab, EDGE_GRID, kept, nfe, steps) == -1
+        long_grid = np.linspace(0, 1, 3 * B * (d + 1) + 1).astype(np.float32)
+        for scheme in (0, 1, 2):
+            assert fixed("cnf", scheme, long_grid, kept, nfe) == -1
+        torch.cuda.synchronize()
+        assert bool((kept == EDGE_SENTINEL).all())
+
+    else:
+        ts = np.array([0.0, 1.0], np.float32)                   # B d >= n_t: only the path decides
+        kept = torch.full((2, B, d), EDGE_SENTINEL, device=dev)
+        wide = R.make_mlp(*R.mlp_params(d, 65, seed=31), dev).hip_params(dev)
+        for tab in (0, 1):
+            nacc.value = -5
+            assert adaptive("rec", tab, ts, kept, nfe, steps, nacc, net=wide[:3], ws=_lib.workspace(_lib.OP_ODE, B, 65, d, dev)) == -1
+            assert nacc.value == 0
+            nacc.value = -5
+            lib.cfm_ode_set_fused(0)
+            try:
+                assert adaptive("rec", tab, ts, kept, nfe, steps, nacc) == -1
+            finally:
+                lib.cfm_ode_set_fused(1)
+            assert nacc.value == 0
+            torch.cuda.synchronize()
+            assert bool((kept == EDGE_SENTINEL).all())
+            took = torch.zeros((2, B, d), device=dev)           # the same arguments on the one-launch path are a solve
+            assert adaptive("rec", tab, ts, took, nfe, steps, nacc) == 0 and 1 <= nacc.value <= steps.value
+            torch.cuda.synchronize()
+            assert torch.equal(took[0], x0["plain"])
+
+
 def test_abi_old_entries_are_the_new_ones_at_dopri5_and_euler(dev):
     from cfm_amd import _lib
     from cfm_amd._lib import ptr, stream_ptr

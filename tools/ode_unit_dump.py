@@ -2,14 +2,26 @@
 fixed seeds, in one .npz:
 
     python tools/ode_unit_dump.py OUT.npz            (CFM_LIB_PATH selects the build of the library)
-    python tools/ode_unit_dump.py --compare A.npz B.npz
+    python tools/ode_unit_dump.py --compare A.npz B.npz [A2.npz]
 
 A refactor of that unit moves no floating-point operation, so two builds must agree bit for bit: run the dump once per
-build, each in a fresh process, then --compare (numpy.array_equal array by array, n_steps / nfe included; exit 1 on any
-difference).  Shapes: B = 1 and 17 (two tiles, the second with one row); d = 2 and 63 (ODE / CNF: d + 1 = 64 is the
+build, each in a fresh process, then --compare (numpy.array_equal array by array, rc / n_steps / nfe / n_accepted
+included; exit 1 on any difference).  A2, a second dump of A's build, tells which arrays that build does not reproduce
+itself (the layer path's fp64 norms are atomic sums of one term per 256 elements: order-free above B d = 256); those are
+counted apart and held against B at the spread A and A2 show.
+Shapes: B = 1 and 17 (two tiles, the second with one row); d = 2 and 63 (ODE / CNF: d + 1 = 64 is the
 envelope's edge) or 64 (SDE); hidden width 64 and 33 (padded columns); n_t = 4 both ways; B = 9000 at d = 2 for the
 adaptive solves (the only shape on the non-resident ode_small_dopri).  The gradient entries besides
 cfm_cnf_euler_grad_f32 (GRAD_SHAPES): B = 4112 is 257 tiles, so workgroup 0 of the 256 runs a second tile; n_t small.
+The host drivers of csrc/ode.hip, entry by entry (EXTRA names them):
+  layer    the layer-per-kernel path of the fixed, adaptive and pair entries, every scheme and tableau: by
+           cfm_ode_set_fused(0) at the shapes above and by a field outside the envelope (hidden width 65, d = 64), on the
+           register-staged layer core (cfm_mlp_set_glds(0)) and on the default engine
+  host     the pair entry on its one-launch path, cfm_mlp_grad_field_f32 with and without the Laplacian, the three
+           gradient-field solves, the four old alias entries
+  edge     n_t = 1 and 2 and the two grids that are not strictly monotone, every entry (B d < n_t: B = 1, d = 2 above)
+  refuse   what every entry declines: unknown selector, n_t below its minimum, B = 0, mode 1 without eps, unknown modes
+           and masks, the fused path switched off, the recording entry outside the envelope
 Measurement infrastructure."""
 import ctypes
 import itertools
@@ -212,22 +224,205 @@ def action_grad_cases(lib, L, ptr, sp):
         put(f"actiongrad B{B} d{d} w{w} xt{with_xt}", dW + db + [loss])
 
 
-def compare(a, b):
+# ---- the host drivers of csrc/ode.hip: every forward entry by a short name -------------------------------------------
+# extra state columns of x0 / traj (the regularised solve at mode 0, reg_mask 1: l and the kinetic energy)
+EXTRA = {"fixed": 0, "euler": 0, "pair": 0, "fixed_cnf": 1, "euler_cnf": 1, "fixed_gradmlp": 0, "fixed_cnf_gradmlp": 1, "reg": 2,
+         "adaptive": 0, "dopri5": 0, "rec": 0, "adaptive_cnf": 1, "dopri5_cnf": 1, "adaptive_gradmlp": 0}
+FIXED_ENTRIES = ("fixed", "pair", "fixed_cnf", "fixed_gradmlp", "fixed_cnf_gradmlp", "reg")
+ADAPTIVE_ENTRIES = ("adaptive", "rec", "adaptive_cnf", "adaptive_gradmlp")
+SELECTORS = {**{e: (0, 1, 2) for e in FIXED_ENTRIES}, **{e: (0, 1) for e in ADAPTIVE_ENTRIES}, "reg": (0,)}
+MAX_STEPS = 64
+
+
+def nets_of(d, w, seed):
+    """field net, second (backward drift) net and action net of one shape: pointer tables and what keeps them alive"""
+    import torch, cfm_amd
+    f, b = net(d, w, seed), net(d, w, seed + 100)
+    torch.manual_seed(seed + 200)
+    a = cfm_amd.MLP(dim=d, out_dim=1, time_varying=True, w=w).hip_params()
+    return {"f": f, "b": b, "a": a}
+
+
+def call(lib, L, name, nets, B, d, w, ts, sel, key, mode=0, eps=None, mask=1, n_t=None, B_arg=None, jsq=False):
+    """One call of a forward entry on seeded inputs; records traj and (rc, n_steps, nfe, n_accepted) under `key`.  n_t / B_arg
+    override what the entry is told (refusals: every buffer still has the true size)."""
+    import torch
+    ptr, sp = L.ptr, L.stream_ptr
+    D = d + EXTRA[name]
+    x, traj = randn(30, B, D), torch.zeros((len(ts), B, D), device="cuda")
+    ws = L.workspace(L.OP_ODE, B, w, D)
+    steps, nfe, nacc = ctypes.c_int(-7), ctypes.c_int(-7), ctypes.c_int(-7)
+    Wp, bp, dims, _ = nets["a" if "gradmlp" in name else "f"]
+    head = (Wp, bp, dims, 4, ptr(x), B if B_arg is None else B_arg, ts.ctypes.data_as(ctypes.c_void_p), len(ts) if n_t is None else n_t)
+    ftail = (ptr(traj), ctypes.byref(nfe), ptr(ws), sp())
+    atail = (1e-4, 1e-4, ptr(traj), ctypes.byref(steps), ctypes.byref(nfe))
+    if name == "fixed":
+        rc = lib.cfm_ode_fixed_mlp_f32(*head, sel, *ftail)
+    elif name == "euler":
+        rc = lib.cfm_ode_euler_mlp_f32(*head, *ftail)
+    elif name == "pair":
+        Wq, bq = nets["b"][:2]
+        rc = lib.cfm_ode_fixed_pair_mlp_f32(Wp, bp, Wq, bq, *head[2:], sel, *ftail)
+    elif name == "fixed_cnf":
+        rc = lib.cfm_ode_fixed_cnf_mlp_f32(*head, mode, ptr(eps), sel, *ftail)
+    elif name == "euler_cnf":
+        rc = lib.cfm_ode_euler_cnf_mlp_f32(*head, mode, ptr(eps), *ftail)
+    elif name == "fixed_gradmlp":
+        rc = lib.cfm_ode_fixed_gradmlp_f32(*head, sel, *ftail)
+    elif name == "fixed_cnf_gradmlp":
+        rc = lib.cfm_ode_fixed_cnf_gradmlp_f32(*head, mode, ptr(eps), sel, *ftail)
+    elif name == "reg":
+        side = torch.zeros((len(ts), B), device="cuda") if jsq else None
+        rc = lib.cfm_ode_euler_cnf_reg_mlp_f32(*head, mode, ptr(eps), mask, ptr(traj), ptr(side), ctypes.byref(nfe), ptr(ws), sp())
+    elif name == "adaptive":
+        rc = lib.cfm_ode_adaptive_mlp_f32(*head, sel, *atail, ptr(ws), sp())
+    elif name == "dopri5":
+        rc = lib.cfm_ode_dopri5_mlp_f32(*head, *atail, ptr(ws), sp())
+    elif name == "rec":
+        log, ysteps = torch.zeros((MAX_STEPS, 4), device="cuda"), torch.zeros((MAX_STEPS, B, d), device="cuda")
+        rc = lib.cfm_ode_adaptive_rec_mlp_f32(*head, sel, *atail, MAX_STEPS, ptr(log), ptr(ysteps), ctypes.byref(nacc), ptr(ws), sp())
+    elif name == "adaptive_cnf":
+        rc = lib.cfm_ode_adaptive_cnf_mlp_f32(*head, mode, ptr(eps), sel, *atail, ptr(ws), sp())
+    elif name == "dopri5_cnf":
+        rc = lib.cfm_ode_dopri5_cnf_mlp_f32(*head, mode, ptr(eps), *atail, ptr(ws), sp())
+    else:
+        rc = lib.cfm_ode_adaptive_gradmlp_f32(*head, sel, *atail, ptr(ws), sp())
+    torch.cuda.synchronize()
+    assert rc in (0, -1), (key, rc)          # a solve or CFM_EINVAL; anything else is a failure of the run itself
+    OUT[key], OUT[key + " counts"] = traj.cpu().numpy(), np.array([rc, steps.value, nfe.value, nacc.value])
+
+
+def layer_cases(lib, L, ptr, sp):
+    """The layer-per-kernel drivers (fixed, adaptive, pair): reached by cfm_ode_set_fused(0) at the shapes of ode_cases and,
+    with the switch on, by a field outside the envelope (hidden width 65, d = 64); on the register-staged layer core
+    (cfm_mlp_set_glds(0)) and on the default engine.  The fp64 norms of the adaptive driver are atomic sums of one term per
+    256 elements: run-dependent above B d = 256."""
+    shapes = [(B, d, w, 0) for B in (1, 17) for d in (2, 63) for w in (64, 33)] + [(1, 64, 65, 1), (17, 64, 65, 1)]
+    glds0 = lib.cfm_mlp_get_glds()
+    try:
+        for (B, d, w, fused), glds, up in itertools.product(shapes, (0, glds0), (1, 0)):
+            lib.cfm_ode_set_fused(fused); lib.cfm_mlp_set_glds(glds)
+            nets, (ts, _) = nets_of(d, w, 40), span(4, up)
+            for name in ("fixed", "adaptive", "pair"):
+                for sel in SELECTORS[name]:
+                    call(lib, L, name, nets, B, d, w, ts, sel, f"layer {name}{sel} B{B} d{d} w{w} fused{fused} "
+                         f"glds{'0' if glds == 0 else 'default'} {'up' if up else 'down'}")
+    finally:
+        lib.cfm_ode_set_fused(1); lib.cfm_mlp_set_glds(glds0)
+
+
+def pair_and_gradmlp_cases(lib, L, ptr, sp):
+    """The pair entry on its one-launch path, the three gradient-field solves and the four old alias entries."""
+    for B, d, w, up in itertools.product((1, 17), (2, 63), (64, 33), (1, 0)):
+        nets, (ts, _) = nets_of(d, w, 41), span(4, up)
+        for name in ("pair", "fixed_gradmlp", "fixed_cnf_gradmlp", "adaptive_gradmlp"):
+            for sel in SELECTORS[name]:
+                call(lib, L, name, nets, B, d, w, ts, sel, f"host {name}{sel} B{B} d{d} w{w} {'up' if up else 'down'}")
+        if w == 64:
+            for name in ("euler", "dopri5", "euler_cnf", "dopri5_cnf"):
+                call(lib, L, name, nets, B, d, w, ts, 0, f"host alias {name} B{B} d{d} {'up' if up else 'down'}")
+
+
+def grad_field_cases(lib, L, ptr, sp):
+    import torch
+    for (B, d), w, with_lap in itertools.product([(1, 2), (17, 2), (17, 63)], (64, 33), (1, 0)):
+        Wa, ba, adims, keep = nets_of(d, w, 42)["a"]
+        v, lap = torch.zeros((B, d), device="cuda"), torch.zeros(B, device="cuda")
+        L.check(lib.cfm_mlp_grad_field_f32(Wa, ba, adims, 4, ptr(randn(43, B, d)), d, B, 0.37, ptr(v), ptr(lap) if with_lap else None,
+                                           None, sp()), "grad field")
+        torch.cuda.synchronize()
+        OUT[f"host gradfield B{B} d{d} w{w} lap{with_lap} v"], OUT[f"host gradfield B{B} d{d} w{w} lap{with_lap} lap"] = v.cpu().numpy(), lap.cpu().numpy()
+
+
+NON_MONOTONE = {"back": [0.0, 0.5, 0.25, 1.0], "repeat": [0.0, 0.5, 0.5, 1.0]}
+
+
+def edge_cases(lib, L, ptr, sp):
+    """n_t = 1 and 2, grids that are not strictly monotone (B d < n_t is ode_cases' B = 1, d = 2), and the refusals of every
+    entry.  A refusal passes only what the entry checks before it touches memory: every pointer is a live buffer of the true
+    size, and the argument under test is an integer, or a NULL that the entry tests for (eps at mode 1, jac_sq at reg_mask 2)."""
+    import torch
+    d, w = 2, 64
+    everything = FIXED_ENTRIES + ADAPTIVE_ENTRIES
+    for B in (1, 17):
+        nets = nets_of(d, w, 44)
+        for name in everything:
+            for sel in SELECTORS[name]:
+                for n_t in (1, 2):               # (n_t = 1: a solve without a step, fixed; a refusal, adaptive)
+                    call(lib, L, name, nets, B, d, w, span(n_t, 1)[0], sel, f"edge {name}{sel} B{B} nt{n_t}")
+                for gname, g in NON_MONOTONE.items():
+                    call(lib, L, name, nets, B, d, w, np.array(g, np.float32), sel, f"edge {name}{sel} B{B} grid {gname}")
+        ts = span(4, 1)[0]
+        for name in everything:
+            bad = 3 if name in FIXED_ENTRIES else 2
+            if name != "reg":
+                for sel in (-1, bad):
+                    call(lib, L, name, nets, B, d, w, ts, sel, f"refuse {name} B{B} selector{sel}")
+            call(lib, L, name, nets, B, d, w, ts, 0, f"refuse {name} B{B} nt0", n_t=0)
+            call(lib, L, name, nets, B, d, w, ts, 0, f"refuse {name} B{B} Bzero", B_arg=0)
+            if EXTRA[name] and name != "reg":
+                for mode in (1, 2, -1):          # mode 1 without eps; unknown modes
+                    call(lib, L, name, nets, B, d, w, ts, 0, f"refuse {name} B{B} mode{mode} noeps", mode=mode)
+        for mode, mask, jsq in ((1, 1, 0), (3, 1, 0), (0, 0, 0), (0, 16, 0), (0, 2, 0), (1, 2, 1)):
+            eps = torch.sign(randn(45, B, d)) if (mode, mask) == (1, 2) else None      # (the Jacobian penalty wants mode 0)
+            call(lib, L, "reg", nets, B, d, w, ts, 0, f"refuse reg B{B} mode{mode} mask{mask} jsq{jsq}", mode=mode, mask=mask, eps=eps, jsq=jsq)
+        v, div = torch.zeros((B, d), device="cuda"), torch.zeros(B, device="cuda")
+        Wp, bp, dims, _ = nets["f"]
+        for mode, Ba in ((1, B), (2, B), (0, 0)):
+            rc = lib.cfm_mlp_divergence_f32(Wp, bp, dims, 4, ptr(randn(46, B, d)), Ba, 0.37, mode, None, ptr(v), ptr(div), None, sp())
+            OUT[f"refuse divergence B{B} mode{mode} Barg{Ba} counts"] = np.array([rc])
+        Wa, ba, adims, _ = nets["a"]
+        for Ba, ldx in ((0, d), (B, d - 1)):
+            rc = lib.cfm_mlp_grad_field_f32(Wa, ba, adims, 4, ptr(randn(46, B, d)), ldx, Ba, 0.37, ptr(v), None, None, sp())
+            OUT[f"refuse gradfield B{B} Barg{Ba} ldx{ldx} counts"] = np.array([rc])
+        torch.cuda.synchronize()
+        OUT[f"refuse evals B{B} v"], OUT[f"refuse evals B{B} div"] = v.cpu().numpy(), div.cpu().numpy()
+        # off the one-launch path the recording entry declines (and every one-launch-only entry with it)
+        lib.cfm_ode_set_fused(0)
+        try:
+            for name in everything:
+                if name not in ("fixed", "pair", "adaptive"):
+                    call(lib, L, name, nets, B, d, w, span(2, 1)[0], 0, f"refuse {name} B{B} fused0")
+        finally:
+            lib.cfm_ode_set_fused(1)
+        call(lib, L, "rec", nets_of(64, 65, 44), B, 64, 65, span(2, 1)[0], 0, f"refuse rec B{B} w65")
+
+
+KINDS = ("ode ", "div ", "grad ", "sde ", "fixedgrad ", "adaptivegrad ", "reggrad ", "actiongrad ", "layer ", "host ", "edge ", "refuse ")
+
+
+def compare(a, b, a2=None):
+    """A (parent) against B (head); with A2, a second run of the parent's build, the arrays that differ between A and A2 are
+    run-dependent: counted apart, and held against B at the spread the two parent runs show (max |A - A2|)."""
     A, B = np.load(a), np.load(b)
-    bad = [k for k in sorted(set(A.files) | set(B.files)) if k not in A.files or k not in B.files or not np.array_equal(A[k], B[k])]
-    for kind in ("ode ", "div ", "grad ", "sde ", "fixedgrad ", "adaptivegrad ", "reggrad ", "actiongrad "):
+    A2 = np.load(a2) if a2 else A
+    differ = lambda X, Y, k: k not in X.files or k not in Y.files or not np.array_equal(X[k], Y[k])       # noqa: E731
+    keys = sorted(set(A.files) | set(B.files) | set(A2.files))
+    loose = [k for k in keys if differ(A, A2, k)]
+    bad = [k for k in keys if k not in loose and differ(A, B, k)]
+    far = []
+    for k in loose:
+        if k in A.files and k in A2.files and k in B.files and A[k].shape == A2[k].shape == B[k].shape:
+            spread, dist = np.abs(A[k].astype(np.float64) - A2[k]).max(), np.abs(A[k].astype(np.float64) - B[k]).max()
+            print(f"run-dependent: {k}: parent runs differ by {spread:.3g}, head from parent by {dist:.3g}")
+            if dist <= spread:
+                continue
+        far.append(k)
+    for kind in KINDS:
         ks = [k for k in A.files if k.startswith(kind)]
-        print(f"{kind.strip()}: {len(ks)} arrays, {sum(k in bad for k in ks)} differ")
+        print(f"{kind.strip()}: {len(ks)} arrays, {sum(k in bad for k in ks)} differ, {sum(k in loose for k in ks)} run-dependent")
     print("differing:", bad if bad else "none")
-    return 1 if bad or set(A.files) != set(B.files) else 0
+    print("run-dependent beyond the parent's spread:", far if far else "none")
+    return 1 if bad or far or set(A.files) != set(B.files) else 0
 
 
 if __name__ == "__main__":
     if sys.argv[1] == "--compare":
-        sys.exit(compare(sys.argv[2], sys.argv[3]))
+        sys.exit(compare(*sys.argv[2:5]))
     import cfm_amd._lib as L
     lib = L.load()
-    for cases in (ode_cases, div_grad_cases, sde_cases, fixed_grad_cases, adaptive_grad_cases, cnf_reg_grad_cases, action_grad_cases):
+    for cases in (ode_cases, div_grad_cases, sde_cases, fixed_grad_cases, adaptive_grad_cases, cnf_reg_grad_cases, action_grad_cases,
+                  layer_cases, pair_and_gradmlp_cases, grad_field_cases, edge_cases):
         cases(lib, L, L.ptr, L.stream_ptr)
     np.savez(sys.argv[1], **OUT)
     print(f"{len(OUT)} arrays from {L.LIB_PATH} -> {sys.argv[1]}")
