@@ -1,7 +1,7 @@
 """MI355X-native minibatch OT coupling — drop-in for ``torchcfm.optimal_transport``.
 
 Same class / method names, arguments, return types and error behaviour as the
-reference (``/root/reference/torchcfm/optimal_transport.py``, cited per method as
+reference (``torchcfm/optimal_transport.py``, cited per method as
 ``ref:LINE``); every numerical step runs in the gfx950 HIP kernels behind the C
 ABI (``include/cfm_gfx950.h``).  What changes underneath:
 
@@ -15,12 +15,16 @@ ABI (``include/cfm_gfx950.h``).  What changes underneath:
   ``np.random`` uniforms ``np.random.choice`` would consume (ref:118-120) and the
   device does the inverse-cdf lookup (``cfm_plan_sample_perm`` / ``_dense``).
 
+Inside the sampler a solved coupling is one ``Coupling`` (kind, sol, M, info), which knows its diagnostics and its two
+draws.  The reference's plan diagnostics (ref:88-96, :118, :244) are written once, above it; ``get_map``,
+``_indices_from_solution`` and ``_trajectory_indices`` apply them and say in a comment where they differ on purpose.
+
 CPU tensors are accepted (they are moved to the GPU and the results moved back)
 so the reference's own tests run unchanged; without a GPU every call raises.
 """
 import math
 import warnings
-from typing import Optional, Union
+from typing import NamedTuple, Optional, Union
 
 import numpy as np
 import torch
@@ -326,65 +330,47 @@ def _u01_to_device(u, dev):
     return torch.from_numpy(np.ascontiguousarray(u, dtype=np.float64)).to(dev)
 
 
-def sample_perm(perm, u01, B):
+def _sample_call(fn, dev, head, n, n_out, plan_shape=None):
+    """One plan-sampling entry: ``fn(*head, n, outputs..., [workspace], stream)`` with its n_out int64 [n] outputs
+    allocated, the OP_SAMPLE_DENSE workspace taken where the entry scans a whole [B0, B1] plan (plan_shape), checked."""
     lib = _lib.load()
-    n = u01.numel()
-    i = torch.empty(n, dtype=torch.int64, device=perm.device)
-    j = torch.empty(n, dtype=torch.int64, device=perm.device)
-    check(lib.cfm_plan_sample_perm(ptr(perm), ptr(u01), B, n, ptr(i), ptr(j), stream_ptr()),
-          "cfm_plan_sample_perm")
-    return i, j
+    out = tuple(torch.empty(n, dtype=torch.int64, device=dev) for _ in range(n_out))
+    tail = [ptr(o) for o in out]
+    if plan_shape is not None:
+        tail.append(ptr(_lib.workspace(_lib.OP_SAMPLE_DENSE, plan_shape[0], plan_shape[1], 0, dev)))
+    check(getattr(lib, fn)(*head, n, *tail, stream_ptr()), fn)
+    return out
 
 
-def sample_dense(r, u01):
-    lib = _lib.load()
+def sample_perm(perm, u01, B):      # cfm_plan_sample_perm(perm, u01, B, n, i, j, stream)
+    return _sample_call("cfm_plan_sample_perm", perm.device, (ptr(perm), ptr(u01), B), u01.numel(), 2)
+
+
+def sample_dense(r, u01):      # cfm_plan_sample_dense(M, B0, B1, reg, sk_ws, u01, n, i, j, ws, stream)
     B0, B1 = r.M.shape
-    n = u01.numel()
-    dev = r.M.device
-    i = torch.empty(n, dtype=torch.int64, device=dev)
-    j = torch.empty(n, dtype=torch.int64, device=dev)
-    ws = _lib.workspace(_lib.OP_SAMPLE_DENSE, B0, B1, 0, dev)
-    check(lib.cfm_plan_sample_dense(ptr(r.M), B0, B1, r.reg, ptr(r.ws), ptr(u01), n, ptr(i), ptr(j),
-                                    ptr(ws), stream_ptr()), "cfm_plan_sample_dense")
-    return i, j
+    return _sample_call("cfm_plan_sample_dense", r.M.device, (ptr(r.M), B0, B1, r.reg, ptr(r.ws), ptr(u01)),
+                        u01.numel(), 2, (B0, B1))
 
 
-def sample_pi(pi_dev, u01):
-    lib = _lib.load()
+def sample_pi(pi_dev, u01):      # cfm_plan_sample_pi_f64(pi, B0, B1, u01, n, i, j, ws, stream)
     B0, B1 = pi_dev.shape
-    n = u01.numel()
-    dev = pi_dev.device
-    i = torch.empty(n, dtype=torch.int64, device=dev)
-    j = torch.empty(n, dtype=torch.int64, device=dev)
-    ws = _lib.workspace(_lib.OP_SAMPLE_DENSE, B0, B1, 0, dev)
-    check(lib.cfm_plan_sample_pi_f64(ptr(pi_dev), B0, B1, ptr(u01), n, ptr(i), ptr(j), ptr(ws),
-                                     stream_ptr()), "cfm_plan_sample_pi_f64")
-    return i, j
+    return _sample_call("cfm_plan_sample_pi_f64", pi_dev.device, (ptr(pi_dev), B0, B1, ptr(u01)), u01.numel(), 2,
+                        (B0, B1))
 
 
-def sample_rows_dense(r, rows, u01):
+def sample_rows_dense(r, rows, u01):    # cfm_plan_sample_rows_dense(M, B0, B1, reg, sk_ws, rows, u01, n, j, ws, stream)
     """One column per entry of `rows` drawn from that row of the entropic plan (ref:244: np.random.choice(B, p=pi[i] /
     pi[i].sum())): device int64 [n].  The plan is never materialised (potentials + cost row)."""
-    lib = _lib.load()
     B0, B1 = r.M.shape
-    n = rows.numel()
-    dev = r.M.device
-    j = torch.empty(n, dtype=torch.int64, device=dev)
-    ws = _lib.workspace(_lib.OP_SAMPLE_DENSE, B0, B1, 0, dev)
-    check(lib.cfm_plan_sample_rows_dense(ptr(r.M), B0, B1, r.reg, ptr(r.ws), ptr(rows), ptr(u01), n, ptr(j), ptr(ws),
-                                         stream_ptr()), "cfm_plan_sample_rows_dense")
-    return j
+    return _sample_call("cfm_plan_sample_rows_dense", r.M.device,
+                        (ptr(r.M), B0, B1, r.reg, ptr(r.ws), ptr(rows), ptr(u01)), rows.numel(), 1, (B0, B1))[0]
 
 
-def sample_rows_pi(pi_dev, rows, u01):
+def sample_rows_pi(pi_dev, rows, u01):      # cfm_plan_sample_rows_pi_f64(pi, B0, B1, rows, u01, n, j, stream)
     """The same draw from an explicit device fp64 plan (unbalanced / partial / rectangular exact plans)."""
-    lib = _lib.load()
     B0, B1 = pi_dev.shape
-    n = rows.numel()
-    j = torch.empty(n, dtype=torch.int64, device=pi_dev.device)
-    check(lib.cfm_plan_sample_rows_pi_f64(ptr(pi_dev), B0, B1, ptr(rows), ptr(u01), n, ptr(j), stream_ptr()),
-          "cfm_plan_sample_rows_pi_f64")
-    return j
+    return _sample_call("cfm_plan_sample_rows_pi_f64", pi_dev.device, (ptr(pi_dev), B0, B1, ptr(rows), ptr(u01)),
+                        rows.numel(), 1)[0]
 
 
 def take_rows(x, idx):
@@ -407,6 +393,82 @@ def gather_rows(src, idx):
     check(lib.cfm_gather_rows(ptr(src), ptr(idx), n, row_bytes, ptr(out), stream_ptr()),
           "cfm_gather_rows")
     return out
+
+
+def _cost(x0, x1, squared=True, normalize=False):
+    """x0, x1 -> (dev, a, b, M): the flattened fp32 device copies of the two clouds and their cost matrix."""
+    dev = _lib.require_gpu()
+    a = _lib.to_dev_f32(_flatten2(x0), dev)
+    b = _lib.to_dev_f32(_flatten2(x1), dev)
+    return dev, a, b, cost_matrix(a, b, squared=squared, normalize=normalize)
+
+
+# --------------------------------------------------------------------------- one solved coupling
+# The reference's plan diagnostics (ref:88-96 in get_map, the exception of np.random.choice at ref:118 / :244)
+_NOT_FINITE = "ERROR: p is not finite"
+_NO_MASS = "Numerical errors in OT plan, reverting to uniform plan."
+_CHOICE_RAISES = "probabilities contain NaN"
+
+
+def _report_not_finite(plan, M, x0, x1):
+    """ref:88-92.  plan: what stands for ``p`` — None for a potential-form coupling, which has no plan to print."""
+    print(_NOT_FINITE)
+    if plan is not None:
+        print(plan)
+    print("Cost mean, max", M.mean(), M.max())
+    print(x0, x1)
+
+
+class Coupling(NamedTuple):
+    """What ``_solve`` returns (``_solve_many``: a list of them).  ``kind`` says what ``sol`` is:
+
+    * "perm"  — the int32 [B] permutation of a square exact coupling;
+    * "dense" — the ``SinkhornResult`` of an entropic coupling (potentials: the plan is never built);
+    * "plan"  — a device fp64 [B0, B1] plan (unbalanced, partial, rectangular exact).
+
+    ``M`` is the fp32 cost matrix; ``info`` the int32[4] device tensor of the unbalanced and partial solvers
+    (iterations, status, zeros / non-finite in K) and None for every other coupling."""
+    kind: str
+    sol: object
+    M: torch.Tensor
+    info: Optional[torch.Tensor] = None
+
+    # ``finite`` and ``total`` of get_map's checks (ref:88, :93), in two forms.  A "dense" coupling keeps its mass while its
+    # potentials are finite (the log-domain row update normalises every row to 1 / n): it checks f and g, its total is 1.
+    def diagnose(self):
+        """``(bool, float)``, read back here — the second reduction only after the first one passed.  A permutation has
+        neither case: nothing is launched or read."""
+        if self.kind == "perm":
+            return True, 1.0
+        if self.kind == "plan":
+            finite = bool(torch.isfinite(self.sol).all())
+            return finite, float(self.sol.sum()) if finite else float("nan")
+        return bool(torch.isfinite(self.sol.f).all() and torch.isfinite(self.sol.g).all()), 1.0
+
+    def diagnose_on_device(self):
+        """The same pair of a "plan" or "dense" coupling as a float64 [2] device tensor: the chain reads all slices once."""
+        if self.kind == "plan":
+            total = torch.nan_to_num(self.sol, nan=0.0, posinf=0.0, neginf=0.0).sum()
+            return torch.stack([torch.isfinite(self.sol).all().double(), total])
+        f, g = self.sol.f, self.sol.g
+        return torch.stack([(torch.isfinite(f).all() & torch.isfinite(g).all()).double(),
+                            torch.ones((), dtype=torch.float64, device=f.device)])
+
+    def draw(self, u01):
+        """Device int64 (i, j), one pair per uniform: the inverse-cdf lookup of sample_map (ref:116-121)."""
+        if self.kind == "perm":
+            return sample_perm(self.sol, u01, self.M.shape[0])
+        if self.kind == "dense":
+            return sample_dense(self.sol, u01)
+        return sample_pi(self.sol, u01)
+
+    def draw_rows(self, rows, u01):
+        """Device int64 j, one column per entry of ``rows`` drawn from that row of the plan (ref:244)."""
+        if self.kind == "perm":
+            return self.sol.long()[rows]      # row i has the single nonzero pi[i, perm[i]]: the uniform decides nothing
+        if self.kind == "dense":
+            return sample_rows_dense(self.sol, rows, u01)
+        return sample_rows_pi(self.sol.contiguous(), rows, u01)
 
 
 # --------------------------------------------------------------------------- public API
@@ -433,7 +495,6 @@ class OTPlanSampler:
         self.normalize_cost = normalize_cost
         self.num_threads = num_threads
         self.warn = warn
-        self._last = None  # diagnostics of the most recent solve
 
     # ---- device-resident solve (no host plan) ----
     def _prepare(self, x0, x1):
@@ -446,62 +507,48 @@ class OTPlanSampler:
             self._warned_f64 = True
             warnings.warn("OTPlanSampler: float64 inputs are coupled on a float32 cost matrix (the device solvers' input "
                           "precision); the reference would solve on the float64 matrix.", UserWarning, stacklevel=3)
-        dev = _lib.require_gpu()
-        a = _lib.to_dev_f32(_flatten2(x0), dev)
-        b = _lib.to_dev_f32(_flatten2(x1), dev)
-        M = cost_matrix(a, b, squared=True, normalize=self.normalize_cost)
-        return dev, M, a, b
+        return _cost(x0, x1, normalize=self.normalize_cost)
 
     def _solve(self, x0, x1):
-        """-> ("perm", perm), ("dense", SinkhornResult) or ("plan", device fp64 plan)."""
-        dev, M, a, b = self._prepare(x0, x1)
-        if self.method == "unbalanced":
-            plan, info = unbalanced_plan(M, self.reg, self.reg_m)
-            self._last = info
-            return "plan", plan, M
-        if self.method == "partial":
-            plan, info = partial_plan(M, self.reg)
-            self._last = info
-            return "plan", plan, M
+        """The coupling of (x0, x1), resident on the device (no host plan)."""
+        dev, a, b, M = self._prepare(x0, x1)
+        if self.method in ("unbalanced", "partial"):
+            plan, info = unbalanced_plan(M, self.reg, self.reg_m) if self.method == "unbalanced" else \
+                partial_plan(M, self.reg)
+            return Coupling("plan", plan, M, info)
         if self.method == "exact":
             if M.shape[0] != M.shape[1]:
-                plan, _ = exact_plan_rect(M)
-                self._last = torch.zeros(4, dtype=torch.int32)
-                return "plan", plan, M
-            perm = assign_exact(M)        # raises unless the fp64 certificate holds; nothing is read back
-            self._last = {"certified": True}
-            return "perm", perm, M
+                return Coupling("plan", exact_plan_rect(M)[0], M)
+            return Coupling("perm", assign_exact(M), M)   # raises unless the fp64 certificate holds; nothing is read back
         if a.shape[1] <= _POINTS_TAKE_DIM and not self.normalize_cost:
             r = sinkhorn_log_points(a, b, M, self.reg)      # low-dimensional clouds: no pass over the matrix
         else:
             r = sinkhorn_log(M, self.reg)
-        self._last = r
-        return "dense", r, M
+        return Coupling("dense", r, M)
 
     def get_map(self, x0, x1):
         """Compute the OT plan between a source and a target minibatch (ref:63-97).
 
         Returns a NumPy float64 array of shape (bs, bs), like the reference.
         """
-        kind, sol, M = self._solve(x0, x1)
-        if kind == "perm":
-            B = M.shape[0]
+        c = self._solve(x0, x1)
+        if c.kind == "perm":
+            B = c.M.shape[0]
             p = np.zeros((B, B), dtype=np.float64)
-            p[np.arange(B), sol.cpu().numpy().astype(np.int64)] = 1.0 / B
-        elif kind == "plan":
-            p = sol.cpu().numpy()
-            if int(self._last[1].item()) == 1:     # POT warns and keeps the last usable iterate
-                warnings.warn("Numerical errors at iteration %d" % int(self._last[0].item()))
+            p[np.arange(B), c.sol.cpu().numpy().astype(np.int64)] = 1.0 / B
+        elif c.kind == "plan":
+            p = c.sol.cpu().numpy()
+            if c.info is not None and int(c.info[1].item()) == 1:     # POT warns and keeps the last usable iterate
+                warnings.warn("Numerical errors at iteration %d" % int(c.info[0].item()))
         else:
-            p = sinkhorn_plan(sol).cpu().numpy()
+            p = sinkhorn_plan(c.sol).cpu().numpy()
+        # The checks run on the host plan, as in the reference: the report is printed and NOTHING is raised (the plan
+        # goes back to the caller; np.random.choice raises once it is sampled), the revert is to the host's uniform plan.
         if not np.all(np.isfinite(p)):   # ref:88-92
-            print("ERROR: p is not finite")
-            print(p)
-            print("Cost mean, max", M.mean(), M.max())
-            print(x0, x1)
+            _report_not_finite(p, c.M, x0, x1)
         if np.abs(p.sum()) < 1e-8:       # ref:93-96
             if self.warn:
-                warnings.warn("Numerical errors in OT plan, reverting to uniform plan.")
+                warnings.warn(_NO_MASS)
             p = np.ones_like(p) / p.size
         return p
 
@@ -553,48 +600,29 @@ class OTPlanSampler:
         return self._indices_from_solution(x0, x1, self._solve(x0, x1))
 
     def _indices_from_solution(self, x0, x1, solution):
-        """The draw of ``_sample_indices`` for an already solved coupling (``_solve`` / ``_solve_many`` result)."""
-        n = x0.shape[0]
-        kind, sol, M = solution
-        dev = M.device
-        if kind == "plan":
-            # get_map's diagnostics (ref:88-96) on the device plan, then sample_map (ref:116-121)
-            finite = bool(torch.isfinite(sol).all())
-            total = float(sol.sum()) if finite else float("nan")
-            if not finite:
-                print("ERROR: p is not finite")
-                print(sol)
-                print("Cost mean, max", M.mean(), M.max())
-                print(x0, x1)
-                raise ValueError("probabilities contain NaN")   # what np.random.choice raises, ref:118
-            u = _u01_to_device(np.random.random_sample(n), dev)
-            if abs(total) < 1e-8:
-                if self.warn:
-                    warnings.warn("Numerical errors in OT plan, reverting to uniform plan.")
-                flat = torch.clamp((u * (M.shape[0] * M.shape[1])).floor().long(), max=M.numel() - 1)
-                return flat // M.shape[1], flat % M.shape[1]
-            return sample_pi(sol, u)
-        if kind == "dense":
-            fin = bool(torch.isfinite(sol.f).all() and torch.isfinite(sol.g).all())
-            if not fin:
-                # what the reference does with a non-finite plan (ref:88-96, 118): the diagnostics, no uniform
-                # revert (|NaN| < 1e-8 is False), and np.random.choice raises
-                print("ERROR: p is not finite")
-                print("Cost mean, max", M.mean(), M.max())
-                print(x0, x1)
-                raise ValueError("probabilities contain NaN")   # (before the draw: the NumPy stream is not consumed)
-            u = _u01_to_device(np.random.random_sample(n), dev)
-            return sample_dense(sol, u)
-        u = _u01_to_device(np.random.random_sample(n), dev)
-        return sample_perm(sol, u, M.shape[0])
+        """The draw of ``_sample_indices`` for an already solved coupling (``_solve`` / ``_solve_many`` result):
+        get_map's diagnostics (ref:88-96) on the device objects, then sample_map (ref:116-121)."""
+        c = solution
+        finite, total = c.diagnose()
+        if not finite:
+            # raised BEFORE the draw — the NumPy stream is not consumed — where np.random.choice raises (ref:118)
+            _report_not_finite(c.sol if c.kind == "plan" else None, c.M, x0, x1)
+            raise ValueError(_CHOICE_RAISES)
+        u = _u01_to_device(np.random.random_sample(x0.shape[0]), c.M.device)
+        # only a "plan" gets here without mass: a potential-form coupling has no uniform revert (its total is 1)
+        if abs(total) < 1e-8:
+            # the uniforms are drawn first; the uniform plan's inverse cdf is written out, not sent through the kernel
+            if self.warn:
+                warnings.warn(_NO_MASS)
+            B0, B1 = c.M.shape
+            flat = torch.clamp((u * (B0 * B1)).floor().long(), max=c.M.numel() - 1)
+            return flat // B1, flat % B1
+        return c.draw(u)
 
     def sample_plan(self, x0, x1, replace=True):
         r"""Compute the OT plan and draw source and target samples from it (ref:123-145)."""
         i, j = self._sample_indices(x0, x1, replace=replace)
-        dev = i.device
-        g0 = take_rows(x0, i)
-        g1 = take_rows(x1, j)
-        return g0, g1
+        return take_rows(x0, i), take_rows(x1, j)
 
     def sample_plan_with_scipy(self, x0, x1):
         r"""Deterministic OT pairing: keeps x0's order and returns x1[perm] (ref:147-182).
@@ -602,10 +630,7 @@ class OTPlanSampler:
         The reference calls scipy.optimize.linear_sum_assignment on the host; here the same
         permutation comes from the device solver.
         """
-        x0f, x1f = _flatten2(x0), _flatten2(x1)
-        dev = _lib.require_gpu()
-        a, b = _lib.to_dev_f32(x0f, dev), _lib.to_dev_f32(x1f, dev)
-        M = cost_matrix(a, b, squared=True, normalize=self.normalize_cost)
+        dev, _, _, M = _cost(x0, x1, normalize=self.normalize_cost)      # (no float64 warning here, unlike _prepare)
         B0, B1 = M.shape
         if B0 == B1:
             perm = assign_exact(M).long()
@@ -624,12 +649,11 @@ class OTPlanSampler:
             Mx[:B0, :B1] = M
             full = assign_exact(Mx).long()[:B0]
             perm = full[full < B1]
-        return x0f, gather_rows(x1f.detach().to(dev), perm).to(x1.device)
+        return _flatten2(x0), gather_rows(_flatten2(x1).detach().to(dev), perm).to(x1.device)
 
     def sample_plan_with_labels(self, x0, x1, y0=None, y1=None, replace=True):
         r"""As sample_plan, also gathering the labels (ref:184-219)."""
         i, j = self._sample_indices(x0, x1, replace=replace)
-        dev = i.device
         return (
             take_rows(x0, i),
             take_rows(x1, j),
@@ -656,14 +680,12 @@ class OTPlanSampler:
         if one_batch:
             # equal, square sizes beyond the one-workgroup solver: the assignment problems share ONE chain of launches
             # (decided from the shapes: the other cases build their cost matrices inside the workers, once)
-            Ms = [self._prepare(a, b)[1] for a, b in pairs]
+            Ms = [self._prepare(a, b)[-1] for a, b in pairs]
             perms = assign_exact_batch(Ms)
-            self._last = {"certified": True}
-            return [("perm", perms[k], Ms[k]) for k in range(len(Ms))]
+            return [Coupling("perm", perms[k], Ms[k]) for k in range(len(Ms))]
         tls = threading.local()
         ready = torch.cuda.Event()
         ready.record(torch.cuda.current_stream(dev))
-        last = self._last
 
         def work(a, b):
             torch.cuda.set_device(dev)
@@ -683,7 +705,6 @@ class OTPlanSampler:
         for out, done in res:
             cur.wait_event(done)
             outs.append(out)
-        self._last = last
         return outs
 
     def sample_trajectory(self, X):
@@ -707,7 +728,8 @@ class OTPlanSampler:
         times = X.shape[1]
         dev = _lib.require_gpu()
         n = X.shape[0]
-        sols = self._solve_many([(X[:, t], X[:, t + 1]) for t in range(times - 1)])
+        # (called without a keyword: tests replace the method with a two-parameter function)
+        sols = list(self._solve_many([(X[:, t], X[:, t + 1]) for t in range(times - 1)]))
         # The chain of per-row draws stays on the device: one kernel per slice reads the plan row where it lies
         # (cfm_plan_sample_rows_*), the indices of a slice feed the next one directly, and the host sees them once,
         # at the end.  The host RNG is consumed exactly as the reference's loop consumes it: one uniform per row and
@@ -716,53 +738,32 @@ class OTPlanSampler:
         chain = [rows]
         # get_map's diagnostics (ref:88-96; the reference calls get_map for every slice before it draws, ref:233): a
         # non-finite plan is reported and np.random.choice raises on it (ref:244); a plan without mass reverts to the
-        # uniform plan.  ONE small device reduction per entropic slice, ONE read-back for all slices, before the chain of
-        # draws starts (exact slices have neither case).  A potential-form ("dense") slice cannot lose its mass while its
-        # potentials are finite: the row update of the log-domain loop normalises every row to 1 / n by construction —
-        # its check is the finiteness of f and g.
-        diag = []
-        for kind, sol, M in sols:
-            if kind == "plan":
-                diag.append(torch.stack([torch.isfinite(sol).all().double(), torch.nan_to_num(sol, nan=0.0, posinf=0.0, neginf=0.0).sum()]))
-            elif kind == "dense":
-                diag.append(torch.stack([(torch.isfinite(sol.f).all() & torch.isfinite(sol.g).all()).double(),
-                                         torch.ones((), dtype=torch.float64, device=dev)]))
-        diag = torch.stack(diag).cpu().numpy() if diag else np.zeros((0, 2))
-        sols = list(sols)
-        q = 0
-        for t, (kind, sol, M) in enumerate(sols):
-            if kind == "perm":
-                continue
-            finite, total = bool(diag[q, 0]), float(diag[q, 1]); q += 1
-            if not finite:
-                print("ERROR: p is not finite")
-                if kind == "plan":
-                    print(sol)
-                print("Cost mean, max", M.mean(), M.max())
-                print(X[:, t], X[:, t + 1])
-                raise ValueError("probabilities contain NaN")
-            if abs(total) < 1e-8:
+        # uniform plan.  ALL slices are diagnosed before the first draw: ONE small device reduction per entropic slice,
+        # ONE read-back for all of them (exact square slices have neither case).
+        checked = [t for t, c in enumerate(sols) if c.kind != "perm"]
+        diag = torch.stack([sols[t].diagnose_on_device() for t in checked]).cpu().numpy() if checked else ()
+        for t, (finite, total) in zip(checked, diag):
+            c = sols[t]
+            if not bool(finite):
+                _report_not_finite(c.sol if c.kind == "plan" else None, c.M, X[:, t], X[:, t + 1])
+                raise ValueError(_CHOICE_RAISES)
+            if abs(float(total)) < 1e-8:
                 if self.warn:
-                    warnings.warn("Numerical errors in OT plan, reverting to uniform plan.")
-                sols[t] = ("plan", torch.full(tuple(M.shape), 1.0 / M.numel(), dtype=torch.float64, device=dev), M)   # ref:96
+                    warnings.warn(_NO_MASS)
+                # here the revert IS the explicit uniform plan (ref:96), drawn row by row like every other plan
+                uniform = torch.full(tuple(c.M.shape), 1.0 / c.M.numel(), dtype=torch.float64, device=dev)
+                sols[t] = Coupling("plan", uniform, c.M)
         massless = torch.zeros((), dtype=torch.bool, device=dev)
-        for t, (kind, sol, M) in enumerate(sols):
-            if kind == "plan":
+        for c in sols:
+            if c.kind == "plan":
                 # a visited row without mass: pi[i] / pi[i].sum() is NaN and np.random.choice raises (ref:244) — the flag
                 # stays on the device and is read once, behind the last slice (the draws of a failing call are discarded)
-                massless = massless | (sol.sum(1)[rows] <= 0).any()
-            u = _u01_to_device(np.random.random_sample(n), dev)
-            if kind == "perm":
-                # a permutation plan: row i has the single nonzero pi[i, perm[i]] (the draw is consumed)
-                j = sol.long()[rows]
-            elif kind == "dense":
-                j = sample_rows_dense(sol, rows, u)
-            else:
-                j = sample_rows_pi(sol.contiguous(), rows, u)
-            chain.append(j)
-            rows = j
+                massless = massless | (c.sol.sum(1)[rows] <= 0).any()
+            u = _u01_to_device(np.random.random_sample(n), dev)     # ("perm" slices consume theirs too)
+            rows = c.draw_rows(rows, u)
+            chain.append(rows)
         if bool(massless):
-            raise ValueError("probabilities contain NaN")
+            raise ValueError(_CHOICE_RAISES)
         return torch.stack(chain)
 
 
@@ -782,10 +783,7 @@ def wasserstein(
         exact = False
     else:
         raise ValueError(f"Unknown method: {method}")
-    dev = _lib.require_gpu()
-    a = _lib.to_dev_f32(_flatten2(x0), dev)
-    b = _lib.to_dev_f32(_flatten2(x1), dev)
-    M = cost_matrix(a, b, squared=(power == 2))
+    dev, _, _, M = _cost(x0, x1, squared=(power == 2))      # (no float64 warning and no normalize_cost here)
     if exact and M.shape[0] != M.shape[1]:
         _, ret = exact_plan_rect(M)
     elif exact:

@@ -200,7 +200,7 @@ class TrajectoryFlowMatcher:
                     i, j = sampler._indices_from_solution(batches[q][0], batches[q][1], sols[q])
                 else:
                     if ident is None:
-                        ident = torch.arange(B, dtype=torch.int64, device=sols[0][2].device)
+                        ident = torch.arange(B, dtype=torch.int64, device=sols[0].M.device)
                     i = j = ident
                 rows += [i, j]
             idx = torch.stack(rows).reshape(T - 1, 2, B)

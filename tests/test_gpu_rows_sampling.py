@@ -82,15 +82,14 @@ def test_trajectory_diagnostics_of_a_plan_without_mass_or_with_nans(dev, monkeyp
     def patched(kind):
         def solve_many(pairs, workers=3):
             sols = real(pairs, workers)
-            k, plan, M = sols[1]
-            plan = plan.clone()
+            plan = sols[1].sol.clone()
             if kind == "zero":
                 plan.zero_()
             elif kind == "nan":
                 plan[3, 5] = float("nan")
             else:                                    # half of the rows without mass, the plan as a whole fine
                 plan[:] = 1.0 / plan.numel(); plan[:32] = 0.0
-            sols[1] = (k, plan, M)
+            sols[1] = sols[1]._replace(sol=plan)
             return sols
         return solve_many
 
